@@ -17,8 +17,14 @@ convention (api.py:230-245 times only the trace).  With N>1 each rank traces its
 own 10^6-photon index range per step (weak scaling) and the tallies are summed
 with an RCCL all-reduce inside the timed region.
 
-Rank 0 prints ONE JSON line; see the task contract for the fields.  `value` is the
-MEDIAN of `1 + --repeats` independent, identically fenced windows of --steps steps
+A plain run does what the headline figure needs and nothing else: it sets up, warms
+up, times ONE fenced window of --steps steps, writes the tallies of that window if
+--dump-outputs DIR is given, and prints the line; `value` = photons of the window /
+its seconds, `ms_per_step` = its seconds / --steps.  Everything below is measured with
+--full only (its legs keep their own flags; given explicitly they also run without it).
+
+Rank 0 prints ONE JSON line; see the task contract for the fields.  With --full `value`
+is the MEDIAN of `1 + --repeats` independent, identically fenced windows of --steps steps
 (`repeats` holds min / max / the first window).  `roofline` is for the trace kernel.
 Its operative bound is FP64 VALU issue (`bound`, `frac` = VALU busy while the launches
 overlap); the HBM figure the metric asks for sits beside it in `roofline.hbm`:
@@ -120,40 +126,56 @@ def parse_args():
     ap.add_argument("--photons", type=int, default=PHOTONS_PER_GPU, help="photons per GPU per step")
     ap.add_argument("--streams", type=int, default=3,
                     help="bundles kept in flight (HIP streams); 1 = strictly serial launches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: repeat windows, the sustained and "
+                         "strong-scaling legs, the other configs, scene sizes and meshes, the README case, host arrays, "
+                         "the CPU baseline, and the roofline with the kernel's own counters")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the tallies they produced (the arrays BundlePipeline.totals_host() "
+                         "returns, float64) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--spinup-s", type=float, default=0.3,
                     help="untimed seconds of the same workload before the warm-up steps (GPU clock ramp)")
     ap.add_argument("--ray-buffers", type=int, default=7,
                     help="distinct resident ray sets the steps rotate through (7 x 56 MB = 392 MB: past the "
                          "256 MiB Infinity Cache, so the ray stream of a step comes from HBM)")
-    ap.add_argument("--repeats", type=int, default=15,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="extra, independent timed windows of --steps steps after the first one; `value` is the "
-                         "median of all of them")
-    ap.add_argument("--sustained-s", type=float, default=12.5,
+                         "median of all of them (default: 15 with --full, else 0)")
+    ap.add_argument("--sustained-s", type=float, default=None,
                     help="length of the sustained leg (back-to-back bundles) in seconds of GPU work (sized from the "
                          "sustained step time of a short probe, so that it really lasts this long: >= two ticks of a "
-                         "5-s utilisation sampler); 0 = skip")
-    ap.add_argument("--total-photons", type=int, default=100_000_000,
+                         "5-s utilisation sampler); 0 = skip (default: 12.5 with --full, else 0)")
+    ap.add_argument("--total-photons", type=int, default=None,
                     help="strong-scaling leg (BASELINE configs[2]): ONE job of this many photons split over the "
-                         "ranks by index range, tallies all-reduced once; 0 = skip")
+                         "ranks by index range, tallies all-reduced once; 0 = skip (default: 10^8 with --full, else 0)")
     ap.add_argument("--reduce", choices=("end", "bundle"), default="end",
                     help="multi-GPU: all-reduce the tallies once per job, inside the timed region "
                          "(default), or after every bundle")
     ap.add_argument("--config", default="cfg2",
                     help="scene of the main loop (developer flag for profiles; the contract's metric is cfg2). "
                          "cfg4/cfg5 use device-side emission")
-    ap.add_argument("--scene-sizes", default="1,3,6,11",
+    ap.add_argument("--scene-sizes", default=None,
                     help="tile-array sizes k of the scene-size leg (k x k slabs of the headline LSC in one world, k*k + 1 "
-                         "nodes; benchmarks/configs.py tiles<k>); 'none' = skip")
-    ap.add_argument("--extra-configs", default="cfg4,cfg5",
-                    help="comma list of further configs timed after the cfg2 legs ('none' = skip)")
+                         "nodes; benchmarks/configs.py tiles<k>); 'none' = skip (default: 1,3,6,11 with --full, else none)")
+    ap.add_argument("--extra-configs", default=None,
+                    help="comma list of further configs timed after the cfg2 legs ('none' = skip; default: cfg4,cfg5 "
+                         "with --full, else none)")
     ap.add_argument("--config-photons", type=int, default=10_000_000,
                     help="photons per GPU per window of an extra config (BASELINE: 10^7)")
     ap.add_argument("--config-sustained-s", type=float, default=2.0,
                     help="seconds of back-to-back bundles per extra config (its steady-state rate, without the closing "
                          "drain of a fenced window); 0 = skip")
     ap.add_argument("--rccl-timeout-s", type=float, default=180.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    # the legs beyond the headline figure: on with --full, off in a plain run unless asked for by their own flags
+    for name, full, plain in (("repeats", 15, 0), ("sustained_s", 12.5, 0.0), ("total_photons", 100_000_000, 0),
+                              ("scene_sizes", "1,3,6,11", "none"), ("extra_configs", "cfg4,cfg5", "none")):
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
+    if not args.full:
+        args.no_cpu_baseline = True   # (the CPU referee's timing is a --full leg)
+    return args
 
 
 def spawn_ranks(args):
@@ -466,10 +488,12 @@ def main():
     # ------------------------------------------------------------------ main loop (the contract's K steps)
     leg = Leg(args.config, n)
     leg.spin_up(args.spinup_s, args.warmup)
-    leg.dscene.counters(reset=True)   # the kernel's own step counters, over the timed windows (read after the last one)
-    first_dt = leg.window(args.warmup, args.steps, timed_events=True)
+    if args.full:
+        leg.dscene.counters(reset=True)   # the kernel's own step counters, over the timed windows (read after the last one)
+    # (a plain run times its one window like the repeat windows of a --full run: no per-launch HIP events)
+    first_dt = leg.window(args.warmup, args.steps, timed_events=args.full)
     kernel_ms = leg.pipe.kernel_ms()
-    mean_kernel_ms = sum(kernel_ms) / len(kernel_ms)
+    mean_kernel_ms = sum(kernel_ms) / len(kernel_ms) if kernel_ms else None
     fractions = leg.fractions(n * world * args.steps)
     launch = leg.dscene.launch_info()
     next_step = args.warmup + args.steps
@@ -477,8 +501,15 @@ def main():
     for _ in range(max(0, args.repeats)):
         window_dts.append(leg.window(next_step, args.steps))
         next_step += args.steps
-    in_kernel = live_counters(leg.dscene.counters(), n * args.steps * len(window_dts))   # (this rank's photons)
-    main_clock = leg.dscene.clock()   # the shader clock of the timed windows' launches (reset with the counters above)
+    outputs = leg.pipe.totals_host()   # what the last timed window computed (summed over the ranks)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for key, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, f"{key}.npy"), np.asarray(arr, dtype=np.float64))
+    in_kernel = main_clock = None
+    if args.full:
+        in_kernel = live_counters(leg.dscene.counters(), n * args.steps * len(window_dts))   # (this rank's photons)
+        main_clock = leg.dscene.clock()   # the shader clock of the timed windows' launches (reset with the counters above)
     ordered = sorted(window_dts)
     median_dt = ordered[(len(ordered) - 1) // 2]   # median (the slower of the two middle ones for an even count)
     per_window = n * world * args.steps
@@ -751,16 +782,11 @@ def main():
     printed = threading.Lock()
     line_is_out = threading.Event()   # set once the line has been written (whoever wrote it)
 
-    def report(more_errors=()):
-        """Rank 0's ONE line, from whatever has been measured when it is called: at the end of the run, or -- from the
-        watcher thread below -- when the launcher takes the job down because another rank is gone."""
-        if not printed.acquire(blocking=False):
-            return
-        sustained, strong, extra, scaling = done["sustained"], done["strong"], done["extra"], done["scaling"]
-        failures = list(errors) + list(more_errors)
+    def roofline():
+        """The kernel against its ceilings (--full): launch durations of the first window, the kernel's own counters and
+        shader clock over the timed windows, and the committed PMC summaries."""
         achieved = ALGORITHMIC_BYTES_PER_PHOTON * n / (mean_kernel_ms * 1e-3) / 1e9 if leg.array_input else 0.0
         traffic, instruction_side = load_pmc(args.config, value / world, cus, in_kernel, main_clock)
-        rates = [per_window / d for d in window_dts]
         side = instruction_side or {}
         busy = side.get("valu_busy_under_overlap") or side.get("valu_issue_frac")
         hbm = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -768,6 +794,43 @@ def main():
                "achieved_at_step_rate": (ALGORITHMIC_BYTES_PER_PHOTON if leg.array_input else 0) * per_window / world / median_dt / 1e9,
                "note": "the figure the metric asks for: 56 algorithmic B/photon x photons per launch / mean launch duration; "
                        "not the binding resource"}
+        return {
+            # The operative ceiling of this kernel is FP64 VALU issue (one wave64 instruction per SIMD every four
+            # cycles); HBM, which the metric names, is kept beside it (`hbm`, same fields as before).
+            "bound": "fp64-valu-issue" if busy else "hbm",
+            "achieved": side.get("valu_issue_rate_per_s") if busy else achieved,
+            "peak": side.get("valu_issue_peak_per_s") if busy else HBM_PEAK_GBS,
+            "unit": "wave64 VALU instructions/s" if busy else "GB/s",
+            "frac": busy if busy else achieved / HBM_PEAK_GBS,
+            "frac_is": ("VALU busy with the launches overlapping: vector instructions per photon (PMC per trip x trips "
+                        "counted in this run) x photons/s x 4 cycles / (SIMDs x shader clock read by the kernel in this run)")
+                       if busy else "hbm",
+            "traffic": traffic,
+            "hbm": hbm,
+            "steps_per_photon": in_kernel["steps_per_photon"] if in_kernel else None,
+            # two different things: lanes HOLDING a live photon when a wave steps (counted by the kernel in this run),
+            # and active lanes per vector instruction, divergence inside the step included (PMC pass)
+            "live_lane_fraction": in_kernel["live_lane_fraction"] if in_kernel else None,
+            "valu_lane_utilisation": side.get("valu_lane_utilisation"),
+            "useful_fp64_lane_throughput_frac": (busy * side["valu_lane_utilisation"]) if busy and side.get("valu_lane_utilisation") else None,
+            "kernel": "trace_kernel_w4<RECORD=0,TAB_LDS=1,SEENW=1,EMIT=%d> (pvt_trace_kernel.h trace_body, MESH=0)"
+                      % (0 if leg.array_input else 1),
+            "kernel_ms_mean": mean_kernel_ms,
+            "instruction_side": instruction_side,
+            "kernel_photons_per_s": n / (mean_kernel_ms * 1e-3),
+            "note": "`value` is a STREAM of overlapping bundles; ONE launch of this size alone runs at kernel_photons_per_s "
+                    "(its drain tail is latency-bound). kernel_ms_mean is per launch (HIP events on the launch's own "
+                    "stream, first window); with several bundles in flight launches overlap, so ms_per_step < kernel_ms_mean",
+        }
+
+    def report(more_errors=()):
+        """Rank 0's ONE line, from whatever has been measured when it is called: at the end of the run, or -- from the
+        watcher thread below -- when the launcher takes the job down because another rank is gone."""
+        if not printed.acquire(blocking=False):
+            return
+        sustained, strong, extra, scaling = done["sustained"], done["strong"], done["extra"], done["scaling"]
+        failures = list(errors) + list(more_errors)
+        rates = [per_window / d for d in window_dts]
         out = {
             "metric": "photons/sec on 5x5x1 cm Lumogen-F-Red LSC",
             "value": value,
@@ -793,44 +856,19 @@ def main():
                           f"ray sets ({nbuf * 56 * n / 1e6:.0f} MB)") if leg.array_input
                          else "device-side emission inside the trace kernel (0 B/photon in)",
                 "bundles_in_flight": args.streams,
-                "value_is": f"median of {len(window_dts)} fenced windows of {args.steps} steps",
+                "value_is": (f"median of {len(window_dts)} fenced windows of {args.steps} steps" if len(window_dts) > 1
+                             else f"one fenced window of {args.steps} steps"),
             },
             "rccl_ranks": rccl_ranks,
             "host": {"usable_cores": usable_cores(), "cores_of_rank0": cores_pinned,
                      "submit_us_per_step_per_rank": submit_us, "gpu_us_per_step": median_dt / args.steps * 1e6},
-            "roofline": {
-                # The operative ceiling of this kernel is FP64 VALU issue (one wave64 instruction per SIMD every four
-                # cycles); HBM, which the metric names, is kept beside it (`hbm`, same fields as before).
-                "bound": "fp64-valu-issue" if busy else "hbm",
-                "achieved": side.get("valu_issue_rate_per_s") if busy else achieved,
-                "peak": side.get("valu_issue_peak_per_s") if busy else HBM_PEAK_GBS,
-                "unit": "wave64 VALU instructions/s" if busy else "GB/s",
-                "frac": busy if busy else achieved / HBM_PEAK_GBS,
-                "frac_is": ("VALU busy with the launches overlapping: vector instructions per photon (PMC per trip x trips "
-                            "counted in this run) x photons/s x 4 cycles / (SIMDs x shader clock read by the kernel in this run)")
-                           if busy else "hbm",
-                "traffic": traffic,
-                "hbm": hbm,
-                "steps_per_photon": in_kernel["steps_per_photon"] if in_kernel else None,
-                # two different things: lanes HOLDING a live photon when a wave steps (counted by the kernel in this run),
-                # and active lanes per vector instruction, divergence inside the step included (PMC pass)
-                "live_lane_fraction": in_kernel["live_lane_fraction"] if in_kernel else None,
-                "valu_lane_utilisation": side.get("valu_lane_utilisation"),
-                "useful_fp64_lane_throughput_frac": (busy * side["valu_lane_utilisation"]) if busy and side.get("valu_lane_utilisation") else None,
-                "kernel": "trace_kernel_w4<RECORD=0,TAB_LDS=1,SEENW=1,EMIT=%d> (pvt_trace_kernel.h trace_body, MESH=0)"
-                          % (0 if leg.array_input else 1),
-                "kernel_ms_mean": mean_kernel_ms,
-                "instruction_side": instruction_side,
-                "kernel_photons_per_s": n / (mean_kernel_ms * 1e-3),
-                "note": "`value` is a STREAM of overlapping bundles; ONE launch of this size alone runs at kernel_photons_per_s "
-                        "(its drain tail is latency-bound). kernel_ms_mean is per launch (HIP events on the launch's own "
-                        "stream, first window); with several bundles in flight launches overlap, so ms_per_step < kernel_ms_mean",
-            },
             "launch": launch,
             "tallies": fractions,
             "repeats": {"windows": len(rates), "steps_each": args.steps, "min": min(rates), "median": value,
                         "max": max(rates), "first_window": rates[0], "spread": (max(rates) - min(rates)) / value},
         }
+        if args.full:
+            out["roofline"] = roofline()
         if sustained is not None:
             out["sustained"] = sustained
         if strong is not None:

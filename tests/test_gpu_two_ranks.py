@@ -90,7 +90,7 @@ def test_bench_script_runs_with_two_ranks_and_reports_every_leg(tmp_path):
     env = dict(os.environ, PVT_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--photons", "20000", "--repeats", "2",
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--photons", "20000", "--repeats", "2",
            "--sustained-s", "0.02", "--total-photons", "100001", "--ray-buffers", "2", "--spinup-s", "0",
            "--no-cpu-baseline", "--config-photons", "60000"]
     done = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
@@ -135,7 +135,7 @@ def test_bench_script_spawns_its_own_ranks():
     env = dict(os.environ, PVT_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--photons", "20000", "--repeats", "2", "--sustained-s", "0.02", "--total-photons", "100001",
            "--ray-buffers", "2", "--spinup-s", "0.05", "--no-cpu-baseline", "--config-photons", "60000"]   # (with the clock spin-up)
     done = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
@@ -175,7 +175,7 @@ def test_bench_script_over_rccl_with_one_rank():
     env = dict(os.environ, PVT_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", LOCAL_WORLD_SIZE="1")
     env.pop("PVT_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full",
            "--photons", "50000", "--repeats", "2", "--sustained-s", "1.0", "--total-photons", "400001",
            "--ray-buffers", "2", "--spinup-s", "0.05", "--no-cpu-baseline", "--config-photons", "100000",
            "--config-sustained-s", "0.2"]
@@ -199,7 +199,7 @@ def test_rank_zero_still_prints_its_line_when_another_rank_is_lost_after_the_tim
     env = dict(os.environ, PVT_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", PVT_BENCH_DIE_AFTER_MAIN="1")
     for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--photons", "20000", "--repeats", "2", "--sustained-s", "0.02", "--total-photons", "100001",
            "--ray-buffers", "2", "--spinup-s", "0", "--no-cpu-baseline", "--config-photons", "60000", "--rccl-timeout-s", "30"]
     done = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)

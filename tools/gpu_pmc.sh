@@ -7,7 +7,7 @@
 set -x
 mode=${1:-pipelined}
 cfg=${2:-cfg2}
-flags="--gpus 1 --steps 6 --warmup 1 --no-cpu-baseline --repeats 0 --sustained-s 0 --total-photons 0 --spinup-s 0 --ray-buffers 2 --extra-configs none --config $cfg"
+flags="--gpus 1 --steps 6 --warmup 1 --full --no-cpu-baseline --repeats 0 --sustained-s 0 --total-photons 0 --spinup-s 0 --ray-buffers 2 --extra-configs none --config $cfg"
 [ "$mode" = serial ] && flags="$flags --streams 1"
 [ "$cfg" != cfg2 ] && mode=${mode}_$cfg
 export TMPDIR=/tmp

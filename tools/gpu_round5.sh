@@ -4,6 +4,7 @@
 # pipelined <config>, run separately; earlier rounds' passes -- gpu_round.sh, gpu_round3.sh, gpu_round4.sh -- were this
 # script's predecessors and are in the history.)
 # usage: tools/gpu_round5.sh [skip-tests]
+OUT=${OUT:-out}; mkdir -p "$OUT"   # where the bench lines of this script go
 set -x
 mkdir -p gpurun_out
 export TMPDIR=/tmp
@@ -12,7 +13,7 @@ if [ "$1" != skip-tests ]; then
 PVT_EIGHT_RANKS_RECORD=$R/gpurun_out/eight_ranks.json timeout 2400 python -m pytest tests -x -q -m gpu > gpurun_out/pytest_gpu.log 2>&1; grep -E "passed|failed|rror" gpurun_out/pytest_gpu.log | tail -5
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/smoke.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2>gpurun_out/bench.err | tee gpurun_out/bench.json | cut -c1-400
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>"$OUT"/bench.err | tee "$OUT"/bench.json | cut -c1-400
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof -o bench -- python $R/bench.py --no-cpu-baseline --repeats 2 --sustained-s 0.2 --total-photons 0 --extra-configs none > $R/gpurun_out/prof_bench.json 2> $R/gpurun_out/prof.err
 cd $R

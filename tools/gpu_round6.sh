@@ -2,6 +2,7 @@
 # One GPU-box pass of round 6 (successor of tools/gpu_round5.sh): tests, smoke, the bench with the driver's flags, rocprofv3
 # --kernel-trace --stats of the same command, the per-scene / mesh / end-to-end / history / lone-step tables.
 # PMC passes: tools/gpu_round6_pmc.sh.   usage: tools/gpu_round6.sh [skip-tests]
+OUT=${OUT:-out}; mkdir -p "$OUT"   # where the bench lines of this script go
 set -x
 mkdir -p gpurun_out
 export TMPDIR=/tmp
@@ -13,7 +14,7 @@ echo "pytest -m gpu: rc $? wall $(( $(date +%s) - t0 )) s" | tee -a gpurun_out/p
 grep -E "passed|failed|rror" gpurun_out/pytest_gpu.log | tail -5
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/smoke.log
-timeout 900 python bench.py 2>gpurun_out/bench.err | tee gpurun_out/bench.json | cut -c1-400
+timeout 900 python bench.py --full 2>"$OUT"/bench.err | tee "$OUT"/bench.json | cut -c1-400
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof -o bench -- python $R/bench.py --no-cpu-baseline --repeats 2 --sustained-s 0.2 --total-photons 0 --extra-configs none > $R/gpurun_out/prof_bench.json 2> $R/gpurun_out/prof.err
 cd $R

@@ -5,6 +5,7 @@
 # launches (the 1000-step photon), lone cfg2 launches, and the bench's stream.
 # (The variant is kept as profiles/r06_coop_tail.patch, not in the tree: apply it first, then build spread0 / spread2 with tools/dev_build_full.sh.)
 # usage: tools/gpu_spread_ab.sh [fuzz-count]
+OUT=${OUT:-out}; mkdir -p "$OUT"   # where the bench lines of this script go
 mkdir -p gpurun_out
 {
 echo "== parity, in-tree library (spread on, from 3 nodes)"
@@ -32,7 +33,7 @@ for n in tree spread0 spread2; do
   echo "== lone launches, $n"; PVT_LIB=$lib timeout 300 python tools/gpu_lone_launch.py 2>&1 | grep -v amdgpu.ids
 done
 one() {
-  PVT_LIB=$2 python bench.py --extra-configs cfg4 --scene-sizes none 2>>gpurun_out/ab.err | python -c "
+  PVT_LIB=$2 python bench.py --full --extra-configs cfg4 --scene-sizes none 2>>"$OUT"/ab.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 c=d['configs']['cfg4']

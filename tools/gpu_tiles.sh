@@ -5,7 +5,7 @@ out=$1; shift
 sizes=${@:-1 2 3 4 6 8 11}
 mkdir -p gpurun_out
 for k in $sizes; do
-  python bench.py --config tiles$k --repeats 4 --steps 10 --sustained-s 1.5 --total-photons 0 --no-cpu-baseline \
+  python bench.py --full --config tiles$k --repeats 4 --steps 10 --sustained-s 1.5 --total-photons 0 --no-cpu-baseline \
       --extra-configs none --spinup-s 0.2 > gpurun_out/${out}_tiles$k.json 2> gpurun_out/${out}_tiles$k.err
   python - <<PY
 import json
