@@ -65,7 +65,8 @@ enum {
  * delegates, compiler.py:237-247).  n_coatings may be 0 with NULL coat_* rows. */
 typedef struct PvtSceneTables {
     int32_t n_nodes, root_id, n_components, n_abs, n_ems;
-    int32_t n_recorders, n_hists, total_bins, n_coatings, reserved0;
+    int32_t n_recorders, n_hists, total_bins, n_coatings,
+            n_coat_tables;   /* reflectivity tables of the coatings (the ctab_* fields at the end; was reserved, 0) */
     /* per node */
     const int32_t* geom_type;
     const double* geom_params;      /* (n_nodes,4) box: sx,sy,sz  sphere: r  cyl: length, radius */
@@ -143,6 +144,22 @@ typedef struct PvtSceneTables {
     const double* mesh_vertices;    /* (n_mesh_vertices,3) pooled */
     const int32_t* mesh_faces;      /* (n_mesh_faces,3) indices into the pooled vertices */
     const double* mesh_normals;     /* (n_mesh_faces,3) outward unit face normals */
+    /* coating reflectivity tables (extension, appended within v13).  A coating row with coat_table[k] >= 0 reflects
+     * with R(lambda, theta) of that table instead of coat_reflectivity[k]: lambda the photon's current wavelength (nm),
+     * theta the angle of incidence from the normal on the side the photon arrives from; piecewise-linear in lambda,
+     * then in theta, clamped at both ends of each axis, each step a + t (b - a).  Beyond the critical angle a coating
+     * with Fresnel transmission still reflects totally.  A caller that leaves n_coat_tables 0 may pass a struct that
+     * ends at mesh_normals (the size before these fields): nothing past it is read. */
+    const int32_t* coat_table;          /* (n_coatings) table of each coating row, -1 = none */
+    int32_t n_ctab_wavelength, n_ctab_angle, n_ctab_value, reserved1;   /* lengths of the three pools */
+    const int32_t* ctab_nw;             /* (n_coat_tables) wavelengths of the table, >= 1 */
+    const int32_t* ctab_na;             /* (n_coat_tables) angles of the table, >= 1 */
+    const int32_t* ctab_wl_start;       /* (n_coat_tables) first wavelength in ctab_wavelength */
+    const int32_t* ctab_angle_start;    /* (n_coat_tables) first angle in ctab_angle */
+    const int32_t* ctab_value_start;    /* (n_coat_tables) first value in ctab_value: na x nw, row-major by angle */
+    const double* ctab_wavelength;      /* pooled, nm, strictly increasing per table */
+    const double* ctab_angle;           /* pooled, degrees in [0, 90], strictly increasing per table */
+    const double* ctab_value;           /* pooled reflectivities in [0, 1] */
 } PvtSceneTables;
 
 /* ---- optional device-side emission (replaces the Python/numpy emitter,

@@ -94,7 +94,7 @@ struct PvtScene {
     EmitOff eoff{};
     int nd = 0, ni = 0;
     int nd_small = 0, ni_small = 0;   // ... of which everything but the spectra / their guide tables (the blobs' heads)
-    int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_lights = 0;
+    int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_lights = 0;
     double* d_gd = nullptr;
     int* d_gi = nullptr;
     double* d_ed = nullptr;
@@ -456,6 +456,33 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
             if (t->mesh_faces[k] < 0 || t->mesh_faces[k] >= t->n_mesh_vertices)
                 return fail(PVT_ERR_INVALID, "mesh face indexes a missing vertex");
     }
+    if (K > 0 && t->n_coat_tables != 0) {   // coating reflectivity tables (the fields appended to the v13 struct)
+        const int NT = t->n_coat_tables;
+        if (NT < 0 || !t->coat_table || !t->ctab_nw || !t->ctab_na || !t->ctab_wl_start || !t->ctab_angle_start ||
+            !t->ctab_value_start || !t->ctab_wavelength || !t->ctab_angle || !t->ctab_value)
+            return fail(PVT_ERR_INVALID, "coating tables: missing arrays");
+        long long total = 0;
+        for (int j = 0; j < NT; j++) {
+            const long long nw = t->ctab_nw[j], na = t->ctab_na[j];
+            const long long w0 = t->ctab_wl_start[j], a0 = t->ctab_angle_start[j], v0 = t->ctab_value_start[j];
+            if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > t->n_ctab_wavelength ||
+                a0 + na > t->n_ctab_angle || v0 + nw * na > t->n_ctab_value)
+                return fail(PVT_ERR_INVALID, "coating tables: axis or value range out of bounds");
+            for (long long i = 0; i < nw; i++)
+                if (!std::isfinite(t->ctab_wavelength[w0 + i]) || (i > 0 && !(t->ctab_wavelength[w0 + i] > t->ctab_wavelength[w0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "coating tables: wavelengths must be finite and strictly increasing");
+            for (long long i = 0; i < na; i++)
+                if (!(t->ctab_angle[a0 + i] >= 0.0 && t->ctab_angle[a0 + i] <= 90.0) || (i > 0 && !(t->ctab_angle[a0 + i] > t->ctab_angle[a0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "coating tables: angles must be strictly increasing, in [0, 90] degrees");
+            for (long long i = 0; i < nw * na; i++)
+                if (!(t->ctab_value[v0 + i] >= 0.0 && t->ctab_value[v0 + i] <= 1.0))
+                    return fail(PVT_ERR_INVALID, "coating tables: values must be in [0, 1]");
+            total += nw + na + nw * na;
+        }
+        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "coating tables: more than 2^27 doubles");
+        for (int k = 0; k < K; k++)
+            if (t->coat_table[k] < -1 || t->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "coating row names a missing table");
+    }
     // ---- classes: what many nodes have in common is stored once (see the enums next to struct Lay) ----
     // unrotated: the 3x3 blocks of both matrices of a node are the identity, bit for bit (+0.0 off the diagonal)
     auto unrotated = [&](int n) {
@@ -679,6 +706,14 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
             c_ems_gx[c] = ems_compact ? -1 : guide_len; guide_len += ems_compact ? 0 : en;
             c_ems_gc[c] = guide_len; guide_len += en;
         }
+    }
+    // coating reflectivity tables (KI_T*): their axes and values follow the spectra, so they go wherever the spectra go
+    // (LDS with the whole blob, else global memory) and a scene without them lays out exactly as before
+    const int NT = K > 0 ? t->n_coat_tables : 0;
+    std::vector<int> ctab_at(NT);
+    for (int j = 0; j < NT; j++) {
+        ctab_at[j] = spec_d + spec_len;
+        spec_len += t->ctab_nw[j] + t->ctab_na[j] + t->ctab_nw[j] * t->ctab_na[j];
     }
     const int spec_end = spec_d + spec_len;
     std::vector<double> gd((size_t)spec_end + 1, 0.0);
@@ -921,6 +956,20 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
         int* q = gi.data() + lay.coat_i + k * KI;
         q[KI_RMODE] = t->coat_reflect_mode[k];
         q[KI_TMODE] = t->coat_transmit_mode[k];
+        const int j = NT > 0 ? t->coat_table[k] : -1;
+        q[KI_TNW] = j >= 0 ? t->ctab_nw[j] : 0;   // 0: no table
+        q[KI_TNA] = j >= 0 ? t->ctab_na[j] : 0;
+        q[KI_TW] = j >= 0 ? ctab_at[j] : 0;
+        q[KI_TA] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] : 0;
+        q[KI_TV] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] + t->ctab_na[j] : 0;
+    }
+    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
+    for (int j = 0; j < NT; j++) {   // wavelengths (nm), angles (radians: the kernel compares pvt_acos of the cosine), values
+        const int nw = t->ctab_nw[j], na = t->ctab_na[j];
+        double* d = gd.data() + ctab_at[j];
+        for (int i = 0; i < nw; i++) d[i] = t->ctab_wavelength[t->ctab_wl_start[j] + i];
+        for (int i = 0; i < na; i++) d[nw + i] = t->ctab_angle[t->ctab_angle_start[j] + i] * kRadPerDeg;
+        for (int i = 0; i < na * nw; i++) d[nw + na + i] = t->ctab_value[t->ctab_value_start[j] + i];
     }
 
     // Lazy root (kernel node loop): the root is a box or a sphere and every other node lies strictly inside it,
@@ -996,6 +1045,7 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
     s->n_rec = R;
     s->total_bins = t->total_bins;
     s->n_coat = K;
+    s->n_ctab = NT;
     s->lazy_root = lazy_root;
     s->lazy_k = lazy_k;
     s->exit_observed = exit_observed;
@@ -1134,7 +1184,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.nd = s->nd; a.ni = s->ni;
     a.nd_lds = 0; a.ni_lds = 0;
     a.n_nodes = s->n_nodes; a.root = s->root; a.n_rec = s->n_rec; a.total_bins = s->total_bins;
-    a.n_coat = s->n_coat; a.n_lights = s->n_lights;
+    a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_lights = s->n_lights;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;

@@ -78,7 +78,10 @@ enum { RI_NODE = 0, RI_EVENT, RI_HAS_FACET, RI_HSTART, RI_HN, RI_SRC_MODE, RI_SR
 enum { HD_LO_A = 0, HD_HI_A, HD_LO_B, HD_HI_B, HD_RA, HD_RB, HD };               // histogram (RA/RB: RN(1/(hi-lo)), NaN = divide)
 enum { HI_PA = 0, HI_PB, HI_NA, HI_NB, HI_OFF, HI };
 enum { KD_FACET = 0, KD_LO = 3, KD_HI = 6, KD_REFL = 9, KD = 10 };              // coating
-enum { KI_RMODE = 0, KI_TMODE, KI };
+enum { KI_RMODE = 0, KI_TMODE, KI_TNW, KI_TNA, KI_TW, KI_TA, KI_TV, KI };   // KI_T*: reflectivity table R(wavelength, angle) --
+                                                                 // its axis lengths (KI_TNW = 0: none) and where its wavelengths,
+                                                                 // angles (radians) and values (row-major by angle) start in
+                                                                 // the double blob, after the spectra
 
 struct Lay {  // record bases (elements) inside the blobs; spectra follow the records and are
               // addressed by absolute offsets stored in the component records
@@ -119,7 +122,7 @@ struct KArgs {
     int nd, ni;         // blob lengths
     int nd_lds, ni_lds; // (variants whose tables do not fit LDS) heads of the blobs that are staged all the same: everything
                         // but the spectra and their guide tables (0: nothing)
-    int n_nodes, root, n_rec, total_bins, n_coat, n_lights;
+    int n_nodes, root, n_rec, total_bins, n_coat, n_ctab, n_lights;   // n_ctab: coating reflectivity tables
     // rays in (null -> device emission)
     const double* pos;
     const double* dir;
@@ -414,6 +417,43 @@ __device__ __forceinline__ double interp_clamped(const Tables<TAB_LDS>& T, doubl
     const double num = (yhi - ylo) * (x - xlo), width = xhi - xlo;
     return ylo + (rcp == rcp ? div_known(num, width, rcp) : num / width);
 }
+// Coating reflectivity tables (KI_T*; the Python ReflectivityTable.at is the same arithmetic): piecewise linear in the
+// wavelength, then in the angle of incidence, clamped at both ends of each axis, each step a + t (b - a) so that a table
+// holding a constant gives exactly that constant.  [lo, hi] brackets x (lo == hi at and beyond the ends, t = 0).
+__device__ __forceinline__ void coat_bracket(const double* xs, int n, double x, int& lo, int& hi, double& t) {
+    lo = 0; hi = 0; t = 0.0;
+    if (!(x > xs[0])) return;
+    if (!(x < xs[n - 1])) { lo = n - 1; hi = n - 1; return; }
+    int a = 0, b = n - 1;   // xs[a] <= x < xs[b]
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (xs[m] <= x) a = m; else b = m;
+    }
+    const double xa = xs[a];
+    lo = a; hi = b; t = (x - xa) / (xs[b] - xa);
+}
+// R at wavelength `wl` and incidence cosine `c1` of the table whose wavelengths (nw), angles in radians (na) and values
+// (na x nw) start at `wls`, `angs`, `vals` (LDS or global memory); the angle is pvt_acos(c1), the arc cosine the
+// recorders' `angle` property uses
+__device__ __forceinline__ double coat_table_r(const double* wls, int nw, const double* angs, int na, const double* vals,
+                                               double wl, double c1) {
+    int w0, w1, a0, a1;
+    double tw, ta;
+    coat_bracket(wls, nw, wl, w0, w1, tw);
+    coat_bracket(angs, na, pvt_acos(c1), a0, a1, ta);
+    const double* v0 = vals + a0 * nw;
+    const double* v1 = vals + a1 * nw;
+    const double p0 = v0[w0], r0 = p0 + tw * (v0[w1] - p0);
+    const double p1 = v1[w0], r1 = p1 + tw * (v1[w1] - p1);
+    return r0 + ta * (r1 - r0);
+}
+// The same as a FUNCTION, for the kernels of mesh scenes: inlined there, the lookup costs their history variants some
+// eighty more spilled registers (it costs the kernels of analytic scenes none, so they inline it).
+__device__ __attribute__((noinline)) double coat_table_r_call(const double* wls, int nw, const double* angs, int na,
+                                                              const double* vals, double wl, double c1) {
+    return coat_table_r(wls, nw, angs, na, vals, wl, c1);
+}
+
 // same, tables in global memory (emitter spectra)
 __device__ __forceinline__ double interp_global(const double* xs, const double* ys, int n, double x) {
     if (n == 1) return ys[0];
@@ -837,12 +877,13 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2 };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
         (A.emit_method == PVT_EMIT_FULL ? 1u << UF_EMIT_FULL : 0u) | (A.emit_method == PVT_EMIT_KT ? 1u << UF_EMIT_KT : 0u) |
-        (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u);
+        (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u) |
+        (A.n_ctab > 0 ? 1u << UF_CTAB : 0u);
     if constexpr (TAIL && PVT_TAIL_LAZY) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
@@ -2463,7 +2504,18 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     // a coating sets the reflectivity -- except beyond the critical angle when it
                     // transmits by Fresnel refraction: no refracted ray exists there
                     double cr = T.dv(L.coat_d + coat * KD + KD_REFL);
-                    if (cr >= 0.0 && !(r == 1.0 && T.iv(L.coat_i + coat * KI + KI_TMODE) != 1)) r = cr;
+                    const bool keep_tir = r == 1.0 && T.iv(L.coat_i + coat * KI + KI_TMODE) != 1;
+                    if (uf(UF_CTAB) && !keep_tir) {   // (scenes with reflectivity tables only) R(wavelength, angle of incidence)
+                        const int q = L.coat_i + coat * KI, nw = T.iv(q + KI_TNW);
+                        if (nw > 0) {
+                            const double* tab = TAB_LDS == 1 ? T.ld : T.hd;   // (where the spectra are read from)
+                            const double *wls = tab + T.iv(q + KI_TW), *angs = tab + T.iv(q + KI_TA), *vals = tab + T.iv(q + KI_TV);
+                            const int na = T.iv(q + KI_TNA);
+                            if constexpr (MESH) cr = coat_table_r_call(wls, nw, angs, na, vals, wl, c1);
+                            else cr = coat_table_r(wls, nw, angs, na, vals, wl, c1);
+                        }
+                    }
+                    if (cr >= 0.0 && !keep_tir) r = cr;
                 }
             }
             double u = 1.0;

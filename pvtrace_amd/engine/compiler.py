@@ -36,6 +36,7 @@ from pvtrace_amd.material import (
     Luminophore,
     NullSurfaceDelegate,
     Reactor,
+    ReflectivityTable,
     Scatterer,
     isotropic,
 )
@@ -178,15 +179,28 @@ class CompiledScene:
         self.coat_reflectivity = np.full(ncoat, -1.0, dtype=_F64)
         self.coat_reflect_mode = np.zeros(ncoat, dtype=_I32)
         self.coat_transmit_mode = np.zeros(ncoat, dtype=_I32)
+        # Reflectivity tables R(wavelength, angle) of the coatings that have one (coat_table: -1 = none), pooled like
+        # the spectra: per table its axis lengths and where its wavelengths, angles (degrees) and values (row-major,
+        # n_angle x n_wavelength) start in the pools.  A table shared by several coatings is pooled once.
+        self.coat_table = np.full(ncoat, -1, dtype=_I32)
+        ctab = {"index": {}, "nw": [], "na": [], "wl_start": [], "angle_start": [], "value_start": [],
+                "wavelength": [], "angle": [], "value": []}
         for r, coating in enumerate(coat_rows):
             self.coat_facet[r] = coating.facet
             self.coat_lo[r] = [b[0] for b in coating.region]
             self.coat_hi[r] = [b[1] for b in coating.region]
-            if coating.reflectivity is not None:
+            if isinstance(coating.reflectivity, ReflectivityTable):
+                self.coat_table[r] = self._pool_coating_table(coating.reflectivity, ctab)
+            elif coating.reflectivity is not None:
                 self.coat_reflectivity[r] = coating.reflectivity
             self.coat_reflect_mode[r] = Coating.REFLECTION_MODES[coating.reflection]
             self.coat_transmit_mode[r] = Coating.TRANSMISSION_MODES[coating.transmission]
         self.n_coatings = ncoat
+        self.n_coat_tables = len(ctab["nw"])
+        for key in ("nw", "na", "wl_start", "angle_start", "value_start"):
+            setattr(self, f"ctab_{key}", np.array(ctab[key], dtype=_I32))
+        for key in ("wavelength", "angle", "value"):
+            setattr(self, f"ctab_{key}", np.array(ctab[key], dtype=_F64))
 
         pool = self._mesh_pool
         self.n_mesh_vertices, self.n_mesh_faces = pool["nv"], pool["nf"]
@@ -260,6 +274,21 @@ class CompiledScene:
             "NullSurfaceDelegate and CoatedSurfaceDelegate (declarative "
             "coatings) are supported."
         )
+
+    @staticmethod
+    def _pool_coating_table(table, ctab):
+        key = id(table)
+        if key not in ctab["index"]:
+            ctab["index"][key] = (len(ctab["nw"]), table)   # (the table itself keeps its id from being reused)
+            ctab["nw"].append(table.wavelength.size)
+            ctab["na"].append(table._angle_axis.size)
+            ctab["wl_start"].append(len(ctab["wavelength"]))
+            ctab["angle_start"].append(len(ctab["angle"]))
+            ctab["value_start"].append(len(ctab["value"]))
+            ctab["wavelength"].extend(table.wavelength.tolist())
+            ctab["angle"].extend(table._angle_axis.tolist())
+            ctab["value"].extend(table._grid.ravel().tolist())
+        return ctab["index"][key][0]
 
     # -- components ------------------------------------------------------
     def _lower_component(self, node, component, cols, pools):
@@ -421,6 +450,8 @@ class CompiledScene:
         "hist_offset",
         "coat_start", "coat_count", "coat_facet", "coat_lo", "coat_hi",
         "coat_reflectivity", "coat_reflect_mode", "coat_transmit_mode",
+        "coat_table", "ctab_nw", "ctab_na", "ctab_wl_start", "ctab_angle_start", "ctab_value_start",
+        "ctab_wavelength", "ctab_angle", "ctab_value",
         "mesh_face_start", "mesh_face_count", "mesh_vertices", "mesh_faces", "mesh_normals",
     )
 

@@ -33,7 +33,7 @@ class PvtSceneTables(C.Structure):
         ("n_nodes", C.c_int32), ("root_id", C.c_int32), ("n_components", C.c_int32),
         ("n_abs", C.c_int32), ("n_ems", C.c_int32), ("n_recorders", C.c_int32),
         ("n_hists", C.c_int32), ("total_bins", C.c_int32), ("n_coatings", C.c_int32),
-        ("reserved0", C.c_int32),
+        ("n_coat_tables", C.c_int32),
         ("geom_type", _p_i32), ("geom_params", _p_f64), ("local_to_world", _p_f64),
         ("world_to_local", _p_f64), ("refractive_index", _p_f64), ("surface_type", _p_i32),
         ("comp_start", _p_i32), ("comp_count", _p_i32), ("coat_start", _p_i32),
@@ -57,6 +57,12 @@ class PvtSceneTables(C.Structure):
         ("n_mesh_vertices", C.c_int32), ("n_mesh_faces", C.c_int32),
         ("mesh_face_start", _p_i32), ("mesh_face_count", _p_i32), ("mesh_vertices", _p_f64),
         ("mesh_faces", _p_i32), ("mesh_normals", _p_f64),
+        # coating reflectivity tables (read only when n_coat_tables > 0)
+        ("coat_table", _p_i32),
+        ("n_ctab_wavelength", C.c_int32), ("n_ctab_angle", C.c_int32), ("n_ctab_value", C.c_int32),
+        ("reserved1", C.c_int32),
+        ("ctab_nw", _p_i32), ("ctab_na", _p_i32), ("ctab_wl_start", _p_i32), ("ctab_angle_start", _p_i32),
+        ("ctab_value_start", _p_i32), ("ctab_wavelength", _p_f64), ("ctab_angle", _p_f64), ("ctab_value", _p_f64),
     ]
 
 
@@ -143,10 +149,17 @@ def scene_tables_struct(compiled):
     st.n_coatings = int(getattr(compiled, "n_coatings", 0))
     st.n_mesh_vertices = int(getattr(compiled, "n_mesh_vertices", 0))
     st.n_mesh_faces = int(getattr(compiled, "n_mesh_faces", 0))
+    st.n_coat_tables = int(getattr(compiled, "n_coat_tables", 0))
+    if st.n_coat_tables:
+        st.n_ctab_wavelength = int(compiled.ctab_wavelength.shape[0])
+        st.n_ctab_angle = int(compiled.ctab_angle.shape[0])
+        st.n_ctab_value = int(compiled.ctab_value.shape[0])
     for name in _TABLE_POINTER_FIELDS:
         want = np.int32 if dict(PvtSceneTables._fields_)[name] is _p_i32 else np.float64
         value = getattr(compiled, name, None)
-        if value is None:  # tables from an engine without the coating extension
+        if value is None and name == "coat_table":   # tables from a flattener without coating tables
+            value = np.full(max(st.n_coatings, 1), -1, dtype=want)
+        elif value is None:  # tables from an engine without the coating extension
             value = np.zeros(max(st.n_nodes, 1) * 3, dtype=want)
         arr = np.ascontiguousarray(value, dtype=want)
         if arr.size == 0:

@@ -287,6 +287,76 @@ class NullSurfaceDelegate(SurfaceDelegate):
         return ray.direction
 
 
+def _bracket(axis, x):
+    """(lo, hi, t) of the piecewise-linear, end-clamped interpolation of `axis` at `x` (the `interp_clamped`
+    convention): lo = hi at and beyond either end, else axis[lo] <= x < axis[hi] and t = (x - axis[lo]) / width."""
+    n = len(axis)
+    if not x > axis[0]:
+        return 0, 0, 0.0
+    if not x < axis[n - 1]:
+        return n - 1, n - 1, 0.0
+    lo = int(np.searchsorted(axis, x, side="right")) - 1
+    return lo, lo + 1, (x - axis[lo]) / (axis[lo + 1] - axis[lo])
+
+
+class ReflectivityTable(object):
+    """Reflectivity of a coating as a table R(wavelength, angle of incidence).
+
+    wavelength : strictly increasing wavelengths in nm.
+    values : shape (n_angle, n_wavelength), or (n_wavelength,) when `angle` is omitted; finite, in [0, 1].
+    angle : strictly increasing angles of incidence in degrees, in [0, 90], measured from the surface normal on the
+        side the photon arrives from; None = the reflectivity does not depend on the angle.
+
+    `at(wavelength, angle)` interpolates piecewise-linearly in wavelength, then in angle, clamping at both ends of
+    each axis, each step formed as a + t (b - a), so a table holding a constant c evaluates to exactly c.  This is
+    what the device computes per photon at the photon's current wavelength.
+    """
+
+    def __init__(self, wavelength, values, angle=None):
+        wl = np.array(wavelength, dtype=np.float64)
+        if wl.ndim != 1 or wl.size < 1:
+            raise ValueError("wavelength must be a non-empty 1-D sequence")
+        if not np.all(np.isfinite(wl)) or np.any(np.diff(wl) <= 0.0):
+            raise ValueError("wavelength must be finite and strictly increasing")
+        if angle is None:
+            ang = np.zeros(1, dtype=np.float64)
+            vals = np.array(values, dtype=np.float64)
+            if vals.shape != (wl.size,):
+                raise ValueError(
+                    f"values must have shape (n_wavelength,) = ({wl.size},) when angle is omitted, got {vals.shape}"
+                )
+            vals = vals.reshape(1, wl.size)
+        else:
+            ang = np.array(angle, dtype=np.float64)
+            if ang.ndim != 1 or ang.size < 1:
+                raise ValueError("angle must be a non-empty 1-D sequence")
+            if not np.all(np.isfinite(ang)) or np.any(np.diff(ang) <= 0.0):
+                raise ValueError("angle must be finite and strictly increasing")
+            if ang[0] < 0.0 or ang[-1] > 90.0:
+                raise ValueError("angle must lie in [0, 90] degrees")
+            vals = np.array(values, dtype=np.float64)
+            if vals.shape != (ang.size, wl.size):
+                raise ValueError(
+                    f"values must have shape (n_angle, n_wavelength) = ({ang.size}, {wl.size}), got {vals.shape}"
+                )
+        if not np.all(np.isfinite(vals)) or np.any(vals < 0.0) or np.any(vals > 1.0):
+            raise ValueError("values must be finite and in [0, 1]")
+        self.wavelength = wl
+        self.angle = None if angle is None else ang
+        self.values = vals if angle is not None else vals[0]
+        self._angle_axis = ang
+        self._grid = vals
+
+    def at(self, wavelength, angle=0.0):
+        """R at `wavelength` (nm) and angle of incidence `angle` (degrees)."""
+        wl_lo, wl_hi, tw = _bracket(self.wavelength, float(wavelength))
+        a_lo, a_hi, ta = _bracket(self._angle_axis, float(angle))
+        g = self._grid
+        r0 = g[a_lo, wl_lo] + tw * (g[a_lo, wl_hi] - g[a_lo, wl_lo])
+        r1 = g[a_hi, wl_lo] + tw * (g[a_hi, wl_hi] - g[a_hi, wl_lo])
+        return float(r0 + ta * (r1 - r0))
+
+
 class Coating(object):
     """Declarative override of the optics on part of a node's surface.
 
@@ -299,7 +369,8 @@ class Coating(object):
         (matched like ``np.allclose``: |n_i - facet_i| <= 1e-8 + 1e-5 |facet_i|).
     region : optional ((xlo, xhi), (ylo, yhi), (zlo, zhi)) open intervals in the
         local frame restricting where on that face it applies (None = unbounded).
-    reflectivity : probability of reflection in [0, 1], or None to keep Fresnel.
+    reflectivity : probability of reflection in [0, 1], a `ReflectivityTable` R(wavelength, angle of incidence),
+        or None to keep Fresnel.
     reflection : "specular" or "lambertian" (cosine-weighted about the outward
         facet normal, in the local frame).
     transmission : "fresnel" (Snell refraction) or "matched" (index-matched:
@@ -320,9 +391,12 @@ class Coating(object):
         self.facet = tuple(float(v) for v in facet)
         if len(self.facet) != 3:
             raise ValueError("facet must be a 3-vector")
-        if reflectivity is not None and not 0.0 <= float(reflectivity) <= 1.0:
-            raise ValueError("reflectivity must be in [0, 1] or None")
-        self.reflectivity = None if reflectivity is None else float(reflectivity)
+        if isinstance(reflectivity, ReflectivityTable):
+            self.reflectivity = reflectivity
+        else:
+            if reflectivity is not None and not 0.0 <= float(reflectivity) <= 1.0:
+                raise ValueError("reflectivity must be in [0, 1], a ReflectivityTable or None")
+            self.reflectivity = None if reflectivity is None else float(reflectivity)
         if reflection not in self.REFLECTION_MODES:
             raise ValueError(f"reflection must be one of {sorted(self.REFLECTION_MODES)}")
         if transmission not in self.TRANSMISSION_MODES:
@@ -378,6 +452,10 @@ class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
             return fresnel
         if fresnel == 1.0 and coating.transmission != "matched":
             return 1.0   # beyond the critical angle no refracted ray exists: stays totally reflected
+        if isinstance(coating.reflectivity, ReflectivityTable):
+            normal = _flipped_normal(geometry, ray)
+            cosang = float(np.clip(np.dot(normal, ray.direction), -1.0, 1.0))
+            return coating.reflectivity.at(ray.wavelength, math.degrees(math.acos(cosang)))
         return coating.reflectivity
 
     def transmitted_direction(self, surface, ray, geometry, container, adjacent):
