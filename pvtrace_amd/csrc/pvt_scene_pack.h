@@ -1,0 +1,911 @@
+// pvt_scene_pack.h — the host half of pvt_scene_create: the scene tables are checked and packed into the two blobs the
+// kernel reads (struct Lay in pvt_trace_kernel.h), the BVHs of the meshes and the shortcuts the host can prove.  No HIP
+// call: pvt_trace.hip includes this after pvt_trace_kernel.h and uploads what pack_scene returns.
+#pragma once
+
+namespace {
+
+// The surface branch asks "is the incidence angle beyond the critical angle?", which the reference evaluates as
+// acos(c) > crit (c = the clamped cosine in [0, 1]).  pvt_acos falls as c grows, so there is a threshold c* with
+// pvt_acos(c) > crit  <=>  c < c*: found here by bisection over the doubles of [0, 1] with the very pvt_acos the
+// device runs, then CHECKED -- pvt_acos is accurate to under an ulp but need not be monotone to the last bit, so
+// the 1024 doubles either side of the boundary are all evaluated; farther away the angle differs from crit by
+// hundreds of ulps (|d acos / dc| >= 1) and the sign of the comparison cannot depend on the rounding.  NaN = no
+// threshold could be proven (the kernel then evaluates the reference's expression); -inf = never total reflection.
+double cosine_threshold(double crit) {
+    if (!(crit < INFINITY)) return -INFINITY;
+    auto beyond = [&](double c) { return pvt_acos(c) > crit; };
+    if (!beyond(0.0)) return -INFINITY;     // (not reachable for crit = asin(x) < pi/2; kept for safety)
+    if (beyond(1.0)) return NAN;
+    auto bits = [](double v) { uint64_t u; std::memcpy(&u, &v, 8); return u; };
+    auto from = [](uint64_t u) { double v; std::memcpy(&v, &u, 8); return v; };
+    uint64_t lo = bits(0.0), hi = bits(1.0);   // beyond(lo), !beyond(hi); non-negative doubles order like their bits
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (beyond(from(mid))) lo = mid; else hi = mid;
+    }
+    for (uint64_t k = 1; k <= 1024; k++) {
+        if (lo >= k && !beyond(from(lo - k))) return NAN;
+        if (hi + k <= bits(1.0) && beyond(from(hi + k))) return NAN;
+    }
+    return from(hi);   // the smallest cosine that is NOT beyond the critical angle
+}
+
+// The node grid of scenes with many nodes (kernel: GRID variants, the walk in the node loop).  Every node but the root
+// is filed under the cells that its world-space bounding box, grown by 2m, touches; m = 1e-6 of the scene's extent, many
+// orders of magnitude above the rounding of any distance the intersection arithmetic forms (1e-16 of it per
+// operation).  What the kernel's early exit relies on, with that margin:
+//   * a crossing the reference's arithmetic reports for a node lies inside that node's box grown by m, so some cell the
+//     walk has visited by then (the walk's own rounding: 1e-13 of the extent) holds the node;
+//   * a node filed under none of the cells visited so far stands clear of the photon by more than m, so a box or a
+//     sphere (radius >= 1e-5 of the extent, checked here) is crossed twice or not at all -- never once.
+// Returns false (no grid: the plain node loop serves the scene) for scenes it cannot vouch for: few nodes, meshes,
+// non-rigid or inconsistent poses, degenerate shapes.
+// Negative controls of the grid tests (tests/test_gpu_grid.py, tests/test_node_grid.py) are environment switches read
+// when a scene is created, and they produce WRONG physics on purpose: whoever has one set gets told, loudly, every time.
+bool dev_switch(const char* name) {
+    if (!getenv(name)) return false;
+    fprintf(stderr, "[pvtrace_hip] WARNING: %s is set -- the node grid of this scene is built WRONG on purpose (a test's negative "
+                    "control); unset it for real work\n", name);
+    return true;
+}
+
+struct NodeGrid {
+    int n[3] = {1, 1, 1};
+    double lo[3], hi[3], cell[3], guard = 0.0;
+    int words = 1;
+    bool odd = false;
+    std::vector<unsigned long long> masks;
+};
+bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
+    const int N = t->n_nodes, root = t->root_id;
+    int min_nodes = 8;
+    if (const char* env = getenv("PVT_GRID_MIN_NODES")) min_nodes = atoi(env);
+    if (getenv("PVT_NO_GRID") || N < min_nodes || N < 3) return false;
+    std::vector<double> blo((size_t)N * 3), bhi((size_t)N * 3);
+    double extent = 0.0;
+    for (int n = 0; n < N; n++) {
+        if (t->geom_type[n] == PVT_GEOM_MESH) return false;
+        const double* w = t->world_to_local + n * 16;
+        const double* l = t->local_to_world + n * 16;
+        const double* gp = t->geom_params + n * 4;
+        double h[3];
+        switch (t->geom_type[n]) {
+            case PVT_GEOM_BOX: h[0] = 0.5 * gp[0]; h[1] = 0.5 * gp[1]; h[2] = 0.5 * gp[2]; break;
+            case PVT_GEOM_SPHERE: h[0] = h[1] = h[2] = gp[0]; break;
+            default: h[0] = h[1] = gp[1]; h[2] = 0.5 * gp[0]; break;   // cylinder about z
+        }
+        for (int a = 0; a < 3; a++)
+            if (!(std::isfinite(h[a]) && h[a] > 0.0)) return false;
+        // rigid and consistent: world->local is a rotation plus a translation, local->world its inverse
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) {
+                double rr = 0.0, wl = 0.0;
+                for (int k = 0; k < 3; k++) { rr += w[r * 4 + k] * w[c * 4 + k]; wl += w[r * 4 + k] * l[k * 4 + c]; }
+                if (!(std::fabs(rr - (r == c ? 1.0 : 0.0)) < 1e-9) || !(std::fabs(wl - (r == c ? 1.0 : 0.0)) < 1e-9)) return false;
+            }
+        double back = 0.0;   // world->local of the node's own origin must be the zero vector
+        for (int r = 0; r < 3; r++) {
+            const double v = w[r * 4] * l[3] + w[r * 4 + 1] * l[7] + w[r * 4 + 2] * l[11] + w[r * 4 + 3];
+            back = std::fmax(back, std::fabs(v));
+        }
+        for (int a = 0; a < 3; a++) {
+            const double c = l[a * 4 + 3];
+            double hw = t->geom_type[n] == PVT_GEOM_SPHERE ? h[0]
+                                                           : std::fabs(l[a * 4]) * h[0] + std::fabs(l[a * 4 + 1]) * h[1] + std::fabs(l[a * 4 + 2]) * h[2];
+            hw *= 1.0 + 1e-9;
+            if (!std::isfinite(c) || !std::isfinite(hw)) return false;
+            blo[(size_t)n * 3 + a] = c - hw; bhi[(size_t)n * 3 + a] = c + hw;
+            extent = std::fmax(extent, std::fabs(c) + hw);
+        }
+        if (!(back <= 1e-9 * (1.0 + extent))) return false;
+    }
+    if (!(extent > 0.0) || !std::isfinite(extent)) return false;
+    const double m = 1e-6 * extent;
+    for (int n = 0; n < N; n++) {
+        if (n == root || t->geom_type[n] == PVT_GEOM_BOX) continue;
+        const double radius = t->geom_type[n] == PVT_GEOM_SPHERE ? t->geom_params[n * 4] : t->geom_params[n * 4 + 1];
+        if (!(radius >= 1e-5 * extent)) return false;
+        if (t->geom_type[n] == PVT_GEOM_CYLINDER) g->odd = true;
+    }
+    // (negative controls of tests/test_gpu_grid.py: file the boxes a centimetre too small / leave the walk as soon as
+    // any two crossings are known -- results must then differ from the referee's)
+    const double grow = dev_switch("PVT_GRID_DEV_SHRINK") ? -1.0 : 2.0 * m;
+    for (int a = 0; a < 3; a++) { g->lo[a] = INFINITY; g->hi[a] = -INFINITY; }
+    for (int n = 0; n < N; n++) {
+        if (n == root) continue;
+        for (int a = 0; a < 3; a++) {
+            blo[(size_t)n * 3 + a] -= grow; bhi[(size_t)n * 3 + a] += grow;
+            g->lo[a] = std::fmin(g->lo[a], blo[(size_t)n * 3 + a] - m);
+            g->hi[a] = std::fmax(g->hi[a], bhi[(size_t)n * 3 + a] + m);
+        }
+    }
+    // ---- resolution.  What a photon pays for is the nodes it tests and the cells it steps through, and both depend on
+    // how the cells fall on the nodes: on an array of 6 x 6 tiles a 6 x 6 grid (one tile per cell) traces 2.26e9
+    // photons/s, 8 x 8 and 15 x 15 grids 1.58e9, 11 x 11 1.93e9 (measured).  So the resolution is CHOSEN: starting from
+    // about one cubic cell per node, each axis in turn tries other counts, and a candidate is priced by walking a fixed
+    // set of sample rays through it -- the kernel's walk with the nodes' boxes standing in for the shapes: cells
+    // visited, nodes tested, exit once two crossings lie before the end of the cells visited.  A wave waits for its
+    // slowest lane, so the price is the mean over the dearest quarter of the rays.
+    const int W = N > 64 ? 2 : 1;
+    auto file_nodes = [&](const int (&dims)[3], double (&cell)[3], std::vector<unsigned long long>& masks) {
+        for (int a = 0; a < 3; a++) cell[a] = (g->hi[a] - g->lo[a]) / dims[a];
+        masks.assign((size_t)dims[0] * dims[1] * dims[2] * W, 0ull);
+        for (int n = 0; n < N; n++) {
+            if (n == root) continue;
+            int c0[3], c1[3];
+            for (int a = 0; a < 3; a++) {   // cells touched, one cell more on either side when a face lies within m of a cell wall
+                c0[a] = (int)std::floor((blo[(size_t)n * 3 + a] - m - g->lo[a]) / cell[a]);
+                c1[a] = (int)std::floor((bhi[(size_t)n * 3 + a] + m - g->lo[a]) / cell[a]);
+                c0[a] = c0[a] < 0 ? 0 : c0[a];
+                c1[a] = c1[a] > dims[a] - 1 ? dims[a] - 1 : c1[a];
+            }
+            for (int z = c0[2]; z <= c1[2]; z++)
+                for (int y = c0[1]; y <= c1[1]; y++)
+                    for (int x = c0[0]; x <= c1[0]; x++)
+                        masks[(((size_t)z * dims[1] + y) * dims[0] + x) * W + (n >> 6)] |= 1ull << (n & 63);
+        }
+    };
+    // sample rays (fixed pseudo-random sequence: the same scene always gets the same grid): from inside a node's box,
+    // from a face of one, from anywhere in the grid's box; directions isotropic
+    struct Ray { double o[3], d[3]; };
+    std::vector<Ray> rays;
+    {
+        unsigned long long st = 0x9E3779B97F4A7C15ull;
+        auto uni = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (double)(st >> 11) * (1.0 / 9007199254740992.0); };
+        std::vector<int> others;
+        for (int n = 0; n < N; n++) if (n != root) others.push_back(n);
+        for (int k = 0; k < 384; k++) {
+            Ray r;
+            const int n = others[(size_t)(uni() * others.size()) % others.size()];
+            for (int a = 0; a < 3; a++) {
+                const double lo = k % 4 == 3 ? g->lo[a] : blo[(size_t)n * 3 + a], hi = k % 4 == 3 ? g->hi[a] : bhi[(size_t)n * 3 + a];
+                r.o[a] = lo + uni() * (hi - lo);
+            }
+            if (k % 4 == 2) { const int a = (int)(uni() * 3) % 3; r.o[a] = uni() < 0.5 ? blo[(size_t)n * 3 + a] + grow : bhi[(size_t)n * 3 + a] - grow; }
+            double z = 2.0 * uni() - 1.0, ph = 6.283185307179586 * uni(), s = std::sqrt(1.0 - z * z);
+            r.d[0] = s * std::cos(ph); r.d[1] = s * std::sin(ph); r.d[2] = z;
+            rays.push_back(r);
+        }
+    }
+    auto price = [&](const int (&dims)[3]) -> double {
+        double cell[3];
+        std::vector<unsigned long long> masks;
+        file_nodes(dims, cell, masks);
+        std::vector<double> cost;
+        for (const Ray& r : rays) {
+            double t_in = 0.0, t_out = INFINITY;
+            bool walk = true;
+            for (int a = 0; a < 3; a++) {
+                if (std::fabs(r.d[a]) < 1e-20) { if (r.o[a] < g->lo[a] || r.o[a] > g->hi[a]) walk = false; continue; }
+                const double ta = (g->lo[a] - r.o[a]) / r.d[a], tb = (g->hi[a] - r.o[a]) / r.d[a];
+                t_in = std::fmax(t_in, std::fmin(ta, tb)); t_out = std::fmin(t_out, std::fmax(ta, tb));
+            }
+            if (!(t_in <= t_out)) walk = false;
+            int c[3] = {0, 0, 0};
+            double tm[3] = {INFINITY, INFINITY, INFINITY};
+            for (int a = 0; a < 3 && walk; a++) {
+                c[a] = (int)((r.o[a] + r.d[a] * t_in - g->lo[a]) / cell[a]);
+                c[a] = c[a] < 0 ? 0 : (c[a] > dims[a] - 1 ? dims[a] - 1 : c[a]);
+                if (std::fabs(r.d[a]) >= 1e-20) tm[a] = (g->lo[a] + (c[a] + (r.d[a] < 0 ? 0 : 1)) * cell[a] - r.o[a]) / r.d[a];
+            }
+            unsigned long long seen[2] = {0ull, 0ull};
+            int cells = 0, tests = 0, nh = 0;
+            double t1 = INFINITY, t2 = INFINITY;
+            while (walk) {
+                cells += 1;
+                const unsigned long long* mk = &masks[(((size_t)c[2] * dims[1] + c[1]) * dims[0] + c[0]) * W];
+                for (int w = 0; w < W; w++) {
+                    unsigned long long fresh = mk[w] & ~seen[w];
+                    seen[w] |= mk[w];
+                    while (fresh) {
+                        const int n = w * 64 + __builtin_ctzll(fresh);
+                        fresh &= fresh - 1;
+                        tests += 1;
+                        double te = -INFINITY, tx = INFINITY;   // the ray against the node's box
+                        bool miss = false;
+                        for (int a = 0; a < 3; a++) {
+                            const double lo = blo[(size_t)n * 3 + a], hi = bhi[(size_t)n * 3 + a];
+                            if (std::fabs(r.d[a]) < 1e-20) { if (r.o[a] < lo || r.o[a] > hi) miss = true; continue; }
+                            const double ta = (lo - r.o[a]) / r.d[a], tb = (hi - r.o[a]) / r.d[a];
+                            te = std::fmax(te, std::fmin(ta, tb)); tx = std::fmin(tx, std::fmax(ta, tb));
+                        }
+                        if (miss || tx < te || !(tx > 0.0)) continue;
+                        const double ts[2] = {te, tx};
+                        for (int q = te > 0.0 ? 0 : 1; q < 2; q++) {
+                            if (ts[q] < t1) { t2 = t1; t1 = ts[q]; } else if (ts[q] < t2) t2 = ts[q];
+                            nh += 1;
+                        }
+                    }
+                }
+                const double t_cell = std::fmin(tm[0], std::fmin(tm[1], tm[2]));
+                const int ax = (tm[0] <= tm[1] && tm[0] <= tm[2]) ? 0 : (tm[1] <= tm[2] ? 1 : 2);
+                const int nxt = c[ax] + (r.d[ax] < 0 ? -1 : 1);
+                if ((nh >= 2 && t2 + m < t_cell) || !(t_cell < INFINITY) || nxt < 0 || nxt >= dims[ax]) break;
+                c[ax] = nxt;
+                tm[ax] += cell[ax] / std::fabs(r.d[ax]);
+            }
+            // a trip of the kernel's walk moves a lane on by one cell AND tests one node
+            cost.push_back((double)(cells > tests ? cells : tests) + 0.25 * (cells + tests));
+        }
+        std::sort(cost.begin(), cost.end());
+        double sum = 0.0;
+        const size_t from = cost.size() - cost.size() / 4;
+        for (size_t i = from; i < cost.size(); i++) sum += cost[i];
+        return sum / (double)(cost.size() - from);
+    };
+    double ext[3], vol = 1.0;
+    for (int a = 0; a < 3; a++) { ext[a] = g->hi[a] - g->lo[a]; vol *= ext[a]; }
+    constexpr int kMaxCells = 512;   // 8 KB of masks in LDS at two words per cell
+    {   // start: about one cell per node, as cubic as the extent allows
+        double target = std::fmin((double)kMaxCells, std::fmax(8.0, 1.0 * (N - 1)));
+        // (developer sweep; never more cells than the mask table's share of LDS holds)
+        if (const char* env = getenv("PVT_GRID_CELLS")) target = std::fmin((double)kMaxCells, std::fmax(1.0, atof(env)));
+        double side = std::cbrt(vol / target);
+        for (int pass = 0; pass < 200; pass++) {
+            long long cells = 1;
+            for (int a = 0; a < 3; a++) {
+                g->n[a] = (int)std::fmin(64.0, std::fmax(1.0, std::floor(ext[a] / side + 0.5)));
+                cells *= g->n[a];
+            }
+            if ((double)cells <= target * 1.25 && cells <= kMaxCells) break;
+            side *= 1.05;
+        }
+    }
+    if (!getenv("PVT_GRID_CELLS") && !getenv("PVT_GRID_NO_TUNING")) {
+        double best = price(g->n);
+        for (int sweep = 0; sweep < 2; sweep++)
+            for (int a = 0; a < 3; a++) {
+                const int n0 = g->n[a];
+                int pick = n0;
+                for (int v = std::max(1, n0 / 2); v <= std::min(64, 2 * n0 + 1); v++) {
+                    if (v == n0) continue;
+                    int dims[3] = {g->n[0], g->n[1], g->n[2]};
+                    dims[a] = v;
+                    if ((long long)dims[0] * dims[1] * dims[2] > kMaxCells) break;
+                    const double p = price(dims);
+                    if (p < best * 0.98) { best = p; pick = v; }   // (a clear gain only: ties keep the coarser grid)
+                }
+                g->n[a] = pick;
+            }
+    }
+    g->words = W;
+    g->guard = dev_switch("PVT_GRID_DEV_GUARD") ? -1e30 : m;
+    file_nodes(g->n, g->cell, g->masks);
+    return true;
+}
+
+// Spectra: RN(1/spacing) when EVERY interval of the abscissae has the same bits and the ordinates keep the quotient
+// inside div_known's domain (no -0.0, no extreme magnitudes):
+double even_rcp(const double* xs, const double* ys, int n) {
+    if (n < 2) return NAN;
+    const double w = xs[1] - xs[0];
+    if (!(w > 1e-100 && w < 1e100)) return NAN;
+    for (int i = 1; i + 1 < n; i++) if (xs[i + 1] - xs[i] != w) return NAN;
+    for (int i = 0; i < n; i++) {
+        if (ys[i] == 0.0 && std::signbit(ys[i])) return NAN;
+        if (!(std::fabs(ys[i]) < 1e100)) return NAN;
+        if (i > 0 && ys[i] != ys[i - 1] && std::fabs(ys[i] - ys[i - 1]) < 1e-100) return NAN;
+    }
+    return 1.0 / w;
+}
+
+// The spacing itself when, additionally, xs[i] == xs[0] + i*w bit for bit AND the kernel's arithmetic
+// (i = int((x - xs[0]) * rcp), one repair step against the computed neighbours) provably lands on the
+// reference's bisection index for every x inside the table: the raw index is monotone in x, so it is enough
+// that every abscissa and its two neighbouring doubles come out right (checked here with the device's own
+// sequence of operations).  Such a table is stored as its first abscissa alone, without a guide table.
+double even_w(const double* xs, int n, double rcp) {
+    if (!(rcp == rcp) || n < 2 || n > (1 << 24)) return NAN;
+    const double w = xs[1] - xs[0];
+    auto grid = [&](int i) { volatile double prod = (double)i * w; volatile double at = xs[0] + prod; return (double)at; };
+    for (int i = 0; i < n; i++)
+        if (grid(i) != xs[i]) return NAN;   // two roundings, never contracted
+    auto lands = [&](double x, int want) {
+        volatile double diff = x - xs[0];
+        volatile double quot = diff * rcp;
+        int i = (int)quot;
+        i = i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
+        double xlo = grid(i);
+        if (x < xlo) { i -= 1; xlo = grid(i); }
+        double xhi = grid(i + 1);
+        if (!(x < xhi)) { i += 1; xlo = xhi; xhi = grid(i + 1); }
+        return i == want && xlo <= x && x < xhi;
+    };
+    for (int i = 0; i < n; i++) {   // x0 < x < xl is all the even path ever sees
+        const double below = std::nextafter(xs[i], -INFINITY), above = std::nextafter(xs[i], INFINITY);
+        if (i > 0 && !lands(below, i - 1)) return NAN;
+        if (i > 0 && i < n - 1 && !lands(xs[i], i)) return NAN;
+        if (i < n - 1 && !lands(above, i)) return NAN;
+    }
+    return w;
+}
+
+// guide[b] = largest i <= n-2 with xs[i] <= xs[0] + b*(xs[n-1]-xs[0])/(n-1), b = 0..n-1; returns the scale the kernel
+// maps x to b with (0: no guide)
+double build_guide(const double* xs, int n, int* guide) {
+    if (n < 2 || !(xs[n - 1] > xs[0])) return 0.0;
+    const int Kb = n - 1;
+    int i = 0;
+    for (int b = 0; b <= Kb; b++) {
+        const double edge = xs[0] + (double)b * ((xs[n - 1] - xs[0]) / (double)Kb);
+        while (i + 1 <= n - 2 && xs[i + 1] <= edge) i++;
+        guide[b] = i;
+    }
+    return (double)Kb / (xs[n - 1] - xs[0]);
+}
+
+// Everything the scene's device tables are made of, derived from PvtSceneTables alone: the fields of PvtScene of the same
+// names, the two blobs (gd, gi) and the BVHs of the meshes (the trees of every mesh node, their triangles, their roots).
+struct PackedScene {
+    Lay lay{};
+    std::vector<double> gd;
+    std::vector<int> gi;
+    int nd_small = 0, ni_small = 0, n_ctab = 0, lazy_root = 0;
+    double lazy_k = 0.0;
+    bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
+    int grid_dims[3] = {0, 0, 0};
+    std::vector<pvt::BvhNode> bvh_nodes;
+    std::vector<pvt::MeshTri> bvh_tris;
+    std::vector<int> bvh_roots;
+};
+
+// Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
+// else is read.
+int validate_tables(const PvtSceneTables* t) {
+    const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
+    if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
+    for (int n = 0; n < N; n++) {
+        const int g = t->geom_type[n];
+        if (g < PVT_GEOM_BOX || g > PVT_GEOM_MESH) return fail(PVT_ERR_INVALID, "unknown geometry type");
+        if (g != PVT_GEOM_MESH) continue;
+        if (!t->mesh_face_start || !t->mesh_face_count || !t->mesh_vertices || !t->mesh_faces || !t->mesh_normals)
+            return fail(PVT_ERR_INVALID, "mesh node without mesh tables");
+        const long long f0 = t->mesh_face_start[n], fc = t->mesh_face_count[n];
+        if (fc <= 0 || f0 < 0 || f0 + fc > t->n_mesh_faces) return fail(PVT_ERR_INVALID, "mesh face range out of bounds");
+        if (t->n_mesh_faces >= (1 << 27)) return fail(PVT_ERR_INVALID, "more than 2^27 mesh faces in one scene");
+        for (long long k = 3 * f0; k < 3 * (f0 + fc); k++)
+            if (t->mesh_faces[k] < 0 || t->mesh_faces[k] >= t->n_mesh_vertices)
+                return fail(PVT_ERR_INVALID, "mesh face indexes a missing vertex");
+    }
+    if (K > 0 && t->n_coat_tables != 0) {   // coating reflectivity tables (the fields appended to the v13 struct)
+        const int NT = t->n_coat_tables;
+        if (NT < 0 || !t->coat_table || !t->ctab_nw || !t->ctab_na || !t->ctab_wl_start || !t->ctab_angle_start ||
+            !t->ctab_value_start || !t->ctab_wavelength || !t->ctab_angle || !t->ctab_value)
+            return fail(PVT_ERR_INVALID, "coating tables: missing arrays");
+        long long total = 0;
+        for (int j = 0; j < NT; j++) {
+            const long long nw = t->ctab_nw[j], na = t->ctab_na[j];
+            const long long w0 = t->ctab_wl_start[j], a0 = t->ctab_angle_start[j], v0 = t->ctab_value_start[j];
+            if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > t->n_ctab_wavelength ||
+                a0 + na > t->n_ctab_angle || v0 + nw * na > t->n_ctab_value)
+                return fail(PVT_ERR_INVALID, "coating tables: axis or value range out of bounds");
+            for (long long i = 0; i < nw; i++)
+                if (!std::isfinite(t->ctab_wavelength[w0 + i]) || (i > 0 && !(t->ctab_wavelength[w0 + i] > t->ctab_wavelength[w0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "coating tables: wavelengths must be finite and strictly increasing");
+            for (long long i = 0; i < na; i++)
+                if (!(t->ctab_angle[a0 + i] >= 0.0 && t->ctab_angle[a0 + i] <= 90.0) || (i > 0 && !(t->ctab_angle[a0 + i] > t->ctab_angle[a0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "coating tables: angles must be strictly increasing, in [0, 90] degrees");
+            for (long long i = 0; i < nw * na; i++)
+                if (!(t->ctab_value[v0 + i] >= 0.0 && t->ctab_value[v0 + i] <= 1.0))
+                    return fail(PVT_ERR_INVALID, "coating tables: values must be in [0, 1]");
+            total += nw + na + nw * na;
+        }
+        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "coating tables: more than 2^27 doubles");
+        for (int k = 0; k < K; k++)
+            if (t->coat_table[k] < -1 || t->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "coating row names a missing table");
+    }
+    for (int n = 0; n < N; n++) {   // (the known-divisor division is proven for these)
+        const double v = t->refractive_index[n];
+        if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) return fail(PVT_ERR_INVALID, "refractive indices must be finite and positive");
+    }
+    // runs [start, start + count) into a table of `size` rows
+    auto bad_run = [](long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; };
+    for (int n = 0; n < N; n++) {
+        if (bad_run(t->comp_start[n], t->comp_count[n], C)) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
+        if (K > 0 && bad_run(t->coat_start[n], t->coat_count[n], K)) return fail(PVT_ERR_INVALID, "coating range of a node out of bounds");
+    }
+    for (int c = 0; c < C; c++) {
+        if (bad_run(t->comp_abs_start[c], t->comp_abs_n[c], t->n_abs))
+            return fail(PVT_ERR_INVALID, "absorption spectrum range of a component out of bounds");
+        if (bad_run(t->comp_ems_start[c], t->comp_ems_n[c], t->n_ems))
+            return fail(PVT_ERR_INVALID, "emission spectrum range of a component out of bounds");
+    }
+    for (int r = 0; r < R; r++) {
+        if (t->rec_node[r] < 0 || t->rec_node[r] >= N) return fail(PVT_ERR_INVALID, "recorder on a missing node");
+        if (t->rec_event[r] < 0 || t->rec_event[r] > PVT_REC_EXIT) return fail(PVT_ERR_INVALID, "recorder selector out of range");
+        if (bad_run(t->rec_hist_start[r], t->rec_hist_n[r], H)) return fail(PVT_ERR_INVALID, "histogram range of a recorder out of bounds");
+    }
+    for (int h = 0; h < H; h++) {   // bins hist_offset + [0, na) (1-D) or + [0, na * nb) (2-D) of the tally
+        const long long bins = (long long)std::max(t->hist_na[h], 0) * (t->hist_prop_b[h] >= 0 ? std::max(t->hist_nb[h], 0) : 1);
+        if (bins > 0 && bad_run(t->hist_offset[h], bins, t->total_bins)) return fail(PVT_ERR_INVALID, "histogram bins out of range of total_bins");
+    }
+    return PVT_OK;
+}
+
+// unrotated: the 3x3 blocks of both matrices of a node are the identity, bit for bit (+0.0 off the diagonal)
+bool unrotated(const PvtSceneTables* t, int n) {
+    const double one = 1.0, zero = 0.0;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const double* want = r == c ? &one : &zero;
+            if (std::memcmp(&t->world_to_local[n * 16 + r * 4 + c], want, 8) != 0) return false;
+            if (std::memcmp(&t->local_to_world[n * 16 + r * 4 + c], want, 8) != 0) return false;
+        }
+    return true;
+}
+
+// ---- classes: what many nodes have in common is stored once (see the enums next to struct Lay) ----
+struct Classes {
+    std::vector<int> rot_class, rot_first;   // rotation classes and the first node of each
+    std::vector<int> idx_class, idx_first;   // refractive-index classes and the first node of each
+    bool by_node = false;                    // Lay::by_node
+};
+
+Classes classify_nodes(const PvtSceneTables* t) {
+    const int N = t->n_nodes;
+    Classes k;
+    // rotation classes: nodes whose two 3x3 blocks have the same bits share a record (and, in the wave-uniform
+    // node loop, the local direction and its reciprocals)
+    k.rot_class.resize(N);
+    for (int n = 0; n < N; n++) {
+        int cls = -1;
+        for (size_t e = 0; e < k.rot_first.size() && cls < 0; e++) {
+            bool same = true;
+            for (int r = 0; r < 3 && same; r++)
+                for (int c = 0; c < 3 && same; c++)
+                    same = std::memcmp(&t->world_to_local[n * 16 + r * 4 + c], &t->world_to_local[k.rot_first[e] * 16 + r * 4 + c], 8) == 0 &&
+                           std::memcmp(&t->local_to_world[n * 16 + r * 4 + c], &t->local_to_world[k.rot_first[e] * 16 + r * 4 + c], 8) == 0;
+            if (same) cls = (int)e;
+        }
+        if (cls < 0) { cls = (int)k.rot_first.size(); k.rot_first.push_back(n); }
+        k.rot_class[n] = cls;
+    }
+    // refractive-index classes (bit-identical indices)
+    k.idx_class.resize(N);
+    for (int n = 0; n < N; n++) {
+        int cls = -1;
+        for (size_t e = 0; e < k.idx_first.size() && cls < 0; e++)
+            if (std::memcmp(&t->refractive_index[k.idx_first[e]], &t->refractive_index[n], 8) == 0) cls = (int)e;
+        if (cls < 0) { cls = (int)k.idx_first.size(); k.idx_first.push_back(n); }
+        k.idx_class[n] = cls;
+    }
+    // scenes of few nodes: classes, component records and candidate blocks numbered like the nodes / the reference's ids
+    // (Lay::by_node: the lanes index the tables without reading NI_NCLS / NI_CREC / NI_CAND first)
+    k.by_node = N <= 16;
+    if (k.by_node) {
+        k.idx_first.resize(N);
+        for (int n = 0; n < N; n++) k.idx_class[n] = k.idx_first[n] = n;
+    }
+    return k;
+}
+
+// ---- pooled spectra.  The reference keeps one set of tables per component of every node (compiler.py:160-215); a
+// scene of many nodes made of the same material repeats them.  Here a table that has the bits of an earlier one
+// (abscissae, ordinates, sampling mode) is that earlier one: the 121 tiles of an LSC array share ONE absorption and
+// ONE emission table.  Every table is searched by its abscissae (absorption x -> y, emission x -> cdf); an emission
+// table is also searched by its CDF (cdf -> x).
+struct SearchedTable {
+    const double *xs, *ys;
+    int n;
+    bool hist, emission;
+    double rcp, rcp_c, w;   // even_rcp of xs (and of the CDF as abscissae), even_w of xs: NaN where not proven
+    int x, y;               // xs / ys, counted from the start of the spectra (a compact table keeps xs[0] alone)
+    int gx, gc;             // guide tables of xs / of the CDF, counted from the start of the guides (-1: none)
+};
+
+struct Spectra {
+    std::vector<SearchedTable> tables;
+    std::vector<int> abs_of, ems_of;   // the table of component c's absorption / emission
+    int len = 0, guide_len = 0;        // doubles of the spectra, ints of their guide tables
+
+    int add(const double* xs, const double* ys, int n, bool hist, bool emission) {
+        for (size_t e = 0; e < tables.size(); e++) {
+            const SearchedTable& o = tables[e];
+            if (o.emission == emission && o.n == n && o.hist == hist && std::memcmp(o.xs, xs, (size_t)n * 8) == 0 &&
+                std::memcmp(o.ys, ys, (size_t)n * 8) == 0)
+                return (int)e;
+        }
+        SearchedTable s{xs, ys, n, hist, emission};
+        s.rcp = even_rcp(xs, ys, n);
+        s.rcp_c = emission ? even_rcp(ys, xs, n) : NAN;
+        s.w = hist ? NAN : even_w(xs, n, s.rcp);
+        const bool compact = s.w == s.w;   // (even_w: n >= 2)
+        s.x = len; len += compact ? 1 : n;
+        s.y = len; len += n;
+        s.gx = compact ? -1 : guide_len; guide_len += compact ? 0 : n;   // guide tables only for the arrays that are searched
+        s.gc = emission ? guide_len : -1; guide_len += emission ? n : 0;
+        tables.push_back(s);
+        return (int)tables.size() - 1;
+    }
+};
+
+Spectra pool_spectra(const PvtSceneTables* t) {
+    const int C = t->n_components;
+    Spectra sp;
+    sp.abs_of.resize(C);
+    sp.ems_of.resize(C);
+    for (int c = 0; c < C; c++) {
+        sp.abs_of[c] = sp.add(t->abs_x + t->comp_abs_start[c], t->abs_y + t->comp_abs_start[c], t->comp_abs_n[c],
+                              t->comp_abs_hist && t->comp_abs_hist[c], false);
+        sp.ems_of[c] = sp.add(t->ems_x + t->comp_ems_start[c], t->ems_cdf + t->comp_ems_start[c], t->comp_ems_n[c],
+                              t->comp_ems_hist && t->comp_ems_hist[c], true);
+    }
+    return sp;
+}
+
+// ---- component RECORDS: the components of a node are a run of records; a node whose run has the contents of an
+// earlier node's run shares it (NI_CREC).  Component IDS (events, `source`, recorder filters) stay the reference's.
+struct Records {
+    std::vector<int> node_crec, rec_comp;   // rec_comp[r] = the component id whose fields record r holds
+    std::vector<int> node_cand;             // recorder candidate block of a node (-1: nobody listens to it)
+    int n_cand = 0;
+};
+
+Records component_records(const PvtSceneTables* t, const Spectra& sp, bool by_node) {
+    const int N = t->n_nodes, C = t->n_components, R = t->n_recorders;
+    auto same_component = [&](int c, int e) {
+        return t->comp_type[c] == t->comp_type[e] && t->comp_phase_type[c] == t->comp_phase_type[e] &&
+               std::memcmp(&t->comp_qy[c], &t->comp_qy[e], 8) == 0 && std::memcmp(&t->comp_tau_rad[c], &t->comp_tau_rad[e], 8) == 0 &&
+               std::memcmp(&t->comp_tau_nr[c], &t->comp_tau_nr[e], 8) == 0 &&
+               std::memcmp(&t->comp_phase_param[c], &t->comp_phase_param[e], 8) == 0 &&
+               sp.abs_of[c] == sp.abs_of[e] && sp.ems_of[c] == sp.ems_of[e];
+    };
+    Records recs;
+    recs.node_crec.assign(N, 0);
+    recs.node_cand.assign(N, -1);
+    if (by_node) {   // one record per component id: NI_CREC == NI_CSTART, which the kernel relies on
+        for (int n = 0; n < N; n++) recs.node_crec[n] = t->comp_start[n];
+        for (int c = 0; c < C; c++) recs.rec_comp.push_back(c);
+        for (int n = 0; n < N; n++) recs.node_cand[n] = n;
+        recs.n_cand = N;
+        return recs;
+    }
+    for (int n = 0; n < N; n++) {
+        const int c0 = t->comp_start[n], cc = t->comp_count[n];
+        int found = -1;
+        for (int e = 0; e < n && found < 0; e++) {
+            if (t->comp_count[e] != cc) continue;
+            bool same = true;
+            for (int k = 0; k < cc && same; k++) same = same_component(c0 + k, t->comp_start[e] + k);
+            if (same) found = recs.node_crec[e];
+        }
+        if (found < 0) {
+            found = (int)recs.rec_comp.size();
+            for (int k = 0; k < cc; k++) recs.rec_comp.push_back(c0 + k);
+        }
+        recs.node_crec[n] = found;
+    }
+    // recorder candidate blocks: only for the nodes somebody listens to
+    for (int r = 0; r < R; r++)
+        if (recs.node_cand[t->rec_node[r]] < 0) recs.node_cand[t->rec_node[r]] = recs.n_cand++;
+    return recs;
+}
+
+// ---- layout: fixed-stride records, then the pooled spectra.  The small tables come first in the blob -- records, then
+// critical angles, rotation classes, index classes and the node grid -- and the spectra last: when a scene's spectra are
+// too large for LDS, a workgroup still stages everything before `spec_d` (KArgs::nd_lds; the guide tables are the tail
+// of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes.
+std::vector<int> lay_out(const PvtSceneTables* t, const Classes& k, const Spectra& sp, const Records& recs, const NodeGrid& grid,
+                         PackedScene* p) {
+    const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
+    const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size(), CR = (int)recs.rec_comp.size();
+    Lay& lay = p->lay;
+    lay.comp_d = N * ND;
+    lay.rec_d = lay.comp_d + CR * CD;
+    lay.hist_d = lay.rec_d + R * RD;
+    lay.coat_d = lay.hist_d + H * HD;
+    const int small_d = lay.coat_d + K * KD;
+    constexpr int kCritClasses = 16;
+    lay.n_cls = M;
+    lay.crit_d = M <= kCritClasses ? small_d : -1;
+    lay.ccrit_d = lay.crit_d >= 0 ? lay.crit_d + M * M : -1;
+    lay.rot_d = small_d + (lay.crit_d >= 0 ? 2 * M * M : 0);
+    lay.ncls_d = lay.rot_d + Q * RT;
+    lay.by_node = k.by_node ? 1 : 0;
+    lay.grid_d = p->grid ? lay.ncls_d + M * 2 : -1;
+    p->nd_small = lay.ncls_d + M * 2 + (p->grid ? 14 + (int)grid.masks.size() : 0);
+    // coating reflectivity tables (KI_T*): their axes and values follow the spectra, so they go wherever the spectra go
+    // (LDS with the whole blob, else global memory) and a scene without them lays out exactly as before
+    int spec_end = p->nd_small + sp.len;
+    std::vector<int> ctab_at(p->n_ctab);
+    for (int j = 0; j < p->n_ctab; j++) {
+        ctab_at[j] = spec_end;
+        spec_end += t->ctab_nw[j] + t->ctab_na[j] + t->ctab_nw[j] * t->ctab_na[j];
+    }
+    p->gd.assign((size_t)spec_end + 1, 0.0);
+    lay.comp_i = N * NI;
+    lay.rec_i = lay.comp_i + CR * CI;
+    lay.hist_i = lay.rec_i + R * RI;
+    lay.coat_i = lay.hist_i + H * HI;
+    lay.cand_i = lay.coat_i + K * KI;
+    lay.cand_list = lay.cand_i + recs.n_cand * 7 * 8;
+    p->ni_small = lay.cand_list + R;   // guide tables: one entry per table point, per searched array
+    p->gi.assign((size_t)p->ni_small + (size_t)sp.guide_len + 1, 0);
+    return ctab_at;
+}
+
+// Recorders grouped by the (node, selector) they listen to.  A facet recorder whose facet has a clearly dominant
+// component, alone in its (axis, sign) bin, goes to the bin table; the rest (no facet, oblique facets, bin collisions)
+// to the walked list, ascending id.
+void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* p) {
+    const int N = t->n_nodes, R = t->n_recorders;
+    auto bin_of = [&](int r) -> int {
+        if (!t->rec_has_facet[r]) return -1;
+        const double* f = t->rec_facet + r * 3;
+        const double a[3] = {std::fabs(f[0]), std::fabs(f[1]), std::fabs(f[2])};
+        int k = (a[0] >= a[1] && a[0] >= a[2]) ? 0 : (a[1] >= a[2] ? 1 : 2);
+        const double other = std::fmax(a[(k + 1) % 3], a[(k + 2) % 3]);
+        // any normal within atol of the facet must have the same dominant axis and sign
+        if (!(a[k] - other > 4.0 * t->rec_atol[r] + 1e-9) || !(a[k] > 2.0 * t->rec_atol[r])) return -1;
+        return k * 2 + (f[k] > 0.0 ? 1 : 0);
+    };
+    auto unfiltered = [&](int r) { return !t->rec_source_mode || t->rec_source_mode[r] == 0; };
+    auto axis_facet = [&](int r, int b) {
+        const double* f = t->rec_facet + r * 3;
+        for (int a = 0; a < 3; a++)
+            if (f[a] != (a == b / 2 ? (b % 2 ? 1.0 : -1.0) : 0.0)) return false;
+        return t->rec_atol[r] >= 0.0;
+    };
+    int at = 0;
+    for (int node = 0; node < N; node++) {
+        if (recs.node_cand[node] < 0) continue;
+        // kRecPlain on an entry: the lane need not read the recorder's row at all -- no source filter, and either no
+        // facet, or a facet that IS the bin's axis (exactly +-1 on it, zeros elsewhere) on an unrotated box, whose
+        // world normals are exactly such unit vectors: |facet - normal| is exactly 0 for every normal of the bin
+        const bool exact_normals = t->geom_type[node] == PVT_GEOM_BOX && unrotated(t, node);
+        for (int sel = 0; sel < 7; sel++) {
+            int* rec = p->gi.data() + p->lay.cand_i + (recs.node_cand[node] * 7 + sel) * 8;
+            rec[0] = at;
+            int owner[6] = {-1, -1, -1, -1, -1, -1};
+            bool clash[6] = {false, false, false, false, false, false};
+            auto listens = [&](int r) { return t->rec_node[r] == node && t->rec_event[r] == sel; };
+            for (int r = 0; r < R; r++) {
+                const int b = listens(r) ? bin_of(r) : -1;
+                if (b >= 0) { if (owner[b] >= 0) clash[b] = true; else owner[b] = r; }
+            }
+            for (int b = 0; b < 6; b++) {
+                rec[2 + b] = (owner[b] >= 0 && !clash[b]) ? owner[b] : -1;
+                if (rec[2 + b] >= 0 && exact_normals && unfiltered(owner[b]) && axis_facet(owner[b], b)) rec[2 + b] |= kRecPlain;
+            }
+            for (int r = 0; r < R; r++) {
+                if (!listens(r)) continue;
+                const int b = bin_of(r);
+                if (b >= 0 && !clash[b]) continue;  // served by the bin table
+                p->gi[p->lay.cand_list + at++] = r | ((unfiltered(r) && !t->rec_has_facet[r]) ? kRecPlain : 0);
+            }
+            rec[1] = at - rec[0];
+        }
+    }
+}
+
+// ---- fill: every record, table and guide table of the two blobs, and the BVHs of the meshes
+int fill(const PvtSceneTables* t, const Classes& k, const Spectra& sp, const Records& recs, const NodeGrid& grid,
+         const std::vector<int>& ctab_at, PackedScene* p) {
+    const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
+    const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size();
+    const Lay& lay = p->lay;
+    std::vector<double>& gd = p->gd;
+    std::vector<int>& gi = p->gi;
+    if (p->grid) {
+        double* d = gd.data() + lay.grid_d;
+        for (int a = 0; a < 3; a++) { d[a] = grid.lo[a]; d[3 + a] = grid.hi[a]; d[6 + a] = grid.cell[a]; d[9 + a] = 1.0 / grid.cell[a]; }
+        d[12] = grid.guard;
+        const unsigned long long bits = (unsigned long long)grid.n[0] | ((unsigned long long)grid.n[1] << 8) | ((unsigned long long)grid.n[2] << 16) |
+                                        ((unsigned long long)grid.words << 24) | ((unsigned long long)(grid.odd ? 1 : 0) << 28);
+        std::memcpy(&d[13], &bits, 8);
+        std::memcpy(&d[14], grid.masks.data(), grid.masks.size() * 8);
+    }
+    if (lay.crit_d >= 0)
+        for (int c = 0; c < M; c++)
+            for (int a = 0; a < M; a++) {
+                const double n1 = t->refractive_index[k.idx_first[c]], n2 = t->refractive_index[k.idx_first[a]];
+                const double crit = n2 < n1 ? pvt_asin(n2 / n1) : INFINITY;   // same pvt_asin as the device
+                gd[lay.crit_d + c * M + a] = crit;
+                gd[lay.ccrit_d + c * M + a] = cosine_threshold(crit);
+            }
+    for (int q = 0; q < Q; q++) {
+        double* d = gd.data() + lay.rot_d + q * RT;
+        const int n = k.rot_first[q];
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) {
+                d[RT_W2L + r * 3 + c] = t->world_to_local[n * 16 + r * 4 + c];
+                d[RT_L2W + r * 3 + c] = t->local_to_world[n * 16 + r * 4 + c];
+            }
+    }
+    for (int m = 0; m < M; m++) {
+        gd[lay.ncls_d + m * 2] = t->refractive_index[k.idx_first[m]];
+        gd[lay.ncls_d + m * 2 + 1] = 1.0 / t->refractive_index[k.idx_first[m]];
+    }
+    fill_candidates(t, recs, p);
+    for (int n = 0; n < N; n++) {
+        double* d = gd.data() + n * ND;
+        for (int r = 0; r < 3; r++) d[ND_T + r] = t->world_to_local[n * 16 + r * 4 + 3];
+        for (int c = 0; c < 3; c++) d[ND_PARAMS + c] = t->geom_params[n * 4 + c];
+        const unsigned long long bits = (unsigned long long)(unsigned int)((unrotated(t, n) ? 1 : 0) | (t->geom_type[n] << 8)) |
+                                        ((unsigned long long)(unsigned int)k.rot_class[n] << 32);
+        std::memcpy(&d[ND_BITS], &bits, 8);
+        d[ND_N] = t->refractive_index[n];
+        int* q = gi.data() + n * NI;
+        q[NI_SURF] = t->surface_type[n];
+        q[NI_CSTART] = t->comp_start[n];
+        q[NI_CCOUNT] = t->comp_count[n];
+        q[NI_CREC] = recs.node_crec[n];
+        q[NI_KSTART] = K > 0 ? t->coat_start[n] : 0;
+        q[NI_KCOUNT] = K > 0 ? t->coat_count[n] : 0;
+        q[NI_MESH] = -1;
+        q[NI_CAND] = recs.node_cand[n];
+        q[NI_NCLS] = k.idx_class[n];
+        if (t->geom_type[n] == PVT_GEOM_MESH) {
+            double centre[3];
+            q[NI_MESH] = pvt::BvhBuilder(t->mesh_vertices, t->mesh_faces, t->mesh_normals, p->bvh_nodes, p->bvh_tris)
+                             .add_mesh(t->mesh_face_start[n], t->mesh_face_count[n], centre);
+            p->bvh_roots.push_back(q[NI_MESH]);
+            for (int c = 0; c < 3; c++) d[ND_PARAMS + c] = centre[c];   // a mesh has no shape parameters: the point its boxes are relative to
+        }
+    }
+    if (p->bvh_nodes.size() >= ((size_t)1 << 26) || p->bvh_tris.size() >= ((size_t)1 << 26))
+        return fail(PVT_ERR_INVALID, "meshes too large: the walk's cursors and leaf references hold 2^26 records / triangles");
+    // the spectra, once per distinct table (a compact table keeps its first abscissa only), and their guide tables
+    const int spec_d = p->nd_small, guide0 = p->ni_small;
+    std::vector<double> scale_x(sp.tables.size()), scale_c(sp.tables.size());
+    for (size_t e = 0; e < sp.tables.size(); e++) {
+        const SearchedTable& s = sp.tables[e];
+        scale_x[e] = s.gx >= 0 ? build_guide(s.xs, s.n, &gi[guide0 + s.gx]) : 0.0;
+        scale_c[e] = s.gc >= 0 ? build_guide(s.ys, s.n, &gi[guide0 + s.gc]) : 0.0;
+        std::copy(s.xs, s.xs + (s.gx >= 0 ? s.n : 1), &gd[spec_d + s.x]);
+        std::copy(s.ys, s.ys + s.n, &gd[spec_d + s.y]);
+    }
+    for (size_t r = 0; r < recs.rec_comp.size(); r++) {
+        const int c = recs.rec_comp[r];
+        const SearchedTable &ab = sp.tables[sp.abs_of[c]], &em = sp.tables[sp.ems_of[c]];
+        double* d = gd.data() + lay.comp_d + r * CD;
+        d[CD_QY] = t->comp_qy[c]; d[CD_TAU_RAD] = t->comp_tau_rad[c]; d[CD_TAU_NR] = t->comp_tau_nr[c];
+        d[CD_PHASE] = t->comp_phase_param[c];
+        int* q = gi.data() + lay.comp_i + r * CI;
+        q[CI_TYPE] = t->comp_type[c];
+        q[CI_PHASE] = t->comp_phase_type[c];
+        if (t->comp_phase_type[c] == PVT_PHASE_LAMBERTIAN) {
+            // The Lambertian phase function, theta = asin(sqrt(p1)), IS the cone's theta = asin(sqrt(p1) sin(theta_max)) at
+            // theta_max = pi/2 -- same two draws in the same order -- provided sin(pi/2) is the double 1.0 in the
+            // kernel's arithmetic (x * 1.0 is exact); checked here with the very function the kernel calls.
+            const double half_pi = 1.5707963267948966;
+            if (pvt_sin(half_pi) != 1.0) return fail(PVT_ERR_INVALID, "pvt_sin(pi/2) != 1: the Lambertian phase function cannot be lowered to a cone");
+            d[CD_PHASE] = half_pi;
+            q[CI_PHASE] = PVT_PHASE_CONE;
+        }
+        // absolute offsets into the blobs; -1: no guide table, never dereferenced
+        q[CI_ABS_X] = spec_d + ab.x; q[CI_ABS_Y] = spec_d + ab.y; q[CI_ABS_N] = ab.n; q[CI_ABS_HIST] = ab.hist;
+        q[CI_EMS_X] = spec_d + em.x; q[CI_EMS_CDF] = spec_d + em.y; q[CI_EMS_N] = em.n; q[CI_EMS_HIST] = em.hist;
+        q[CI_ABS_G] = ab.gx < 0 ? -1 : guide0 + ab.gx; q[CI_EMS_GX] = em.gx < 0 ? -1 : guide0 + em.gx; q[CI_EMS_GC] = guide0 + em.gc;
+        d[CD_ABS_RCP] = ab.rcp; d[CD_ABS_W] = ab.w; d[CD_ABS_SCALE] = scale_x[sp.abs_of[c]];
+        d[CD_EMS_RCP_X] = em.rcp; d[CD_EMS_RCP_C] = em.rcp_c; d[CD_EMS_W] = em.w;
+        d[CD_EMS_SCALE_X] = scale_x[sp.ems_of[c]]; d[CD_EMS_SCALE_C] = scale_c[sp.ems_of[c]];
+    }
+    for (int r = 0; r < R; r++) {
+        double* d = gd.data() + lay.rec_d + r * RD;
+        for (int a = 0; a < 3; a++) d[RD_FACET + a] = t->rec_facet[r * 3 + a];
+        d[RD_ATOL] = t->rec_atol[r];
+        int* q = gi.data() + lay.rec_i + r * RI;
+        q[RI_NODE] = t->rec_node[r];
+        q[RI_EVENT] = t->rec_event[r];
+        q[RI_HAS_FACET] = t->rec_has_facet[r];
+        q[RI_HSTART] = t->rec_hist_start[r];
+        q[RI_HN] = t->rec_hist_n[r];
+        q[RI_SRC_MODE] = t->rec_source_mode ? t->rec_source_mode[r] : 0;
+        q[RI_SRC_ID] = t->rec_source_id ? t->rec_source_id[r] : -1;
+    }
+    auto rcp_or_nan = [](double width) {   // NaN: the kernel divides for real
+        return (std::isfinite(width) && std::fabs(width) > 1e-290 && std::fabs(width) < 1e290) ? 1.0 / width : NAN;
+    };
+    for (int h = 0; h < H; h++) {
+        double* d = gd.data() + lay.hist_d + h * HD;
+        d[HD_LO_A] = t->hist_lo_a[h]; d[HD_HI_A] = t->hist_hi_a[h];
+        d[HD_LO_B] = t->hist_lo_b[h]; d[HD_HI_B] = t->hist_hi_b[h];
+        d[HD_RA] = rcp_or_nan(t->hist_hi_a[h] - t->hist_lo_a[h]);
+        d[HD_RB] = rcp_or_nan(t->hist_hi_b[h] - t->hist_lo_b[h]);
+        int* q = gi.data() + lay.hist_i + h * HI;
+        q[HI_PA] = t->hist_prop_a[h]; q[HI_PB] = t->hist_prop_b[h];
+        q[HI_NA] = t->hist_na[h]; q[HI_NB] = t->hist_nb[h]; q[HI_OFF] = t->hist_offset[h];
+        if (t->hist_prop_a[h] >= 4 || t->hist_prop_b[h] >= 4) p->hist_reads_position = true;
+    }
+    for (int c = 0; c < K; c++) {
+        double* d = gd.data() + lay.coat_d + c * KD;
+        for (int a = 0; a < 3; a++) {
+            d[KD_FACET + a] = t->coat_facet[c * 3 + a];
+            d[KD_LO + a] = t->coat_lo[c * 3 + a];
+            d[KD_HI + a] = t->coat_hi[c * 3 + a];
+        }
+        d[KD_REFL] = t->coat_reflectivity[c];
+        int* q = gi.data() + lay.coat_i + c * KI;
+        q[KI_RMODE] = t->coat_reflect_mode[c];
+        q[KI_TMODE] = t->coat_transmit_mode[c];
+        const int j = p->n_ctab > 0 ? t->coat_table[c] : -1;
+        q[KI_TNW] = j >= 0 ? t->ctab_nw[j] : 0;   // 0: no table
+        q[KI_TNA] = j >= 0 ? t->ctab_na[j] : 0;
+        q[KI_TW] = j >= 0 ? ctab_at[j] : 0;
+        q[KI_TA] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] : 0;
+        q[KI_TV] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] + t->ctab_na[j] : 0;
+    }
+    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
+    for (int j = 0; j < p->n_ctab; j++) {   // wavelengths (nm), angles (radians: the kernel compares pvt_acos of the cosine), values
+        const int nw = t->ctab_nw[j], na = t->ctab_na[j];
+        double* d = gd.data() + ctab_at[j];
+        for (int i = 0; i < nw; i++) d[i] = t->ctab_wavelength[t->ctab_wl_start[j] + i];
+        for (int i = 0; i < na; i++) d[nw + i] = t->ctab_angle[t->ctab_angle_start[j] + i] * kRadPerDeg;
+        for (int i = 0; i < na * nw; i++) d[nw + na + i] = t->ctab_value[t->ctab_value_start[j] + i];
+    }
+    return PVT_OK;
+}
+
+void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
+    const int N = t->n_nodes, R = t->n_recorders, root = t->root_id;
+    for (int r = 0; r < R; r++)
+        if (t->rec_node[r] == root && t->rec_event[r] == PVT_REC_EXIT) p->exit_observed = true;
+    // Lazy root (kernel node loop): the root is a box or a sphere and every other node lies strictly inside it,
+    // its bounding sphere clearing the root's surface by a margin -- then a ray from inside the root meets every
+    // other node's surface strictly before the root's.
+    if (!getenv("PVT_NO_LAZY_ROOT") && (t->geom_type[root] == PVT_GEOM_BOX || t->geom_type[root] == PVT_GEOM_SPHERE)) {
+        const double* w2l = t->world_to_local + root * 16;
+        const double* rp = t->geom_params + root * 4;
+        const bool box = t->geom_type[root] == PVT_GEOM_BOX;
+        const double scale = box ? std::fmax(rp[0], std::fmax(rp[1], rp[2])) : rp[0];
+        const double margin = 1e-6 * scale + 1e-9;
+        bool inside = std::isfinite(scale) && scale > 0.0;
+        for (int n = 0; n < N && inside; n++) {
+            if (n == root) continue;
+            const double* l2w = t->local_to_world + n * 16;
+            const double* gp = t->geom_params + n * 4;
+            double radius;   // of a sphere about the node's origin that holds the whole shape
+            switch (t->geom_type[n]) {
+                case PVT_GEOM_BOX: radius = 0.5 * std::sqrt(gp[0] * gp[0] + gp[1] * gp[1] + gp[2] * gp[2]); break;
+                case PVT_GEOM_SPHERE: radius = gp[0]; break;
+                case PVT_GEOM_CYLINDER: radius = std::sqrt(gp[1] * gp[1] + 0.25 * gp[0] * gp[0]); break;
+                default: radius = INFINITY; break;   // (mesh scenes never take this path)
+            }
+            radius *= 1.0 + 1e-12;
+            double c[3];   // the node's origin in the root's frame
+            for (int a = 0; a < 3; a++)
+                c[a] = w2l[a * 4] * l2w[3] + w2l[a * 4 + 1] * l2w[7] + w2l[a * 4 + 2] * l2w[11] + w2l[a * 4 + 3];
+            if (box) {
+                for (int a = 0; a < 3; a++)
+                    if (!(0.5 * rp[a] - std::fabs(c[a]) - radius > margin)) inside = false;
+            } else {
+                if (!(rp[0] - std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) - radius > margin)) inside = false;
+            }
+        }
+        if (inside) {
+            p->lazy_root = box ? 1 : 2;
+            p->lazy_k = box ? 0.0 : 1.0 / (2.0 * rp[0]);
+        }
+    }
+    // Fused exit (kernel surface branch): the scene is ONE unrotated box inside a lazy root whose medium neither
+    // absorbs nor is listened to -- a photon that leaves the box's surface outwards can only leave the scene.
+    if (p->lazy_root && N == 2 && !getenv("PVT_NO_FUSED_EXIT")) {
+        const int child = 1 - root;
+        bool ok = t->geom_type[child] == PVT_GEOM_BOX && unrotated(t, child) && t->comp_count[root] == 0;
+        for (int r = 0; r < R; r++)
+            if (t->rec_node[r] == root) ok = false;
+        p->fuse_exit = ok;
+    }
+}
+
+// The tables (n_nodes and n_recorders already checked by the caller) -> *p.  No HIP call.
+int pack_scene(const PvtSceneTables* t, PackedScene* p) {
+    int rc = validate_tables(t);
+    if (rc != PVT_OK) return rc;
+    const Classes classes = classify_nodes(t);
+    Spectra spectra = pool_spectra(t);
+    const Records records = component_records(t, spectra, classes.by_node);
+    NodeGrid grid;
+    p->grid = plan_node_grid(t, &grid);
+    for (int a = 0; a < 3; a++) p->grid_dims[a] = p->grid ? grid.n[a] : 0;
+    p->n_ctab = t->n_coatings > 0 ? t->n_coat_tables : 0;
+    const std::vector<int> ctab_at = lay_out(t, classes, spectra, records, grid, p);
+    rc = fill(t, classes, spectra, records, grid, ctab_at, p);
+    if (rc != PVT_OK) return rc;
+    prove_shortcuts(t, p);
+    return PVT_OK;
+}
+
+}  // namespace

@@ -88,6 +88,8 @@ int push(std::vector<T>& blob, const T* src, size_t n) {
 
 }  // namespace
 
+#include "pvt_scene_pack.h"
+
 struct PvtScene {
     int device = 0;
     Lay lay{};
@@ -139,16 +141,11 @@ struct PvtScene {
     bool exit_observed = false;     // a recorder listens to (root, exit)
     bool grid = false;              // the scene has a node grid (many nodes; see plan_node_grid)
     int grid_dims[3] = {0, 0, 0};
-    bool fuse_exit = false;         // see scene_create: photons leaving the only child's surface outwards are done
+    bool fuse_exit = false;         // see prove_shortcuts: photons leaving the only child's surface outwards are done
     bool hist_reads_position = false;   // a histogram axis is x, y or z
     bool consolidate = true;        // developer switches (environment), read once at scene creation
     double dev_blocks_per_cu = 0.0;
 };
-
-namespace {
-struct LdsPlan { size_t bytes; bool tab_lds, small_lds; int bins_in_lds, xslots, tq_pos; bool ok; };
-LdsPlan plan_lds(const PvtScene* s, bool record);   // (defined with the launch code)
-}  // namespace
 
 extern "C" {
 
@@ -159,963 +156,6 @@ int pvt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
-}
-
-// The surface branch asks "is the incidence angle beyond the critical angle?", which the reference evaluates as
-// acos(c) > crit (c = the clamped cosine in [0, 1]).  pvt_acos falls as c grows, so there is a threshold c* with
-// pvt_acos(c) > crit  <=>  c < c*: found here by bisection over the doubles of [0, 1] with the very pvt_acos the
-// device runs, then CHECKED -- pvt_acos is accurate to under an ulp but need not be monotone to the last bit, so
-// the 1024 doubles either side of the boundary are all evaluated; farther away the angle differs from crit by
-// hundreds of ulps (|d acos / dc| >= 1) and the sign of the comparison cannot depend on the rounding.  NaN = no
-// threshold could be proven (the kernel then evaluates the reference's expression); -inf = never total reflection.
-static double cosine_threshold(double crit) {
-    if (!(crit < INFINITY)) return -INFINITY;
-    auto beyond = [&](double c) { return pvt_acos(c) > crit; };
-    if (!beyond(0.0)) return -INFINITY;     // (not reachable for crit = asin(x) < pi/2; kept for safety)
-    if (beyond(1.0)) return NAN;
-    auto bits = [](double v) { uint64_t u; std::memcpy(&u, &v, 8); return u; };
-    auto from = [](uint64_t u) { double v; std::memcpy(&v, &u, 8); return v; };
-    uint64_t lo = bits(0.0), hi = bits(1.0);   // beyond(lo), !beyond(hi); non-negative doubles order like their bits
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (beyond(from(mid))) lo = mid; else hi = mid;
-    }
-    for (uint64_t k = 1; k <= 1024; k++) {
-        if (lo >= k && !beyond(from(lo - k))) return NAN;
-        if (hi + k <= bits(1.0) && beyond(from(hi + k))) return NAN;
-    }
-    return from(hi);   // the smallest cosine that is NOT beyond the critical angle
-}
-
-// The node grid of scenes with many nodes (kernel: GRID variants, the walk in the node loop).  Every node but the root
-// is filed under the cells that its world-space bounding box, grown by 2m, touches; m = 1e-6 of the scene's extent, many
-// orders of magnitude above the rounding of any distance the intersection arithmetic forms (1e-16 of it per
-// operation).  What the kernel's early exit relies on, with that margin:
-//   * a crossing the reference's arithmetic reports for a node lies inside that node's box grown by m, so some cell the
-//     walk has visited by then (the walk's own rounding: 1e-13 of the extent) holds the node;
-//   * a node filed under none of the cells visited so far stands clear of the photon by more than m, so a box or a
-//     sphere (radius >= 1e-5 of the extent, checked here) is crossed twice or not at all -- never once.
-// Returns false (no grid: the plain node loop serves the scene) for scenes it cannot vouch for: few nodes, meshes,
-// non-rigid or inconsistent poses, degenerate shapes.
-// Negative controls of the grid tests (tests/test_gpu_grid.py, tests/test_node_grid.py) are environment switches read
-// when a scene is created, and they produce WRONG physics on purpose: whoever has one set gets told, loudly, every time.
-bool dev_switch(const char* name) {
-    if (!getenv(name)) return false;
-    fprintf(stderr, "[pvtrace_hip] WARNING: %s is set -- the node grid of this scene is built WRONG on purpose (a test's negative "
-                    "control); unset it for real work\n", name);
-    return true;
-}
-
-struct NodeGrid {
-    int n[3] = {1, 1, 1};
-    double lo[3], hi[3], cell[3], guard = 0.0;
-    int words = 1;
-    bool odd = false;
-    std::vector<unsigned long long> masks;
-};
-static bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
-    const int N = t->n_nodes, root = t->root_id;
-    int min_nodes = 8;
-    if (const char* env = getenv("PVT_GRID_MIN_NODES")) min_nodes = atoi(env);
-    if (getenv("PVT_NO_GRID") || N < min_nodes || N < 3) return false;
-    std::vector<double> blo((size_t)N * 3), bhi((size_t)N * 3);
-    double extent = 0.0;
-    for (int n = 0; n < N; n++) {
-        if (t->geom_type[n] == PVT_GEOM_MESH) return false;
-        const double* w = t->world_to_local + n * 16;
-        const double* l = t->local_to_world + n * 16;
-        const double* gp = t->geom_params + n * 4;
-        double h[3];
-        switch (t->geom_type[n]) {
-            case PVT_GEOM_BOX: h[0] = 0.5 * gp[0]; h[1] = 0.5 * gp[1]; h[2] = 0.5 * gp[2]; break;
-            case PVT_GEOM_SPHERE: h[0] = h[1] = h[2] = gp[0]; break;
-            default: h[0] = h[1] = gp[1]; h[2] = 0.5 * gp[0]; break;   // cylinder about z
-        }
-        for (int a = 0; a < 3; a++)
-            if (!(std::isfinite(h[a]) && h[a] > 0.0)) return false;
-        // rigid and consistent: world->local is a rotation plus a translation, local->world its inverse
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) {
-                double rr = 0.0, wl = 0.0;
-                for (int k = 0; k < 3; k++) { rr += w[r * 4 + k] * w[c * 4 + k]; wl += w[r * 4 + k] * l[k * 4 + c]; }
-                if (!(std::fabs(rr - (r == c ? 1.0 : 0.0)) < 1e-9) || !(std::fabs(wl - (r == c ? 1.0 : 0.0)) < 1e-9)) return false;
-            }
-        double back = 0.0;   // world->local of the node's own origin must be the zero vector
-        for (int r = 0; r < 3; r++) {
-            const double v = w[r * 4] * l[3] + w[r * 4 + 1] * l[7] + w[r * 4 + 2] * l[11] + w[r * 4 + 3];
-            back = std::fmax(back, std::fabs(v));
-        }
-        for (int a = 0; a < 3; a++) {
-            const double c = l[a * 4 + 3];
-            double hw = t->geom_type[n] == PVT_GEOM_SPHERE ? h[0]
-                                                           : std::fabs(l[a * 4]) * h[0] + std::fabs(l[a * 4 + 1]) * h[1] + std::fabs(l[a * 4 + 2]) * h[2];
-            hw *= 1.0 + 1e-9;
-            if (!std::isfinite(c) || !std::isfinite(hw)) return false;
-            blo[(size_t)n * 3 + a] = c - hw; bhi[(size_t)n * 3 + a] = c + hw;
-            extent = std::fmax(extent, std::fabs(c) + hw);
-        }
-        if (!(back <= 1e-9 * (1.0 + extent))) return false;
-    }
-    if (!(extent > 0.0) || !std::isfinite(extent)) return false;
-    const double m = 1e-6 * extent;
-    for (int n = 0; n < N; n++) {
-        if (n == root || t->geom_type[n] == PVT_GEOM_BOX) continue;
-        const double radius = t->geom_type[n] == PVT_GEOM_SPHERE ? t->geom_params[n * 4] : t->geom_params[n * 4 + 1];
-        if (!(radius >= 1e-5 * extent)) return false;
-        if (t->geom_type[n] == PVT_GEOM_CYLINDER) g->odd = true;
-    }
-    // (negative controls of tests/test_gpu_grid.py: file the boxes a centimetre too small / leave the walk as soon as
-    // any two crossings are known -- results must then differ from the referee's)
-    const double grow = dev_switch("PVT_GRID_DEV_SHRINK") ? -1.0 : 2.0 * m;
-    for (int a = 0; a < 3; a++) { g->lo[a] = INFINITY; g->hi[a] = -INFINITY; }
-    for (int n = 0; n < N; n++) {
-        if (n == root) continue;
-        for (int a = 0; a < 3; a++) {
-            blo[(size_t)n * 3 + a] -= grow; bhi[(size_t)n * 3 + a] += grow;
-            g->lo[a] = std::fmin(g->lo[a], blo[(size_t)n * 3 + a] - m);
-            g->hi[a] = std::fmax(g->hi[a], bhi[(size_t)n * 3 + a] + m);
-        }
-    }
-    // ---- resolution.  What a photon pays for is the nodes it tests and the cells it steps through, and both depend on
-    // how the cells fall on the nodes: on an array of 6 x 6 tiles a 6 x 6 grid (one tile per cell) traces 2.26e9
-    // photons/s, 8 x 8 and 15 x 15 grids 1.58e9, 11 x 11 1.93e9 (measured).  So the resolution is CHOSEN: starting from
-    // about one cubic cell per node, each axis in turn tries other counts, and a candidate is priced by walking a fixed
-    // set of sample rays through it -- the kernel's walk with the nodes' boxes standing in for the shapes: cells
-    // visited, nodes tested, exit once two crossings lie before the end of the cells visited.  A wave waits for its
-    // slowest lane, so the price is the mean over the dearest quarter of the rays.
-    const int W = N > 64 ? 2 : 1;
-    auto file_nodes = [&](const int (&dims)[3], double (&cell)[3], std::vector<unsigned long long>& masks) {
-        for (int a = 0; a < 3; a++) cell[a] = (g->hi[a] - g->lo[a]) / dims[a];
-        masks.assign((size_t)dims[0] * dims[1] * dims[2] * W, 0ull);
-        for (int n = 0; n < N; n++) {
-            if (n == root) continue;
-            int c0[3], c1[3];
-            for (int a = 0; a < 3; a++) {   // cells touched, one cell more on either side when a face lies within m of a cell wall
-                c0[a] = (int)std::floor((blo[(size_t)n * 3 + a] - m - g->lo[a]) / cell[a]);
-                c1[a] = (int)std::floor((bhi[(size_t)n * 3 + a] + m - g->lo[a]) / cell[a]);
-                c0[a] = c0[a] < 0 ? 0 : c0[a];
-                c1[a] = c1[a] > dims[a] - 1 ? dims[a] - 1 : c1[a];
-            }
-            for (int z = c0[2]; z <= c1[2]; z++)
-                for (int y = c0[1]; y <= c1[1]; y++)
-                    for (int x = c0[0]; x <= c1[0]; x++)
-                        masks[(((size_t)z * dims[1] + y) * dims[0] + x) * W + (n >> 6)] |= 1ull << (n & 63);
-        }
-    };
-    // sample rays (fixed pseudo-random sequence: the same scene always gets the same grid): from inside a node's box,
-    // from a face of one, from anywhere in the grid's box; directions isotropic
-    struct Ray { double o[3], d[3]; };
-    std::vector<Ray> rays;
-    {
-        unsigned long long st = 0x9E3779B97F4A7C15ull;
-        auto uni = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (double)(st >> 11) * (1.0 / 9007199254740992.0); };
-        std::vector<int> others;
-        for (int n = 0; n < N; n++) if (n != root) others.push_back(n);
-        for (int k = 0; k < 384; k++) {
-            Ray r;
-            const int n = others[(size_t)(uni() * others.size()) % others.size()];
-            for (int a = 0; a < 3; a++) {
-                const double lo = k % 4 == 3 ? g->lo[a] : blo[(size_t)n * 3 + a], hi = k % 4 == 3 ? g->hi[a] : bhi[(size_t)n * 3 + a];
-                r.o[a] = lo + uni() * (hi - lo);
-            }
-            if (k % 4 == 2) { const int a = (int)(uni() * 3) % 3; r.o[a] = uni() < 0.5 ? blo[(size_t)n * 3 + a] + grow : bhi[(size_t)n * 3 + a] - grow; }
-            double z = 2.0 * uni() - 1.0, ph = 6.283185307179586 * uni(), s = std::sqrt(1.0 - z * z);
-            r.d[0] = s * std::cos(ph); r.d[1] = s * std::sin(ph); r.d[2] = z;
-            rays.push_back(r);
-        }
-    }
-    auto price = [&](const int (&dims)[3]) -> double {
-        double cell[3];
-        std::vector<unsigned long long> masks;
-        file_nodes(dims, cell, masks);
-        std::vector<double> cost;
-        for (const Ray& r : rays) {
-            double t_in = 0.0, t_out = INFINITY;
-            bool walk = true;
-            for (int a = 0; a < 3; a++) {
-                if (std::fabs(r.d[a]) < 1e-20) { if (r.o[a] < g->lo[a] || r.o[a] > g->hi[a]) walk = false; continue; }
-                const double ta = (g->lo[a] - r.o[a]) / r.d[a], tb = (g->hi[a] - r.o[a]) / r.d[a];
-                t_in = std::fmax(t_in, std::fmin(ta, tb)); t_out = std::fmin(t_out, std::fmax(ta, tb));
-            }
-            if (!(t_in <= t_out)) walk = false;
-            int c[3] = {0, 0, 0};
-            double tm[3] = {INFINITY, INFINITY, INFINITY};
-            for (int a = 0; a < 3 && walk; a++) {
-                c[a] = (int)((r.o[a] + r.d[a] * t_in - g->lo[a]) / cell[a]);
-                c[a] = c[a] < 0 ? 0 : (c[a] > dims[a] - 1 ? dims[a] - 1 : c[a]);
-                if (std::fabs(r.d[a]) >= 1e-20) tm[a] = (g->lo[a] + (c[a] + (r.d[a] < 0 ? 0 : 1)) * cell[a] - r.o[a]) / r.d[a];
-            }
-            unsigned long long seen[2] = {0ull, 0ull};
-            int cells = 0, tests = 0, nh = 0;
-            double t1 = INFINITY, t2 = INFINITY;
-            while (walk) {
-                cells += 1;
-                const unsigned long long* mk = &masks[(((size_t)c[2] * dims[1] + c[1]) * dims[0] + c[0]) * W];
-                for (int w = 0; w < W; w++) {
-                    unsigned long long fresh = mk[w] & ~seen[w];
-                    seen[w] |= mk[w];
-                    while (fresh) {
-                        const int n = w * 64 + __builtin_ctzll(fresh);
-                        fresh &= fresh - 1;
-                        tests += 1;
-                        double te = -INFINITY, tx = INFINITY;   // the ray against the node's box
-                        bool miss = false;
-                        for (int a = 0; a < 3; a++) {
-                            const double lo = blo[(size_t)n * 3 + a], hi = bhi[(size_t)n * 3 + a];
-                            if (std::fabs(r.d[a]) < 1e-20) { if (r.o[a] < lo || r.o[a] > hi) miss = true; continue; }
-                            const double ta = (lo - r.o[a]) / r.d[a], tb = (hi - r.o[a]) / r.d[a];
-                            te = std::fmax(te, std::fmin(ta, tb)); tx = std::fmin(tx, std::fmax(ta, tb));
-                        }
-                        if (miss || tx < te || !(tx > 0.0)) continue;
-                        const double ts[2] = {te, tx};
-                        for (int q = te > 0.0 ? 0 : 1; q < 2; q++) {
-                            if (ts[q] < t1) { t2 = t1; t1 = ts[q]; } else if (ts[q] < t2) t2 = ts[q];
-                            nh += 1;
-                        }
-                    }
-                }
-                const double t_cell = std::fmin(tm[0], std::fmin(tm[1], tm[2]));
-                const int ax = (tm[0] <= tm[1] && tm[0] <= tm[2]) ? 0 : (tm[1] <= tm[2] ? 1 : 2);
-                const int nxt = c[ax] + (r.d[ax] < 0 ? -1 : 1);
-                if ((nh >= 2 && t2 + m < t_cell) || !(t_cell < INFINITY) || nxt < 0 || nxt >= dims[ax]) break;
-                c[ax] = nxt;
-                tm[ax] += cell[ax] / std::fabs(r.d[ax]);
-            }
-            // a trip of the kernel's walk moves a lane on by one cell AND tests one node
-            cost.push_back((double)(cells > tests ? cells : tests) + 0.25 * (cells + tests));
-        }
-        std::sort(cost.begin(), cost.end());
-        double sum = 0.0;
-        const size_t from = cost.size() - cost.size() / 4;
-        for (size_t i = from; i < cost.size(); i++) sum += cost[i];
-        return sum / (double)(cost.size() - from);
-    };
-    double ext[3], vol = 1.0;
-    for (int a = 0; a < 3; a++) { ext[a] = g->hi[a] - g->lo[a]; vol *= ext[a]; }
-    constexpr int kMaxCells = 512;   // 8 KB of masks in LDS at two words per cell
-    {   // start: about one cell per node, as cubic as the extent allows
-        double target = std::fmin((double)kMaxCells, std::fmax(8.0, 1.0 * (N - 1)));
-        // (developer sweep; never more cells than the mask table's share of LDS holds)
-        if (const char* env = getenv("PVT_GRID_CELLS")) target = std::fmin((double)kMaxCells, std::fmax(1.0, atof(env)));
-        double side = std::cbrt(vol / target);
-        for (int pass = 0; pass < 200; pass++) {
-            long long cells = 1;
-            for (int a = 0; a < 3; a++) {
-                g->n[a] = (int)std::fmin(64.0, std::fmax(1.0, std::floor(ext[a] / side + 0.5)));
-                cells *= g->n[a];
-            }
-            if ((double)cells <= target * 1.25 && cells <= kMaxCells) break;
-            side *= 1.05;
-        }
-    }
-    if (!getenv("PVT_GRID_CELLS") && !getenv("PVT_GRID_NO_TUNING")) {
-        double best = price(g->n);
-        for (int sweep = 0; sweep < 2; sweep++)
-            for (int a = 0; a < 3; a++) {
-                const int n0 = g->n[a];
-                int pick = n0;
-                for (int v = std::max(1, n0 / 2); v <= std::min(64, 2 * n0 + 1); v++) {
-                    if (v == n0) continue;
-                    int dims[3] = {g->n[0], g->n[1], g->n[2]};
-                    dims[a] = v;
-                    if ((long long)dims[0] * dims[1] * dims[2] > kMaxCells) break;
-                    const double p = price(dims);
-                    if (p < best * 0.98) { best = p; pick = v; }   // (a clear gain only: ties keep the coarser grid)
-                }
-                g->n[a] = pick;
-            }
-    }
-    g->words = W;
-    g->guard = dev_switch("PVT_GRID_DEV_GUARD") ? -1e30 : m;
-    file_nodes(g->n, g->cell, g->masks);
-    return true;
-}
-
-int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
-    if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
-    if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
-    if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
-    if (t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "more than 256 recorders");
-    if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
-    HIP_TRY(hipSetDevice(device));
-
-    const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
-    std::vector<pvt::BvhNode> bvh_nodes;
-    std::vector<pvt::MeshTri> bvh_tris;
-    std::vector<int> bvh_roots;
-    for (int n = 0; n < N; n++) {
-        const int g = t->geom_type[n];
-        if (g < PVT_GEOM_BOX || g > PVT_GEOM_MESH) return fail(PVT_ERR_INVALID, "unknown geometry type");
-        if (g != PVT_GEOM_MESH) continue;
-        if (!t->mesh_face_start || !t->mesh_face_count || !t->mesh_vertices || !t->mesh_faces || !t->mesh_normals)
-            return fail(PVT_ERR_INVALID, "mesh node without mesh tables");
-        const long long f0 = t->mesh_face_start[n], fc = t->mesh_face_count[n];
-        if (fc <= 0 || f0 < 0 || f0 + fc > t->n_mesh_faces) return fail(PVT_ERR_INVALID, "mesh face range out of bounds");
-        if (t->n_mesh_faces >= (1 << 27)) return fail(PVT_ERR_INVALID, "more than 2^27 mesh faces in one scene");
-        for (long long k = 3 * f0; k < 3 * (f0 + fc); k++)
-            if (t->mesh_faces[k] < 0 || t->mesh_faces[k] >= t->n_mesh_vertices)
-                return fail(PVT_ERR_INVALID, "mesh face indexes a missing vertex");
-    }
-    if (K > 0 && t->n_coat_tables != 0) {   // coating reflectivity tables (the fields appended to the v13 struct)
-        const int NT = t->n_coat_tables;
-        if (NT < 0 || !t->coat_table || !t->ctab_nw || !t->ctab_na || !t->ctab_wl_start || !t->ctab_angle_start ||
-            !t->ctab_value_start || !t->ctab_wavelength || !t->ctab_angle || !t->ctab_value)
-            return fail(PVT_ERR_INVALID, "coating tables: missing arrays");
-        long long total = 0;
-        for (int j = 0; j < NT; j++) {
-            const long long nw = t->ctab_nw[j], na = t->ctab_na[j];
-            const long long w0 = t->ctab_wl_start[j], a0 = t->ctab_angle_start[j], v0 = t->ctab_value_start[j];
-            if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > t->n_ctab_wavelength ||
-                a0 + na > t->n_ctab_angle || v0 + nw * na > t->n_ctab_value)
-                return fail(PVT_ERR_INVALID, "coating tables: axis or value range out of bounds");
-            for (long long i = 0; i < nw; i++)
-                if (!std::isfinite(t->ctab_wavelength[w0 + i]) || (i > 0 && !(t->ctab_wavelength[w0 + i] > t->ctab_wavelength[w0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "coating tables: wavelengths must be finite and strictly increasing");
-            for (long long i = 0; i < na; i++)
-                if (!(t->ctab_angle[a0 + i] >= 0.0 && t->ctab_angle[a0 + i] <= 90.0) || (i > 0 && !(t->ctab_angle[a0 + i] > t->ctab_angle[a0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "coating tables: angles must be strictly increasing, in [0, 90] degrees");
-            for (long long i = 0; i < nw * na; i++)
-                if (!(t->ctab_value[v0 + i] >= 0.0 && t->ctab_value[v0 + i] <= 1.0))
-                    return fail(PVT_ERR_INVALID, "coating tables: values must be in [0, 1]");
-            total += nw + na + nw * na;
-        }
-        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "coating tables: more than 2^27 doubles");
-        for (int k = 0; k < K; k++)
-            if (t->coat_table[k] < -1 || t->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "coating row names a missing table");
-    }
-    // ---- classes: what many nodes have in common is stored once (see the enums next to struct Lay) ----
-    // unrotated: the 3x3 blocks of both matrices of a node are the identity, bit for bit (+0.0 off the diagonal)
-    auto unrotated = [&](int n) {
-        const double one = 1.0, zero = 0.0;
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) {
-                const double* want = r == c ? &one : &zero;
-                if (std::memcmp(&t->world_to_local[n * 16 + r * 4 + c], want, 8) != 0) return false;
-                if (std::memcmp(&t->local_to_world[n * 16 + r * 4 + c], want, 8) != 0) return false;
-            }
-        return true;
-    };
-    // rotation classes: nodes whose two 3x3 blocks have the same bits share a record (and, in the wave-uniform
-    // node loop, the local direction and its reciprocals)
-    std::vector<int> rot_class(N), rot_first;
-    for (int n = 0; n < N; n++) {
-        int cls = -1;
-        for (size_t e = 0; e < rot_first.size() && cls < 0; e++) {
-            bool same = true;
-            for (int r = 0; r < 3 && same; r++)
-                for (int c = 0; c < 3 && same; c++)
-                    same = std::memcmp(&t->world_to_local[n * 16 + r * 4 + c], &t->world_to_local[rot_first[e] * 16 + r * 4 + c], 8) == 0 &&
-                           std::memcmp(&t->local_to_world[n * 16 + r * 4 + c], &t->local_to_world[rot_first[e] * 16 + r * 4 + c], 8) == 0;
-            if (same) cls = (int)e;
-        }
-        if (cls < 0) { cls = (int)rot_first.size(); rot_first.push_back(n); }
-        rot_class[n] = cls;
-    }
-    const int Q = (int)rot_first.size();
-    // refractive-index classes (bit-identical indices)
-    bool index_ok = true;   // refractive indices the known-divisor division is proven for
-    std::vector<int> idx_class(N), idx_first;
-    for (int n = 0; n < N; n++) {
-        const double v = t->refractive_index[n];
-        if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) index_ok = false;
-        int cls = -1;
-        for (size_t e = 0; e < idx_first.size() && cls < 0; e++)
-            if (std::memcmp(&t->refractive_index[idx_first[e]], &v, 8) == 0) cls = (int)e;
-        if (cls < 0) { cls = (int)idx_first.size(); idx_first.push_back(n); }
-        idx_class[n] = cls;
-    }
-    if (!index_ok) return fail(PVT_ERR_INVALID, "refractive indices must be finite and positive");
-    // scenes of few nodes: classes, component records and candidate blocks numbered like the nodes / the reference's ids
-    // (Lay::by_node: the lanes index the tables without reading NI_NCLS / NI_CREC / NI_CAND first)
-    const bool by_node = N <= 16;
-    if (by_node) {
-        idx_first.resize((size_t)N);
-        for (int n = 0; n < N; n++) { idx_class[n] = n; idx_first[(size_t)n] = n; }
-    }
-    const int M = (int)idx_first.size();
-
-    // Spectra, packed per DISTINCT table.  RN(1/spacing) when EVERY interval of the abscissae has the same bits and
-    // the ordinates keep the quotient inside div_known's domain (no -0.0, no extreme magnitudes):
-    auto even_rcp = [](const double* xs, const double* ys, int n) -> double {
-        if (n < 2) return NAN;
-        const double w = xs[1] - xs[0];
-        if (!(w > 1e-100 && w < 1e100)) return NAN;
-        for (int i = 1; i + 1 < n; i++) if (xs[i + 1] - xs[i] != w) return NAN;
-        for (int i = 0; i < n; i++) {
-            if (ys[i] == 0.0 && std::signbit(ys[i])) return NAN;
-            if (!(std::fabs(ys[i]) < 1e100)) return NAN;
-            if (i > 0 && ys[i] != ys[i - 1] && std::fabs(ys[i] - ys[i - 1]) < 1e-100) return NAN;
-        }
-        return 1.0 / w;
-    };
-    // The spacing itself when, additionally, xs[i] == xs[0] + i*w bit for bit AND the kernel's arithmetic
-    // (i = int((x - xs[0]) * rcp), one repair step against the computed neighbours) provably lands on the
-    // reference's bisection index for every x inside the table: the raw index is monotone in x, so it is enough
-    // that every abscissa and its two neighbouring doubles come out right (checked here with the device's own
-    // sequence of operations).  Such a table is stored as its first abscissa alone, without a guide table.
-    auto even_w = [](const double* xs, int n, double rcp) -> double {
-        if (!(rcp == rcp) || n < 2 || n > (1 << 24)) return NAN;
-        const double w = xs[1] - xs[0];
-        auto grid = [&](int i) { volatile double prod = (double)i * w; volatile double at = xs[0] + prod; return (double)at; };
-        for (int i = 0; i < n; i++)
-            if (grid(i) != xs[i]) return NAN;   // two roundings, never contracted
-        auto lands = [&](double x, int want) {
-            volatile double diff = x - xs[0];
-            volatile double quot = diff * rcp;
-            int i = (int)quot;
-            i = i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
-            double xlo = grid(i);
-            if (x < xlo) { i -= 1; xlo = grid(i); }
-            double xhi = grid(i + 1);
-            if (!(x < xhi)) { i += 1; xlo = xhi; xhi = grid(i + 1); }
-            return i == want && xlo <= x && x < xhi;
-        };
-        for (int i = 0; i < n; i++) {   // x0 < x < xl is all the even path ever sees
-            const double below = std::nextafter(xs[i], -INFINITY), above = std::nextafter(xs[i], INFINITY);
-            if (i > 0 && !lands(below, i - 1)) return NAN;
-            if (i > 0 && i < n - 1 && !lands(xs[i], i)) return NAN;
-            if (i < n - 1 && !lands(above, i)) return NAN;
-        }
-        return w;
-    };
-    // The reference keeps one set of tables per component of every node (compiler.py:160-215); a scene of many nodes
-    // made of the same material repeats them.  Here a table that has the bits of an earlier one (abscissae, ordinates,
-    // sampling mode) is that earlier one: the 121 tiles of an LSC array share ONE absorption and ONE emission table.
-    auto abs_hist = [&](int c) { return t->comp_abs_hist && t->comp_abs_hist[c] ? 1 : 0; };
-    auto ems_hist = [&](int c) { return t->comp_ems_hist && t->comp_ems_hist[c] ? 1 : 0; };
-    auto same_abs = [&](int c, int e) {
-        const int n = t->comp_abs_n[c];
-        return n == t->comp_abs_n[e] && abs_hist(c) == abs_hist(e) &&
-               std::memcmp(t->abs_x + t->comp_abs_start[c], t->abs_x + t->comp_abs_start[e], (size_t)n * 8) == 0 &&
-               std::memcmp(t->abs_y + t->comp_abs_start[c], t->abs_y + t->comp_abs_start[e], (size_t)n * 8) == 0;
-    };
-    auto same_ems = [&](int c, int e) {
-        const int n = t->comp_ems_n[c];
-        return n == t->comp_ems_n[e] && ems_hist(c) == ems_hist(e) &&
-               std::memcmp(t->ems_x + t->comp_ems_start[c], t->ems_x + t->comp_ems_start[e], (size_t)n * 8) == 0 &&
-               std::memcmp(t->ems_cdf + t->comp_ems_start[c], t->ems_cdf + t->comp_ems_start[e], (size_t)n * 8) == 0;
-    };
-    std::vector<int> abs_of(C), ems_of(C);   // the component whose tables component c uses (itself: it owns them)
-    {
-        std::vector<int> abs_owners, ems_owners;
-        for (int c = 0; c < C; c++) {
-            abs_of[c] = ems_of[c] = c;
-            for (int e : abs_owners) if (same_abs(c, e)) { abs_of[c] = e; break; }
-            for (int e : ems_owners) if (same_ems(c, e)) { ems_of[c] = e; break; }
-            if (abs_of[c] == c) abs_owners.push_back(c);
-            if (ems_of[c] == c) ems_owners.push_back(c);
-        }
-    }
-    // component RECORDS: the components of a node are a run of records; a node whose run has the contents of an
-    // earlier node's run shares it (NI_CREC).  Component IDS (events, `source`, recorder filters) stay the reference's.
-    auto same_component = [&](int c, int e) {
-        return t->comp_type[c] == t->comp_type[e] && t->comp_phase_type[c] == t->comp_phase_type[e] &&
-               std::memcmp(&t->comp_qy[c], &t->comp_qy[e], 8) == 0 && std::memcmp(&t->comp_tau_rad[c], &t->comp_tau_rad[e], 8) == 0 &&
-               std::memcmp(&t->comp_tau_nr[c], &t->comp_tau_nr[e], 8) == 0 &&
-               std::memcmp(&t->comp_phase_param[c], &t->comp_phase_param[e], 8) == 0 &&
-               abs_of[c] == abs_of[e] && ems_of[c] == ems_of[e];
-    };
-    std::vector<int> node_crec(N, 0), rec_comp;   // rec_comp[r] = the component id whose fields record r holds
-    for (int n = 0; n < N; n++) {
-        const int c0 = t->comp_start[n], cc = t->comp_count[n];
-        if (cc < 0 || c0 < 0 || c0 + cc > C) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
-        int found = -1;
-        if (by_node) found = c0;   // (one record per component id: NI_CREC == NI_CSTART, which the kernel relies on)
-        for (int e = 0; e < n && found < 0 && !by_node; e++) {
-            if (t->comp_count[e] != cc) continue;
-            bool same = true;
-            for (int k = 0; k < cc && same; k++) same = same_component(c0 + k, t->comp_start[e] + k);
-            if (same) found = node_crec[e];
-        }
-        if (found < 0) {
-            found = (int)rec_comp.size();
-            for (int k = 0; k < cc; k++) rec_comp.push_back(c0 + k);
-        }
-        node_crec[n] = found;
-    }
-    if (by_node) {
-        rec_comp.resize((size_t)C);
-        for (int c = 0; c < C; c++) rec_comp[(size_t)c] = c;
-    }
-    const int CR = (int)rec_comp.size();
-    // recorder candidate blocks: only for the nodes somebody listens to
-    std::vector<int> node_cand(N, -1);
-    int n_cand = 0;
-    for (int r = 0; r < R; r++) {
-        const int n = t->rec_node[r];
-        if (n < 0 || n >= N) return fail(PVT_ERR_INVALID, "recorder on a missing node");
-        if (!by_node && node_cand[n] < 0) node_cand[n] = n_cand++;
-    }
-    if (by_node) {
-        for (int n = 0; n < N; n++) node_cand[n] = n;
-        n_cand = N;
-    }
-
-    // fixed-stride records, then the pooled spectra
-    Lay lay{};
-    lay.comp_d = N * ND;
-    lay.rec_d = lay.comp_d + CR * CD;
-    lay.hist_d = lay.rec_d + R * RD;
-    lay.coat_d = lay.hist_d + H * HD;
-    // The small tables come first in the blob -- records, then critical angles, rotation classes, index classes and the
-    // node grid -- and the spectra last: when a scene's spectra are too large for LDS, a workgroup still stages everything
-    // before `spec_d` (KArgs::nd_lds; the guide tables are the tail of the int blob in the same way).
-    const int small_d = lay.coat_d + K * KD;
-    constexpr int kCritClasses = 16;
-    lay.n_cls = M;
-    lay.crit_d = M <= kCritClasses ? small_d : -1;
-    lay.ccrit_d = lay.crit_d >= 0 ? lay.crit_d + M * M : -1;
-    lay.rot_d = small_d + (lay.crit_d >= 0 ? 2 * M * M : 0);
-    lay.ncls_d = lay.rot_d + Q * RT;
-    lay.by_node = by_node ? 1 : 0;
-    NodeGrid grid;
-    const bool has_grid = plan_node_grid(t, &grid);
-    lay.grid_d = has_grid ? lay.ncls_d + M * 2 : -1;
-    const int spec_d = lay.ncls_d + M * 2 + (has_grid ? 14 + (int)grid.masks.size() : 0);
-    std::vector<double> c_abs_rcp(C), c_abs_w(C), c_ems_rcp_x(C), c_ems_rcp_c(C), c_ems_w(C);
-    std::vector<int> c_abs_x(C), c_abs_y(C), c_ems_x(C), c_ems_c(C), c_abs_g(C), c_ems_gx(C), c_ems_gc(C);
-    int spec_len = 0, guide_len = 0;
-    for (int c = 0; c < C; c++) {
-        const double* ax = t->abs_x + t->comp_abs_start[c];
-        const double* ay = t->abs_y + t->comp_abs_start[c];
-        const double* ex = t->ems_x + t->comp_ems_start[c];
-        const double* ec = t->ems_cdf + t->comp_ems_start[c];
-        const int an = t->comp_abs_n[c], en = t->comp_ems_n[c];
-        if (abs_of[c] != c) {
-            const int e = abs_of[c];
-            c_abs_rcp[c] = c_abs_rcp[e]; c_abs_w[c] = c_abs_w[e]; c_abs_x[c] = c_abs_x[e]; c_abs_y[c] = c_abs_y[e]; c_abs_g[c] = c_abs_g[e];
-        } else {
-            c_abs_rcp[c] = even_rcp(ax, ay, an);
-            c_abs_w[c] = abs_hist(c) ? NAN : even_w(ax, an, c_abs_rcp[c]);
-            const bool abs_compact = c_abs_w[c] == c_abs_w[c];
-            c_abs_x[c] = spec_d + spec_len; spec_len += abs_compact ? (an > 0 ? 1 : 0) : an;
-            c_abs_y[c] = spec_d + spec_len; spec_len += an;
-            c_abs_g[c] = abs_compact ? -1 : guide_len; guide_len += abs_compact ? 0 : an;
-        }
-        if (ems_of[c] != c) {
-            const int e = ems_of[c];
-            c_ems_rcp_x[c] = c_ems_rcp_x[e]; c_ems_rcp_c[c] = c_ems_rcp_c[e]; c_ems_w[c] = c_ems_w[e];
-            c_ems_x[c] = c_ems_x[e]; c_ems_c[c] = c_ems_c[e]; c_ems_gx[c] = c_ems_gx[e]; c_ems_gc[c] = c_ems_gc[e];
-        } else {
-            c_ems_rcp_x[c] = even_rcp(ex, ec, en);
-            c_ems_rcp_c[c] = even_rcp(ec, ex, en);
-            c_ems_w[c] = ems_hist(c) ? NAN : even_w(ex, en, c_ems_rcp_x[c]);
-            const bool ems_compact = c_ems_w[c] == c_ems_w[c];
-            c_ems_x[c] = spec_d + spec_len; spec_len += ems_compact ? (en > 0 ? 1 : 0) : en;
-            c_ems_c[c] = spec_d + spec_len; spec_len += en;
-            c_ems_gx[c] = ems_compact ? -1 : guide_len; guide_len += ems_compact ? 0 : en;
-            c_ems_gc[c] = guide_len; guide_len += en;
-        }
-    }
-    // coating reflectivity tables (KI_T*): their axes and values follow the spectra, so they go wherever the spectra go
-    // (LDS with the whole blob, else global memory) and a scene without them lays out exactly as before
-    const int NT = K > 0 ? t->n_coat_tables : 0;
-    std::vector<int> ctab_at(NT);
-    for (int j = 0; j < NT; j++) {
-        ctab_at[j] = spec_d + spec_len;
-        spec_len += t->ctab_nw[j] + t->ctab_na[j] + t->ctab_nw[j] * t->ctab_na[j];
-    }
-    const int spec_end = spec_d + spec_len;
-    std::vector<double> gd((size_t)spec_end + 1, 0.0);
-    if (has_grid) {
-        double* d = gd.data() + lay.grid_d;
-        for (int a = 0; a < 3; a++) { d[a] = grid.lo[a]; d[3 + a] = grid.hi[a]; d[6 + a] = grid.cell[a]; d[9 + a] = 1.0 / grid.cell[a]; }
-        d[12] = grid.guard;
-        const unsigned long long bits = (unsigned long long)grid.n[0] | ((unsigned long long)grid.n[1] << 8) | ((unsigned long long)grid.n[2] << 16) |
-                                        ((unsigned long long)grid.words << 24) | ((unsigned long long)(grid.odd ? 1 : 0) << 28);
-        std::memcpy(&d[13], &bits, 8);
-        std::memcpy(&d[14], grid.masks.data(), grid.masks.size() * 8);
-    }
-    if (lay.crit_d >= 0)
-        for (int c = 0; c < M; c++)
-            for (int a = 0; a < M; a++) {
-                const double n1 = t->refractive_index[idx_first[c]], n2 = t->refractive_index[idx_first[a]];
-                const double crit = n2 < n1 ? pvt_asin(n2 / n1) : INFINITY;   // same pvt_asin as the device
-                gd[lay.crit_d + c * M + a] = crit;
-                gd[lay.ccrit_d + c * M + a] = cosine_threshold(crit);
-            }
-    for (int q = 0; q < Q; q++) {
-        double* d = gd.data() + lay.rot_d + q * RT;
-        const int n = rot_first[q];
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) {
-                d[RT_W2L + r * 3 + c] = t->world_to_local[n * 16 + r * 4 + c];
-                d[RT_L2W + r * 3 + c] = t->local_to_world[n * 16 + r * 4 + c];
-            }
-    }
-    for (int m = 0; m < M; m++) {
-        gd[lay.ncls_d + m * 2] = t->refractive_index[idx_first[m]];
-        gd[lay.ncls_d + m * 2 + 1] = 1.0 / t->refractive_index[idx_first[m]];
-    }
-    lay.comp_i = N * NI;
-    lay.rec_i = lay.comp_i + CR * CI;
-    lay.hist_i = lay.rec_i + R * RI;
-    lay.coat_i = lay.hist_i + H * HI;
-    lay.cand_i = lay.coat_i + K * KI;
-    lay.cand_list = lay.cand_i + n_cand * 7 * 8;
-    const int guide0 = lay.cand_list + R;  // guide tables: one entry per table point, per searched array
-    std::vector<int> gi((size_t)guide0 + (size_t)guide_len + 1, 0);
-    // guide[b] = largest i <= n-2 with xs[i] <= xs[0] + b*(xs[n-1]-xs[0])/(n-1), b = 0..n-1
-    auto build_guide = [&](const double* xs, int n, int at, double* scale) {
-        *scale = 0.0;
-        if (n < 2 || !(xs[n - 1] > xs[0])) return;
-        const int Kb = n - 1;
-        *scale = (double)Kb / (xs[n - 1] - xs[0]);
-        int i = 0;
-        for (int b = 0; b <= Kb; b++) {
-            const double edge = xs[0] + (double)b * ((xs[n - 1] - xs[0]) / (double)Kb);
-            while (i + 1 <= n - 2 && xs[i + 1] <= edge) i++;
-            gi[at + b] = i;
-        }
-    };
-    {   // recorders grouped by the (node, selector) they listen to.  A facet recorder whose facet
-        // has a clearly dominant component, alone in its (axis, sign) bin, goes to the bin table;
-        // the rest (no facet, oblique facets, bin collisions) to the walked list, ascending id.
-        int at = 0;
-        for (int node_of_key = 0; node_of_key < N; node_of_key++) {
-          if (node_cand[node_of_key] < 0) continue;
-          for (int sel = 0; sel < 7; sel++) {
-            const int key = node_of_key * 7 + sel;
-            int* rec = gi.data() + lay.cand_i + (node_cand[node_of_key] * 7 + sel) * 8;
-            rec[0] = at;
-            int owner[6] = {-1, -1, -1, -1, -1, -1};
-            bool clash[6] = {false, false, false, false, false, false};
-            auto bin_of = [&](int r) -> int {
-                if (!t->rec_has_facet[r]) return -1;
-                const double* f = t->rec_facet + r * 3;
-                const double a[3] = {std::fabs(f[0]), std::fabs(f[1]), std::fabs(f[2])};
-                int k = (a[0] >= a[1] && a[0] >= a[2]) ? 0 : (a[1] >= a[2] ? 1 : 2);
-                const double other = std::fmax(a[(k + 1) % 3], a[(k + 2) % 3]);
-                // any normal within atol of the facet must have the same dominant axis and sign
-                if (!(a[k] - other > 4.0 * t->rec_atol[r] + 1e-9) || !(a[k] > 2.0 * t->rec_atol[r])) return -1;
-                return k * 2 + (f[k] > 0.0 ? 1 : 0);
-            };
-            for (int r = 0; r < R; r++) {
-                if (t->rec_node[r] * 7 + t->rec_event[r] != key) continue;
-                int b = bin_of(r);
-                if (b >= 0) { if (owner[b] >= 0) clash[b] = true; else owner[b] = r; }
-            }
-            // kRecPlain on an entry: the lane need not read the recorder's row at all -- no source filter, and either no
-            // facet, or a facet that IS the bin's axis (exactly +-1 on it, zeros elsewhere) on an unrotated box, whose
-            // world normals are exactly such unit vectors: |facet - normal| is exactly 0 for every normal of the bin
-            const bool exact_normals = t->geom_type[node_of_key] == PVT_GEOM_BOX && unrotated(node_of_key);
-            auto unfiltered = [&](int r) { return !t->rec_source_mode || t->rec_source_mode[r] == 0; };
-            auto axis_facet = [&](int r, int b) {
-                const double* f = t->rec_facet + r * 3;
-                for (int a = 0; a < 3; a++)
-                    if (f[a] != (a == b / 2 ? (b % 2 ? 1.0 : -1.0) : 0.0)) return false;
-                return t->rec_atol[r] >= 0.0;
-            };
-            for (int b = 0; b < 6; b++) {
-                rec[2 + b] = (owner[b] >= 0 && !clash[b]) ? owner[b] : -1;
-                if (rec[2 + b] >= 0 && exact_normals && unfiltered(owner[b]) && axis_facet(owner[b], b)) rec[2 + b] |= kRecPlain;
-            }
-            for (int r = 0; r < R; r++) {
-                if (t->rec_node[r] * 7 + t->rec_event[r] != key) continue;
-                int b = bin_of(r);
-                if (b >= 0 && !clash[b]) continue;  // served by the bin table
-                gi[lay.cand_list + at++] = r | ((unfiltered(r) && !t->rec_has_facet[r]) ? kRecPlain : 0);
-            }
-            rec[1] = at - rec[0];
-          }
-        }
-    }
-    for (int n = 0; n < N; n++) {
-        double* d = gd.data() + n * ND;
-        for (int r = 0; r < 3; r++) d[ND_T + r] = t->world_to_local[n * 16 + r * 4 + 3];
-        for (int c = 0; c < 3; c++) d[ND_PARAMS + c] = t->geom_params[n * 4 + c];
-        const unsigned long long bits = (unsigned long long)(unsigned int)((unrotated(n) ? 1 : 0) | (t->geom_type[n] << 8)) |
-                                        ((unsigned long long)(unsigned int)rot_class[n] << 32);
-        std::memcpy(&d[ND_BITS], &bits, 8);
-        d[ND_N] = t->refractive_index[n];
-        int* q = gi.data() + n * NI;
-        q[NI_SURF] = t->surface_type[n];
-        q[NI_CSTART] = t->comp_start[n];
-        q[NI_CCOUNT] = t->comp_count[n];
-        q[NI_CREC] = node_crec[n];
-        q[NI_KSTART] = K > 0 ? t->coat_start[n] : 0;
-        q[NI_KCOUNT] = K > 0 ? t->coat_count[n] : 0;
-        q[NI_MESH] = -1;
-        q[NI_CAND] = node_cand[n];
-        q[NI_NCLS] = idx_class[n];
-        if (t->geom_type[n] == PVT_GEOM_MESH) {
-            const int f0 = t->mesh_face_start[n], fc = t->mesh_face_count[n];
-            double centre[3];
-            q[NI_MESH] = pvt::BvhBuilder(t->mesh_vertices, t->mesh_faces, t->mesh_normals, bvh_nodes, bvh_tris)
-                             .add_mesh(f0, fc, centre);
-            bvh_roots.push_back(q[NI_MESH]);
-            for (int c = 0; c < 3; c++) d[ND_PARAMS + c] = centre[c];   // a mesh has no shape parameters: the point its boxes are relative to
-        }
-    }
-    for (int rc = 0; rc < CR; rc++) {
-        const int c = rec_comp[rc];
-        double* d = gd.data() + lay.comp_d + rc * CD;
-        d[CD_QY] = t->comp_qy[c];
-        d[CD_TAU_RAD] = t->comp_tau_rad[c];
-        d[CD_TAU_NR] = t->comp_tau_nr[c];
-        d[CD_PHASE] = t->comp_phase_param[c];
-        int* q = gi.data() + lay.comp_i + rc * CI;
-        q[CI_TYPE] = t->comp_type[c];
-        q[CI_PHASE] = t->comp_phase_type[c];
-        if (t->comp_phase_type[c] == PVT_PHASE_LAMBERTIAN) {
-            // The Lambertian phase function, theta = asin(sqrt(p1)), IS the cone's theta = asin(sqrt(p1) sin(theta_max)) at
-            // theta_max = pi/2 -- same two draws in the same order -- provided sin(pi/2) is the double 1.0 in the
-            // kernel's arithmetic (x * 1.0 is exact); checked here with the very function the kernel calls.
-            const double half_pi = 1.5707963267948966;
-            if (pvt_sin(half_pi) != 1.0) return fail(PVT_ERR_INVALID, "pvt_sin(pi/2) != 1: the Lambertian phase function cannot be lowered to a cone");
-            d[CD_PHASE] = half_pi;
-            q[CI_PHASE] = PVT_PHASE_CONE;
-        }
-        q[CI_ABS_X] = c_abs_x[c];   // absolute offsets into the double blob
-        q[CI_ABS_Y] = c_abs_y[c];
-        q[CI_ABS_N] = t->comp_abs_n[c];
-        q[CI_EMS_X] = c_ems_x[c];
-        q[CI_EMS_CDF] = c_ems_c[c];
-        q[CI_EMS_N] = t->comp_ems_n[c];
-        q[CI_ABS_HIST] = abs_hist(c);
-        q[CI_EMS_HIST] = ems_hist(c);
-        // guide tables only for the arrays that are searched (see even_w); -1 is never dereferenced
-        q[CI_ABS_G] = c_abs_g[c] < 0 ? -1 : guide0 + c_abs_g[c];
-        q[CI_EMS_GX] = c_ems_gx[c] < 0 ? -1 : guide0 + c_ems_gx[c];
-        q[CI_EMS_GC] = guide0 + c_ems_gc[c];
-        d[CD_ABS_RCP] = c_abs_rcp[c];
-        d[CD_EMS_RCP_X] = c_ems_rcp_x[c];
-        d[CD_EMS_RCP_C] = c_ems_rcp_c[c];
-        d[CD_ABS_W] = c_abs_w[c];
-        d[CD_EMS_W] = c_ems_w[c];
-        // the guide scales are functions of the tables alone: computed (and the tables written) by whoever owns them,
-        // which is always a component with a record of its own or an earlier one -- fill in from the owner below
-    }
-    // the tables themselves, once per owner (a compact table keeps its first abscissa only), and their guide tables
-    std::vector<double> abs_scale(C, 0.0), ems_scale_x(C, 0.0), ems_scale_c(C, 0.0);
-    for (int c = 0; c < C; c++) {
-        const double* ax = t->abs_x + t->comp_abs_start[c];
-        const double* ex = t->ems_x + t->comp_ems_start[c];
-        const double* ec = t->ems_cdf + t->comp_ems_start[c];
-        const int an = t->comp_abs_n[c], en = t->comp_ems_n[c];
-        if (abs_of[c] == c) {
-            const bool abs_compact = c_abs_g[c] < 0;
-            if (!abs_compact) build_guide(ax, an, guide0 + c_abs_g[c], &abs_scale[c]);
-            for (int i = 0; i < (abs_compact ? (an > 0 ? 1 : 0) : an); i++) gd[c_abs_x[c] + i] = ax[i];
-            for (int i = 0; i < an; i++) gd[c_abs_y[c] + i] = t->abs_y[t->comp_abs_start[c] + i];
-        } else {
-            abs_scale[c] = abs_scale[abs_of[c]];
-        }
-        if (ems_of[c] == c) {
-            const bool ems_compact = c_ems_gx[c] < 0;
-            if (!ems_compact) build_guide(ex, en, guide0 + c_ems_gx[c], &ems_scale_x[c]);
-            build_guide(ec, en, guide0 + c_ems_gc[c], &ems_scale_c[c]);
-            for (int i = 0; i < (ems_compact ? (en > 0 ? 1 : 0) : en); i++) gd[c_ems_x[c] + i] = ex[i];
-            for (int i = 0; i < en; i++) gd[c_ems_c[c] + i] = ec[i];
-        } else {
-            ems_scale_x[c] = ems_scale_x[ems_of[c]];
-            ems_scale_c[c] = ems_scale_c[ems_of[c]];
-        }
-    }
-    for (int rc = 0; rc < CR; rc++) {
-        const int c = rec_comp[rc];
-        double* d = gd.data() + lay.comp_d + rc * CD;
-        d[CD_ABS_SCALE] = abs_scale[c];
-        d[CD_EMS_SCALE_X] = ems_scale_x[c];
-        d[CD_EMS_SCALE_C] = ems_scale_c[c];
-    }
-    for (int r = 0; r < R; r++) {
-        double* d = gd.data() + lay.rec_d + r * RD;
-        for (int a = 0; a < 3; a++) d[RD_FACET + a] = t->rec_facet[r * 3 + a];
-        d[RD_ATOL] = t->rec_atol[r];
-        int* q = gi.data() + lay.rec_i + r * RI;
-        q[RI_NODE] = t->rec_node[r];
-        q[RI_EVENT] = t->rec_event[r];
-        q[RI_HAS_FACET] = t->rec_has_facet[r];
-        q[RI_HSTART] = t->rec_hist_start[r];
-        q[RI_HN] = t->rec_hist_n[r];
-        q[RI_SRC_MODE] = t->rec_source_mode ? t->rec_source_mode[r] : 0;
-        q[RI_SRC_ID] = t->rec_source_id ? t->rec_source_id[r] : -1;
-    }
-    for (int h = 0; h < H; h++) {
-        double* d = gd.data() + lay.hist_d + h * HD;
-        d[HD_LO_A] = t->hist_lo_a[h]; d[HD_HI_A] = t->hist_hi_a[h];
-        d[HD_LO_B] = t->hist_lo_b[h]; d[HD_HI_B] = t->hist_hi_b[h];
-        auto rcp_or_nan = [](double width) {   // NaN: the kernel divides for real
-            return (std::isfinite(width) && std::fabs(width) > 1e-290 && std::fabs(width) < 1e290) ? 1.0 / width : NAN;
-        };
-        d[HD_RA] = rcp_or_nan(t->hist_hi_a[h] - t->hist_lo_a[h]);
-        d[HD_RB] = rcp_or_nan(t->hist_hi_b[h] - t->hist_lo_b[h]);
-        int* q = gi.data() + lay.hist_i + h * HI;
-        q[HI_PA] = t->hist_prop_a[h]; q[HI_PB] = t->hist_prop_b[h];
-        q[HI_NA] = t->hist_na[h]; q[HI_NB] = t->hist_nb[h]; q[HI_OFF] = t->hist_offset[h];
-    }
-    for (int k = 0; k < K; k++) {
-        double* d = gd.data() + lay.coat_d + k * KD;
-        for (int a = 0; a < 3; a++) {
-            d[KD_FACET + a] = t->coat_facet[k * 3 + a];
-            d[KD_LO + a] = t->coat_lo[k * 3 + a];
-            d[KD_HI + a] = t->coat_hi[k * 3 + a];
-        }
-        d[KD_REFL] = t->coat_reflectivity[k];
-        int* q = gi.data() + lay.coat_i + k * KI;
-        q[KI_RMODE] = t->coat_reflect_mode[k];
-        q[KI_TMODE] = t->coat_transmit_mode[k];
-        const int j = NT > 0 ? t->coat_table[k] : -1;
-        q[KI_TNW] = j >= 0 ? t->ctab_nw[j] : 0;   // 0: no table
-        q[KI_TNA] = j >= 0 ? t->ctab_na[j] : 0;
-        q[KI_TW] = j >= 0 ? ctab_at[j] : 0;
-        q[KI_TA] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] : 0;
-        q[KI_TV] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] + t->ctab_na[j] : 0;
-    }
-    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
-    for (int j = 0; j < NT; j++) {   // wavelengths (nm), angles (radians: the kernel compares pvt_acos of the cosine), values
-        const int nw = t->ctab_nw[j], na = t->ctab_na[j];
-        double* d = gd.data() + ctab_at[j];
-        for (int i = 0; i < nw; i++) d[i] = t->ctab_wavelength[t->ctab_wl_start[j] + i];
-        for (int i = 0; i < na; i++) d[nw + i] = t->ctab_angle[t->ctab_angle_start[j] + i] * kRadPerDeg;
-        for (int i = 0; i < na * nw; i++) d[nw + na + i] = t->ctab_value[t->ctab_value_start[j] + i];
-    }
-
-    // Lazy root (kernel node loop): the root is a box or a sphere and every other node lies strictly inside it,
-    // its bounding sphere clearing the root's surface by a margin -- then a ray from inside the root meets every
-    // other node's surface strictly before the root's.
-    int lazy_root = 0;
-    double lazy_k = 0.0;
-    bool exit_observed = false;
-    for (int r = 0; r < R; r++)
-        if (t->rec_node[r] == t->root_id && t->rec_event[r] == PVT_REC_EXIT) exit_observed = true;
-    if (!getenv("PVT_NO_LAZY_ROOT") && (t->geom_type[t->root_id] == PVT_GEOM_BOX || t->geom_type[t->root_id] == PVT_GEOM_SPHERE)) {
-        const int root = t->root_id;
-        const double* w2l = t->world_to_local + root * 16;
-        const double* rp = t->geom_params + root * 4;
-        const bool box = t->geom_type[root] == PVT_GEOM_BOX;
-        const double scale = box ? std::fmax(rp[0], std::fmax(rp[1], rp[2])) : rp[0];
-        const double margin = 1e-6 * scale + 1e-9;
-        bool inside = std::isfinite(scale) && scale > 0.0;
-        for (int n = 0; n < N && inside; n++) {
-            if (n == root) continue;
-            const double* l2w = t->local_to_world + n * 16;
-            const double* gp = t->geom_params + n * 4;
-            double radius;   // of a sphere about the node's origin that holds the whole shape
-            switch (t->geom_type[n]) {
-                case PVT_GEOM_BOX: radius = 0.5 * std::sqrt(gp[0] * gp[0] + gp[1] * gp[1] + gp[2] * gp[2]); break;
-                case PVT_GEOM_SPHERE: radius = gp[0]; break;
-                case PVT_GEOM_CYLINDER: radius = std::sqrt(gp[1] * gp[1] + 0.25 * gp[0] * gp[0]); break;
-                default: radius = INFINITY; break;   // (mesh scenes never take this path)
-            }
-            radius *= 1.0 + 1e-12;
-            double c[3];   // the node's origin in the root's frame
-            for (int a = 0; a < 3; a++)
-                c[a] = w2l[a * 4] * l2w[3] + w2l[a * 4 + 1] * l2w[7] + w2l[a * 4 + 2] * l2w[11] + w2l[a * 4 + 3];
-            if (box) {
-                for (int a = 0; a < 3; a++)
-                    if (!(0.5 * rp[a] - std::fabs(c[a]) - radius > margin)) inside = false;
-            } else {
-                if (!(rp[0] - std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) - radius > margin)) inside = false;
-            }
-        }
-        if (inside) {
-            lazy_root = box ? 1 : 2;
-            lazy_k = box ? 0.0 : 1.0 / (2.0 * rp[0]);
-        }
-    }
-    // Fused exit (kernel surface branch): the scene is ONE unrotated box inside a lazy root whose medium neither
-    // absorbs nor is listened to -- a photon that leaves the box's surface outwards can only leave the scene.
-    bool fuse_exit = false;
-    if (lazy_root && N == 2 && !getenv("PVT_NO_FUSED_EXIT")) {
-        const int child = 1 - t->root_id;
-        bool ok = t->geom_type[child] == PVT_GEOM_BOX && unrotated(child) && t->comp_count[t->root_id] == 0;
-        for (int r = 0; r < R; r++)
-            if (t->rec_node[r] == t->root_id) ok = false;
-        fuse_exit = ok;
-    }
-
-    // owned until every upload has succeeded: a failing HIP call must not leak the scene
-    struct Owner {
-        PvtScene* p;
-        ~Owner() { if (p) pvt_scene_destroy(p); }
-    } owner{new PvtScene()};
-    PvtScene* s = owner.p;
-    s->stage.reserve(kCursorSlots); s->stage_bytes.reserve(kCursorSlots); s->carry.reserve(kCursorSlots);   // (references stay valid)
-    s->emit_pool.reserve(kCursorSlots); s->emit_pool_bytes.reserve(kCursorSlots);
-    s->device = device;
-    s->lay = lay;
-    s->nd = (int)gd.size();
-    s->ni = (int)gi.size();
-    s->nd_small = spec_d;
-    s->ni_small = guide0;
-    s->n_nodes = N;
-    s->root = t->root_id;
-    s->n_rec = R;
-    s->total_bins = t->total_bins;
-    s->n_coat = K;
-    s->n_ctab = NT;
-    s->lazy_root = lazy_root;
-    s->lazy_k = lazy_k;
-    s->exit_observed = exit_observed;
-    s->fuse_exit = fuse_exit;
-    s->grid = has_grid;
-    for (int a = 0; a < 3; a++) s->grid_dims[a] = has_grid ? grid.n[a] : 0;
-    for (int h = 0; h < H; h++)
-        if (t->hist_prop_a[h] >= 4 || t->hist_prop_b[h] >= 4) s->hist_reads_position = true;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    s->num_cu = prop.multiProcessorCount;
-    s->lds_limit = prop.sharedMemPerBlock;
-    s->consolidate = getenv("PVT_NO_CONSOLIDATE") == nullptr;
-    if (const char* env = getenv("PVT_BLOCKS_PER_CU")) s->dev_blocks_per_cu = atof(env);
-    if (const char* env = getenv("PVT_STAGE_BYTES")) s->stage_limit = (size_t)atoll(env);   // (tests: force several launches)
-    HIP_TRY(hipMalloc(&s->d_gd, gd.size() * sizeof(double)));
-    HIP_TRY(hipMalloc(&s->d_gi, gi.size() * sizeof(int)));
-    HIP_TRY(hipMalloc(&s->d_cursor, 64 * kCursorSlots + 256));   // + room for the PVT_STATS counters
-    HIP_TRY(hipMemset(s->d_cursor, 0, 64 * kCursorSlots + 256));
-    HIP_TRY(hipMalloc(&s->d_set_cursor, (size_t)kCursorSlots * kMaxSets * 4));
-    HIP_TRY(hipMalloc(&s->d_counters, 64 * 8 * 8));
-    HIP_TRY(hipMemset(s->d_counters, 0, 64 * 8 * 8));
-    HIP_TRY(hipMalloc(&s->d_stamp, (size_t)kCursorSlots * 2 * 8));
-    HIP_TRY(hipMemset(s->d_stamp, 0, (size_t)kCursorSlots * 2 * 8));
-    if (bvh_nodes.size() >= ((size_t)1 << 26) || bvh_tris.size() >= ((size_t)1 << 26))
-        return fail(PVT_ERR_INVALID, "meshes too large: the walk's cursors and leaf references hold 2^26 records / triangles");
-    if (!bvh_nodes.empty()) {
-        // a lane of a walk notes kMeshQ leaves before their triangles are tested -- one, in trees of a handful of records
-        // (the kernel applies the same rule per tree)
-        s->meshq = 1;
-        for (int r : bvh_roots)
-            if (bvh_nodes[r].skip - r > 16) s->meshq = kMeshQ;   // (15 records and the unused one after the root)
-        // The top levels of the trees go to LDS (pvt_bvh.h: stage_top), as many records as leave four workgroups per CU
-        // -- the mesh variants' four waves per SIMD -- their LDS in either kind of launch (tallies / histories).
-        {
-            const LdsPlan tally = plan_lds(s, false), hist = plan_lds(s, true);
-            const size_t other = (tally.bytes > hist.bytes ? tally.bytes : hist.bytes) + (size_t)s->meshq * kBlock * 4;
-            const size_t per_wg = (size_t)39 * 1024 * 4 / kMeshWaves;
-            size_t room = tally.ok && hist.ok && other < per_wg ? per_wg - other : 0;
-            if (room > 32 * 1024) room = 32 * 1024;
-            if (const char* env = getenv("PVT_MESH_TOP_BYTES")) {   // (developer override, never past the room computed above; 0: no copy)
-                const size_t asked = (size_t)atoll(env);
-                room = asked < room ? asked : room;
-            }
-            std::vector<pvt::BvhNode> top;
-            pvt::stage_top(bvh_nodes, bvh_roots, room / sizeof(pvt::BvhNode), top);
-            s->top_n = (int)top.size();
-            // what was planned without the copy must still hold with it (plan_lds reserves the copy first): same table
-            // placement, everything inside the LDS of a workgroup
-            const LdsPlan tally2 = plan_lds(s, false), hist2 = plan_lds(s, true);
-            const size_t with_top = (size_t)s->meshq * kBlock * 4 + (size_t)s->top_n * sizeof(pvt::BvhNode);
-            if (tally2.ok != tally.ok || hist2.ok != hist.ok || tally2.tab_lds != tally.tab_lds || hist2.tab_lds != hist.tab_lds ||
-                tally2.bytes + with_top > s->lds_limit || hist2.bytes + with_top > s->lds_limit)
-                return fail(PVT_ERR_INVALID, "internal: the LDS plan of a mesh scene changed when the copy of its trees' top levels was added");
-            if (s->top_n > 0) {
-                HIP_TRY(hipMalloc(&s->d_bvh_top, top.size() * sizeof(pvt::BvhNode)));
-                HIP_TRY(hipMemcpy(s->d_bvh_top, top.data(), top.size() * sizeof(pvt::BvhNode), hipMemcpyHostToDevice));
-            }
-        }
-        bvh_nodes.push_back(pvt::BvhNode{});   // (one record past the end, kept for walks that fetch ahead)
-        HIP_TRY(hipMalloc(&s->d_bvh, bvh_nodes.size() * sizeof(pvt::BvhNode)));
-        HIP_TRY(hipMalloc(&s->d_tris, bvh_tris.size() * sizeof(pvt::MeshTri)));
-        HIP_TRY(hipMemcpy(s->d_bvh, bvh_nodes.data(), bvh_nodes.size() * sizeof(pvt::BvhNode), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->d_tris, bvh_tris.data(), bvh_tris.size() * sizeof(pvt::MeshTri), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(s->d_gd, gd.data(), gd.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_gi, gi.data(), gi.size() * sizeof(int), hipMemcpyHostToDevice));
-    owner.p = nullptr;
-    *out = s;
-    return PVT_OK;
 }
 
 int pvt_scene_set_emitter(PvtScene* s, const PvtEmitterTables* e) {
@@ -1243,10 +283,6 @@ hipError_t launch_seen(int n_rec, bool emit, int grid, size_t lds, hipStream_t s
 
 }  // namespace
 
-extern "C" {
-
-}  // extern "C"
-
 namespace {
 
 // cursor / staging slot of a stream (launches on one stream are ordered and share it)
@@ -1283,6 +319,7 @@ int check_trace_args(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, 
 // LDS of a launch, before what mesh walks add: recorder accumulators + control words, tables if they fit, bins if
 // they fit, then the drain-phase consolidation buffer (kXSlots photon states, also the seed pools) within 40 KB.
 // `s->meshq` and `s->top_n` (mesh scenes) are reserved first, so that what is decided here still fits with them.
+struct LdsPlan { size_t bytes; bool tab_lds, small_lds; int bins_in_lds, xslots, tq_pos; bool ok; };
 LdsPlan plan_lds(const PvtScene* s, bool record) {
     LdsPlan lp{0, false, false, 0, 0, 0, true};
     const size_t reserved = (size_t)s->meshq * kBlock * 4 + (size_t)s->top_n * sizeof(pvt::BvhNode);
@@ -1550,6 +587,95 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
 }  // namespace
 
 extern "C" {
+
+int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
+    if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
+    if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
+    if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
+    if (t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "more than 256 recorders");
+    if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
+    HIP_TRY(hipSetDevice(device));
+    PackedScene packed;
+    const int rc = pack_scene(t, &packed);
+    if (rc != PVT_OK) return rc;
+
+    // owned until every upload has succeeded: a failing HIP call must not leak the scene
+    struct Owner {
+        PvtScene* p;
+        ~Owner() { if (p) pvt_scene_destroy(p); }
+    } owner{new PvtScene()};
+    PvtScene* s = owner.p;
+    s->stage.reserve(kCursorSlots); s->stage_bytes.reserve(kCursorSlots); s->carry.reserve(kCursorSlots);   // (references stay valid)
+    s->emit_pool.reserve(kCursorSlots); s->emit_pool_bytes.reserve(kCursorSlots);
+    s->device = device;
+    s->lay = packed.lay;
+    s->nd = (int)packed.gd.size(); s->ni = (int)packed.gi.size();
+    s->nd_small = packed.nd_small; s->ni_small = packed.ni_small;
+    s->n_nodes = t->n_nodes; s->root = t->root_id; s->n_rec = t->n_recorders;
+    s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab;
+    s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
+    s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
+    s->grid = packed.grid;
+    for (int a = 0; a < 3; a++) s->grid_dims[a] = packed.grid_dims[a];
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    s->num_cu = prop.multiProcessorCount;
+    s->lds_limit = prop.sharedMemPerBlock;
+    s->consolidate = getenv("PVT_NO_CONSOLIDATE") == nullptr;
+    if (const char* env = getenv("PVT_BLOCKS_PER_CU")) s->dev_blocks_per_cu = atof(env);
+    if (const char* env = getenv("PVT_STAGE_BYTES")) s->stage_limit = (size_t)atoll(env);   // (tests: force several launches)
+    HIP_TRY(hipMalloc(&s->d_gd, packed.gd.size() * sizeof(double)));
+    HIP_TRY(hipMalloc(&s->d_gi, packed.gi.size() * sizeof(int)));
+    HIP_TRY(hipMalloc(&s->d_cursor, 64 * kCursorSlots + 256));   // + room for the PVT_STATS counters
+    HIP_TRY(hipMemset(s->d_cursor, 0, 64 * kCursorSlots + 256));
+    HIP_TRY(hipMalloc(&s->d_set_cursor, (size_t)kCursorSlots * kMaxSets * 4));
+    HIP_TRY(hipMalloc(&s->d_counters, 64 * 8 * 8));
+    HIP_TRY(hipMemset(s->d_counters, 0, 64 * 8 * 8));
+    HIP_TRY(hipMalloc(&s->d_stamp, (size_t)kCursorSlots * 2 * 8));
+    HIP_TRY(hipMemset(s->d_stamp, 0, (size_t)kCursorSlots * 2 * 8));
+    if (!packed.bvh_nodes.empty()) {
+        // a lane of a walk notes kMeshQ leaves before their triangles are tested -- one, in trees of a handful of records
+        // (the kernel applies the same rule per tree)
+        s->meshq = 1;
+        for (int r : packed.bvh_roots)
+            if (packed.bvh_nodes[r].skip - r > 16) s->meshq = kMeshQ;   // (15 records and the unused one after the root)
+        // The top levels of the trees go to LDS (pvt_bvh.h: stage_top), as many records as leave four workgroups per CU
+        // -- the mesh variants' four waves per SIMD -- their LDS in either kind of launch (tallies / histories).
+        const LdsPlan tally = plan_lds(s, false), hist = plan_lds(s, true);
+        const size_t other = (tally.bytes > hist.bytes ? tally.bytes : hist.bytes) + (size_t)s->meshq * kBlock * 4;
+        const size_t per_wg = (size_t)39 * 1024 * 4 / kMeshWaves;
+        size_t room = tally.ok && hist.ok && other < per_wg ? per_wg - other : 0;
+        if (room > 32 * 1024) room = 32 * 1024;
+        if (const char* env = getenv("PVT_MESH_TOP_BYTES")) {   // (developer override, never past the room computed above; 0: no copy)
+            const size_t asked = (size_t)atoll(env);
+            room = asked < room ? asked : room;
+        }
+        std::vector<pvt::BvhNode> top;
+        pvt::stage_top(packed.bvh_nodes, packed.bvh_roots, room / sizeof(pvt::BvhNode), top);
+        s->top_n = (int)top.size();
+        // what was planned without the copy must still hold with it (plan_lds reserves the copy first): same table
+        // placement, everything inside the LDS of a workgroup
+        const LdsPlan tally2 = plan_lds(s, false), hist2 = plan_lds(s, true);
+        const size_t with_top = (size_t)s->meshq * kBlock * 4 + (size_t)s->top_n * sizeof(pvt::BvhNode);
+        if (tally2.ok != tally.ok || hist2.ok != hist.ok || tally2.tab_lds != tally.tab_lds || hist2.tab_lds != hist.tab_lds ||
+            tally2.bytes + with_top > s->lds_limit || hist2.bytes + with_top > s->lds_limit)
+            return fail(PVT_ERR_INVALID, "internal: the LDS plan of a mesh scene changed when the copy of its trees' top levels was added");
+        if (s->top_n > 0) {
+            HIP_TRY(hipMalloc(&s->d_bvh_top, top.size() * sizeof(pvt::BvhNode)));
+            HIP_TRY(hipMemcpy(s->d_bvh_top, top.data(), top.size() * sizeof(pvt::BvhNode), hipMemcpyHostToDevice));
+        }
+        packed.bvh_nodes.push_back(pvt::BvhNode{});   // (one record past the end, kept for walks that fetch ahead)
+        HIP_TRY(hipMalloc(&s->d_bvh, packed.bvh_nodes.size() * sizeof(pvt::BvhNode)));
+        HIP_TRY(hipMalloc(&s->d_tris, packed.bvh_tris.size() * sizeof(pvt::MeshTri)));
+        HIP_TRY(hipMemcpy(s->d_bvh, packed.bvh_nodes.data(), packed.bvh_nodes.size() * sizeof(pvt::BvhNode), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_tris, packed.bvh_tris.data(), packed.bvh_tris.size() * sizeof(pvt::MeshTri), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(s->d_gd, packed.gd.data(), packed.gd.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_gi, packed.gi.data(), packed.gi.size() * sizeof(int), hipMemcpyHostToDevice));
+    owner.p = nullptr;
+    *out = s;
+    return PVT_OK;
+}
 
 int pvt_trace_device_records(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
                              const PvtEventRecords* rec, void* stream) {
