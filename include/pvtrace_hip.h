@@ -162,6 +162,24 @@ typedef struct PvtSceneTables {
     const double* ctab_value;           /* pooled reflectivities in [0, 1] */
 } PvtSceneTables;
 
+/* ---- refractive-index tables n(lambda): dispersion (extension within v13, passed to pvt_scene_create_ex) -----------
+ * A node with node_table[i] >= 0 refracts with n(lambda) of that table instead of refractive_index[i]: lambda the
+ * photon's current wavelength (nm), piecewise-linear, clamped at both ends, each step a + t (b - a), so a table
+ * holding a constant gives exactly that constant.  It is read wherever the index is: Fresnel reflectivity, the
+ * critical angle and Snell refraction on either side of a surface, and the clock (duration += d n / c, the phase
+ * index).  refractive_index[i] of such a node stays a finite positive number (the flattener stores n at the table's
+ * first wavelength); the tracer does not use it.  These tables are a separate struct so that PvtSceneTables keeps
+ * the length old callers pass. */
+typedef struct PvtIndexTables {
+    int32_t n_tables;               /* 0 = no dispersion (as a NULL struct) */
+    int32_t n_points;               /* length of the wavelength and value pools */
+    const int32_t* node_table;      /* (n_nodes) table of each node, -1 = its scalar refractive_index */
+    const int32_t* table_n;         /* (n_tables) points of each table, >= 1 */
+    const int32_t* table_start;     /* (n_tables) first point of each table in the pools */
+    const double* wavelength;       /* (n_points) pooled, nm, finite and strictly increasing per table */
+    const double* value;            /* (n_points) pooled indices, finite and positive */
+} PvtIndexTables;
+
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
@@ -296,6 +314,8 @@ int pvt_device_count(void);
 
 /* Pack the tables and upload them once to `device`. */
 int pvt_scene_create(const PvtSceneTables* tables, int device, PvtScene** out);
+/* The same with refractive-index tables (NULL = none: then exactly pvt_scene_create). */
+int pvt_scene_create_ex(const PvtSceneTables* tables, const PvtIndexTables* index_tables, int device, PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);

@@ -11,7 +11,8 @@ from pvtrace_amd.light import (
 )
 from pvtrace_amd.material import (
     Absorber, CoatedSurfaceDelegate, Coating, Distribution, FresnelSurfaceDelegate,
-    Luminophore, Material, NullSurfaceDelegate, Reactor, ReflectivityTable, Scatterer, Surface,
+    Luminophore, Material, NullSurfaceDelegate, Reactor, ReflectivityTable,
+    RefractiveIndexTable, Scatterer, Surface,
     SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian,
 )
 from pvtrace_amd.scene import Node, Scene

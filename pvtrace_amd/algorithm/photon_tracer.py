@@ -92,7 +92,7 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
     `maxpathlength`; EXIT when the interface is the world's; else ask the container's material whether the photon is
     absorbed on the way (ABSORB, then EMIT / SCATTER and on, or NONRADIATIVE / REACT and out) or reaches the surface,
     where the hit node's surface reflects or transmits it in that node's frame."""
-    from pvtrace_amd.material import Luminophore, Reactor, Scatterer
+    from pvtrace_amd.material import Luminophore, Reactor, Scatterer, index_at
 
     root = scene.root
     yield ray, Event.GENERATE, None
@@ -107,7 +107,7 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
             yield ray, Event.KILL, {"maxsteps": taken, "maxpathlength": ray.travelled, "container": container.name}
             return
         medium = container.geometry.material
-        index = medium.refractive_index
+        index = index_at(medium, ray.wavelength)
         names = {"hit": hit.name, "container": container.name, "adjacent": None if beyond is None else beyond.name}
         if hit is root:
             yield ray.propagate(distance, index), Event.EXIT, names

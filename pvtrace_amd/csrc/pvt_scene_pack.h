@@ -341,7 +341,7 @@ struct PackedScene {
     Lay lay{};
     std::vector<double> gd;
     std::vector<int> gi;
-    int nd_small = 0, ni_small = 0, n_ctab = 0, lazy_root = 0;
+    int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, lazy_root = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     int grid_dims[3] = {0, 0, 0};
@@ -352,7 +352,7 @@ struct PackedScene {
 
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
-int validate_tables(const PvtSceneTables* t) {
+int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -399,6 +399,27 @@ int validate_tables(const PvtSceneTables* t) {
         const double v = t->refractive_index[n];
         if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) return fail(PVT_ERR_INVALID, "refractive indices must be finite and positive");
     }
+    if (x && x->n_tables != 0) {   // refractive-index tables n(lambda) (PvtIndexTables, pvt_scene_create_ex)
+        const int NT = x->n_tables;
+        if (NT < 0 || !x->node_table || !x->table_n || !x->table_start || !x->wavelength || !x->value)
+            return fail(PVT_ERR_INVALID, "index tables: missing arrays");
+        for (int n = 0; n < N; n++)
+            if (x->node_table[n] < -1 || x->node_table[n] >= NT) return fail(PVT_ERR_INVALID, "index tables: node names a missing table");
+        long long total = 0;
+        for (int j = 0; j < NT; j++) {
+            const long long np = x->table_n[j], p0 = x->table_start[j];
+            if (np < 1 || p0 < 0 || p0 + np > x->n_points) return fail(PVT_ERR_INVALID, "index tables: point range out of bounds");
+            for (long long i = 0; i < np; i++)
+                if (!std::isfinite(x->wavelength[p0 + i]) || (i > 0 && !(x->wavelength[p0 + i] > x->wavelength[p0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "index tables: wavelengths must be finite and strictly increasing");
+            for (long long i = 0; i < np; i++) {   // (the bounds of the scalar indices: the lanes divide by these)
+                const double v = x->value[p0 + i];
+                if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) return fail(PVT_ERR_INVALID, "index tables: values must be finite and positive, in (1e-100, 1e100)");
+            }
+            total += 2 * np;
+        }
+        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "index tables: more than 2^27 doubles");
+    }
     // runs [start, start + count) into a table of `size` rows
     auto bad_run = [](long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; };
     for (int n = 0; n < N; n++) {
@@ -442,7 +463,7 @@ struct Classes {
     bool by_node = false;                    // Lay::by_node
 };
 
-Classes classify_nodes(const PvtSceneTables* t) {
+Classes classify_nodes(const PvtSceneTables* t, const PvtIndexTables* x) {
     const int N = t->n_nodes;
     Classes k;
     // rotation classes: nodes whose two 3x3 blocks have the same bits share a record (and, in the wave-uniform
@@ -461,12 +482,15 @@ Classes classify_nodes(const PvtSceneTables* t) {
         if (cls < 0) { cls = (int)k.rot_first.size(); k.rot_first.push_back(n); }
         k.rot_class[n] = cls;
     }
-    // refractive-index classes (bit-identical indices)
+    // refractive-index classes (bit-identical indices and the same index table: a dispersive node never shares a class
+    // with a scalar one)
+    auto table_of = [&](int n) { return x && x->n_tables > 0 ? x->node_table[n] : -1; };
     k.idx_class.resize(N);
     for (int n = 0; n < N; n++) {
         int cls = -1;
         for (size_t e = 0; e < k.idx_first.size() && cls < 0; e++)
-            if (std::memcmp(&t->refractive_index[k.idx_first[e]], &t->refractive_index[n], 8) == 0) cls = (int)e;
+            if (std::memcmp(&t->refractive_index[k.idx_first[e]], &t->refractive_index[n], 8) == 0 && table_of(k.idx_first[e]) == table_of(n))
+                cls = (int)e;
         if (cls < 0) { cls = (int)k.idx_first.size(); k.idx_first.push_back(n); }
         k.idx_class[n] = cls;
     }
@@ -585,9 +609,10 @@ Records component_records(const PvtSceneTables* t, const Spectra& sp, bool by_no
 // ---- layout: fixed-stride records, then the pooled spectra.  The small tables come first in the blob -- records, then
 // critical angles, rotation classes, index classes and the node grid -- and the spectra last: when a scene's spectra are
 // too large for LDS, a workgroup still stages everything before `spec_d` (KArgs::nd_lds; the guide tables are the tail
-// of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes.
-std::vector<int> lay_out(const PvtSceneTables* t, const Classes& k, const Spectra& sp, const Records& recs, const NodeGrid& grid,
-                         PackedScene* p) {
+// of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes, and in
+// *rtab_at where each refractive-index table goes.
+std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const Classes& k, const Spectra& sp, const Records& recs,
+                         const NodeGrid& grid, PackedScene* p, std::vector<int>* rtab_at) {
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size(), CR = (int)recs.rec_comp.size();
     Lay& lay = p->lay;
@@ -603,8 +628,11 @@ std::vector<int> lay_out(const PvtSceneTables* t, const Classes& k, const Spectr
     lay.rot_d = small_d + (lay.crit_d >= 0 ? 2 * M * M : 0);
     lay.ncls_d = lay.rot_d + Q * RT;
     lay.by_node = k.by_node ? 1 : 0;
-    lay.grid_d = p->grid ? lay.ncls_d + M * 2 : -1;
-    p->nd_small = lay.ncls_d + M * 2 + (p->grid ? 14 + (int)grid.masks.size() : 0);
+    // (scenes with index tables) the index classes' dispersion records follow theirs: M x {where the class's table
+    // starts in the double blob, its points (0: the class is scalar)}, as doubles
+    const int disp = p->n_rtab > 0 ? M * 2 : 0;
+    lay.grid_d = p->grid ? lay.ncls_d + M * 2 + disp : -1;
+    p->nd_small = lay.ncls_d + M * 2 + disp + (p->grid ? 14 + (int)grid.masks.size() : 0);
     // coating reflectivity tables (KI_T*): their axes and values follow the spectra, so they go wherever the spectra go
     // (LDS with the whole blob, else global memory) and a scene without them lays out exactly as before
     int spec_end = p->nd_small + sp.len;
@@ -612,6 +640,12 @@ std::vector<int> lay_out(const PvtSceneTables* t, const Classes& k, const Spectr
     for (int j = 0; j < p->n_ctab; j++) {
         ctab_at[j] = spec_end;
         spec_end += t->ctab_nw[j] + t->ctab_na[j] + t->ctab_nw[j] * t->ctab_na[j];
+    }
+    // refractive-index tables (wavelengths, then values) likewise, after the coating tables
+    rtab_at->assign(p->n_rtab, 0);
+    for (int j = 0; j < p->n_rtab; j++) {
+        (*rtab_at)[j] = spec_end;
+        spec_end += 2 * x->table_n[j];
     }
     p->gd.assign((size_t)spec_end + 1, 0.0);
     lay.comp_i = N * NI;
@@ -680,8 +714,8 @@ void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* 
 }
 
 // ---- fill: every record, table and guide table of the two blobs, and the BVHs of the meshes
-int fill(const PvtSceneTables* t, const Classes& k, const Spectra& sp, const Records& recs, const NodeGrid& grid,
-         const std::vector<int>& ctab_at, PackedScene* p) {
+int fill(const PvtSceneTables* t, const PvtIndexTables* x, const Classes& k, const Spectra& sp, const Records& recs,
+         const NodeGrid& grid, const std::vector<int>& ctab_at, const std::vector<int>& rtab_at, PackedScene* p) {
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size();
     const Lay& lay = p->lay;
@@ -696,13 +730,17 @@ int fill(const PvtSceneTables* t, const Classes& k, const Spectra& sp, const Rec
         std::memcpy(&d[13], &bits, 8);
         std::memcpy(&d[14], grid.masks.data(), grid.masks.size() * 8);
     }
+    // index table of each class (-1: scalar)
+    auto class_table = [&](int m) { return p->n_rtab > 0 ? x->node_table[k.idx_first[m]] : -1; };
     if (lay.crit_d >= 0)
         for (int c = 0; c < M; c++)
             for (int a = 0; a < M; a++) {
                 const double n1 = t->refractive_index[k.idx_first[c]], n2 = t->refractive_index[k.idx_first[a]];
-                const double crit = n2 < n1 ? pvt_asin(n2 / n1) : INFINITY;   // same pvt_asin as the device
+                double crit = n2 < n1 ? pvt_asin(n2 / n1) : INFINITY;   // same pvt_asin as the device
+                // a pair with a dispersive side has no angle of its own: NaN sends its lanes to the computed branch
+                if (class_table(c) >= 0 || class_table(a) >= 0) crit = NAN;
                 gd[lay.crit_d + c * M + a] = crit;
-                gd[lay.ccrit_d + c * M + a] = cosine_threshold(crit);
+                gd[lay.ccrit_d + c * M + a] = crit == crit ? cosine_threshold(crit) : NAN;
             }
     for (int q = 0; q < Q; q++) {
         double* d = gd.data() + lay.rot_d + q * RT;
@@ -716,6 +754,17 @@ int fill(const PvtSceneTables* t, const Classes& k, const Spectra& sp, const Rec
     for (int m = 0; m < M; m++) {
         gd[lay.ncls_d + m * 2] = t->refractive_index[k.idx_first[m]];
         gd[lay.ncls_d + m * 2 + 1] = 1.0 / t->refractive_index[k.idx_first[m]];
+        if (p->n_rtab > 0) {
+            const int j = class_table(m);
+            gd[lay.ncls_d + M * 2 + m * 2] = j >= 0 ? rtab_at[j] : 0;
+            gd[lay.ncls_d + M * 2 + m * 2 + 1] = j >= 0 ? x->table_n[j] : 0;
+        }
+    }
+    for (int j = 0; j < p->n_rtab; j++) {   // wavelengths (nm), then the indices
+        const int np = x->table_n[j], p0 = x->table_start[j];
+        double* d = gd.data() + rtab_at[j];
+        for (int i = 0; i < np; i++) d[i] = x->wavelength[p0 + i];
+        for (int i = 0; i < np; i++) d[np + i] = x->value[p0 + i];
     }
     fill_candidates(t, recs, p);
     for (int n = 0; n < N; n++) {
@@ -890,19 +939,25 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
     }
 }
 
-// The tables (n_nodes and n_recorders already checked by the caller) -> *p.  No HIP call.
-int pack_scene(const PvtSceneTables* t, PackedScene* p) {
-    int rc = validate_tables(t);
+// The tables (n_nodes and n_recorders already checked by the caller) and the refractive-index tables (x, NULL = none)
+// -> *p.  No HIP call.
+int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, PackedScene* p) {
+    int rc = validate_tables(t, x);
     if (rc != PVT_OK) return rc;
-    const Classes classes = classify_nodes(t);
+    const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
     const Records records = component_records(t, spectra, classes.by_node);
     NodeGrid grid;
     p->grid = plan_node_grid(t, &grid);
     for (int a = 0; a < 3; a++) p->grid_dims[a] = p->grid ? grid.n[a] : 0;
     p->n_ctab = t->n_coatings > 0 ? t->n_coat_tables : 0;
-    const std::vector<int> ctab_at = lay_out(t, classes, spectra, records, grid, p);
-    rc = fill(t, classes, spectra, records, grid, ctab_at, p);
+    p->n_rtab = 0;   // (a table no node uses is validated, never placed)
+    if (x)
+        for (int n = 0; n < t->n_nodes; n++)
+            if (x->n_tables > 0 && x->node_table[n] >= 0) p->n_rtab = x->n_tables;
+    std::vector<int> rtab_at;
+    const std::vector<int> ctab_at = lay_out(t, x, classes, spectra, records, grid, p, &rtab_at);
+    rc = fill(t, x, classes, spectra, records, grid, ctab_at, rtab_at, p);
     if (rc != PVT_OK) return rc;
     prove_shortcuts(t, p);
     return PVT_OK;

@@ -96,7 +96,7 @@ struct PvtScene {
     EmitOff eoff{};
     int nd = 0, ni = 0;
     int nd_small = 0, ni_small = 0;   // ... of which everything but the spectra / their guide tables (the blobs' heads)
-    int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_lights = 0;
+    int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
     double* d_gd = nullptr;
     int* d_gi = nullptr;
     double* d_ed = nullptr;
@@ -224,7 +224,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.nd = s->nd; a.ni = s->ni;
     a.nd_lds = 0; a.ni_lds = 0;
     a.n_nodes = s->n_nodes; a.root = s->root; a.n_rec = s->n_rec; a.total_bins = s->total_bins;
-    a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_lights = s->n_lights;
+    a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_rtab = s->n_rtab; a.n_lights = s->n_lights;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -589,6 +589,10 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
 extern "C" {
 
 int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
+    return pvt_scene_create_ex(t, nullptr, device, out);
+}
+
+int pvt_scene_create_ex(const PvtSceneTables* t, const PvtIndexTables* x, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -596,7 +600,7 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, &packed);
+    const int rc = pack_scene(t, x, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -612,7 +616,7 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
     s->nd = (int)packed.gd.size(); s->ni = (int)packed.gi.size();
     s->nd_small = packed.nd_small; s->ni_small = packed.ni_small;
     s->n_nodes = t->n_nodes; s->root = t->root_id; s->n_rec = t->n_recorders;
-    s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab;
+    s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab; s->n_rtab = packed.n_rtab;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
     s->grid = packed.grid;

@@ -98,7 +98,8 @@ struct Lay {  // record bases (elements) inside the blobs; spectra follow the re
                     // guard, one word of {nx | ny << 8 | nz << 16 | 64-bit words per cell << 24 | odd << 28}}, then per
                     // cell the bit mask of the nodes filed under it (x fastest)
     int rot_d;      // rotation classes x RT doubles (every node has one; the identity's is only read by the Lambertian branch)
-    int ncls_d;     // refractive-index classes x {n, RN(1/n)}
+    int ncls_d;     // refractive-index classes x {n, RN(1/n)}; in scenes with index tables (KArgs::n_rtab) followed by
+                    // n_cls x {where the class's table n(lambda) starts in the double blob, its points (0: scalar class)}
     int n_cls;      // refractive-index classes (side of the crit tables)
     int by_node;    // 1: a scene of few nodes -- index classes and recorder candidate blocks are numbered like the nodes, so the
                     // lanes index the tables by node without reading NI_NCLS / NI_CAND first (one dependent LDS read fewer
@@ -122,7 +123,8 @@ struct KArgs {
     int nd, ni;         // blob lengths
     int nd_lds, ni_lds; // (variants whose tables do not fit LDS) heads of the blobs that are staged all the same: everything
                         // but the spectra and their guide tables (0: nothing)
-    int n_nodes, root, n_rec, total_bins, n_coat, n_ctab, n_lights;   // n_ctab: coating reflectivity tables
+    int n_nodes, root, n_rec, total_bins, n_coat, n_ctab, n_rtab, n_lights;   // n_ctab: coating reflectivity tables,
+                                                                               // n_rtab: refractive-index tables
     // rays in (null -> device emission)
     const double* pos;
     const double* dir;
@@ -452,6 +454,26 @@ __device__ __forceinline__ double coat_table_r(const double* wls, int nw, const 
 __device__ __attribute__((noinline)) double coat_table_r_call(const double* wls, int nw, const double* angs, int na,
                                                               const double* vals, double wl, double c1) {
     return coat_table_r(wls, nw, angs, na, vals, wl, c1);
+}
+
+// Refractive-index tables n(lambda) (the Python RefractiveIndexTable.at is the same arithmetic): `np` wavelengths, then
+// `np` indices, from `xs` (LDS or global memory); piecewise linear, clamped at both ends, a + t (b - a)
+__device__ __forceinline__ double index_table_n(const double* xs, int np, double wl) {
+    int lo, hi;
+    double t;
+    coat_bracket(xs, np, wl, lo, hi, t);
+    const double a = xs[np + lo];
+    return a + t * (xs[np + hi] - a);
+}
+// The whole lookup of a node of index class k as a FUNCTION: `recs` points at the classes' {table offset, points}
+// records, `tab` at the blob the tables are read from.  Inlined at its three sites, the lookup (never taken there: the
+// flag is off) put 1.5 KB into the step loop of the headline scene and cost it 1.3 % of its throughput; called, the
+// sites add 0.5 KB and the throughput is the parent's within the noise of an alternating A/B.  (The 256-recorder
+// tally variants inline it: with a call one of their vector registers goes to scratch.)
+__device__ __attribute__((noinline)) double index_class_n_call(const double* recs, const double* tab, int k, double n, double wl) {
+    const int np = (int)recs[2 * k + 1];
+    if (np == 0) return n;
+    return index_table_n(tab + (int)recs[2 * k], np, wl);
 }
 
 // same, tables in global memory (emitter spectra)
@@ -877,13 +899,13 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
         (A.emit_method == PVT_EMIT_FULL ? 1u << UF_EMIT_FULL : 0u) | (A.emit_method == PVT_EMIT_KT ? 1u << UF_EMIT_KT : 0u) |
         (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u) |
-        (A.n_ctab > 0 ? 1u << UF_CTAB : 0u);
+        (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u);
     if constexpr (TAIL && PVT_TAIL_LAZY) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
@@ -1064,6 +1086,17 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     int hr_surf = 0;
     double hr_n2 = 0.0, hr_rn2 = 0.0, hr_cc = 0.0;
     constexpr bool kHoist = TAIL && PVT_TAIL_HOIST;
+    // (scenes with index tables, UF_DISP) the refractive index of `node` at the photon's wavelength: its class's table
+    // n(lambda), or `n`, the node's scalar index, when the class has none (a dispersive node has a class of its own)
+    auto index_at = [&](int node, double n) -> double {
+        const int k = uf(UF_BY_NODE) ? node : T.iv(node * NI + NI_NCLS);
+        const int q = L.ncls_d + 2 * L.n_cls;
+        const double* tab = TAB_LDS == 1 ? T.ld : T.hd;   // (where the spectra are read from)
+        if constexpr (MESH || SEENW == 1) return index_class_n_call((TAB_LDS != 0 ? T.ld : T.hd) + q, tab, k, n, wl);
+        const int np = (int)T.dv(q + 2 * k + 1);
+        if (np == 0) return n;
+        return index_table_n(tab + (int)T.dv(q + 2 * k), np, wl);
+    };
     int rec_slot = -1;   // recorded rays: index among them (row block rec_slot * max_events), else -1
     Seen<SEENW> seen;
 #pragma unroll
@@ -2145,6 +2178,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         int cbase = 0, ccount = 0, crec = 0;   // first component id, count, first component record (identical components share records)
         if (pend) {
             n_container = T.dv(container * ND + ND_N);
+            if (uf(UF_DISP)) n_container = index_at(container, n_container);
             cbase = T.iv(container * NI + NI_CSTART); ccount = T.iv(container * NI + NI_CCOUNT);
             if (uf(UF_BY_NODE)) crec = cbase;   // (scenes of few nodes keep one record per component id)
             else crec = T.iv(container * NI + NI_CREC);
@@ -2164,6 +2198,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     hr_n2 = T.dv(adjacent * ND + ND_N);
                     hr_rn2 = T.dv(L.ncls_d + ka * 2 + 1);
                     hr_cc = uf(UF_CRIT) ? T.dv(L.ccrit_d + kc * L.n_cls + ka) : __builtin_nan("");
+                    if (uf(UF_DISP)) { hr_n2 = index_at(adjacent, hr_n2); hr_rn2 = div_normal(1.0, hr_n2); }
                 }
             }
             // (tail function: a photon that bounces inside one body keeps its wavelength, and with it the coefficients of
@@ -2452,6 +2487,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if (!kHoist && !uf(UF_BY_NODE)) { kc = T.iv(container * NI + NI_NCLS); ka = T.iv(adjacent * NI + NI_NCLS); }
                 const int ncls_d = L.ncls_d, n_cls = L.n_cls;
                 rn2 = kHoist ? hr_rn2 : T.dv(ncls_d + ka * 2 + 1);
+                if (!kHoist && uf(UF_DISP)) {   // (the tail function has looked them up with the records above)
+                    n1 = n_container;               // (the clock's: the same node at the same wavelength)
+                    n2 = index_at(adjacent, n2);
+                    rn2 = div_normal(1.0, n2);
+                }
                 // critical angle asin(n2/n1): a function of the node pair, tabulated by the host
                 // with the same pvt_asin (small scenes), else computed here
                 bool tir;
@@ -2462,8 +2502,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if (cc == cc) tir = c1 < cc;
                 else {   // (rare: the threshold could not be proven, or the scene has too many indices for the tables)
                     if (kHoist && !uf(UF_BY_NODE)) { kc = T.iv(container * NI + NI_NCLS); ka = T.iv(adjacent * NI + NI_NCLS); }
-                    if (crit_tab) tir = pvt_acos(c1) > T.dv(L.crit_d + kc * n_cls + ka);
-                    else tir = n2 < n1 && pvt_acos(c1) > pvt_asin(div_known(n2, n1, T.dv(ncls_d + kc * 2 + 1)));
+                    // (a pair with a dispersive side has a NaN angle in the table: its quotient is formed here, with n at
+                    // the photon's wavelength)
+                    const double crit = crit_tab ? T.dv(L.crit_d + kc * n_cls + ka) : __builtin_nan("");
+                    if (crit == crit) tir = pvt_acos(c1) > crit;
+                    else tir = n2 < n1 && pvt_acos(c1) > pvt_asin(uf(UF_DISP) ? div_normal(n2, n1) : div_known(n2, n1, T.dv(ncls_d + kc * 2 + 1)));
                 }
                 if (tir) {
                     r = 1.0;

@@ -31,6 +31,19 @@ def _host_outputs(compiled, n_rays, record_every, max_events):
     return out, n_recorded, rows
 
 
+def _host_buffer_scene(compiled):
+    """PvtSceneTables of `compiled` for the host-buffer entries, which keep the reference's interface: that has no
+    place for refractive-index tables, and tracing the scalar column instead would silently drop the dispersion."""
+    if int(getattr(compiled, "n_ri_tables", 0)) > 0:
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has refractive-index tables (dispersion), which the host-buffer trace_bundle entry (the "
+            "reference's interface) cannot take; trace it with engine.simulate."
+        )
+    return N.scene_tables_struct(compiled)
+
+
 def trace_bundle(compiled, positions, directions, wavelengths, seed, maxsteps, max_events,
                  emit_method, num_threads, record_every, *, device=0, devices=None, ray_offset=0,
                  emitter=None, emit_seed=0, timing=None, flags=0):
@@ -42,7 +55,7 @@ def trace_bundle(compiled, positions, directions, wavelengths, seed, maxsteps, m
     ids, repeats allowed) splits the bundle over several GPUs inside this one call
     (`pvt_trace_bundle_multi`); the result is independent of the list."""
     lib = N.load_library()
-    st, keep = N.scene_tables_struct(compiled)
+    st, keep = _host_buffer_scene(compiled)
     if positions is None:
         n = int(wavelengths)
         rays_ref = None
@@ -99,7 +112,7 @@ def trace_bundle_sets(compiled, positions, directions, wavelengths, seed, maxste
     """Tally-mode trace of consecutive bundles of `bundle` rays in ONE launch (host buffers; the C entry
     `pvt_trace_bundle` with `PvtTraceParams.tally_bundle`) -> one dict of rec_* arrays per bundle."""
     lib = N.load_library()
-    st, keep = N.scene_tables_struct(compiled)
+    st, keep = _host_buffer_scene(compiled)
     pos = np.ascontiguousarray(positions, dtype=np.float64)
     dirs = np.ascontiguousarray(directions, dtype=np.float64)
     wl = np.ascontiguousarray(wavelengths, dtype=np.float64)

@@ -13,6 +13,8 @@ Coatings-notebook scene run on the device.
 Everything here is host-side numpy executed once per `simulate` call; the
 tables (a few KB) are packed and uploaded to HBM once by `native.DeviceScene`.
 """
+import numbers
+
 import numpy as np
 
 from pvtrace_amd.engine.recorder import (
@@ -37,6 +39,7 @@ from pvtrace_amd.material import (
     NullSurfaceDelegate,
     Reactor,
     ReflectivityTable,
+    RefractiveIndexTable,
     Scatterer,
     isotropic,
 )
@@ -116,6 +119,11 @@ class CompiledScene:
         self.comp_count = np.zeros(count, dtype=_I32)
         self.coat_start = np.zeros(count, dtype=_I32)
         self.coat_count = np.zeros(count, dtype=_I32)
+        # Refractive-index tables n(wavelength) of the dispersive nodes (ri_table: -1 = the scalar index), pooled like
+        # the coating tables: per table its length and where its wavelengths and values start in the pools.  The
+        # scalar column of a dispersive node holds n at the table's first wavelength.
+        self.ri_table = np.full(count, -1, dtype=_I32)
+        rtab = {"index": {}, "n": [], "start": [], "wavelength": [], "value": []}
         self.mesh_face_start = np.zeros(count, dtype=_I32)
         self.mesh_face_count = np.zeros(count, dtype=_I32)
         self._mesh_pool = {"vertices": [], "faces": [], "normals": [], "nv": 0, "nf": 0}
@@ -141,7 +149,7 @@ class CompiledScene:
                 raise UnsupportedSceneError(
                     f"Node {node.name!r} has geometry without a material."
                 )
-            self.refractive_index[i] = float(material.refractive_index)
+            self.ri_table[i] = self._lower_refractive_index(i, node, material.refractive_index, rtab)
 
             self.coat_start[i] = len(coat_rows)
             self.surface_type[i] = self._lower_surface(node, material, coat_rows)
@@ -152,6 +160,12 @@ class CompiledScene:
                 self._lower_component(node, component, comp_cols, pools)
                 self.component_names.append(component.name)
             self.comp_count[i] = len(material.components)
+
+        self.n_ri_tables = len(rtab["n"])
+        self.rtab_n = np.array(rtab["n"], dtype=_I32)
+        self.rtab_start = np.array(rtab["start"], dtype=_I32)
+        self.rtab_wavelength = np.array(rtab["wavelength"], dtype=_F64)
+        self.rtab_value = np.array(rtab["value"], dtype=_F64)
 
         self.comp_type = np.array(comp_cols["type"], dtype=_I32)
         self.comp_qy = np.array(comp_cols["qy"], dtype=_F64)
@@ -274,6 +288,25 @@ class CompiledScene:
             "NullSurfaceDelegate and CoatedSurfaceDelegate (declarative "
             "coatings) are supported."
         )
+
+    def _lower_refractive_index(self, i, node, index, rtab):
+        if isinstance(index, RefractiveIndexTable):
+            key = id(index)
+            if key not in rtab["index"]:
+                rtab["index"][key] = (len(rtab["n"]), index)   # (the table itself keeps its id from being reused)
+                rtab["n"].append(index.wavelength.size)
+                rtab["start"].append(len(rtab["wavelength"]))
+                rtab["wavelength"].extend(index.wavelength.tolist())
+                rtab["value"].extend(index.values.tolist())
+            self.refractive_index[i] = float(index.values[0])
+            return rtab["index"][key][0]
+        if not isinstance(index, numbers.Real):
+            raise UnsupportedSceneError(
+                f"Node {node.name!r}: refractive_index must be a number or a RefractiveIndexTable, "
+                f"got {type(index).__name__}."
+            )
+        self.refractive_index[i] = float(index)
+        return -1
 
     @staticmethod
     def _pool_coating_table(table, ctab):
@@ -453,6 +486,7 @@ class CompiledScene:
         "coat_table", "ctab_nw", "ctab_na", "ctab_wl_start", "ctab_angle_start", "ctab_value_start",
         "ctab_wavelength", "ctab_angle", "ctab_value",
         "mesh_face_start", "mesh_face_count", "mesh_vertices", "mesh_faces", "mesh_normals",
+        "ri_table", "rtab_n", "rtab_start", "rtab_wavelength", "rtab_value",
     )
 
     def tables(self):

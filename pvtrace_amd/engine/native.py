@@ -66,6 +66,15 @@ class PvtSceneTables(C.Structure):
     ]
 
 
+class PvtIndexTables(C.Structure):
+    """Refractive-index tables n(wavelength) of a scene (include/pvtrace_hip.h; pvt_scene_create_ex)."""
+    _fields_ = [
+        ("n_tables", C.c_int32), ("n_points", C.c_int32),
+        ("node_table", _p_i32), ("table_n", _p_i32), ("table_start", _p_i32),
+        ("wavelength", _p_f64), ("value", _p_f64),
+    ]
+
+
 class PvtEmitterTables(C.Structure):
     _fields_ = [
         ("n_lights", C.c_int32), ("n_spec", C.c_int32),
@@ -169,6 +178,24 @@ def scene_tables_struct(compiled):
     return st, keep
 
 
+def index_tables_struct(compiled):
+    """PvtIndexTables over the refractive-index tables of a CompiledScene -> (struct or None, keepalive); None when
+    the scene has no dispersive node (what pvt_scene_create_ex takes for "none")."""
+    if int(getattr(compiled, "n_ri_tables", 0)) == 0:
+        return None, {}
+    st = PvtIndexTables()
+    st.n_tables = int(compiled.n_ri_tables)
+    st.n_points = int(compiled.rtab_wavelength.shape[0])
+    keep = {}
+    for name, field, want in (("ri_table", "node_table", np.int32), ("rtab_n", "table_n", np.int32),
+                              ("rtab_start", "table_start", np.int32), ("rtab_wavelength", "wavelength", np.float64),
+                              ("rtab_value", "value", np.float64)):
+        arr = np.ascontiguousarray(getattr(compiled, name), dtype=want)
+        keep[field] = arr
+        setattr(st, field, np_ptr(arr))
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -237,6 +264,7 @@ def declare_signatures(lib, names):
         "pvt_last_error": ([], C.c_char_p),
         "pvt_device_count": ([], C.c_int),
         "pvt_scene_create": ([C.POINTER(PvtSceneTables), C.c_int, C.POINTER(vp)], C.c_int),
+        "pvt_scene_create_ex": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
@@ -290,6 +318,7 @@ ABI_SYMBOLS = (
     "pvt_trace_bundle_multi", "pvt_shard_range", "pvt_trace_device_records", "pvt_unpack_records_device",
     "pvt_scene_carry_pending", "pvt_last_multi_reduce", "pvt_node_grid_plan", "pvt_scene_carry_discard", "pvt_scene_trim",
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
+    "pvt_scene_create_ex",
 )
 
 _lib = None
@@ -439,9 +468,11 @@ class DeviceScene:
         self.compiled = compiled
         self.device = int(device)
         st, keep = scene_tables_struct(compiled)
+        xt, xkeep = index_tables_struct(compiled)
         handle = C.c_void_p()
-        check(self.lib.pvt_scene_create(C.byref(st), self.device, C.byref(handle)),
-              "pvt_scene_create")
+        check(self.lib.pvt_scene_create_ex(C.byref(st), None if xt is None else C.byref(xt), self.device,
+                                           C.byref(handle)),
+              "pvt_scene_create_ex")
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a

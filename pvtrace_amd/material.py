@@ -253,12 +253,24 @@ def _flipped_normal(geometry, ray):
     return normal
 
 
+def index_at(material, wavelength):
+    """The refractive index of `material` at `wavelength` (nm): its `RefractiveIndexTable` evaluated there, or its
+    scalar index AS IT IS.  The one place the host evaluates an index (`Material.refractive_index_at` is this, as a
+    float).  The surface delegates call it directly: they are handed any object with a `refractive_index` (the
+    reference's duck-typed nodes, rays without a wavelength), and a scalar index passed on unconverted keeps their
+    arithmetic what it was, float for float."""
+    n = material.refractive_index
+    if isinstance(n, RefractiveIndexTable):
+        return n.at(wavelength)
+    return n
+
+
 class FresnelSurfaceDelegate(SurfaceDelegate):
     """Fresnel reflection / Snell refraction from the two refractive indices."""
 
     def reflectivity(self, surface, ray, geometry, container, adjacent):
-        n1 = container.geometry.material.refractive_index
-        n2 = adjacent.geometry.material.refractive_index
+        n1 = index_at(container.geometry.material, getattr(ray, "wavelength", None))
+        n2 = index_at(adjacent.geometry.material, getattr(ray, "wavelength", None))
         normal = _flipped_normal(geometry, ray)
         cosang = float(np.clip(np.dot(normal, ray.direction), -1.0, 1.0))
         return float(fresnel_reflectivity(math.acos(cosang), n1, n2))
@@ -268,8 +280,8 @@ class FresnelSurfaceDelegate(SurfaceDelegate):
         return tuple(specular_reflection(ray.direction, normal).tolist())
 
     def transmitted_direction(self, surface, ray, geometry, container, adjacent):
-        n1 = container.geometry.material.refractive_index
-        n2 = adjacent.geometry.material.refractive_index
+        n1 = index_at(container.geometry.material, getattr(ray, "wavelength", None))
+        n2 = index_at(adjacent.geometry.material, getattr(ray, "wavelength", None))
         normal = _flipped_normal(geometry, ray)
         return tuple(fresnel_refraction(ray.direction, normal, n1, n2).tolist())
 
@@ -355,6 +367,54 @@ class ReflectivityTable(object):
         r0 = g[a_lo, wl_lo] + tw * (g[a_lo, wl_hi] - g[a_lo, wl_lo])
         r1 = g[a_hi, wl_lo] + tw * (g[a_hi, wl_hi] - g[a_hi, wl_lo])
         return float(r0 + ta * (r1 - r0))
+
+
+class RefractiveIndexTable(object):
+    """Refractive index of a material as a table n(wavelength): dispersion.
+
+    wavelength : strictly increasing wavelengths in nm, at least one.
+    values : the index at each wavelength; finite and positive, in (1e-100, 1e100) like every index the engine takes.
+
+    `at(wavelength)` interpolates piecewise-linearly, clamping at both ends, each step formed as a + t (b - a), so a
+    table holding a constant c evaluates to exactly c.  This is what the device computes per photon at the photon's
+    current wavelength, wherever the scalar index would be used: Fresnel reflectivity, the critical angle, Snell
+    refraction and the time of flight (the phase index).
+    """
+
+    def __init__(self, wavelength, values):
+        wl = np.array(wavelength, dtype=np.float64)
+        if wl.ndim != 1 or wl.size < 1:
+            raise ValueError("wavelength must be a non-empty 1-D sequence")
+        if not np.all(np.isfinite(wl)) or np.any(np.diff(wl) <= 0.0):
+            raise ValueError("wavelength must be finite and strictly increasing")
+        vals = np.array(values, dtype=np.float64)
+        if vals.shape != (wl.size,):
+            raise ValueError(f"values must have shape (n_wavelength,) = ({wl.size},), got {vals.shape}")
+        if not np.all(np.isfinite(vals)) or np.any(vals <= 1e-100) or np.any(vals >= 1e100):
+            # (the bounds the engine holds every index to, scalar or tabulated: the device divides by them)
+            raise ValueError("values must be finite and positive, in (1e-100, 1e100)")
+        self.wavelength = wl
+        self.values = vals
+
+    def at(self, wavelength):
+        """n at `wavelength` (nm)."""
+        lo, hi, t = _bracket(self.wavelength, float(wavelength))
+        a = self.values[lo]
+        return float(a + t * (self.values[hi] - a))
+
+    @classmethod
+    def from_sellmeier(cls, B, C, wavelength):
+        """Tabulate the Sellmeier equation n^2 = 1 + sum_i B_i lam^2 / (lam^2 - C_i) (lam in um, C_i in um^2) at the
+        wavelengths `wavelength` (nm).  Host only: the device interpolates the table."""
+        B = np.asarray(B, dtype=np.float64)
+        C = np.asarray(C, dtype=np.float64)
+        if B.ndim != 1 or B.shape != C.shape:
+            raise ValueError("B and C must be 1-D sequences of the same length")
+        lam2 = (np.asarray(wavelength, dtype=np.float64) * 1e-3) ** 2
+        n2 = 1.0 + np.sum(B[:, None] * lam2[None, :] / (lam2[None, :] - C[:, None]), axis=0)
+        if not np.all(n2 > 0.0):
+            raise ValueError("the Sellmeier equation gives no real index on this grid")
+        return cls(wavelength, np.sqrt(n2))
 
 
 class Coating(object):
@@ -643,10 +703,16 @@ class Luminophore(Scatterer):
 
 
 class Material(object):
+    """refractive_index : a number, or a `RefractiveIndexTable` n(wavelength); stored as given."""
+
     def __init__(self, refractive_index, surface=None, components=None):
         self.refractive_index = refractive_index
         self.surface = Surface() if surface is None else surface
         self.components = [] if components is None else components
+
+    def refractive_index_at(self, wavelength):
+        """The refractive index at `wavelength` (nm), a float for either form of `refractive_index`."""
+        return float(index_at(self, wavelength))
 
     def total_attenutation_coefficient(self, wavelength):
         return float(np.sum([c.coefficient(wavelength) for c in self.components]))
