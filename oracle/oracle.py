@@ -47,6 +47,10 @@ def lib():
             C.POINTER(N.PvtSceneTables), C.POINTER(N.PvtRays), C.POINTER(N.PvtTraceParams),
             C.POINTER(N.PvtTallies), C.POINTER(N.PvtEventLog), C.c_int, C.c_int]
         L.pvt_oracle_trace.restype = C.c_int
+        L.pvt_oracle_trace_ex.argtypes = [
+            C.POINTER(N.PvtSceneTables), C.POINTER(N.PvtIndexTables), C.POINTER(N.PvtRays), C.POINTER(N.PvtTraceParams),
+            C.POINTER(N.PvtTallies), C.POINTER(N.PvtEventLog), C.c_int, C.c_int]
+        L.pvt_oracle_trace_ex.restype = C.c_int
         L.pvt_oracle_emit.argtypes = [
             C.POINTER(N.PvtEmitterTables), C.POINTER(N.PvtTraceParams), C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_int]
@@ -57,6 +61,10 @@ def lib():
         L.pvt_oracle_fresnel_reflectivity.restype = C.c_double
         L.pvt_oracle_interp.argtypes = [C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         L.pvt_oracle_interp.restype = C.c_double
+        L.pvt_oracle_index_at.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double]
+        L.pvt_oracle_index_at.restype = C.c_double
+        L.pvt_oracle_coat_table_r.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double]
+        L.pvt_oracle_coat_table_r.restype = C.c_double
         L.pvt_oracle_step_lookup.argtypes = [C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         L.pvt_oracle_step_lookup.restype = C.c_double
         L.pvt_oracle_intersect.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -131,8 +139,14 @@ def trace_bundle(compiled, positions, directions, wavelengths, seed, maxsteps, m
     tl, el = structs_for_outputs(out)
     rays = N.PvtRays(N.np_ptr(pos), N.np_ptr(dirs), N.np_ptr(wl))
     params = N.trace_params(n, seed, ray_offset, 0, record_every, maxsteps, max_events, emit_method)
-    code = L.pvt_oracle_trace(C.byref(st), C.byref(rays), C.byref(params), C.byref(tl),
-                              C.byref(el), int(num_threads), int(math_mode))
+    # refractive-index tables (dispersive nodes) through the _ex entry, with the struct DeviceScene hands the library
+    xt, xkeep = N.index_tables_struct(compiled)
+    if xt is None:
+        code = L.pvt_oracle_trace(C.byref(st), C.byref(rays), C.byref(params), C.byref(tl),
+                                  C.byref(el), int(num_threads), int(math_mode))
+    else:
+        code = L.pvt_oracle_trace_ex(C.byref(st), C.byref(xt), C.byref(rays), C.byref(params), C.byref(tl),
+                                     C.byref(el), int(num_threads), int(math_mode))
     if code == -2:
         raise ValueError("Engine supports at most 128 geometry nodes.")
     if code != 0:
@@ -217,6 +231,21 @@ def phase(phase_type, param, seed, math_mode=MATH_LIBM):
 def interp(x, xs, ys):
     xs = np.ascontiguousarray(xs, dtype=np.float64); ys = np.ascontiguousarray(ys, dtype=np.float64)
     return lib().pvt_oracle_interp(float(x), xs.ctypes.data, ys.ctypes.data, xs.size)
+
+
+def index_at(xs, vs, wl):
+    """n(wl) of one refractive-index table (wavelengths xs, indices vs), as the referee traces it."""
+    xs = np.ascontiguousarray(xs, dtype=np.float64); vs = np.ascontiguousarray(vs, dtype=np.float64)
+    return lib().pvt_oracle_index_at(xs.ctypes.data, vs.ctypes.data, xs.size, float(wl))
+
+
+def coat_table_r(wavelength, angle_deg, values, wl, angle_rad):
+    """R(wl, angle) of one coating reflectivity table as the referee traces it: axes as stored (angles in degrees),
+    values (n_angle, n_wavelength), the query angle in RADIANS (the arc cosine the trace forms)."""
+    w = np.ascontiguousarray(wavelength, dtype=np.float64); a = np.ascontiguousarray(angle_deg, dtype=np.float64)
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(a.size, w.size)
+    return lib().pvt_oracle_coat_table_r(w.ctypes.data, w.size, a.ctypes.data, a.size, v.ctypes.data, float(wl),
+                                         float(angle_rad))
 
 
 def step_lookup(x, xs, ys):

@@ -29,12 +29,18 @@
  *                tests/golden/tallies_*_1e6.npz (3 sigma per recorder against
  *                the reference kernel; mode 0 exact).
  *
- * Two things go beyond the reference kernel and are marked EXTENSION:
+ * What goes beyond the reference kernel is marked EXTENSION:
  * declarative surface coatings (coat_* tables; semantics restated from the
  * Python delegates in pvtrace/device/lsc.py:22-86 and examples/006
  * Coatings.ipynb cell 3 — parity for these is UNPINNED against the reference
- * engine, which cannot express them) and device-style emission
- * (pvt_oracle_emit; distributions from pvtrace/engine/emit.py:22-89).
+ * engine, which cannot express them); their reflectivity tables R(lambda,
+ * theta) (ctab_*, the rule of pvtrace_hip.h at PvtSceneTables.coat_table);
+ * refractive-index tables n(lambda) (PvtIndexTables, passed to
+ * pvt_oracle_trace_ex; the rule of pvtrace_hip.h at PvtIndexTables) — both
+ * kinds of table pinned statistically to the reference's Python tracer with
+ * delegates that express them (tests/test_oracle_tables.py) and exactly to
+ * rational arithmetic (tests/test_table_lookup_exact.py); and device-style
+ * emission (pvt_oracle_emit; distributions from pvtrace/engine/emit.py:22-89).
  *
  * Build: see oracle/Makefile (gcc -O2 -fopenmp -ffp-contract=off).
  */
@@ -128,6 +134,59 @@ static double step_lookup(double x, const double* xs, const double* ys, int n) {
 }
 static inline double table_value(int hist, double x, const double* xs, const double* ys, int n) {
     return hist ? step_lookup(x, xs, ys, n) : interp_clamped(x, xs, ys, n);
+}
+
+/* EXTENSION: the lookup rule of the index and reflectivity tables (pvtrace_hip.h; the Python
+ * RefractiveIndexTable.at / ReflectivityTable.at), restated: piecewise linear, clamped at both ends,
+ * each step a + t (b - a) with t = (x - xa) / (xb - xa) on the cell xa <= x < xb.  The axis is read
+ * as xs[i] * scale (scale 1 for wavelengths; degrees -> radians for coating angles, the packer's very
+ * product, pvt_scene_pack.h).  Returns t and sets *lo / *hi (equal, t = 0, at and beyond either end). */
+#define RAD_PER_DEG (3.14159265358979323846 / 180.0)
+static double table_cell(const double* xs, int n, double scale, double x, int* lo, int* hi) {
+    *lo = *hi = 0;
+    if (!(x > xs[0] * scale)) return 0.0;
+    if (!(x < xs[n - 1] * scale)) { *lo = *hi = n - 1; return 0.0; }
+    int base = 0, span = n - 1;              /* xs[0] <= x < xs[n-1]: the first xs[i] > x lies in [1, n-1] */
+    while (span > 0) {                       /* (upper bound by halving, not the kernel's bisection) */
+        const int half = span >> 1, mid = base + half;
+        if (xs[mid] * scale <= x) { base = mid + 1; span -= half + 1; }
+        else span = half;
+    }
+    *lo = base - 1; *hi = base;
+    const double xa = xs[*lo] * scale;
+    return (x - xa) / (xs[*hi] * scale - xa);
+}
+/* n(wl) of a table of n points: wavelengths xs[0..n), indices vs[0..n) */
+static double index_table_at(const double* xs, const double* vs, int n, double wl) {
+    int lo, hi;
+    const double t = table_cell(xs, n, 1.0, wl, &lo, &hi);
+    return vs[lo] + t * (vs[hi] - vs[lo]);
+}
+/* refractive index of `node` at wavelength wl: its table, else its scalar index */
+static inline double index_of(const PvtSceneTables* S, const PvtIndexTables* X, int node, double wl) {
+    if (X && X->n_tables > 0 && X->node_table[node] >= 0) {
+        const int j = X->node_table[node], o = X->table_start[j];
+        return index_table_at(X->wavelength + o, X->value + o, X->table_n[j], wl);
+    }
+    return S->refractive_index[node];
+}
+/* R at wavelength wl (nm) and angle of incidence `angle` (radians) of a table: nw wavelengths, na
+ * angles (degrees), values row-major by angle; linear in wavelength on the two bracketing angle rows,
+ * then linear in angle */
+static double coat_table_at(const double* wls, int nw, const double* angs, int na, const double* vals,
+                            double wl, double angle) {
+    int w0, w1, a0, a1;
+    const double tw = table_cell(wls, nw, 1.0, wl, &w0, &w1);
+    const double ta = table_cell(angs, na, RAD_PER_DEG, angle, &a0, &a1);
+    const double* lo_row = vals + (long)a0 * nw;
+    const double* hi_row = vals + (long)a1 * nw;
+    const double r_lo = lo_row[w0] + tw * (lo_row[w1] - lo_row[w0]);
+    const double r_hi = hi_row[w0] + tw * (hi_row[w1] - hi_row[w0]);
+    return r_lo + ta * (r_hi - r_lo);
+}
+static double coat_table_r(const PvtSceneTables* S, int j, double wl, double angle) {
+    return coat_table_at(S->ctab_wavelength + S->ctab_wl_start[j], S->ctab_nw[j], S->ctab_angle + S->ctab_angle_start[j],
+                         S->ctab_na[j], S->ctab_value + S->ctab_value_start[j], wl, angle);
 }
 
 /* ---- intersections in the local frame (_kernel.pyx:245-356) ------------- */
@@ -517,7 +576,7 @@ static _Thread_local long g_last_steps = 0;
 long pvt_oracle_last_steps(void) { return g_last_steps; }
 
 /* ---- one photon (_kernel.pyx:603-897) ----------------------------------- */
-static int trace_one(const PvtSceneTables* S, const MathSel* M, const PvtEventLog* L, int max_events,
+static int trace_one(const PvtSceneTables* S, const PvtIndexTables* X, const MathSel* M, const PvtEventLog* L, int max_events,
                      long base, Acc* A, double* pos, double* dir, double wl, uint64_t seed,
                      int maxsteps, int emit_method, long* steps) {
     Rng rng;
@@ -606,7 +665,7 @@ static int trace_one(const PvtSceneTables* S, const MathSel* M, const PvtEventLo
             }
             break;
         }
-        double n_container = S->refractive_index[container];
+        double n_container = index_of(S, X, container, wl);   /* EXTENSION: n at the photon's wavelength */
 
         if (hit == S->root_id) { /* exit through the root boundary (:728-744) */
             for (int i = 0; i < 3; i++) pos[i] = pos[i] + dir[i] * t0;
@@ -722,15 +781,19 @@ static int trace_one(const PvtSceneTables* S, const MathSel* M, const PvtEventLo
         double r = 0.0, n1 = 0.0, n2 = 0.0;
         int fres = S->surface_type[hit] == PVT_SURF_FRESNEL;
         if (fres) {
-            n1 = S->refractive_index[container];
-            n2 = S->refractive_index[adjacent];
+            n1 = n_container;            /* (the container's index at wl, as for the clock) */
+            n2 = index_of(S, X, adjacent, wl);
             r = fresnel_reflectivity(M, angle, ddot, n1, n2);
         }
         int coat = fres ? find_coating(S, hit, nl, lp) : -1;          /* EXTENSION */
-        /* a coating sets the reflectivity -- except beyond the critical angle when it transmits by
-         * Fresnel refraction: no refracted ray exists there, the light stays totally reflected */
-        if (coat >= 0 && S->coat_reflectivity[coat] >= 0.0 && !(r == 1.0 && S->coat_transmit_mode[coat] != 1))
-            r = S->coat_reflectivity[coat];
+        /* a coating sets the reflectivity -- its table's R(wl, angle) or its scalar -- except beyond the
+         * critical angle when it transmits by Fresnel refraction: no refracted ray exists there, the light
+         * stays totally reflected */
+        if (coat >= 0 && !(r == 1.0 && S->coat_transmit_mode[coat] != 1)) {
+            double cr = S->coat_reflectivity[coat];
+            if (S->n_coat_tables > 0 && S->coat_table[coat] >= 0) cr = coat_table_r(S, S->coat_table[coat], wl, angle);
+            if (cr >= 0.0) r = cr;
+        }
 
         double u = 1.0;
         if (r > 0.0) u = rng_uniform(&rng);
@@ -772,8 +835,8 @@ static int trace_one(const PvtSceneTables* S, const MathSel* M, const PvtEventLo
  * Rays are read from `rays` (never mutated; the reference copies them too,
  * :1064-1066).  Tallies are ADDED into the caller's arrays; the event log is
  * pre-filled here like the reference's np.zeros / np.full(-1) allocations. */
-int pvt_oracle_trace(const PvtSceneTables* S, const PvtRays* rays, const PvtTraceParams* P,
-                     const PvtTallies* out, const PvtEventLog* L, int num_threads, int math_mode) {
+int pvt_oracle_trace_ex(const PvtSceneTables* S, const PvtIndexTables* X, const PvtRays* rays, const PvtTraceParams* P,
+                        const PvtTallies* out, const PvtEventLog* L, int num_threads, int math_mode) {
     if (S->n_nodes > PVT_MAX_NODES) return PVT_ERR_TOO_MANY_NODES;
     if (S->n_recorders > PVT_MAX_RECORDERS) return PVT_ERR_INVALID;
     long n = (long)P->n_rays;
@@ -820,7 +883,7 @@ int pvt_oracle_trace(const PvtSceneTables* S, const PvtRays* rays, const PvtTrac
         if (rec_every > 0 && i % rec_every == 0) base = (i / rec_every) * P->max_events;
         double pos[3] = {rays->position[i * 3], rays->position[i * 3 + 1], rays->position[i * 3 + 2]};
         double dir[3] = {rays->direction[i * 3], rays->direction[i * 3 + 1], rays->direction[i * 3 + 2]};
-        int nev = trace_one(S, &M, L, P->max_events, base, &A, pos, dir, rays->wavelength[i],
+        int nev = trace_one(S, X, &M, L, P->max_events, base, &A, pos, dir, rays->wavelength[i],
                             P->seed + P->ray_offset + (uint64_t)i, P->maxsteps, P->emit_method, &steps_total);
         if (base >= 0) L->counts[i / rec_every] = nev;
     }
@@ -845,6 +908,12 @@ int pvt_oracle_trace(const PvtSceneTables* S, const PvtRays* rays, const PvtTrac
     free(a_dist); free(a_cross); free(a_sums); free(a_bins);
     g_last_steps = steps_total;
     return PVT_OK;
+}
+
+/* without refractive-index tables (every caller of the reference's signature) */
+int pvt_oracle_trace(const PvtSceneTables* S, const PvtRays* rays, const PvtTraceParams* P,
+                     const PvtTallies* out, const PvtEventLog* L, int num_threads, int math_mode) {
+    return pvt_oracle_trace_ex(S, NULL, rays, P, out, L, num_threads, math_mode);
 }
 
 /* ---- EXTENSION: per-ray-stream emission ---------------------------------
@@ -966,6 +1035,15 @@ void pvt_oracle_specular_reflect(const double* d, const double* normal, double* 
 }
 double pvt_oracle_interp(double x, const double* xs, const double* ys, int n) {
     return interp_clamped(x, xs, ys, n);
+}
+/* the table lookups alone, for the exact-arithmetic tests: n(wl) of one index table, and R(wl, angle) of one
+ * reflectivity table (angles in degrees as stored, the query angle in radians as traced) */
+double pvt_oracle_index_at(const double* xs, const double* vs, int n, double wl) {
+    return index_table_at(xs, vs, n, wl);
+}
+double pvt_oracle_coat_table_r(const double* wls, int nw, const double* angs_deg, int na, const double* vals,
+                               double wl, double angle_rad) {
+    return coat_table_at(wls, nw, angs_deg, na, vals, wl, angle_rad);
 }
 double pvt_oracle_step_lookup(double x, const double* xs, const double* ys, int n) {
     return step_lookup(x, xs, ys, n);

@@ -2,12 +2,15 @@
 surface tag, light mask and recorder kind in random combinations, with random (also overlapping)
 placement and nesting.  Overlaps are deliberate -- two implementations of the same rules must agree
 on ill-posed scenes too.  `extensions=True` adds what the reference engine cannot express
-(meshes, coatings, histogram-sampled spectra, source-filtered recorders)."""
+(meshes, coatings, histogram-sampled spectra, source-filtered recorders).  `tables=True` then gives some
+materials refractive-index tables n(wavelength) and some coatings reflectivity tables R(wavelength, angle), drawn
+from a generator of their own: the scene of a seed without tables is the one it always was."""
 import numpy as np
 
 from pvtrace_amd import (
     Absorber, Box, Coating, CoatedSurfaceDelegate, Cylinder, Light, Luminophore, Material, Mesh, Node,
-    NullSurfaceDelegate, Reactor, Scatterer, Scene, Sphere, Surface, isotropic, lambertian,
+    NullSurfaceDelegate, Reactor, ReflectivityTable, RefractiveIndexTable, Scatterer, Scene, Sphere, Surface, isotropic,
+    lambertian,
 )
 from pvtrace_amd.engine import Heatmap, Histogram, Recorder
 from pvtrace_amd.light import CircularMask, ConstantWavelengthMask, CubeMask, RectangularMask, SpectrumWavelengthMask
@@ -92,7 +95,67 @@ def _recorders(rng, node, is_root, component_names, extensions):
     return recs
 
 
-def random_scene(seed, extensions=False):
+# wavelength ranges of the tables against the lights' and emitters' spectra (360-840 nm): covering them, missing them
+# below or above, straddling either end
+TABLE_SPANS = ((300.0, 900.0), (120.0, 340.0), (860.0, 1300.0), (200.0, 600.0), (600.0, 1100.0), (500.0, 700.0))
+
+
+def _axis(rng, n, lo, hi):
+    x = np.unique(np.sort(rng.uniform(lo, hi, n)))
+    if len(x) >= 2 and rng.random() < 0.5:   # exactly the span's ends
+        x[0], x[-1] = lo, hi
+    return x
+
+
+def _index_table(rng):
+    n = int(rng.integers(1, 41))
+    wl = _axis(rng, n, *TABLE_SPANS[int(rng.integers(0, len(TABLE_SPANS)))])
+    kind = rng.integers(0, 3)
+    if kind == 0:     # smooth: Cauchy-like, falling with wavelength
+        values = float(rng.uniform(1.3, 1.9)) + float(rng.uniform(0.0, 2e4)) / wl ** 2
+    elif kind == 1:   # steep and rough
+        values = rng.uniform(1.0, 2.4, len(wl))
+    else:             # flat
+        values = np.full(len(wl), float(rng.uniform(1.0, 2.2)))
+    return RefractiveIndexTable(wl, values)
+
+
+def _reflectivity_table(rng):
+    nw, na = int(rng.integers(1, 9)), int(rng.integers(1, 9))
+    wl = _axis(rng, nw, *TABLE_SPANS[int(rng.integers(0, len(TABLE_SPANS)))])
+    if na == 1 and rng.random() < 0.5:
+        return ReflectivityTable(wl, rng.uniform(0.0, 1.0, len(wl)))
+    ang = _axis(rng, na, 0.0, 90.0)
+    if len(ang) >= 2 and rng.random() < 0.5:
+        ang[0], ang[-1] = 0.0, 90.0
+    values = rng.uniform(0.0, 1.0, (len(ang), len(wl)))
+    if rng.random() < 0.3:   # a step table: every value 0 or 1
+        values = np.round(values)
+    return ReflectivityTable(wl, values, angle=ang)
+
+
+def _add_tables(seed, nodes):
+    """Refractive-index tables on some materials (some tables shared between materials, the world's included) and
+    reflectivity tables on some coatings, from the generator of (seed, 7)."""
+    rng = np.random.default_rng([seed, 7])
+    made = []
+    for node in nodes:
+        material = node.geometry.material
+        if isinstance(material.refractive_index, RefractiveIndexTable) or rng.random() < 0.4:
+            continue
+        if made and rng.random() < 0.3:
+            material.refractive_index = made[int(rng.integers(0, len(made)))]
+        else:
+            made.append(_index_table(rng))
+            material.refractive_index = made[-1]
+        delegate = material.surface.delegate
+        if isinstance(delegate, CoatedSurfaceDelegate):
+            for coating in delegate.coatings:
+                if rng.random() < 0.7:
+                    coating.reflectivity = _reflectivity_table(rng)
+
+
+def random_scene(seed, extensions=False, tables=False):
     rng = np.random.default_rng(seed)
     world_material = Material(1.0, components=_components(rng, extensions) if rng.random() < 0.3 else [])
     world = Node(name="world", geometry=(Sphere(12.0, material=world_material) if rng.random() < 0.7
@@ -137,15 +200,18 @@ def random_scene(seed, extensions=False):
         light = Node(name=f"light{k}", parent=world, light=Light(wavelength=wl, position=pos, direction=direc, name=f"light{k}"))
         light.translate(tuple(rng.uniform(-3.0, 3.0, 3)))
         light.look_at(tuple(-np.asarray(light.location) + rng.normal(scale=0.3, size=3)))
+    if tables:
+        _add_tables(seed, nodes)
     return Scene(world)
 
 
-def random_many_scene(seed, n_nodes=None):
+def random_many_scene(seed, n_nodes=None, tables=False):
     """Scenes of MANY nodes (8 ... 120; the kernel's node-grid path): small shapes from a pool of shared materials
     scattered over a box region, a good part of them on a lattice whose pitch EQUALS their size (faces shared with
     the neighbours: crossings of two nodes at the very same distance, which the reference orders by node index),
     some rotated by one of a few shared rotations or a random one, some nested inside earlier ones, some overlapping.
-    The reference engine can express all of it (no extensions)."""
+    The reference engine can express all of it (no extensions) -- but for `tables=True`, which also coats some of the
+    shared materials with a reflectivity table on one facet."""
     rng = np.random.default_rng(50_000 + seed)
     n = int(n_nodes or rng.integers(8, 121))
     world_material = Material(1.0, components=[Absorber(float(rng.uniform(0.001, 0.01)), name="haze")] if rng.random() < 0.2 else [])
@@ -209,4 +275,13 @@ def random_many_scene(seed, n_nodes=None):
                                                                  position=pos, direction=direc, name=f"light{k}"))
         light.translate(tuple(rng.uniform(-1.0, 1.0, 3) * (1.0, 1.0, 0.0) + (0.0, 0.0, float(rng.choice([-1, 1])) * (0.8 if flat else 0.6 * span) * lattice + 0.3)))
         light.look_at(tuple(-np.asarray(light.location) + rng.normal(scale=0.5, size=3)))
+    if tables:
+        trng = np.random.default_rng([seed, 8])
+        for material in pool:
+            if trng.random() < 0.4:
+                facet = np.zeros(3); facet[trng.integers(0, 3)] = trng.choice([-1.0, 1.0])
+                material.surface = Surface(delegate=CoatedSurfaceDelegate([Coating(
+                    facet=tuple(facet), reflectivity=_reflectivity_table(trng),
+                    reflection=str(trng.choice(["specular", "lambertian"])), transmission=str(trng.choice(["fresnel", "matched"])))]))
+        _add_tables(seed, nodes)
     return Scene(world)

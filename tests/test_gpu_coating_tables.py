@@ -1,6 +1,6 @@
-"""Coating reflectivity tables on the GPU.  The C referee ignores the tables, so nothing here compares a scene that has
-them with it: a table holding a constant must give, bit for bit, what the scalar coating gives (same draws, same
-events); step tables decide hand-traced rays exactly as the host tracer does; a mid-cell photon beam is reflected at the
+"""Coating reflectivity tables on the GPU, by properties that need no referee (the GPU against the C referee on scenes
+with varying tables is tests/test_gpu_table_parity.py): a table holding a constant must give, bit for bit, what the
+scalar coating gives (same draws, same events); step tables decide hand-traced rays exactly as the host tracer does; a mid-cell photon beam is reflected at the
 bilinear value; a table too large for LDS gives the same results wherever the library or the caller puts it; and the
 reference's own Python tracer, calling a selective-mirror delegate written as the reference lets users write one, pins
 the outcome fractions of a Lumogen F Red slab (tests/golden/coating_table_tracer.npz)."""

@@ -1,6 +1,6 @@
-"""Refractive-index tables n(wavelength) on the GPU.  The C referee knows no tables, so nothing here compares a dispersive
-scene with it: a table holding a constant must give, bit for bit, what the scalar index gives (same draws, same events,
-same clocks); hand-traced rays through a strongly dispersive block refract, reflect totally and keep time with n at
+"""Refractive-index tables n(wavelength) on the GPU, by properties that need no referee (the GPU against the C referee
+on dispersive scenes is tests/test_gpu_table_parity.py): a table holding a constant must give, bit for bit, what the
+scalar index gives (same draws, same events, same clocks); hand-traced rays through a strongly dispersive block refract, reflect totally and keep time with n at
 their own wavelength; the reference's own Python tracer, with the dispersion written as a delegate the reference lets
 users write, pins the outcome fractions and event counts of a dispersive Lumogen slab
 (tests/golden/dispersion_tracer.npz); and pvt_scene_create_ex rejects every malformed table with its own message."""
