@@ -59,9 +59,7 @@ struct NodeGrid {
 };
 bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
     const int N = t->n_nodes, root = t->root_id;
-    int min_nodes = 8;
-    if (const char* env = getenv("PVT_GRID_MIN_NODES")) min_nodes = atoi(env);
-    if (getenv("PVT_NO_GRID") || N < min_nodes || N < 3) return false;
+    if (getenv("PVT_NO_GRID") || N < 8) return false;
     std::vector<double> blo((size_t)N * 3), bhi((size_t)N * 3);
     double extent = 0.0;
     for (int n = 0; n < N; n++) {
@@ -238,9 +236,7 @@ bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
     for (int a = 0; a < 3; a++) { ext[a] = g->hi[a] - g->lo[a]; vol *= ext[a]; }
     constexpr int kMaxCells = 512;   // 8 KB of masks in LDS at two words per cell
     {   // start: about one cell per node, as cubic as the extent allows
-        double target = std::fmin((double)kMaxCells, std::fmax(8.0, 1.0 * (N - 1)));
-        // (developer sweep; never more cells than the mask table's share of LDS holds)
-        if (const char* env = getenv("PVT_GRID_CELLS")) target = std::fmin((double)kMaxCells, std::fmax(1.0, atof(env)));
+        const double target = std::fmin((double)kMaxCells, std::fmax(8.0, 1.0 * (N - 1)));
         double side = std::cbrt(vol / target);
         for (int pass = 0; pass < 200; pass++) {
             long long cells = 1;
@@ -252,7 +248,7 @@ bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
             side *= 1.05;
         }
     }
-    if (!getenv("PVT_GRID_CELLS") && !getenv("PVT_GRID_NO_TUNING")) {
+    {   // then: each axis in turn, finer or coarser, where the sampled walk gets clearly cheaper
         double best = price(g->n);
         for (int sweep = 0; sweep < 2; sweep++)
             for (int a = 0; a < 3; a++) {

@@ -143,8 +143,6 @@ struct PvtScene {
     int grid_dims[3] = {0, 0, 0};
     bool fuse_exit = false;         // see prove_shortcuts: photons leaving the only child's surface outwards are done
     bool hist_reads_position = false;   // a histogram axis is x, y or z
-    bool consolidate = true;        // developer switches (environment), read once at scene creation
-    double dev_blocks_per_cu = 0.0;
 };
 
 extern "C" {
@@ -347,7 +345,7 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     const size_t xbytes = (size_t)kXSlots * xw * 8;
     // (mesh scenes do without: measured, repacking a draining workgroup buys their launches nothing, and the 9 KB hold
     // another level of the trees' top)
-    if (s->consolidate && s->meshq == 0 && lds + xbytes <= 40 * 1024 && lds + xbytes <= lds_limit) {
+    if (s->meshq == 0 && lds + xbytes <= 40 * 1024 && lds + xbytes <= lds_limit) {
         lp.xslots = kXSlots;
         lds += xbytes;
     }
@@ -443,7 +441,6 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     // never more than the rays can feed
     long long blocks_for_rays = (p->n_rays + (carry_in ? carry.bound : 0) + kBlock - 1) / kBlock;
     double per_cu = p->workgroups_per_cu > 0 ? (double)p->workgroups_per_cu : 4.0;
-    if (s->dev_blocks_per_cu > 0) per_cu = s->dev_blocks_per_cu;   // developer override, read once per scene
     long long grid = (long long)((double)s->num_cu * per_cu);
     if (grid > blocks_for_rays) grid = blocks_for_rays;
     if (grid < 1) grid = 1;
@@ -625,8 +622,6 @@ int pvt_scene_create_ex(const PvtSceneTables* t, const PvtIndexTables* x, int de
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     s->num_cu = prop.multiProcessorCount;
     s->lds_limit = prop.sharedMemPerBlock;
-    s->consolidate = getenv("PVT_NO_CONSOLIDATE") == nullptr;
-    if (const char* env = getenv("PVT_BLOCKS_PER_CU")) s->dev_blocks_per_cu = atof(env);
     if (const char* env = getenv("PVT_STAGE_BYTES")) s->stage_limit = (size_t)atoll(env);   // (tests: force several launches)
     HIP_TRY(hipMalloc(&s->d_gd, packed.gd.size() * sizeof(double)));
     HIP_TRY(hipMalloc(&s->d_gi, packed.gi.size() * sizeof(int)));

@@ -5,14 +5,10 @@
 #pragma once
 // Developer switches (build-time; everything else that used to be one is a constant now -- the experiments behind them are
 // closed, docs/history.md): PVT_STATS (tools/: -DPVT_STATS=1 builds print per-launch lane statistics), PVT_TIMELINE (per-wave
-// stamps), PVT_COUNTERS / PVT_TAIL_CALL / PVT_TAIL_ALPHA (round 5's A/B switches: profiles/r05_tail_ab.txt), and
-// PVT_DEV_VARIANTS in pvt_trace.hip (fast developer builds of a few variants).
+// stamps), and PVT_DEV_VARIANTS in pvt_trace.hip (fast developer builds of a few variants).
 constexpr int kMeshWaves = 4;   // waves per SIMD the mesh variants are held to (registers: 512 / waves; LDS per workgroup: 160 KB / waves)
 #ifndef PVT_STATS
 #define PVT_STATS 0
-#endif
-#ifndef PVT_COUNTERS
-#define PVT_COUNTERS 1   // (0: a developer build without the always-on step counters, to price them: tools/gpu_ab.sh)
 #endif
 // Developer-only: every wave writes wall-clock stamps (start, tables staged, first step, cursor dry, end) and its
 // iteration count to KArgs::timeline (tools/gpu_wave_timeline.py)
@@ -785,18 +781,6 @@ struct Seen {
 // GRID: scenes of many nodes -- every lane finds the nodes its ray can cross through a uniform grid (see the node loop).
 // TAIL: the same loop as a FUNCTION for the last wave of a draining workgroup (`tail_run`, below): no rays to claim, no
 // rendezvous -- it takes the `tail_total` photons its caller left in the exchange buffer and steps them until none is left.
-#ifndef PVT_TAIL_CALL
-#define PVT_TAIL_CALL 1
-#endif
-#ifndef PVT_TAIL_HOIST
-#define PVT_TAIL_HOIST 1   // (0: a developer build whose tail function reads the hit node's record where the kernels' loop does)
-#endif
-#ifndef PVT_TAIL_LAZY
-#define PVT_TAIL_LAZY 1   // (0: a developer build whose tail function intersects the root wherever the kernels' loop does)
-#endif
-#ifndef PVT_TAIL_ALPHA
-#define PVT_TAIL_ALPHA 1   // (0: a developer build whose tail function looks the absorption coefficients up in every step)
-#endif
 template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID>
 __device__ void tail_run(const KArgs* kernel_args, int total, unsigned int lds);
 
@@ -906,7 +890,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (A.emit_method == PVT_EMIT_FULL ? 1u << UF_EMIT_FULL : 0u) | (A.emit_method == PVT_EMIT_KT ? 1u << UF_EMIT_KT : 0u) |
         (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u) |
         (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u);
-    if constexpr (TAIL && PVT_TAIL_LAZY) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
+    if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
@@ -1074,7 +1058,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // (tail function) the absorption coefficients this lane's photon met last: container, wavelength bits, sum, first term
     // -- kept in LDS, in the exchange buffer the function was handed its photons through (free once they are read): four
     // words per lane, read together (one wait) where two table lookups stood; in registers they were seven more than the
-    // function has (the hit node's record, below, went to scratch for them: PVT_TAIL_ALPHA 2 keeps that variant)
+    // function has (the hit node's record, below, went to scratch for them)
     int ac_node = -1;
     unsigned long long ac_wl = 0ull;
     double ac_alpha = 0.0, ac_pre0 = 0.0;
@@ -1085,7 +1069,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     unsigned long long hr_bits = 0ull;
     int hr_surf = 0;
     double hr_n2 = 0.0, hr_rn2 = 0.0, hr_cc = 0.0;
-    constexpr bool kHoist = TAIL && PVT_TAIL_HOIST;
+    constexpr bool kHoist = TAIL;
     // (scenes with index tables, UF_DISP) the refractive index of `node` at the photon's wavelength: its class's table
     // n(lambda), or `n`, the node's scalar index, when the class has none (a dispersive node has a class of its own)
     auto index_at = [&](int node, double n) -> double {
@@ -1140,7 +1124,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     int tail_n = 0;   // photons this wave hands to the tail function when it leaves the loop (0: none)
     // (mesh scenes never repack a draining workgroup -- KArgs::xslots is 0 there -- and the history variant of the grid walk
     // has no register to spare for the call: both keep their last wave in this loop)
-    constexpr bool kTailCall = PVT_TAIL_CALL && !TAIL && !MESH && !(GRID && RECORD);
+    constexpr bool kTailCall = !TAIL && !MESH && !(GRID && RECORD);
 
     // Statistics of the parked first crossings, one lane per record: the recorder's distinct count, the
     // eight running sums (the angle is acos of the parked cosine; 1.0 -> exactly 0 for events without a
@@ -1209,7 +1193,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             }
         }
     }
-    if constexpr (TAIL && PVT_TAIL_ALPHA == 1) ac_lds[0] = ~0ull;   // (nothing known yet; after the reads above, same wave: in order)
+    if constexpr (TAIL) ac_lds[0] = ~0ull;   // (nothing known yet; after the reads above, same wave: in order)
     for (;;) {
         if constexpr (TAIL) {
             if (__ballot(alive) == 0ull) break;
@@ -1530,9 +1514,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         }
 #endif
 
-#if PVT_COUNTERS
         c_iters += 1u;
-#endif
 #if PVT_TIMELINE
         if (tl_iters == 0) tl_t[2] = wall_clock64();
         if ((ws & WS_EXHAUSTED) && tl_t[3] == 0) tl_t[3] = wall_clock64();
@@ -1588,7 +1570,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // root's intersection; in a typical scene (a 5 cm slab in a 5 m world) none ever does.
                 // (tail function: also where exits are looked at -- `lazy_exact`: the root's own distance is worked out whenever
                 // it is the nearest crossing, i.e. the photon leaves the scene)
-                const bool lazy_exact = TAIL && PVT_TAIL_LAZY && !MESH && (uf(UF_TAIL_LAZY1) || uf(UF_TAIL_LAZY2));
+                const bool lazy_exact = TAIL && !MESH && (uf(UF_TAIL_LAZY1) || uf(UF_TAIL_LAZY2));
                 const int lazy_root = MESH ? 0 : (lazy_exact ? (uf(UF_TAIL_LAZY1) ? 1 : 2)
                                                               : (RECORD ? 0 : (uf(UF_LAZY1) ? 1 : (uf(UF_LAZY2) ? 2 : 0))));   // wave-uniform
                 // Grid scenes fold a crossing by the key (t, node): what the reference's first-minimum scans over its hit
@@ -2186,7 +2168,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             // step needs -- the hit node's, the far side's refractive index, the pair's Fresnel constants -- are all
             // addressed by what the node loop has just found: read together HERE they cost one wait instead of five spread
             // over the step; the same words, so the same bits)
-            if constexpr (TAIL && PVT_TAIL_HOIST) {
+            if constexpr (TAIL) {
                 const int hn = hit * ND;
                 hr_t = V3{T.dv(hn + ND_T), T.dv(hn + ND_T + 1), T.dv(hn + ND_T + 2)};
                 hr_g = V3{T.dv(hn + ND_PARAMS), T.dv(hn + ND_PARAMS + 1), T.dv(hn + ND_PARAMS + 2)};
@@ -2205,11 +2187,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             // the step before -- the same table values, read once instead of once per bounce; not in the kernels' own loop,
             // where the seven registers cost more than the lookups: docs/history.md, round 4)
             bool known = false;
-            if constexpr (TAIL && PVT_TAIL_ALPHA == 1) {
+            if constexpr (TAIL) {
                 ac_node = (int)(unsigned int)ac_lds[0]; ac_wl = ac_lds[64];
                 ac_alpha = pvt_u2d(ac_lds[128]); ac_pre0 = pvt_u2d(ac_lds[192]);
             }
-            if constexpr (TAIL && PVT_TAIL_ALPHA) known = container == ac_node && pvt_d2u(wl) == ac_wl;
+            if constexpr (TAIL) known = container == ac_node && pvt_d2u(wl) == ac_wl;
             if (hit != k_root && !known) {
                 for (int k = 0; k < ccount; k++) {
                     const int ci = L.comp_i + (crec + k) * CI, cd = L.comp_d + (crec + k) * CD;
@@ -2218,10 +2200,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                                                             T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
                     if (k == 0) pre0 = alpha;
                 }
-                if constexpr (TAIL && PVT_TAIL_ALPHA == 1) {
+                if constexpr (TAIL) {
                     ac_lds[0] = (unsigned long long)(unsigned int)container; ac_lds[64] = pvt_d2u(wl);
                     ac_lds[128] = pvt_d2u(alpha); ac_lds[192] = pvt_d2u(pre0);
-                } else if constexpr (TAIL) { ac_node = container; ac_wl = pvt_d2u(wl); ac_alpha = alpha; ac_pre0 = pre0; }
+                }
             }
             if constexpr (TAIL) {
                 if (known && hit != k_root) { alpha = ac_alpha; pre0 = ac_pre0; }
@@ -2627,9 +2609,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 const double g = h - dot3(nrm, lp), dn = dot3(nrm, dir);
                 if (dn > 0.0 && g <= (0.5 * kEps) * dn) {
                     terminal = true;
-#if PVT_COUNTERS
                     c_fused += 1u;
-#endif
                 }
             }
         }
@@ -2744,9 +2724,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             if constexpr (RECORD) {
                 if (rec_slot >= 0) A.log_counts[rec_slot] = nev;
             }
-#if PVT_COUNTERS
             c_steps += (unsigned int)count;   // the trips this photon took, in whichever launches and lanes
-#endif
             alive = false;
         }
     }

@@ -292,7 +292,7 @@ def to_host(tensor):
     and, once the result that owns it has been dropped, is handed out again by the allocator without being faulted in
     a second time.  The array keeps its block alive (numpy `base`); nothing here is shared between results."""
     nbytes = tensor.numel() * tensor.element_size()
-    if nbytes < _PINNED_FROM or nbytes > _PINNED_UP_TO or os.environ.get("PVT_NO_PINNED_RESULTS"):
+    if nbytes < _PINNED_FROM or nbytes > _PINNED_UP_TO:
         return tensor.cpu().numpy()
     import torch
 
@@ -389,7 +389,7 @@ def download(compiled, tallies, log, n_rays, record_every, max_events, packed=Fa
 # creating the device scene (a dozen allocations, the packed tables, for meshes the BVH) and destroying it again
 # (hipFree synchronises the device) cost 0.4 ms per call -- as much as tracing 10^6 photons of the headline scene.
 # The key is a digest of every flat table (and of the emitter tables), so a scene edited between two calls is a
-# different scene; a resident scene is handed to ONE session at a time.  PVT_NO_SCENE_CACHE=1 switches it off.
+# different scene; a resident scene is handed to ONE session at a time.
 _RESIDENT = []        # [(key, DeviceScene)], most recently released last
 _RESIDENT_MAX = 4
 _RESIDENT_LOCK = __import__("threading").Lock()
@@ -413,20 +413,18 @@ def _scene_key(compiled, emitter, device):
 
 
 def _acquire_scene(compiled, emitter, device):
-    key = None
-    if not os.environ.get("PVT_NO_SCENE_CACHE"):
-        key = _scene_key(compiled, emitter, device)
-        with _RESIDENT_LOCK:
-            for k, (have, dscene) in enumerate(_RESIDENT):
-                if have == key:
-                    del _RESIDENT[k]
-                    dscene.compiled = compiled
-                    return key, dscene
+    key = _scene_key(compiled, emitter, device)
+    with _RESIDENT_LOCK:
+        for k, (have, dscene) in enumerate(_RESIDENT):
+            if have == key:
+                del _RESIDENT[k]
+                dscene.compiled = compiled
+                return key, dscene
     return key, native.DeviceScene(compiled, device=device, emitter=emitter)
 
 
 def _release_scene(key, dscene):
-    if key is None or dscene.handle is None:
+    if dscene.handle is None:
         dscene.close()
         return
     evicted = None

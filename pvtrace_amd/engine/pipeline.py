@@ -24,8 +24,6 @@ class BundlePipeline:
         a launch does not trace its last, longest histories to completion but hands the photons still alive to the
         next launch on its stream (PVT_FLAG_CARRY_OUT); `reduce_totals()` / `reset_totals()` finish what is
         waiting, so totals always cover every photon submitted, completely traced."""
-        import os
-
         import torch
 
         if reduce not in ("end", "bundle"):
@@ -34,8 +32,6 @@ class BundlePipeline:
         self._reduced = False
         self._unordered = set()   # streams whose totals were zero-filled on streams[0] by the last reduce_totals()
         self.carry = bool(carry) and not (distributed and reduce == "bundle")
-        if os.environ.get("PVT_NO_CARRY"):   # developer A/B switch
-            self.carry = False
         self._parked = {}         # stream index -> (maxsteps, max_events, emit_method) of the launch that parked photons
 
         self.torch = torch
@@ -50,8 +46,6 @@ class BundlePipeline:
         self.workgroups_per_cu = {1: 4}.get(self.depth, 2)
         if not self.carry and self.depth == 2:
             self.workgroups_per_cu = 3
-        if os.environ.get("PVT_PIPE_WGS"):   # developer sweep
-            self.workgroups_per_cu = int(os.environ["PVT_PIPE_WGS"])
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.depth)]
         # torch hands out streams from a small pool and a resident scene outlives a pipeline: photons an ABANDONED
         # pipeline left parked on one of these stream handles (an exception between two bundles, an object simply

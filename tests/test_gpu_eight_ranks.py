@@ -60,7 +60,7 @@ def test_bench_with_eight_ranks_on_one_gpu(tmp_path):
     # the kernel's own counters of rank 0's timed windows: the headline scene's loop count per photon
     assert abs(out["roofline"]["steps_per_photon"] - 6.92) < 0.07
     assert wall < 120.0, wall
-    record = os.environ.get("PVT_EIGHT_RANKS_RECORD")   # (tools/gpu_round5.sh keeps the line under profiles/)
+    record = os.environ.get("PVT_EIGHT_RANKS_RECORD")   # (a measurement pass keeps the line under profiles/)
     if record:
         out["wall_s_of_the_whole_run"] = wall
         with open(record, "w") as fp:

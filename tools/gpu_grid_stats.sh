@@ -3,7 +3,7 @@
 # usage: tools/gpu_grid_stats.sh lib.so [k ...]      (build/dev/<lib>.so made by tools/dev_build.sh <lib> -DPVT_STATS=1)
 export PVT_LIB=$GRAFT_REPO_ROOT/build/dev/$1; shift
 for k in ${@:-11}; do
-echo "== tiles$k  (PVT_GRID_CELLS=${PVT_GRID_CELLS:-default})"
+echo "== tiles$k"
 K=$k python - <<'PY' 2>&1 | grep "pvt stats\|ms" | tail -5
 import os, sys
 sys.path.insert(0, os.environ["GRAFT_REPO_ROOT"])

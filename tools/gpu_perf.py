@@ -1,5 +1,5 @@
 """Developer tool (GPU box): kernel-time probe of the trace kernel on the headline scene
-and a few others; env PVT_BLOCKS_PER_CU is honoured by the library."""
+and a few others."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

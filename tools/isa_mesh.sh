@@ -1,7 +1,9 @@
 #!/bin/bash
 # Developer tool: register / spill metadata of the MESH dev variants (-DPVT_DEV_VARIANTS=2).  usage: tools/isa_mesh.sh [extra flags]
-cd /root/repo/pvtrace_amd/csrc
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -mllvm -disable-machine-licm -fno-unroll-loops -DPVT_DEV_VARIANTS=2 "$@" \
+root=$(cd "$(dirname "$0")/.." && pwd)
+flags=$(cd "$root" && python3 -c 'import __graft_entry__ as g; print(" ".join(g.HIPCC_FLAGS))') || exit 1   # build()'s own flags
+cd "$root"/pvtrace_amd/csrc
+hipcc $flags -DPVT_DEV_VARIANTS=2 "$@" \
     --cuda-device-only -S pvt_trace.hip -o /tmp/isa_mesh.s 2>/dev/null
 python3 - <<'PY'
 import re

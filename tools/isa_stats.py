@@ -5,9 +5,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 variant = sys.argv[1] if len(sys.argv) > 1 else "trace_kernel_w4ILb0ELi1ELi1ELb0E"
 tmp = tempfile.mkdtemp(prefix="isa_")
 src = os.path.join(ROOT, "pvtrace_amd", "csrc", "pvt_trace.hip")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                       "-fno-fast-math", "-munsafe-fp-atomics", "-mllvm", "-disable-machine-licm", "-fno-unroll-loops", "--cuda-device-only", "-S", src, "-o",
-                       os.path.join(tmp, "k.s")])
+sys.path.insert(0, ROOT)
+import __graft_entry__   # build()'s own flags
+subprocess.check_call(["/opt/rocm/bin/hipcc", *__graft_entry__.HIPCC_FLAGS, "--cuda-device-only", "-S", src, "-o", os.path.join(tmp, "k.s")])
 s = open(os.path.join(tmp, "k.s")).read()
 for f in re.split(r"\n\s*\.globl\s+", s)[1:]:
     name = f.split("\n", 1)[0].strip()
