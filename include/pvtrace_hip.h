@@ -42,7 +42,10 @@ enum { PVT_COMP_ABSORBER = 0, PVT_COMP_SCATTERER = 1, PVT_COMP_LUMINOPHORE = 2, 
 enum { PVT_PHASE_ISOTROPIC = 0, PVT_PHASE_HG = 1, PVT_PHASE_CONE = 2,
        /* EXTENSION (the reference engine rejects it, compiler.py:300-310; its Python path and its scene-spec parser have it,
         * material/utils.py:176-186, cli/parse.py:166-167): cosine-weighted about +z, theta = asin(sqrt(p1)), phi = 2 pi p2 */
-       PVT_PHASE_LAMBERTIAN = 3 };
+       PVT_PHASE_LAMBERTIAN = 3,
+       /* EXTENSION within v13: a tabulated phase function (PvtPhaseTables), sampled about the INCOMING direction;
+        * only pvt_scene_create_phase takes it */
+       PVT_PHASE_TABLE = 4 };
 enum { PVT_EMIT_KT = 0, PVT_EMIT_REDSHIFT = 1, PVT_EMIT_FULL = 2 };
 /* recorder selectors (engine/recorder.py:45-53) */
 enum {
@@ -180,6 +183,40 @@ typedef struct PvtIndexTables {
     const double* value;            /* (n_points) pooled indices, finite and positive */
 } PvtIndexTables;
 
+/* ---- tabulated phase functions p(theta) (extension within v13, passed to pvt_scene_create_phase) ------------------
+ * A component with comp_phase_type PVT_PHASE_TABLE names table comp_table[c] (its comp_phase_param is not read); every
+ * other component has comp_table -1.  Unlike the built-ins, which draw about world +z, a table draws the scattering
+ * angle about the photon's incoming direction d.  The sampling contract (the Python PhaseFunctionTable is the same):
+ *  1. Axis and CDF: mu_j = cos(theta_j) ascending from exactly -1 to exactly 1 (n_mu >= 2 points); each of the
+ *     n_wavelength rows is the trapezoid integral of p in mu with a leading 0, divided by its last entry: it rises
+ *     (non-decreasing) from exactly 0 to exactly 1.
+ *  2. Row, only when n_wavelength > 1: lambda (the photon's current wavelength, nm) clamped into the table's range;
+ *     k with lambda_k <= lambda < lambda_k+1, t = (lambda - lambda_k) / (lambda_k+1 - lambda_k) (t = 0 at either
+ *     clamped end: the first row below the range, the last above); draw u1, row k+1 if u1 < t, else row k.  u1 is
+ *     drawn whenever n_wavelength > 1.
+ *  3. Polar angle: draw u2; j = the first segment with C_j+1 > u2 (binary search; zero-mass segments are never chosen);
+ *     mu = mu_j + (u2 - C_j) / (C_j+1 - C_j) (mu_j+1 - mu_j), clamped to [-1, 1].
+ *  4. Azimuth: draw u3; (sin phi, cos phi) = pvt_sincos2pi(u3); d' = mu d + sqrt(1 - mu^2) (cos phi e1 + sin phi e2),
+ *     with the basis of Duff et al. 2017 about d = (x, y, z): s = copysign(1, z), a = -1 / (s + z), b = x y a,
+ *     e1 = (1 + s x^2 a, s b, -s x), e2 = (b, s + y^2 a, -y).
+ *  5. Draw order: u1 (if drawn), u2, u3 in place of the built-ins' phase draws; a luminophore's wavelength and
+ *     delay draws follow as before.
+ * A separate struct so that PvtSceneTables and PvtIndexTables keep the lengths old callers pass. */
+typedef struct PvtPhaseTables {
+    int32_t n_tables;               /* 0 = none (as a NULL struct) */
+    int32_t n_points;               /* length of the mu pool */
+    int32_t n_wavelength, n_cdf;    /* lengths of the wavelength and CDF pools */
+    const int32_t* comp_table;      /* (n_components) table of each component, -1 = a built-in phase function */
+    const int32_t* table_nw;        /* (n_tables) rows (wavelengths) of each table, >= 1 */
+    const int32_t* table_nmu;       /* (n_tables) mu points of each table, >= 2 */
+    const int32_t* wl_start;        /* (n_tables) first wavelength of each table in `wavelength` */
+    const int32_t* mu_start;        /* (n_tables) first point of each table in `mu` */
+    const int32_t* cdf_start;       /* (n_tables) first CDF entry of each table in `cdf` (nw x nmu, row-major) */
+    const double* wavelength;       /* pooled row wavelengths, nm, finite and strictly increasing per table */
+    const double* mu;               /* pooled mu axes */
+    const double* cdf;              /* pooled CDF rows */
+} PvtPhaseTables;
+
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
@@ -316,6 +353,10 @@ int pvt_device_count(void);
 int pvt_scene_create(const PvtSceneTables* tables, int device, PvtScene** out);
 /* The same with refractive-index tables (NULL = none: then exactly pvt_scene_create). */
 int pvt_scene_create_ex(const PvtSceneTables* tables, const PvtIndexTables* index_tables, int device, PvtScene** out);
+/* The same with phase-function tables (NULL = none: then exactly pvt_scene_create_ex).  pvt_scene_create and
+ * pvt_scene_create_ex refuse a component tagged PVT_PHASE_TABLE (PVT_ERR_INVALID). */
+int pvt_scene_create_phase(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                           const PvtPhaseTables* phase_tables, int device, PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);

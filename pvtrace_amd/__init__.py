@@ -11,7 +11,7 @@ from pvtrace_amd.light import (
 )
 from pvtrace_amd.material import (
     Absorber, CoatedSurfaceDelegate, Coating, Distribution, FresnelSurfaceDelegate,
-    Luminophore, Material, NullSurfaceDelegate, Reactor, ReflectivityTable,
+    Luminophore, Material, NullSurfaceDelegate, PhaseFunctionTable, Reactor, ReflectivityTable,
     RefractiveIndexTable, Scatterer, Surface,
     SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian,
 )

@@ -337,7 +337,7 @@ struct PackedScene {
     Lay lay{};
     std::vector<double> gd;
     std::vector<int> gi;
-    int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, lazy_root = 0;
+    int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, n_ptab = 0, lazy_root = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     int grid_dims[3] = {0, 0, 0};
@@ -348,7 +348,7 @@ struct PackedScene {
 
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
-int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x) {
+int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -415,6 +415,45 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x) {
             total += 2 * np;
         }
         if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "index tables: more than 2^27 doubles");
+    }
+    // phase-function tables (PvtPhaseTables, pvt_scene_create_phase): a component tagged PVT_PHASE_TABLE names one, and
+    // only such a component does; without the struct the tag is refused
+    const int NP = ph ? ph->n_tables : 0;
+    if (NP < 0 || (NP > 0 && (!ph->comp_table || !ph->table_nw || !ph->table_nmu || !ph->wl_start || !ph->mu_start ||
+                              !ph->cdf_start || !ph->wavelength || !ph->mu || !ph->cdf)))
+        return fail(PVT_ERR_INVALID, "phase tables: missing arrays");
+    for (int c = 0; c < C; c++) {
+        const bool tagged = t->comp_phase_type[c] == PVT_PHASE_TABLE;
+        if (tagged && NP == 0)
+            return fail(PVT_ERR_INVALID, "a component has a tabulated phase function (PVT_PHASE_TABLE): pass its tables to pvt_scene_create_phase");
+        if (NP > 0 && (ph->comp_table[c] < -1 || ph->comp_table[c] >= NP)) return fail(PVT_ERR_INVALID, "phase tables: component names a missing table");
+        if (NP > 0 && tagged != (ph->comp_table[c] >= 0))
+            return fail(PVT_ERR_INVALID, "phase tables: a component names a table exactly when it is tagged PVT_PHASE_TABLE");
+    }
+    if (NP > 0) {
+        long long total = 0;
+        for (int j = 0; j < NP; j++) {
+            const long long nw = ph->table_nw[j], nm = ph->table_nmu[j];
+            const long long w0 = ph->wl_start[j], m0 = ph->mu_start[j], c0 = ph->cdf_start[j];
+            if (nw < 1 || nm < 2 || w0 < 0 || m0 < 0 || c0 < 0 || w0 + nw > ph->n_wavelength || m0 + nm > ph->n_points ||
+                c0 + nw * nm > ph->n_cdf)
+                return fail(PVT_ERR_INVALID, "phase tables: wavelength, mu or CDF range out of bounds");
+            for (long long i = 0; i < nw; i++)
+                if (!std::isfinite(ph->wavelength[w0 + i]) || (i > 0 && !(ph->wavelength[w0 + i] > ph->wavelength[w0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "phase tables: wavelengths must be finite and strictly increasing");
+            const double* mu = ph->mu + m0;
+            if (mu[0] != -1.0 || mu[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "phase tables: the mu axis must run from exactly -1 to exactly 1");
+            for (long long i = 1; i < nm; i++)
+                if (!(mu[i] > mu[i - 1])) return fail(PVT_ERR_INVALID, "phase tables: the mu axis must be strictly increasing");
+            for (long long r = 0; r < nw; r++) {
+                const double* cdf = ph->cdf + c0 + r * nm;
+                if (cdf[0] != 0.0 || cdf[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "phase tables: every CDF row must run from exactly 0 to exactly 1");
+                for (long long i = 1; i < nm; i++)
+                    if (!(cdf[i] >= cdf[i - 1])) return fail(PVT_ERR_INVALID, "phase tables: every CDF row must be non-decreasing");
+            }
+            total += 2 + nw + nm + nw * nm;
+        }
+        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "phase tables: more than 2^27 doubles");
     }
     // runs [start, start + count) into a table of `size` rows
     auto bad_run = [](long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; };
@@ -562,10 +601,11 @@ struct Records {
     int n_cand = 0;
 };
 
-Records component_records(const PvtSceneTables* t, const Spectra& sp, bool by_node) {
+Records component_records(const PvtSceneTables* t, const PvtPhaseTables* ph, const Spectra& sp, bool by_node) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders;
+    auto table_of = [&](int c) { return ph && ph->n_tables > 0 ? ph->comp_table[c] : -1; };
     auto same_component = [&](int c, int e) {
-        return t->comp_type[c] == t->comp_type[e] && t->comp_phase_type[c] == t->comp_phase_type[e] &&
+        return t->comp_type[c] == t->comp_type[e] && t->comp_phase_type[c] == t->comp_phase_type[e] && table_of(c) == table_of(e) &&
                std::memcmp(&t->comp_qy[c], &t->comp_qy[e], 8) == 0 && std::memcmp(&t->comp_tau_rad[c], &t->comp_tau_rad[e], 8) == 0 &&
                std::memcmp(&t->comp_tau_nr[c], &t->comp_tau_nr[e], 8) == 0 &&
                std::memcmp(&t->comp_phase_param[c], &t->comp_phase_param[e], 8) == 0 &&
@@ -605,10 +645,11 @@ Records component_records(const PvtSceneTables* t, const Spectra& sp, bool by_no
 // ---- layout: fixed-stride records, then the pooled spectra.  The small tables come first in the blob -- records, then
 // critical angles, rotation classes, index classes and the node grid -- and the spectra last: when a scene's spectra are
 // too large for LDS, a workgroup still stages everything before `spec_d` (KArgs::nd_lds; the guide tables are the tail
-// of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes, and in
-// *rtab_at where each refractive-index table goes.
-std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const Classes& k, const Spectra& sp, const Records& recs,
-                         const NodeGrid& grid, PackedScene* p, std::vector<int>* rtab_at) {
+// of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes, in
+// *rtab_at where each refractive-index table goes and in *ptab_at where each phase-function table goes.
+std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const Classes& k,
+                         const Spectra& sp, const Records& recs, const NodeGrid& grid, PackedScene* p, std::vector<int>* rtab_at,
+                         std::vector<int>* ptab_at) {
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size(), CR = (int)recs.rec_comp.size();
     Lay& lay = p->lay;
@@ -642,6 +683,13 @@ std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const
     for (int j = 0; j < p->n_rtab; j++) {
         (*rtab_at)[j] = spec_end;
         spec_end += 2 * x->table_n[j];
+    }
+    // phase-function tables likewise, after the index tables: {n_wavelength, n_mu} as doubles, the wavelengths, the mu
+    // axis, then the CDF rows (row-major) -- the record the kernel's PVT_PHASE_TABLE branch reads from CD_PHASE on
+    ptab_at->assign(p->n_ptab, 0);
+    for (int j = 0; j < p->n_ptab; j++) {
+        (*ptab_at)[j] = spec_end;
+        spec_end += 2 + ph->table_nw[j] + ph->table_nmu[j] + ph->table_nw[j] * ph->table_nmu[j];
     }
     p->gd.assign((size_t)spec_end + 1, 0.0);
     lay.comp_i = N * NI;
@@ -710,8 +758,9 @@ void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* 
 }
 
 // ---- fill: every record, table and guide table of the two blobs, and the BVHs of the meshes
-int fill(const PvtSceneTables* t, const PvtIndexTables* x, const Classes& k, const Spectra& sp, const Records& recs,
-         const NodeGrid& grid, const std::vector<int>& ctab_at, const std::vector<int>& rtab_at, PackedScene* p) {
+int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const Classes& k, const Spectra& sp,
+         const Records& recs, const NodeGrid& grid, const std::vector<int>& ctab_at, const std::vector<int>& rtab_at,
+         const std::vector<int>& ptab_at, PackedScene* p) {
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size();
     const Lay& lay = p->lay;
@@ -761,6 +810,15 @@ int fill(const PvtSceneTables* t, const PvtIndexTables* x, const Classes& k, con
         double* d = gd.data() + rtab_at[j];
         for (int i = 0; i < np; i++) d[i] = x->wavelength[p0 + i];
         for (int i = 0; i < np; i++) d[np + i] = x->value[p0 + i];
+    }
+    for (int j = 0; j < p->n_ptab; j++) {   // {n_wavelength, n_mu}, wavelengths (nm), mu axis, CDF rows
+        const int nw = ph->table_nw[j], nm = ph->table_nmu[j];
+        double* d = gd.data() + ptab_at[j];
+        d[0] = nw;
+        d[1] = nm;
+        for (int i = 0; i < nw; i++) d[2 + i] = ph->wavelength[ph->wl_start[j] + i];
+        for (int i = 0; i < nm; i++) d[2 + nw + i] = ph->mu[ph->mu_start[j] + i];
+        for (int i = 0; i < nw * nm; i++) d[2 + nw + nm + i] = ph->cdf[ph->cdf_start[j] + i];
     }
     fill_candidates(t, recs, p);
     for (int n = 0; n < N; n++) {
@@ -819,6 +877,7 @@ int fill(const PvtSceneTables* t, const PvtIndexTables* x, const Classes& k, con
             d[CD_PHASE] = half_pi;
             q[CI_PHASE] = PVT_PHASE_CONE;
         }
+        if (t->comp_phase_type[c] == PVT_PHASE_TABLE) d[CD_PHASE] = ptab_at[ph->comp_table[c]];   // where its table starts
         // absolute offsets into the blobs; -1: no guide table, never dereferenced
         q[CI_ABS_X] = spec_d + ab.x; q[CI_ABS_Y] = spec_d + ab.y; q[CI_ABS_N] = ab.n; q[CI_ABS_HIST] = ab.hist;
         q[CI_EMS_X] = spec_d + em.x; q[CI_EMS_CDF] = spec_d + em.y; q[CI_EMS_N] = em.n; q[CI_EMS_HIST] = em.hist;
@@ -935,14 +994,14 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
     }
 }
 
-// The tables (n_nodes and n_recorders already checked by the caller) and the refractive-index tables (x, NULL = none)
-// -> *p.  No HIP call.
-int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, PackedScene* p) {
-    int rc = validate_tables(t, x);
+// The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none) and
+// the phase-function tables (ph, NULL = none) -> *p.  No HIP call.
+int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, PackedScene* p) {
+    int rc = validate_tables(t, x, ph);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
-    const Records records = component_records(t, spectra, classes.by_node);
+    const Records records = component_records(t, ph, spectra, classes.by_node);
     NodeGrid grid;
     p->grid = plan_node_grid(t, &grid);
     for (int a = 0; a < 3; a++) p->grid_dims[a] = p->grid ? grid.n[a] : 0;
@@ -951,9 +1010,13 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, PackedScene* p)
     if (x)
         for (int n = 0; n < t->n_nodes; n++)
             if (x->n_tables > 0 && x->node_table[n] >= 0) p->n_rtab = x->n_tables;
-    std::vector<int> rtab_at;
-    const std::vector<int> ctab_at = lay_out(t, x, classes, spectra, records, grid, p, &rtab_at);
-    rc = fill(t, x, classes, spectra, records, grid, ctab_at, rtab_at, p);
+    p->n_ptab = 0;   // (likewise: a table no component uses is validated, never placed)
+    if (ph)
+        for (int c = 0; c < t->n_components; c++)
+            if (ph->n_tables > 0 && ph->comp_table[c] >= 0) p->n_ptab = ph->n_tables;
+    std::vector<int> rtab_at, ptab_at;
+    const std::vector<int> ctab_at = lay_out(t, x, ph, classes, spectra, records, grid, p, &rtab_at, &ptab_at);
+    rc = fill(t, x, ph, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
     if (rc != PVT_OK) return rc;
     prove_shortcuts(t, p);
     return PVT_OK;

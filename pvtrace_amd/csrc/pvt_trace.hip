@@ -590,6 +590,10 @@ int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
 }
 
 int pvt_scene_create_ex(const PvtSceneTables* t, const PvtIndexTables* x, int device, PvtScene** out) {
+    return pvt_scene_create_phase(t, x, nullptr, device, out);
+}
+
+int pvt_scene_create_phase(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -597,7 +601,7 @@ int pvt_scene_create_ex(const PvtSceneTables* t, const PvtIndexTables* x, int de
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, &packed);
+    const int rc = pack_scene(t, x, ph, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene

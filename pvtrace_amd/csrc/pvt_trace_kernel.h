@@ -472,6 +472,48 @@ __device__ __attribute__((noinline)) double index_class_n_call(const double* rec
     return index_table_n(tab + (int)recs[2 * k], np, wl);
 }
 
+// Tabulated phase functions (PVT_PHASE_TABLE; include/pvtrace_hip.h states the contract, the Python
+// PhaseFunctionTable samples the same way): the new direction about the incoming one `d` from the draws u1 (the row;
+// read only when the table has several), u2 (the polar cosine) and u3 (the azimuth).  `tab` is the table's record in
+// the blob the spectra are read from: {n_wavelength, n_mu}, the wavelengths, the mu axis, the CDF rows.  A FUNCTION,
+// entered only by lanes whose component has a table, so the scenes without one keep the step loop they had; the
+// 256-recorder variants of analytic scenes inline it instead (with a call one of their vector registers goes to scratch).
+__device__ __forceinline__ V3 phase_table_turn(const double* tab, double wl, double u1, double u2, double u3,
+                                               double dx, double dy, double dz) {
+    const int nw = (int)tab[0], nm = (int)tab[1];
+    const double* mus = tab + 2 + nw;
+    const double* cdf = mus + nm;
+    if (nw > 1) {   // row k + 1 with probability t, else row k (t = 0 at and beyond the ends)
+        int lo, hi;
+        double t;
+        coat_bracket(tab + 2, nw, wl, lo, hi, t);
+        cdf += (u1 < t ? hi : lo) * nm;
+    }
+    int a = 0, b = nm - 1;   // cdf[a] <= u2 < cdf[b]: cdf[0] = 0 <= u2 < 1 = cdf[nm - 1]
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (cdf[m] <= u2) a = m; else b = m;
+    }
+    const double ca = cdf[a], ma = mus[a];
+    double mu = ma + (u2 - ca) / (cdf[b] - ca) * (mus[b] - ma);
+    mu = __builtin_fmin(__builtin_fmax(mu, -1.0), 1.0);
+    const double st = sqrt1m2_normal(mu);
+    double sp, cp;
+    pvt_sincos2pi(u3, &sp, &cp);
+    // the orthonormal basis about d of Duff et al. 2017, branch-free
+    const double s = __builtin_copysign(1.0, dz);
+    const double ra = -1.0 / (s + dz);
+    const double rb = dx * dy * ra;
+    const V3 e1{1.0 + s * dx * dx * ra, s * rb, -s * dx};
+    const V3 e2{rb, s + dy * dy * ra, -dy};
+    return V3{mu * dx + st * (cp * e1.x + sp * e2.x), mu * dy + st * (cp * e1.y + sp * e2.y),
+              mu * dz + st * (cp * e1.z + sp * e2.z)};
+}
+__device__ __attribute__((noinline)) V3 phase_table_turn_call(const double* tab, double wl, double u1, double u2, double u3,
+                                                              double dx, double dy, double dz) {
+    return phase_table_turn(tab, wl, u1, u2, u3, dx, dy, dz);
+}
+
 // same, tables in global memory (emitter spectra)
 __device__ __forceinline__ double interp_global(const double* xs, const double* ys, int n, double x) {
     if (n == 1) return ys[0];
@@ -2283,6 +2325,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     double em_s, em_c, em_turn;
                     const int pt = T.iv(ci + CI_PHASE);
                     const double pp = T.dv(cd + CD_PHASE);
+                    // a tabulated phase function: CD_PHASE is where its record starts, with the spectra.  (A
+                    // wave-uniform "the scene has tables" flag in front of the lane test put a vector register of the
+                    // 256-recorder tally variants in scratch; without it the headline variant keeps its registers.)
+                    const bool tabled = pt == PVT_PHASE_TABLE;
+                    const double* ptab = (TAB_LDS == 1 ? T.ld : T.hd) + (tabled ? (int)pp : 0);
+                    double u1 = 0.0, u3 = 0.0;
                     if (pt == PVT_PHASE_HG && pvt_fabs(pp) >= kEps) {
                         double g1 = rng_uniform(rng);
                         double sg = 2.0 * g1 - 1.0;
@@ -2296,12 +2344,19 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         em_turn = g2;
                         em_c = sqrt1m2_normal(em_s);
                     } else {
+                        // isotropic; a table draws its row u1 first (when it has several), then these two are its u2
+                        // (em_turn) and u3: one set of draw sites for both
+                        if (tabled && ptab[0] > 1.0) u1 = rng_uniform(rng);
                         double g1 = rng_uniform(rng), g2 = rng_uniform(rng);
                         em_turn = g1;
                         em_c = 2.0 * g2 - 1.0;
                         em_s = sqrt1m2_normal(em_c);
+                        u3 = g2;
                     }
-                    {
+                    if (tabled) {   // about the incoming direction (PvtPhaseTables)
+                        if constexpr (MESH || SEENW == 1) dir = phase_table_turn_call(ptab, wl, u1, em_turn, u3, dir.x, dir.y, dir.z);
+                        else dir = phase_table_turn(ptab, wl, u1, em_turn, u3, dir.x, dir.y, dir.z);
+                    } else {
                         double sp, cp;
                         pvt_sincos2pi(em_turn, &sp, &cp);
                         dir = V3{em_s * cp, em_s * sp, em_c};

@@ -37,6 +37,7 @@ from pvtrace_amd.material import (
     HenyeyGreenstein,
     Luminophore,
     NullSurfaceDelegate,
+    PhaseFunctionTable,
     Reactor,
     ReflectivityTable,
     RefractiveIndexTable,
@@ -52,6 +53,7 @@ SURF_FRESNEL, SURF_NULL = 0, 1
 COMP_ABSORBER, COMP_SCATTERER, COMP_LUMINOPHORE, COMP_REACTOR = 0, 1, 2, 3
 PHASE_ISOTROPIC, PHASE_HENYEY_GREENSTEIN, PHASE_CONE = 0, 1, 2
 PHASE_LAMBERTIAN = 3   # extension: the reference compiler rejects it (compiler.py:300-310); cli/parse.py:166-167 builds it
+PHASE_TABLE = 4        # extension: a PhaseFunctionTable, sampled about the incoming direction (comp_phase_table)
 EMIT_KT, EMIT_REDSHIFT, EMIT_FULL = 0, 1, 2
 EMIT_METHODS = {"kT": EMIT_KT, "redshift": EMIT_REDSHIFT, "full": EMIT_FULL}
 
@@ -78,6 +80,8 @@ def _phase_of(node, component):
         return PHASE_CONE, float(phase.theta_max)
     if phase is M.lambertian:   # (reference material/utils.py:176-186; what `phase-function: {lambertian:}` parses to)
         return PHASE_LAMBERTIAN, 0.0
+    if isinstance(phase, PhaseFunctionTable):   # (the table itself is pooled by _lower_component)
+        return PHASE_TABLE, 0.0
     # functools.partial spellings of the same built-ins (not recognised by the
     # reference compiler, which raises for them)
     if isinstance(phase, functools.partial) and not phase.keywords:
@@ -124,6 +128,11 @@ class CompiledScene:
         # scalar column of a dispersive node holds n at the table's first wavelength.
         self.ri_table = np.full(count, -1, dtype=_I32)
         rtab = {"index": {}, "n": [], "start": [], "wavelength": [], "value": []}
+        # Phase-function tables of the components (comp_phase_table: -1 = a built-in phase function), pooled by
+        # identity: per table its rows (wavelengths) and mu points, and where its wavelengths, mu axis and CDF rows
+        # (row-major, n_wavelength x n_mu) start in the pools.
+        self._ptab = {"index": {}, "nw": [], "nmu": [], "wl_start": [], "mu_start": [], "cdf_start": [],
+                      "wavelength": [], "mu": [], "cdf": []}
         self.mesh_face_start = np.zeros(count, dtype=_I32)
         self.mesh_face_count = np.zeros(count, dtype=_I32)
         self._mesh_pool = {"vertices": [], "faces": [], "normals": [], "nv": 0, "nf": 0}
@@ -132,7 +141,7 @@ class CompiledScene:
         comp_cols = {
             key: []
             for key in (
-                "type", "qy", "tau_rad", "tau_nr", "phase_type", "phase_param",
+                "type", "qy", "tau_rad", "tau_nr", "phase_type", "phase_param", "phase_table",
                 "abs_start", "abs_n", "ems_start", "ems_n", "abs_hist", "ems_hist",
             )
         }
@@ -173,6 +182,18 @@ class CompiledScene:
         self.comp_tau_nr = np.array(comp_cols["tau_nr"], dtype=_F64)
         self.comp_phase_type = np.array(comp_cols["phase_type"], dtype=_I32)
         self.comp_phase_param = np.array(comp_cols["phase_param"], dtype=_F64)
+        self.comp_phase_table = np.array(comp_cols["phase_table"], dtype=_I32)
+        ptab = self._ptab
+        self.n_phase_tables = len(ptab["nw"])
+        self.ptab_nw = np.array(ptab["nw"], dtype=_I32)
+        self.ptab_nmu = np.array(ptab["nmu"], dtype=_I32)
+        self.ptab_wl_start = np.array(ptab["wl_start"], dtype=_I32)
+        self.ptab_mu_start = np.array(ptab["mu_start"], dtype=_I32)
+        self.ptab_cdf_start = np.array(ptab["cdf_start"], dtype=_I32)
+        self.ptab_wavelength = np.array(ptab["wavelength"], dtype=_F64)
+        self.ptab_mu = np.array(ptab["mu"], dtype=_F64)
+        self.ptab_cdf = np.array(ptab["cdf"], dtype=_F64)
+        del self._ptab
         self.comp_abs_start = np.array(comp_cols["abs_start"], dtype=_I32)
         self.comp_abs_n = np.array(comp_cols["abs_n"], dtype=_I32)
         self.comp_ems_start = np.array(comp_cols["ems_start"], dtype=_I32)
@@ -323,6 +344,23 @@ class CompiledScene:
             ctab["value"].extend(table._grid.ravel().tolist())
         return ctab["index"][key][0]
 
+    def _pool_phase_table(self, table):
+        ptab = self._ptab
+        key = id(table)
+        if key not in ptab["index"]:
+            ptab["index"][key] = (len(ptab["nw"]), table)   # (the table itself keeps its id from being reused)
+            nw, nmu = table.cdf.shape
+            ptab["nw"].append(nw)
+            ptab["nmu"].append(nmu)
+            ptab["wl_start"].append(len(ptab["wavelength"]))
+            ptab["mu_start"].append(len(ptab["mu"]))
+            ptab["cdf_start"].append(len(ptab["cdf"]))
+            # (a table without wavelengths has one row: its wavelength is never read, 0 stands in for it)
+            ptab["wavelength"].extend([0.0] if table.wavelength is None else table.wavelength.tolist())
+            ptab["mu"].extend(table.mu.tolist())
+            ptab["cdf"].extend(table.cdf.ravel().tolist())
+        return ptab["index"][key][0]
+
     # -- components ------------------------------------------------------
     def _lower_component(self, node, component, cols, pools):
         # Subclass order matters: Reactor < Absorber < Scatterer > Luminophore
@@ -357,6 +395,8 @@ class CompiledScene:
         cols["tau_nr"].append(float(component.tau_nr) if component.tau_nr else 0.0)
         cols["phase_type"].append(phase_type)
         cols["phase_param"].append(phase_param)
+        cols["phase_table"].append(
+            self._pool_phase_table(component.phase_function) if phase_type == PHASE_TABLE else -1)
         cols["abs_start"].append(a_start)
         cols["abs_n"].append(a_n)
         cols["ems_start"].append(e_start)
@@ -487,6 +527,8 @@ class CompiledScene:
         "ctab_wavelength", "ctab_angle", "ctab_value",
         "mesh_face_start", "mesh_face_count", "mesh_vertices", "mesh_faces", "mesh_normals",
         "ri_table", "rtab_n", "rtab_start", "rtab_wavelength", "rtab_value",
+        "comp_phase_table", "ptab_nw", "ptab_nmu", "ptab_wl_start", "ptab_mu_start", "ptab_cdf_start",
+        "ptab_wavelength", "ptab_mu", "ptab_cdf",
     )
 
     def tables(self):

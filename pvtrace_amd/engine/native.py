@@ -75,6 +75,16 @@ class PvtIndexTables(C.Structure):
     ]
 
 
+class PvtPhaseTables(C.Structure):
+    """Phase-function tables of a scene (include/pvtrace_hip.h; pvt_scene_create_phase)."""
+    _fields_ = [
+        ("n_tables", C.c_int32), ("n_points", C.c_int32), ("n_wavelength", C.c_int32), ("n_cdf", C.c_int32),
+        ("comp_table", _p_i32), ("table_nw", _p_i32), ("table_nmu", _p_i32),
+        ("wl_start", _p_i32), ("mu_start", _p_i32), ("cdf_start", _p_i32),
+        ("wavelength", _p_f64), ("mu", _p_f64), ("cdf", _p_f64),
+    ]
+
+
 class PvtEmitterTables(C.Structure):
     _fields_ = [
         ("n_lights", C.c_int32), ("n_spec", C.c_int32),
@@ -196,6 +206,28 @@ def index_tables_struct(compiled):
     return st, keep
 
 
+def phase_tables_struct(compiled):
+    """PvtPhaseTables over the phase-function tables of a CompiledScene -> (struct or None, keepalive); None when no
+    component has a table (the scene is then created exactly as before)."""
+    if int(getattr(compiled, "n_phase_tables", 0)) == 0:
+        return None, {}
+    st = PvtPhaseTables()
+    st.n_tables = int(compiled.n_phase_tables)
+    st.n_points = int(compiled.ptab_mu.shape[0])
+    st.n_wavelength = int(compiled.ptab_wavelength.shape[0])
+    st.n_cdf = int(compiled.ptab_cdf.shape[0])
+    keep = {}
+    for name, field, want in (("comp_phase_table", "comp_table", np.int32), ("ptab_nw", "table_nw", np.int32),
+                              ("ptab_nmu", "table_nmu", np.int32), ("ptab_wl_start", "wl_start", np.int32),
+                              ("ptab_mu_start", "mu_start", np.int32), ("ptab_cdf_start", "cdf_start", np.int32),
+                              ("ptab_wavelength", "wavelength", np.float64), ("ptab_mu", "mu", np.float64),
+                              ("ptab_cdf", "cdf", np.float64)):
+        arr = np.ascontiguousarray(getattr(compiled, name), dtype=want)
+        keep[field] = arr
+        setattr(st, field, np_ptr(arr))
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -265,6 +297,8 @@ def declare_signatures(lib, names):
         "pvt_device_count": ([], C.c_int),
         "pvt_scene_create": ([C.POINTER(PvtSceneTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_scene_create_ex": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.c_int, C.POINTER(vp)], C.c_int),
+        "pvt_scene_create_phase": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables), C.c_int,
+                                    C.POINTER(vp)], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
@@ -318,7 +352,7 @@ ABI_SYMBOLS = (
     "pvt_trace_bundle_multi", "pvt_shard_range", "pvt_trace_device_records", "pvt_unpack_records_device",
     "pvt_scene_carry_pending", "pvt_last_multi_reduce", "pvt_node_grid_plan", "pvt_scene_carry_discard", "pvt_scene_trim",
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
-    "pvt_scene_create_ex",
+    "pvt_scene_create_ex", "pvt_scene_create_phase",
 )
 
 _lib = None
@@ -469,10 +503,16 @@ class DeviceScene:
         self.device = int(device)
         st, keep = scene_tables_struct(compiled)
         xt, xkeep = index_tables_struct(compiled)
+        pt, pkeep = phase_tables_struct(compiled)
         handle = C.c_void_p()
-        check(self.lib.pvt_scene_create_ex(C.byref(st), None if xt is None else C.byref(xt), self.device,
-                                           C.byref(handle)),
-              "pvt_scene_create_ex")
+        if pt is None:   # (scenes without phase-function tables are created exactly as before)
+            check(self.lib.pvt_scene_create_ex(C.byref(st), None if xt is None else C.byref(xt), self.device,
+                                               C.byref(handle)),
+                  "pvt_scene_create_ex")
+        else:
+            check(self.lib.pvt_scene_create_phase(C.byref(st), None if xt is None else C.byref(xt), C.byref(pt),
+                                                  self.device, C.byref(handle)),
+                  "pvt_scene_create_phase")
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a

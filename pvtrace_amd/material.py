@@ -417,6 +417,164 @@ class RefractiveIndexTable(object):
         return cls(wavelength, np.sqrt(n2))
 
 
+def ray_basis(direction):
+    """(e1, e2): the orthonormal basis about the unit vector `direction` = (x, y, z) that tabulated phase functions
+    scatter in (Duff et al. 2017, "Building an orthonormal basis, revisited"), branch-free:
+    s = copysign(1, z), a = -1 / (s + z), b = x y a,
+    e1 = (1 + s x^2 a, s b, -s x), e2 = (b, s + y^2 a, -y).
+    `direction` may be (3,) or (n, 3); the device evaluates the same expressions."""
+    d = np.asarray(direction, dtype=np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    s = np.copysign(1.0, z)
+    a = -1.0 / (s + z)
+    b = x * y * a
+    e1 = np.stack([1.0 + s * x * x * a, s * b, -s * x], axis=-1)
+    e2 = np.stack([b, s + y * y * a, -y], axis=-1)
+    return e1, e2
+
+
+class PhaseFunctionTable(object):
+    """A tabulated phase function p(theta), optionally one row per wavelength, sampled about the INCOMING direction.
+
+    angle : scattering angles theta in degrees, strictly increasing from exactly 0 to exactly 180, at least 2.
+    values : p(theta) per unit solid angle, unnormalised, finite and >= 0, each row with a positive integral; shape
+        (n_angle,) without `wavelength`, else (n_wavelength, n_angle).
+    wavelength : None, or strictly increasing finite wavelengths in nm, one per row of `values`.
+
+    Unlike the built-in phase functions, which draw about +z, the scattering angle is measured from the photon's
+    incoming direction d.  The sampling contract, the same on the host and on the device (include/pvtrace_hip.h):
+
+    1. Axis and CDF.  mu_j = cos(theta_j), reordered so mu runs from -1 to 1, the ends exactly -1 and 1.  Each row's
+       CDF in mu is the trapezoid integral sum 0.5 (p_j + p_j+1)(mu_j+1 - mu_j) with a leading 0, divided by its last
+       entry, which is then exactly 1 (the structure of `Distribution(hist=False)`, with the widths of the mu axis).
+    2. Row, only when n_wavelength > 1: clamp the photon's wavelength lambda into the table's range, find k with
+       lambda_k <= lambda < lambda_k+1, t = (lambda - lambda_k) / (lambda_k+1 - lambda_k) (t = 0 at either clamped
+       end, the last row above the range); draw u1 and take row k+1 if u1 < t, else row k: the linear-in-lambda mixture
+       of the normalised rows.  u1 is drawn whenever n_wavelength > 1.  Without a wavelength (a light's direction),
+       the first row is used, u1 still drawn.
+    3. Polar angle: draw u2; j is the first segment with C_j+1 > u2 (segments of zero mass are never chosen);
+       mu = mu_j + (u2 - C_j) / (C_j+1 - C_j) (mu_j+1 - mu_j), clamped to [-1, 1].
+    4. Azimuth: draw u3, phi = 2 pi u3 (pvt_sincos2pi on the device); the new direction is
+       d' = mu d + sqrt(1 - mu^2) (cos(phi) e1 + sin(phi) e2), (e1, e2) = `ray_basis(d)`.
+    5. Draw order: u1 (if drawn), u2, u3, in place of the built-ins' phase-function draws; a luminophore's wavelength
+       and delay draws follow as before.
+
+    As a light's `direction`, the incoming direction is the light's +z: `sample(n)` gives a bundle, a call without
+    arguments one direction.
+    """
+
+    def __init__(self, angle, values, wavelength=None):
+        ang = np.array(angle, dtype=np.float64)
+        if ang.ndim != 1 or ang.size < 2:
+            raise ValueError("angle must be a 1-D sequence of at least 2 scattering angles")
+        if not np.all(np.isfinite(ang)) or np.any(np.diff(ang) <= 0.0):
+            raise ValueError("angle must be finite and strictly increasing")
+        if ang[0] != 0.0 or ang[-1] != 180.0:
+            raise ValueError("angle must start at exactly 0 and end at exactly 180 degrees")
+        vals = np.array(values, dtype=np.float64)
+        if wavelength is None:
+            if vals.shape != (ang.size,):
+                raise ValueError(f"values must have shape (n_angle,) = ({ang.size},), got {vals.shape}")
+            wl = None
+            rows = vals[None, :]
+        else:
+            wl = np.array(wavelength, dtype=np.float64)
+            if wl.ndim != 1 or wl.size < 1:
+                raise ValueError("wavelength must be a non-empty 1-D sequence")
+            if not np.all(np.isfinite(wl)) or np.any(np.diff(wl) <= 0.0):
+                raise ValueError("wavelength must be finite and strictly increasing")
+            if vals.shape != (wl.size, ang.size):
+                raise ValueError(
+                    f"values must have shape (n_wavelength, n_angle) = ({wl.size}, {ang.size}), got {vals.shape}")
+            rows = vals
+        if not np.all(np.isfinite(vals)) or np.any(vals < 0.0):
+            raise ValueError("values must be finite and >= 0")
+        mu = np.cos(np.radians(ang))[::-1].copy()
+        mu[0], mu[-1] = -1.0, 1.0
+        if np.any(np.diff(mu) <= 0.0):
+            raise ValueError("angle: neighbouring angles too close to give distinct cosines")
+        p = rows[:, ::-1]
+        cdf = np.cumsum(0.5 * (p[:, :-1] + p[:, 1:]) * np.diff(mu)[None, :], axis=1)
+        total = cdf[:, -1:]
+        if not np.all(np.isfinite(total)) or np.any(total <= 0.0):
+            raise ValueError("every row of values must have a positive, finite integral")
+        cdf = np.hstack([np.zeros((rows.shape[0], 1)), cdf / total])
+        cdf[:, -1] = 1.0
+        self.angle = ang
+        self.values = vals
+        self.wavelength = wl
+        self.mu = mu
+        self.cdf = cdf
+
+    @property
+    def n_wavelength(self):
+        return self.cdf.shape[0]
+
+    def rows(self, wavelength, u1):
+        """The row each photon takes (step 2): `wavelength` and `u1` scalars or arrays; None = the first row."""
+        u1 = np.asarray(u1, dtype=np.float64)
+        if self.n_wavelength == 1 or wavelength is None:
+            return np.zeros(u1.shape, dtype=np.int64)
+        wl = np.broadcast_to(np.asarray(wavelength, dtype=np.float64), u1.shape)
+        axis = self.wavelength
+        n = axis.size
+        lo = np.clip(np.searchsorted(axis, wl, side="right") - 1, 0, n - 1)
+        hi = np.minimum(lo + 1, n - 1)
+        inside = (wl > axis[0]) & (wl < axis[-1])
+        t = np.where(inside, (wl - axis[lo]) / np.where(inside, axis[hi] - axis[lo], 1.0), 0.0)
+        lo = np.where(wl < axis[-1], lo, n - 1)
+        hi = np.where(inside, hi, lo)
+        return np.where(u1 < t, hi, lo)
+
+    def sample_mu(self, u2, row=0):
+        """mu = cos(theta) of step 3 for the draws `u2` in the rows `row` (scalars or arrays)."""
+        u2 = np.asarray(u2, dtype=np.float64)
+        row = np.broadcast_to(np.asarray(row, dtype=np.int64), u2.shape)
+        j = np.zeros(u2.shape, dtype=np.int64)
+        for r in np.unique(row):   # the last C_j <= u2 is the first segment with C_j+1 > u2
+            at = row == r
+            j[at] = np.searchsorted(self.cdf[r], u2[at], side="right") - 1
+        j = np.minimum(j, self.mu.size - 2)
+        cj, cj1 = self.cdf[row, j], self.cdf[row, j + 1]
+        mu = self.mu[j] + (u2 - cj) / (cj1 - cj) * (self.mu[j + 1] - self.mu[j])
+        return np.clip(mu, -1.0, 1.0)
+
+    def turn(self, direction, mu, u3):
+        """Step 4: the direction at polar cosine `mu` and azimuth 2 pi `u3` about the unit vector(s) `direction`."""
+        d = np.asarray(direction, dtype=np.float64)
+        mu = np.asarray(mu, dtype=np.float64)[..., None]
+        phi = 2.0 * np.pi * np.asarray(u3, dtype=np.float64)[..., None]
+        e1, e2 = ray_basis(d)
+        return mu * d + np.sqrt((1.0 - mu) * (1.0 + mu)) * (np.cos(phi) * e1 + np.sin(phi) * e2)
+
+    def __call__(self, direction=None, wavelength=None):
+        """One new direction about `direction` (None: +z, a light's axis) for a photon of `wavelength` (nm), drawn
+        from numpy's global generator in the contract's order."""
+        u1 = np.random.uniform() if self.n_wavelength > 1 else 0.0
+        u2 = np.random.uniform()
+        u3 = np.random.uniform()
+        d = (0.0, 0.0, 1.0) if direction is None else direction
+        mu = self.sample_mu(u2, self.rows(wavelength, u1))
+        return self.turn(d, mu, u3)
+
+    def sample(self, n):
+        """(n, 3) directions about +z: a light's `direction` delegate, vectorised (engine/emit.py)."""
+        n = int(n)
+        k = 3 if self.n_wavelength > 1 else 2
+        u = np.random.uniform(size=(n, k))
+        row = self.rows(None, u[:, 0])
+        mu = self.sample_mu(u[:, k - 2], row)
+        return self.turn(np.array([0.0, 0.0, 1.0]), mu, u[:, k - 1])
+
+
+def phase_direction(phase_function, ray):
+    """A scattered or re-emitted direction: a `PhaseFunctionTable` draws about the ray's own direction at its
+    wavelength, the built-ins (and user callables) are called with no arguments, about +z."""
+    if isinstance(phase_function, PhaseFunctionTable):
+        return phase_function(ray.direction, ray.wavelength)
+    return phase_function()
+
+
 class Coating(object):
     """Declarative override of the optics on part of a node's surface.
 
@@ -645,8 +803,9 @@ class Scatterer(Component):
         return ray
 
     def emit(self, ray, **kwargs):
-        """Scattered: a new direction from the phase function (in the frame the ray is given in), the scatterer as source."""
-        return replace(ray, direction=self.phase_function(), source=self.name)
+        """Scattered: a new direction from the phase function (in the frame the ray is given in; a `PhaseFunctionTable`
+        draws about the ray's direction), the scatterer as source."""
+        return replace(ray, direction=phase_direction(self.phase_function, ray), source=self.name)
 
 
 class Absorber(Scatterer):
@@ -686,7 +845,7 @@ class Luminophore(Scatterer):
         above the absorbed photon's energy, "redshift": from the absorbed wavelength, "full": the whole spectrum -- and,
         with `tau_rad` set, an exponentially distributed emission delay.  Like the reference's it raises when "kT" lands
         outside the spectrum's range; the engine clamps there (differences between the two tracers)."""
-        direction = self.phase_function()
+        direction = phase_direction(self.phase_function, ray)
         nm = ray.wavelength
         if method == "kT":
             nm = 1240.0 / (1240.0 / nm + 3 / 2 * KB_EV * T)

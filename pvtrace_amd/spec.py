@@ -24,8 +24,8 @@ from pvtrace_amd.light import (
     CircularMask, ConstantWavelengthMask, CubeMask, Light, RectangularMask, SpectrumWavelengthMask,
 )
 from pvtrace_amd.material import (
-    Absorber, Cone, Distribution, HenyeyGreenstein, Luminophore, Material, Scatterer, isotropic,
-    lambertian,
+    Absorber, Cone, Distribution, HenyeyGreenstein, Luminophore, Material, PhaseFunctionTable, Scatterer,
+    isotropic, lambertian,
 )
 from pvtrace_amd.scene import Node, Scene
 
@@ -116,6 +116,14 @@ class _Builder:
             return Cone(float(np.radians(float(entry["cone"]["half-angle"]))))
         if "henyey-greenstein" in entry:
             return HenyeyGreenstein(float(entry["henyey-greenstein"]["g"]))
+        if "table" in entry:   # tabulated p(theta), sampled about the incoming direction (PhaseFunctionTable)
+            t = entry["table"]
+            if not isinstance(t, dict) or "angle" not in t or "values" not in t:
+                raise SpecError(f"phase-function table needs `angle` and `values`: {entry!r}")
+            try:
+                return PhaseFunctionTable(t["angle"], t["values"], wavelength=t.get("wavelength"))
+            except ValueError as exc:
+                raise SpecError(f"phase-function table: {exc}") from exc
         raise SpecError(f"unknown direction / phase function {entry!r}")
 
     @staticmethod
