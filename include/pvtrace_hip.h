@@ -217,6 +217,33 @@ typedef struct PvtPhaseTables {
     const double* cdf;              /* pooled CDF rows */
 } PvtPhaseTables;
 
+/* ---- rough interfaces (extension within v13, passed to pvt_scene_create_rough) ------------------------------------
+ * node_roughness[n] is the GGX (Trowbridge-Reitz) width alpha, finite and 0 <= alpha <= 1, of node n's surface: the
+ * HIT node's alpha applies, at points that no coating covers (a covered point behaves as a smooth one, no draw); a
+ * NULL struct, n_nodes 0 or every alpha 0 is exactly pvt_scene_create_phase.  The sampling contract (the Python
+ * FresnelSurfaceDelegate(roughness=...) is the same):
+ *  1. Frame: N is the geometric normal at the hit turned to face the photon (d.N < 0), v = -d, (e1, e2) the basis of
+ *     Duff et al. 2017 about N (the expressions of the phase-table contract above), v_l = (v.e1, v.e2, v.N).
+ *  2. Microfacet normal (the GGX distribution of visible normals, Heitz 2018, JCGT 7(4)): draw u_a, then u_b;
+ *     Vh = normalize(alpha v_l.x, alpha v_l.y, v_l.z); T1 = (-Vh.y, Vh.x, 0) / sqrt(Vh.x^2 + Vh.y^2), (1, 0, 0) when
+ *     that sum is 0; T2 = Vh x T1; r = sqrt(u_a), (sin phi, cos phi) = pvt_sincos2pi(u_b); t1 = r cos phi,
+ *     s = (1 + Vh.z) / 2, t2 = (1 - s) sqrt(1 - t1^2) + s r sin phi; Nh = t1 T1 + t2 T2 + sqrt(max(0, 1 - t1^2 - t2^2)) Vh;
+ *     m_l = normalize(alpha Nh.x, alpha Nh.y, max(0, Nh.z)); m = m_l.x e1 + m_l.y e2 + m_l.z N (v.m > 0).
+ *  3. Fresnel about m: cos theta_m = v.m clamped to [0, 1], n1 and n2 at the photon's wavelength, the smooth branch's
+ *     Hecht formula; R = 1 where q = n1 / n2 sin theta_m >= 1 (total internal reflection about m).
+ *  4. Decision: the reflect-or-transmit draw u as for a smooth interface, only when R > 0.
+ *  5. Direction: reflection d' = d - 2 (d.m) m; transmission by the smooth branch's vector form of Snell's law with m
+ *     in place of the normal.
+ *  6. Fold: a reflected d' with d'.N < 0, or a transmitted d' with d'.N > 0, is mirrored across the tangent plane:
+ *     d' <- d' - 2 (d'.N) N (no draw).
+ *  7. Draw order: u_a, u_b, then u (if R > 0); event kinds, recorder selectors and the logged normal (the geometric
+ *     one) follow the smooth rules.
+ * A separate struct so that PvtSceneTables, PvtIndexTables and PvtPhaseTables keep the lengths old callers pass. */
+typedef struct PvtSurfaceTables {
+    int32_t n_nodes;                /* 0 = none (as a NULL struct), else the scene's n_nodes */
+    const double* node_roughness;   /* (n_nodes) GGX alpha of each node's surface, 0 = smooth */
+} PvtSurfaceTables;
+
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
@@ -357,6 +384,10 @@ int pvt_scene_create_ex(const PvtSceneTables* tables, const PvtIndexTables* inde
  * pvt_scene_create_ex refuse a component tagged PVT_PHASE_TABLE (PVT_ERR_INVALID). */
 int pvt_scene_create_phase(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                            const PvtPhaseTables* phase_tables, int device, PvtScene** out);
+/* The same with rough interfaces (NULL, n_nodes 0 or every alpha 0 = none: then exactly pvt_scene_create_phase). */
+int pvt_scene_create_rough(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                           const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables, int device,
+                           PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);

@@ -338,6 +338,7 @@ struct PackedScene {
     std::vector<double> gd;
     std::vector<int> gi;
     int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, n_ptab = 0, lazy_root = 0;
+    int rough_d = -1;   // where the nodes' GGX widths start in the double blob (-1: no node is rough)
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     int grid_dims[3] = {0, 0, 0};
@@ -348,7 +349,7 @@ struct PackedScene {
 
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
-int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph) {
+int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -454,6 +455,15 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
             total += 2 + nw + nm + nw * nm;
         }
         if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "phase tables: more than 2^27 doubles");
+    }
+    // rough interfaces (PvtSurfaceTables, pvt_scene_create_rough): one finite GGX width 0 <= alpha <= 1 per node
+    if (rs && rs->n_nodes != 0) {
+        if (rs->n_nodes != N || !rs->node_roughness) return fail(PVT_ERR_INVALID, "surface tables: need one roughness per node");
+        for (int n = 0; n < N; n++) {
+            const double a = rs->node_roughness[n];
+            if (!(std::isfinite(a) && a >= 0.0 && a <= 1.0))
+                return fail(PVT_ERR_INVALID, "surface tables: roughness must be finite and within [0, 1]");
+        }
     }
     // runs [start, start + count) into a table of `size` rows
     auto bad_run = [](long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; };
@@ -646,7 +656,8 @@ Records component_records(const PvtSceneTables* t, const PvtPhaseTables* ph, con
 // critical angles, rotation classes, index classes and the node grid -- and the spectra last: when a scene's spectra are
 // too large for LDS, a workgroup still stages everything before `spec_d` (KArgs::nd_lds; the guide tables are the tail
 // of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes, in
-// *rtab_at where each refractive-index table goes and in *ptab_at where each phase-function table goes.
+// *rtab_at where each refractive-index table goes and in *ptab_at where each phase-function table goes (p->rough_d, set by
+// the caller when some node is rough, is moved to where the nodes' GGX widths go).
 std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const Classes& k,
                          const Spectra& sp, const Records& recs, const NodeGrid& grid, PackedScene* p, std::vector<int>* rtab_at,
                          std::vector<int>* ptab_at) {
@@ -690,6 +701,12 @@ std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const
     for (int j = 0; j < p->n_ptab; j++) {
         (*ptab_at)[j] = spec_end;
         spec_end += 2 + ph->table_nw[j] + ph->table_nmu[j] + ph->table_nw[j] * ph->table_nmu[j];
+    }
+    // (scenes with a rough node) the GGX width alpha of every node, after the phase-function tables: the kernel's
+    // UF_ROUGH lanes read their hit node's from where the spectra are read
+    if (p->rough_d >= 0) {
+        p->rough_d = spec_end;
+        spec_end += N;
     }
     p->gd.assign((size_t)spec_end + 1, 0.0);
     lay.comp_i = N * NI;
@@ -758,7 +775,8 @@ void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* 
 }
 
 // ---- fill: every record, table and guide table of the two blobs, and the BVHs of the meshes
-int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const Classes& k, const Spectra& sp,
+int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+         const Classes& k, const Spectra& sp,
          const Records& recs, const NodeGrid& grid, const std::vector<int>& ctab_at, const std::vector<int>& rtab_at,
          const std::vector<int>& ptab_at, PackedScene* p) {
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
@@ -820,6 +838,8 @@ int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables*
         for (int i = 0; i < nm; i++) d[2 + nw + i] = ph->mu[ph->mu_start[j] + i];
         for (int i = 0; i < nw * nm; i++) d[2 + nw + nm + i] = ph->cdf[ph->cdf_start[j] + i];
     }
+    if (p->rough_d >= 0)
+        for (int n = 0; n < N; n++) gd[p->rough_d + n] = rs->node_roughness[n];
     fill_candidates(t, recs, p);
     for (int n = 0; n < N; n++) {
         double* d = gd.data() + n * ND;
@@ -994,10 +1014,11 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
     }
 }
 
-// The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none) and
-// the phase-function tables (ph, NULL = none) -> *p.  No HIP call.
-int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, PackedScene* p) {
-    int rc = validate_tables(t, x, ph);
+// The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the
+// phase-function tables (ph, NULL = none) and the nodes' surface roughness (rs, NULL = none) -> *p.  No HIP call.
+int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+               PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
@@ -1014,9 +1035,13 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     if (ph)
         for (int c = 0; c < t->n_components; c++)
             if (ph->n_tables > 0 && ph->comp_table[c] >= 0) p->n_ptab = ph->n_tables;
+    p->rough_d = -1;   // (a struct of zeros places nothing: the scene lays out as a smooth one)
+    if (rs && rs->n_nodes > 0)
+        for (int n = 0; n < t->n_nodes; n++)
+            if (rs->node_roughness[n] > 0.0) p->rough_d = 0;
     std::vector<int> rtab_at, ptab_at;
     const std::vector<int> ctab_at = lay_out(t, x, ph, classes, spectra, records, grid, p, &rtab_at, &ptab_at);
-    rc = fill(t, x, ph, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
+    rc = fill(t, x, ph, rs, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
     if (rc != PVT_OK) return rc;
     prove_shortcuts(t, p);
     return PVT_OK;

@@ -97,6 +97,7 @@ struct PvtScene {
     int nd = 0, ni = 0;
     int nd_small = 0, ni_small = 0;   // ... of which everything but the spectra / their guide tables (the blobs' heads)
     int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
+    int rough_d = -1;                   // where the nodes' GGX widths start in the double blob (-1: no rough node)
     double* d_gd = nullptr;
     int* d_gi = nullptr;
     double* d_ed = nullptr;
@@ -223,6 +224,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.nd_lds = 0; a.ni_lds = 0;
     a.n_nodes = s->n_nodes; a.root = s->root; a.n_rec = s->n_rec; a.total_bins = s->total_bins;
     a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_rtab = s->n_rtab; a.n_lights = s->n_lights;
+    a.rough_d = s->rough_d;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -237,8 +239,37 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
 #ifndef PVT_DEV_VARIANTS
 #define PVT_DEV_VARIANTS 0   // developer builds: only the analytic, array-input, <=64-recorder variants (fast compile)
 #endif
+// Scenes with a rough node (KArgs::rough_d >= 0) run the trace_kernel_rough* families: the same choice of variant.
+template <bool RECORD, int TAB_LDS, int SEENW>
+hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
+#if PVT_DEV_VARIANTS
+    (void)emit; (void)grid; (void)lds; (void)st; (void)a;
+    return hipErrorNotSupported;
+#else
+    const bool mesh = a.bvh != nullptr;
+    if constexpr (TAB_LDS == 1) {
+        if (a.lay.grid_d >= 0 && !mesh) {
+            if (emit) hipLaunchKernelGGL((trace_kernel_rough_grid<RECORD, SEENW, true>), dim3(grid), dim3(kBlock), lds, st, a);
+            else hipLaunchKernelGGL((trace_kernel_rough_grid<RECORD, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
+            return hipGetLastError();
+        }
+    }
+    constexpr int MESH_TAB = TAB_LDS == 2 ? 0 : TAB_LDS;
+    if (mesh && TAB_LDS == 2) return hipErrorNotSupported;
+    if (emit) {
+        if (mesh) hipLaunchKernelGGL((trace_kernel_rough<RECORD, MESH_TAB, SEENW, true, true>), dim3(grid), dim3(kBlock), lds, st, a);
+        else hipLaunchKernelGGL((trace_kernel_rough_w4<RECORD, TAB_LDS, SEENW, true>), dim3(grid), dim3(kBlock), lds, st, a);
+    } else {
+        if (mesh) hipLaunchKernelGGL((trace_kernel_rough<RECORD, MESH_TAB, SEENW, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
+        else hipLaunchKernelGGL((trace_kernel_rough_w4<RECORD, TAB_LDS, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
+    }
+    return hipGetLastError();
+#endif
+}
+
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
+    if (a.rough_d >= 0) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
     const bool mesh = a.bvh != nullptr;
     if constexpr (TAB_LDS == 1 && (!PVT_DEV_VARIANTS || SEENW == 1) && PVT_DEV_VARIANTS != 2) {
         if (a.lay.grid_d >= 0 && !mesh && (!PVT_DEV_VARIANTS || !emit)) {   // many nodes: per-lane walk of the node grid
@@ -594,6 +625,11 @@ int pvt_scene_create_ex(const PvtSceneTables* t, const PvtIndexTables* x, int de
 }
 
 int pvt_scene_create_phase(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, int device, PvtScene** out) {
+    return pvt_scene_create_rough(t, x, ph, nullptr, device, out);
+}
+
+int pvt_scene_create_rough(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                           const PvtSurfaceTables* rs, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -601,7 +637,7 @@ int pvt_scene_create_phase(const PvtSceneTables* t, const PvtIndexTables* x, con
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, &packed);
+    const int rc = pack_scene(t, x, ph, rs, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -618,6 +654,7 @@ int pvt_scene_create_phase(const PvtSceneTables* t, const PvtIndexTables* x, con
     s->nd_small = packed.nd_small; s->ni_small = packed.ni_small;
     s->n_nodes = t->n_nodes; s->root = t->root_id; s->n_rec = t->n_recorders;
     s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab; s->n_rtab = packed.n_rtab;
+    s->rough_d = packed.rough_d;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
     s->grid = packed.grid;

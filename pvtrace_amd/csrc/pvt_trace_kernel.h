@@ -205,6 +205,9 @@ struct KArgs {
     // the scene -- an event log, an `exit` recorder): there the root's crossing is skipped only when another crossing is known
     // to lie before it, and worked out exactly when it is the nearest one -- among a lone wave's few photons hardly ever.
     int lazy_tail;
+    // Rough interfaces (pvt_scene_create_rough): where the nodes' GGX widths alpha start in the double blob, read from
+    // where the spectra are read; -1 = no node is rough (UF_ROUGH off)
+    int rough_d;
 };
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
 constexpr int kCarryBase = 14;     // u64 words of a parked photon before its seen-mask
@@ -512,6 +515,85 @@ __device__ __forceinline__ V3 phase_table_turn(const double* tab, double wl, dou
 __device__ __attribute__((noinline)) V3 phase_table_turn_call(const double* tab, double wl, double u1, double u2, double u3,
                                                               double dx, double dy, double dz) {
     return phase_table_turn(tab, wl, u1, u2, u3, dx, dy, dz);
+}
+
+// Rough interfaces (PvtSurfaceTables; include/pvtrace_hip.h states the contract, the Python FresnelSurfaceDelegate samples
+// the same way): one surface event of a lane whose hit node is rough where no coating covers it (UF_ROUGH) -- the draws
+// u_a, u_b, the microfacet normal m from the GGX distribution of visible normals of width `alpha` (Heitz 2018) about the
+// geometric normal `n` (either orientation) facing the photon, Fresnel about m, the draw u when R > 0, the reflected or
+// refracted direction about m and the fold.  The photon's random stream goes in and comes back by value (a reference
+// would put it in scratch).  A FUNCTION, called only from the trace_kernel_rough* variants.
+struct RoughEvent {
+    double dx, dy, dz;                   // the new direction
+    unsigned long long s0, s1, s2, s3;   // the photon's random stream after the event's draws
+    int reflect;                         // 1: REFLECT, 0: TRANSMIT
+};
+__device__ __attribute__((noinline)) RoughEvent rough_event_call(double alpha, double nx, double ny, double nz, double dx, double dy,
+                                                        double dz, double n1, double n2, unsigned long long s0,
+                                                        unsigned long long s1, unsigned long long s2, unsigned long long s3) {
+    Rng rng{s0, s1, s2, s3};
+    const double ua = rng_uniform(rng);
+    const double ub = rng_uniform(rng);
+    // N: the geometric normal facing the photon (d.N < 0); (e1, e2) the basis of Duff et al. 2017 about it
+    const double o = nx * dx + ny * dy + nz * dz > 0.0 ? -1.0 : 1.0;
+    const V3 N{o * nx, o * ny, o * nz};
+    const double s = __builtin_copysign(1.0, N.z);
+    const double ra = -1.0 / (s + N.z);
+    const double rb = N.x * N.y * ra;
+    const V3 e1{1.0 + s * N.x * N.x * ra, s * rb, -s * N.x};
+    const V3 e2{rb, s + N.y * N.y * ra, -N.y};
+    const V3 d{dx, dy, dz};
+    // v = -d in the frame, stretched by alpha: the hemisphere configuration
+    double hx = -alpha * dot3(d, e1), hy = -alpha * dot3(d, e2), hz = -dot3(d, N);
+    double il = 1.0 / pvt_sqrt(hx * hx + hy * hy + hz * hz);
+    hx *= il; hy *= il; hz *= il;
+    const double lensq = hx * hx + hy * hy;
+    double t1x = 1.0, t1y = 0.0;
+    if (lensq > 0.0) {
+        const double it = 1.0 / pvt_sqrt(lensq);
+        t1x = -hy * it;
+        t1y = hx * it;
+    }
+    const double t2x = -hz * t1y, t2y = hz * t1x, t2z = hx * t1y - hy * t1x;   // Vh x T1 (T1.z = 0)
+    const double r = pvt_sqrt(ua);
+    double sp, cp;
+    pvt_sincos2pi(ub, &sp, &cp);
+    const double t1 = r * cp, sw = 0.5 * (1.0 + hz);
+    const double t2 = (1.0 - sw) * pvt_sqrt(__builtin_fmax(0.0, 1.0 - t1 * t1)) + sw * r * sp;
+    const double tz = pvt_sqrt(__builtin_fmax(0.0, 1.0 - t1 * t1 - t2 * t2));
+    double lx = alpha * (t1 * t1x + t2 * t2x + tz * hx), ly = alpha * (t1 * t1y + t2 * t2y + tz * hy);
+    double lz = __builtin_fmax(0.0, t2 * t2z + tz * hz);
+    il = 1.0 / pvt_sqrt(lx * lx + ly * ly + lz * lz);
+    lx *= il; ly *= il; lz *= il;
+    const V3 m{lx * e1.x + ly * e2.x + lz * N.x, lx * e1.y + ly * e2.y + lz * N.y, lx * e1.z + ly * e2.z + lz * N.z};
+    // Fresnel about m (the smooth branch's Hecht formula), 1 under total internal reflection about m
+    const double dm = dot3(d, m);   // -(v.m)
+    const double c = __builtin_fmin(__builtin_fmax(-dm, 0.0), 1.0);
+    const double q = n1 / n2 * pvt_sqrt((1.0 - c) * (1.0 + c));
+    double R = 1.0;
+    if (q < 1.0) {
+        const double k = pvt_sqrt(1.0 - q * q);
+        const double as = (n1 * c - n2 * k) / (n1 * c + n2 * k), ap = (n1 * k - n2 * c) / (n1 * k + n2 * c);
+        R = 0.5 * (as * as + ap * ap);
+    }
+    double u = 1.0;
+    if (R > 0.0) u = rng_uniform(rng);
+    RoughEvent e;
+    e.reflect = u < R ? 1 : 0;
+    V3 t;
+    if (e.reflect) {
+        t = V3{dx - 2.0 * dm * m.x, dy - 2.0 * dm * m.y, dz - 2.0 * dm * m.z};
+    } else {   // Snell, vector form, about -m (the microfacet normal along the ray)
+        const double n = n1 / n2;
+        const double k = pvt_sqrt(__builtin_fmax(0.0, 1.0 - n * n * (1.0 - c * c))) - n * c;
+        t = V3{n * dx - k * m.x, n * dy - k * m.y, n * dz - k * m.z};
+    }
+    // fold: back across the tangent plane when on the wrong side of the geometric normal (N faces the photon)
+    const double tn = dot3(t, N);
+    if (e.reflect ? tn < 0.0 : tn > 0.0) t = V3{t.x - 2.0 * tn * N.x, t.y - 2.0 * tn * N.y, t.z - 2.0 * tn * N.z};
+    e.dx = t.x; e.dy = t.y; e.dz = t.z;
+    e.s0 = rng.s0; e.s1 = rng.s1; e.s2 = rng.s2; e.s3 = rng.s3;
+    return e;
 }
 
 // same, tables in global memory (emitter spectra)
@@ -823,7 +905,7 @@ struct Seen {
 // GRID: scenes of many nodes -- every lane finds the nodes its ray can cross through a uniform grid (see the node loop).
 // TAIL: the same loop as a FUNCTION for the last wave of a draining workgroup (`tail_run`, below): no rays to claim, no
 // rendezvous -- it takes the `tail_total` photons its caller left in the exchange buffer and steps them until none is left.
-template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID>
+template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH = false>
 __device__ void tail_run(const KArgs* kernel_args, int total, unsigned int lds);
 
 // A wave leaves its workgroup: the LAST one to do so adds the workgroup's accumulators (LDS) to the launch's outputs -- one
@@ -894,7 +976,7 @@ __device__ __attribute__((noinline)) void leave_workgroup(const KArgs* kernel_ar
         }
 }
 
-template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false>
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, bool ROUGH = false>
 __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, unsigned int tail_lds = 0u) {
     extern __shared__ double smem_of_kernel[];
     // (In a called function the address of the kernel's dynamic LDS is looked up in a table in memory wherever it is used --
@@ -925,13 +1007,14 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
         (A.emit_method == PVT_EMIT_FULL ? 1u << UF_EMIT_FULL : 0u) | (A.emit_method == PVT_EMIT_KT ? 1u << UF_EMIT_KT : 0u) |
         (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u) |
-        (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u);
+        (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u) |
+        (ROUGH && A.rough_d >= 0 ? 1u << UF_ROUGH : 0u);   // (only the rough variants read rough_d)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
@@ -2598,9 +2681,25 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     if (cr >= 0.0 && !keep_tir) r = cr;
                 }
             }
+            // (scenes with a rough node) a microfacet normal m for lanes whose hit node is rough and whose point no coating
+            // covers: Fresnel about m, then the direction about m (PvtSurfaceTables); draws u_a, u_b before u
+            bool rough = false, rough_reflect = false;
+            if constexpr (ROUGH) {   // (the variants of scenes with a rough node only: the smooth ones keep their step loop)
+              if (uf(UF_ROUGH) && fres && coat < 0) {
+                const double alpha = T.sd(A.rough_d + hit);
+                if (alpha > 0.0) {
+                    const RoughEvent e = rough_event_call(alpha, nrm.x, nrm.y, nrm.z, dir.x, dir.y, dir.z, n1, n2, rng.s0, rng.s1,
+                                                          rng.s2, rng.s3);
+                    dir = V3{e.dx, e.dy, e.dz};
+                    rng = Rng{e.s0, e.s1, e.s2, e.s3};
+                    rough = true;
+                    rough_reflect = e.reflect != 0;
+                }
+              }
+            }
             double u = 1.0;
-            if (r > 0.0) u = rng_uniform(rng);
-            if (u < r) {
+            if (r > 0.0 && !rough) u = rng_uniform(rng);
+            if (rough ? rough_reflect : u < r) {
                 bool lamb = false;
                 if (coat >= 0) lamb = T.iv(L.coat_i + coat * KI + KI_RMODE) == 1;
                 if (lamb) {
@@ -2622,7 +2721,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     dir.x = T.dv(q + 0) * dl.x + T.dv(q + 1) * dl.y + T.dv(q + 2) * dl.z;
                     dir.y = T.dv(q + 3) * dl.x + T.dv(q + 4) * dl.y + T.dv(q + 5) * dl.z;
                     dir.z = T.dv(q + 6) * dl.x + T.dv(q + 7) * dl.y + T.dv(q + 8) * dl.z;
-                } else {  // specular (:422-433): nf is nrm flipped along dir, dd their dot product (formed above)
+                } else if (!rough) {  // specular (:422-433): nf is nrm flipped along dir, dd their dot product (formed above)
                     const V3 nf{flip ? -nrm.x : nrm.x, flip ? -nrm.y : nrm.y, flip ? -nrm.z : nrm.z};
                     const double dd = ddot;
                     dir = V3{dir.x - 2.0 * dd * nf.x, dir.y - 2.0 * dd * nf.y, dir.z - 2.0 * dd * nf.z};
@@ -2632,7 +2731,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             } else {
                 bool matched = false;
                 if (coat >= 0) matched = T.iv(L.coat_i + coat * KI + KI_TMODE) == 1;
-                if (fres && !matched) {  // Snell, vector form (:436-446)
+                if (fres && !matched && !rough) {  // Snell, vector form (:436-446)
                     double n = div_known(n1, n2, rn2);
                     const V3 nf{flip ? -nrm.x : nrm.x, flip ? -nrm.y : nrm.y, flip ? -nrm.z : nrm.z};
                     const double dd = ddot;   // dir . nf
@@ -2839,7 +2938,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // propagation would otherwise put back into the callee -- table lookups and all)
                 unsigned int lds_at = (unsigned int)(unsigned long long)(__attribute__((address_space(3))) double*)smem_of_kernel;
                 asm volatile("" : "+s"(lds_at));
-                tail_run<RECORD, TAB_LDS, SEENW, MESH, GRID>((const KArgs*)ak, tail_n, lds_at);
+                tail_run<RECORD, TAB_LDS, SEENW, MESH, GRID, ROUGH>((const KArgs*)ak, tail_n, lds_at);
             }
         }
         leave_workgroup<TAB_LDS>((const KArgs*)ak);
@@ -2850,7 +2949,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
 // The last wave of a draining workgroup finishes its photons here (see the drain in trace_body): the step loop alone, as a
 // function -- the kernels' own loop keeps its registers whatever this one needs, and what is specific to a wave that runs
 // alone on its SIMD (every step is latency, nothing overlaps) can be done here without a price on the bulk.
-template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID>
+template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH>
 __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int total, unsigned int lds) {
     // The kernel's arguments, read where the kernel itself reads them.  The pointer arrives in vector registers: it is made
     // a scalar again (readfirstlane) and a pointer into the constant address space, so that the fields come through the
@@ -2859,7 +2958,7 @@ __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int
     const unsigned long long bits = (unsigned long long)kernel_args;
     const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)bits), hi = __builtin_amdgcn_readfirstlane((unsigned int)(bits >> 32));
     const __attribute__((address_space(4))) KArgs* ak = (const __attribute__((address_space(4))) KArgs*)(((unsigned long long)hi << 32) | lo);
-    trace_body<RECORD, TAB_LDS, SEENW, false, MESH, GRID, true>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
+    trace_body<RECORD, TAB_LDS, SEENW, false, MESH, GRID, true, ROUGH>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
                                                                 __builtin_amdgcn_readfirstlane(lds));
 }
 
@@ -2881,6 +2980,22 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 template <bool RECORD, int SEENW, bool EMIT>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_grid(KArgs A) {
     trace_body<RECORD, 1, SEENW, EMIT, false, true>(A);
+}
+// The same three families for scenes with a rough node (KArgs::rough_d >= 0): the microfacet sampler of the surface branch
+// is compiled into these alone, so the smooth variants keep their registers, spills and text bit for bit.  (A call of
+// the sampler from the smooth loop spilled 20-30 vector registers of every variant: the surface branch holds more values
+// than the callee-saved registers take.)
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMeshWaves, kMeshWaves))) trace_kernel_rough(KArgs A) {
+    trace_body<RECORD, TAB_LDS, SEENW, EMIT, MESH, false, false, true>(A);
+}
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_rough_w4(KArgs A) {
+    trace_body<RECORD, TAB_LDS, SEENW, EMIT, false, false, false, true>(A);
+}
+template <bool RECORD, int SEENW, bool EMIT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_rough_grid(KArgs A) {
+    trace_body<RECORD, 1, SEENW, EMIT, false, true, false, true>(A);
 }
 
 }  // namespace

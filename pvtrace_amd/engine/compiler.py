@@ -13,6 +13,7 @@ Coatings-notebook scene run on the device.
 Everything here is host-side numpy executed once per `simulate` call; the
 tables (a few KB) are packed and uploaded to HBM once by `native.DeviceScene`.
 """
+import math
 import numbers
 
 import numpy as np
@@ -123,6 +124,9 @@ class CompiledScene:
         self.comp_count = np.zeros(count, dtype=_I32)
         self.coat_start = np.zeros(count, dtype=_I32)
         self.coat_count = np.zeros(count, dtype=_I32)
+        # GGX width alpha of each node's surface (FresnelSurfaceDelegate / CoatedSurfaceDelegate `roughness`): all zeros
+        # unless some node is rough, and then passed to the library as PvtSurfaceTables
+        self.surface_roughness = np.zeros(count, dtype=_F64)
         # Refractive-index tables n(wavelength) of the dispersive nodes (ri_table: -1 = the scalar index), pooled like
         # the coating tables: per table its length and where its wavelengths and values start in the pools.  The
         # scalar column of a dispersive node holds n at the table's first wavelength.
@@ -162,6 +166,7 @@ class CompiledScene:
 
             self.coat_start[i] = len(coat_rows)
             self.surface_type[i] = self._lower_surface(node, material, coat_rows)
+            self.surface_roughness[i] = self._surface_roughness(node, material)
             self.coat_count[i] = len(coat_rows) - self.coat_start[i]
 
             self.comp_start[i] = len(comp_cols["type"])
@@ -309,6 +314,19 @@ class CompiledScene:
             "NullSurfaceDelegate and CoatedSurfaceDelegate (declarative "
             "coatings) are supported."
         )
+
+    def _surface_roughness(self, node, material):
+        delegate = material.surface.delegate
+        if type(delegate) is NullSurfaceDelegate:
+            return 0.0
+        alpha = float(getattr(delegate, "roughness", 0.0))
+        if not (math.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+            raise UnsupportedSceneError(f"Node {node.name!r}: surface roughness must satisfy 0 <= alpha <= 1, got {alpha!r}.")
+        return alpha
+
+    @property
+    def has_roughness(self):
+        return bool(np.any(self.surface_roughness > 0.0))
 
     def _lower_refractive_index(self, i, node, index, rtab):
         if isinstance(index, RefractiveIndexTable):
@@ -529,6 +547,7 @@ class CompiledScene:
         "ri_table", "rtab_n", "rtab_start", "rtab_wavelength", "rtab_value",
         "comp_phase_table", "ptab_nw", "ptab_nmu", "ptab_wl_start", "ptab_mu_start", "ptab_cdf_start",
         "ptab_wavelength", "ptab_mu", "ptab_cdf",
+        "surface_roughness",
     )
 
     def tables(self):

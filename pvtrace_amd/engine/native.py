@@ -85,6 +85,11 @@ class PvtPhaseTables(C.Structure):
     ]
 
 
+class PvtSurfaceTables(C.Structure):
+    """Rough interfaces of a scene (include/pvtrace_hip.h; pvt_scene_create_rough)."""
+    _fields_ = [("n_nodes", C.c_int32), ("node_roughness", _p_f64)]
+
+
 class PvtEmitterTables(C.Structure):
     _fields_ = [
         ("n_lights", C.c_int32), ("n_spec", C.c_int32),
@@ -228,6 +233,19 @@ def phase_tables_struct(compiled):
     return st, keep
 
 
+def surface_tables_struct(compiled):
+    """PvtSurfaceTables over the surface roughness of a CompiledScene -> (struct or None, keepalive); None when no node
+    is rough (the scene is then created exactly as before)."""
+    alpha = getattr(compiled, "surface_roughness", None)
+    if alpha is None or not np.any(np.asarray(alpha) > 0.0):
+        return None, {}
+    arr = np.ascontiguousarray(alpha, dtype=np.float64)
+    st = PvtSurfaceTables()
+    st.n_nodes = int(arr.shape[0])
+    st.node_roughness = np_ptr(arr)
+    return st, {"node_roughness": arr}
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -299,6 +317,8 @@ def declare_signatures(lib, names):
         "pvt_scene_create_ex": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_scene_create_phase": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables), C.c_int,
                                     C.POINTER(vp)], C.c_int),
+        "pvt_scene_create_rough": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                    C.POINTER(PvtSurfaceTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
@@ -352,7 +372,7 @@ ABI_SYMBOLS = (
     "pvt_trace_bundle_multi", "pvt_shard_range", "pvt_trace_device_records", "pvt_unpack_records_device",
     "pvt_scene_carry_pending", "pvt_last_multi_reduce", "pvt_node_grid_plan", "pvt_scene_carry_discard", "pvt_scene_trim",
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
-    "pvt_scene_create_ex", "pvt_scene_create_phase",
+    "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough",
 )
 
 _lib = None
@@ -504,8 +524,14 @@ class DeviceScene:
         st, keep = scene_tables_struct(compiled)
         xt, xkeep = index_tables_struct(compiled)
         pt, pkeep = phase_tables_struct(compiled)
+        rt, rkeep = surface_tables_struct(compiled)
         handle = C.c_void_p()
-        if pt is None:   # (scenes without phase-function tables are created exactly as before)
+        if rt is not None:
+            check(self.lib.pvt_scene_create_rough(C.byref(st), None if xt is None else C.byref(xt),
+                                                  None if pt is None else C.byref(pt), C.byref(rt), self.device,
+                                                  C.byref(handle)),
+                  "pvt_scene_create_rough")
+        elif pt is None:   # (scenes without phase-function tables or rough nodes are created exactly as before)
             check(self.lib.pvt_scene_create_ex(C.byref(st), None if xt is None else C.byref(xt), self.device,
                                                C.byref(handle)),
                   "pvt_scene_create_ex")

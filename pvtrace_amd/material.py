@@ -265,23 +265,180 @@ def index_at(material, wavelength):
     return n
 
 
-class FresnelSurfaceDelegate(SurfaceDelegate):
-    """Fresnel reflection / Snell refraction from the two refractive indices."""
+def _check_roughness(roughness):
+    a = float(roughness)
+    if not (math.isfinite(a) and 0.0 <= a <= 1.0):
+        raise ValueError(f"roughness must be a finite GGX width alpha with 0 <= alpha <= 1, got {roughness!r}")
+    return a
 
-    def reflectivity(self, surface, ray, geometry, container, adjacent):
-        n1 = index_at(container.geometry.material, getattr(ray, "wavelength", None))
-        n2 = index_at(adjacent.geometry.material, getattr(ray, "wavelength", None))
+
+def ggx_visible_normal(normal, direction, alpha, ua, ub):
+    """Step 2 of the rough-interface contract (`FresnelSurfaceDelegate`): the microfacet normal m drawn from the GGX
+    distribution of visible normals (Heitz 2018, JCGT 7(4)) of width `alpha` for a photon travelling along `direction`
+    towards a surface of geometric normal `normal` (either orientation; it is turned to face the photon).  Every
+    argument may carry leading batch dimensions; (n, 3) directions with (n,) draws give (n, 3) normals."""
+    d = np.asarray(direction, dtype=np.float64)
+    nrm = np.asarray(normal, dtype=np.float64)
+    a = np.asarray(alpha, dtype=np.float64)[..., None]
+    ua = np.asarray(ua, dtype=np.float64)[..., None]
+    ub = np.asarray(ub, dtype=np.float64)[..., None]
+    facing = np.where(np.sum(d * nrm, axis=-1, keepdims=True) > 0.0, -nrm, nrm)   # d . N <= 0
+    v = -d
+    e1, e2 = ray_basis(facing)
+    vx = np.sum(v * e1, axis=-1, keepdims=True)
+    vy = np.sum(v * e2, axis=-1, keepdims=True)
+    vz = np.sum(v * facing, axis=-1, keepdims=True)
+    hx, hy, hz = a * vx, a * vy, vz
+    inv = 1.0 / np.sqrt(hx * hx + hy * hy + hz * hz)
+    hx, hy, hz = hx * inv, hy * inv, hz * inv
+    lensq = hx * hx + hy * hy
+    safe = np.where(lensq > 0.0, lensq, 1.0)
+    il = 1.0 / np.sqrt(safe)
+    t1x = np.where(lensq > 0.0, -hy * il, 1.0)
+    t1y = np.where(lensq > 0.0, hx * il, 0.0)
+    t2x, t2y, t2z = -hz * t1y, hz * t1x, hx * t1y - hy * t1x   # Vh x T1, T1.z = 0
+    r = np.sqrt(ua)
+    phi = 2.0 * np.pi * ub
+    t1 = r * np.cos(phi)
+    s = 0.5 * (1.0 + hz)
+    t2 = (1.0 - s) * np.sqrt(1.0 - t1 * t1) + s * r * np.sin(phi)
+    tz = np.sqrt(np.maximum(0.0, 1.0 - t1 * t1 - t2 * t2))
+    nx = t1 * t1x + t2 * t2x + tz * hx
+    ny = t1 * t1y + t2 * t2y + tz * hy
+    nz = t2 * t2z + tz * hz
+    mx, my, mz = a * nx, a * ny, np.maximum(0.0, nz)
+    inv = 1.0 / np.sqrt(mx * mx + my * my + mz * mz)
+    return (mx * inv) * e1 + (my * inv) * e2 + (mz * inv) * facing
+
+
+def rough_fresnel_reflectivity(cos_m, n1, n2):
+    """Step 3: the unpolarised Fresnel reflectivity about a microfacet, from cos(theta_m) = v . m (clamped to [0, 1]):
+    the smooth branch's Hecht formula, 1.0 where q = n1 / n2 sin(theta_m) >= 1 (total internal reflection)."""
+    c = min(max(float(cos_m), 0.0), 1.0)
+    q = n1 / n2 * math.sqrt((1.0 - c) * (1.0 + c))
+    if q >= 1.0:
+        return 1.0
+    k = math.sqrt(1.0 - q * q)
+    rs = ((n1 * c - n2 * k) / (n1 * c + n2 * k)) ** 2
+    rp = ((n1 * k - n2 * c) / (n1 * k + n2 * c)) ** 2
+    return 0.5 * (rs + rp)
+
+
+def rough_directions(direction, normal, m, n1, n2):
+    """Steps 5 and 6: (reflected, transmitted) directions of a photon travelling along `direction` about the microfacet
+    normal `m` (v . m > 0), each folded back across the tangent plane of the geometric `normal` when it lies on the
+    wrong side of it.  The transmitted one is None under total internal reflection about m."""
+    d = np.asarray(direction, dtype=np.float64)
+    nrm = np.asarray(normal, dtype=np.float64)
+    along = nrm if float(np.dot(nrm, d)) >= 0.0 else -nrm   # the geometric normal along the ray (-N)
+    m = np.asarray(m, dtype=np.float64)
+    dm = float(np.dot(d, m))
+    reflected = d - 2.0 * dm * m
+    if float(np.dot(reflected, along)) > 0.0:
+        reflected = reflected - 2.0 * float(np.dot(reflected, along)) * along
+    nf = -m                                  # the microfacet normal along the ray, as Snell's vector form takes it
+    dd = min(max(-dm, 0.0), 1.0)
+    n = n1 / n2
+    c2 = 1.0 - n * n * (1.0 - dd * dd)
+    if c2 < 0.0:
+        return reflected, None
+    transmitted = n * d + (math.sqrt(c2) - n * dd) * nf
+    if float(np.dot(transmitted, along)) < 0.0:
+        transmitted = transmitted - 2.0 * float(np.dot(transmitted, along)) * along
+    return reflected, transmitted
+
+
+class FresnelSurfaceDelegate(SurfaceDelegate):
+    """Fresnel reflection / Snell refraction from the two refractive indices.
+
+    roughness : the GGX (Trowbridge-Reitz) width alpha of the interface, finite, 0 <= alpha <= 1 (default 0: an
+        optically perfect interface, exactly as before).  It is the roughness of the surface of the node that is HIT.
+
+    A rough interface draws a microfacet normal per surface event and applies Fresnel and Snell about it.  The
+    sampling contract, the same on the host and on the device (include/pvtrace_hip.h):
+
+    1. Frame.  N is the geometric normal at the hit turned to face the photon (d . N < 0), v = -d, (e1, e2) =
+       `ray_basis(N)` (Duff et al. 2017), v_l = (v . e1, v . e2, v . N).
+    2. Microfacet normal (GGX visible normals, Heitz 2018): draw u_a, then u_b.
+       Vh = normalize(alpha v_l.x, alpha v_l.y, v_l.z); T1 = (-Vh.y, Vh.x, 0) / sqrt(Vh.x^2 + Vh.y^2), or (1, 0, 0)
+       when that sum is 0; T2 = Vh x T1; r = sqrt(u_a), phi = 2 pi u_b (pvt_sincos2pi on the device);
+       t1 = r cos(phi), s = (1 + Vh.z) / 2, t2 = (1 - s) sqrt(1 - t1^2) + s r sin(phi);
+       Nh = t1 T1 + t2 T2 + sqrt(max(0, 1 - t1^2 - t2^2)) Vh; m_l = normalize(alpha Nh.x, alpha Nh.y, max(0, Nh.z));
+       m = m_l.x e1 + m_l.y e2 + m_l.z N, so that v . m > 0.
+    3. Fresnel about m: cos(theta_m) = v . m clamped to [0, 1], n1 and n2 at the photon's wavelength; the smooth
+       branch's Hecht formula, R = 1 where q = n1 / n2 sin(theta_m) >= 1 (total internal reflection about m).
+    4. Decision: the reflect-or-transmit draw u as before, only when R > 0.
+    5. Direction: reflection d' = d - 2 (d . m) m; transmission by the smooth branch's vector form of Snell's law with
+       m in place of the normal.
+    6. Fold: a reflected d' with d' . N < 0 or a transmitted d' with d' . N > 0 is mirrored across the tangent plane,
+       d' <- d' - 2 (d' . N) N (no draw).
+    7. Draw order u_a, u_b, then u (if R > 0); event kinds, recorder selectors and the logged normal (the geometric
+       one) follow the smooth rules.
+
+    On the host `reflectivity()` draws u_a and u_b from numpy's global generator and keeps m; `reflected_direction()`
+    and `transmitted_direction()` of the same ray use that m.
+    """
+
+    def __init__(self, roughness=0.0):
+        super(FresnelSurfaceDelegate, self).__init__()
+        self._roughness = _check_roughness(roughness)
+        self._facet = None   # ((position, direction), m) of the last microfacet drawn
+
+    @property
+    def roughness(self):
+        return getattr(self, "_roughness", 0.0)   # (subclasses that skip __init__ stay smooth)
+
+    def _rough_here(self, ray, geometry):
+        """True when this event samples a microfacet (a rough surface; coated points never do)."""
+        return self.roughness > 0.0
+
+    def _indices(self, ray, container, adjacent):
+        wl = getattr(ray, "wavelength", None)
+        return index_at(container.geometry.material, wl), index_at(adjacent.geometry.material, wl)
+
+    def _microfacet(self, ray, geometry, draw):
+        """The microfacet normal of this event: the one reflectivity() drew for the same ray, else (draw=True) a new one."""
+        key = (tuple(np.asarray(ray.position, dtype=np.float64).tolist()),
+               tuple(np.asarray(ray.direction, dtype=np.float64).tolist()))
+        facet = getattr(self, "_facet", None)
+        if facet is not None and facet[0] == key and not draw:
+            return facet[1]
+        ua = np.random.uniform()
+        ub = np.random.uniform()
+        normal = np.asarray(geometry.normal(ray.position), dtype=np.float64)
+        m = ggx_visible_normal(normal, ray.direction, self.roughness, ua, ub)
+        self._facet = (key, m)
+        return m
+
+    def _smooth_reflectivity(self, surface, ray, geometry, container, adjacent):
+        n1, n2 = self._indices(ray, container, adjacent)
         normal = _flipped_normal(geometry, ray)
         cosang = float(np.clip(np.dot(normal, ray.direction), -1.0, 1.0))
         return float(fresnel_reflectivity(math.acos(cosang), n1, n2))
 
+    def reflectivity(self, surface, ray, geometry, container, adjacent):
+        if not self._rough_here(ray, geometry):
+            return self._smooth_reflectivity(surface, ray, geometry, container, adjacent)
+        n1, n2 = self._indices(ray, container, adjacent)
+        m = self._microfacet(ray, geometry, draw=True)
+        return rough_fresnel_reflectivity(-float(np.dot(np.asarray(ray.direction, dtype=np.float64), m)), n1, n2)
+
     def reflected_direction(self, surface, ray, geometry, container, adjacent):
         normal = geometry.normal(ray.position)
+        if self._rough_here(ray, geometry):
+            n1, n2 = self._indices(ray, container, adjacent)
+            reflected, _ = rough_directions(ray.direction, normal, self._microfacet(ray, geometry, draw=False), n1, n2)
+            return tuple(reflected.tolist())
         return tuple(specular_reflection(ray.direction, normal).tolist())
 
     def transmitted_direction(self, surface, ray, geometry, container, adjacent):
-        n1 = index_at(container.geometry.material, getattr(ray, "wavelength", None))
-        n2 = index_at(adjacent.geometry.material, getattr(ray, "wavelength", None))
+        n1, n2 = self._indices(ray, container, adjacent)
+        if self._rough_here(ray, geometry):
+            m = self._microfacet(ray, geometry, draw=False)
+            _, transmitted = rough_directions(ray.direction, geometry.normal(ray.position), m, n1, n2)
+            if transmitted is None:
+                raise ValueError("no transmitted direction: total internal reflection about the microfacet normal")
+            return tuple(transmitted.tolist())
         normal = _flipped_normal(geometry, ray)
         return tuple(fresnel_refraction(ray.direction, normal, n1, n2).tolist())
 
@@ -644,10 +801,12 @@ class Coating(object):
 
 class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
     """Fresnel surface with an ordered list of `Coating` overrides; the first
-    coating covering the hit point wins, uncovered points are plain Fresnel."""
+    coating covering the hit point wins, uncovered points are plain Fresnel.
+    `roughness` (GGX alpha, see `FresnelSurfaceDelegate`) applies to the
+    uncovered points only: a covered point behaves as a smooth one."""
 
-    def __init__(self, coatings=None):
-        super(CoatedSurfaceDelegate, self).__init__()
+    def __init__(self, coatings=None, roughness=0.0):
+        super(CoatedSurfaceDelegate, self).__init__(roughness=roughness)
         self._coatings = [] if coatings is None else list(coatings)
 
     @property
@@ -661,12 +820,15 @@ class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
                 return coating
         return None
 
+    def _rough_here(self, ray, geometry):
+        return self.roughness > 0.0 and self._match(ray, geometry) is None
+
     def reflectivity(self, surface, ray, geometry, container, adjacent):
-        fresnel = super(CoatedSurfaceDelegate, self).reflectivity(
-            surface, ray, geometry, container, adjacent
-        )
         coating = self._match(ray, geometry)
-        if coating is None or coating.reflectivity is None:
+        if coating is None:
+            return super(CoatedSurfaceDelegate, self).reflectivity(surface, ray, geometry, container, adjacent)
+        fresnel = self._smooth_reflectivity(surface, ray, geometry, container, adjacent)
+        if coating.reflectivity is None:
             return fresnel
         if fresnel == 1.0 and coating.transmission != "matched":
             return 1.0   # beyond the critical angle no refracted ray exists: stays totally reflected
