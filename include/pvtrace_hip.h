@@ -244,6 +244,44 @@ typedef struct PvtSurfaceTables {
     const double* node_roughness;   /* (n_nodes) GGX alpha of each node's surface, 0 = smooth */
 } PvtSurfaceTables;
 
+/* ---- concentration fields (extension within v13, passed to pvt_scene_create_field) --------------------------------
+ * A node with node_field[n] >= 0 carries lattice node_field[n]: shape (nx, ny, nz), each >= 1, and finite bounds
+ * lower < upper on each axis, in the node's own frame (the frame of its world_to_local).  Each component c of such a
+ * node names a value table comp_values[c] of nx ny nz finite values >= 0 (index (ix ny + iy) nz + iz); the components of
+ * an unfielded node are not read.  The root node carries no lattice.  The absorption contract (the Python
+ * ConcentrationGrid is the same):
+ *  1. Cells: h = (upper - lower) / n per axis; a point p lies in cell clamp(floor((p - lower) / h), 0, n - 1) per axis,
+ *     so a point outside the box takes the nearest edge cell.  Only the interior planes lower + i h, i = 1 .. n - 1,
+ *     are crossed.
+ *  2. Coefficient of a cell: alpha_cell = sum_k alpha_k(lambda) c_k[cell], summed in component order.
+ *  3. Draw: tau* = -ln(1 - u), drawn as for an unfielded container, on the UNSCALED sum sum_k alpha_k(lambda).
+ *  4. March: from the photon's position (s = 0) along its direction up to the surface distance t0, cell by cell; a
+ *     cell entered at s_in with accumulated depth tau_in and left at s_out (the next plane crossed, or t0) absorbs at
+ *     s_in + (tau* - tau_in) / alpha_cell when that is < s_out; else tau_in grows by alpha_cell (s_out - s_in).  Cells
+ *     with alpha_cell = 0 add nothing.  No absorption before t0: the photon reaches the surface.
+ *  5. Component: the draw and the cumulative rule of an unfielded container over alpha_k c_k[cell] of the cell the
+ *     march absorbed in (not a cell derived again from the rounded position).
+ * A 1 x 1 x 1 lattice of value 1 has no interior planes: the march is (tau* - 0) / alpha with the same alpha, and such
+ * a scene traces bit for bit as one without fields.  A NULL struct, n_nodes 0 or every node_field -1 is exactly
+ * pvt_scene_create_rough.  Field values live in global memory, outside the tables a launch stages in LDS.  A separate
+ * struct so that the other table structs keep the lengths old callers pass. */
+typedef struct PvtFieldTables {
+    int32_t n_nodes;                /* 0 = none (as a NULL struct), else the scene's n_nodes */
+    int32_t n_fields;               /* lattices */
+    const int32_t* node_field;      /* (n_nodes) lattice of each node, -1 = none */
+    const int32_t* field_shape;     /* (n_fields, 3) nx, ny, nz, each >= 1 */
+    const double* field_lower;      /* (n_fields, 3) finite, < field_upper on each axis */
+    const double* field_upper;      /* (n_fields, 3) */
+    int32_t n_components;           /* the scene's n_components */
+    int32_t n_values;               /* value tables */
+    const int32_t* comp_values;     /* (n_components) value table of each component, -1 = none */
+    const int32_t* values_start;    /* (n_values) first value of each table in `values` */
+    const int32_t* values_count;    /* (n_values) length of each table: nx ny nz of every lattice that uses it */
+    int32_t n_points;               /* length of the value pool */
+    int32_t reserved;
+    const double* values;           /* (n_points) pooled relative concentrations, finite and >= 0 */
+} PvtFieldTables;
+
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
@@ -388,6 +426,11 @@ int pvt_scene_create_phase(const PvtSceneTables* tables, const PvtIndexTables* i
 int pvt_scene_create_rough(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                            const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables, int device,
                            PvtScene** out);
+/* The same with concentration fields (NULL, n_nodes 0 or no node with a lattice = none: then exactly
+ * pvt_scene_create_rough). */
+int pvt_scene_create_field(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                           const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                           const PvtFieldTables* field_tables, int device, PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);

@@ -91,7 +91,9 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
     the objects' own methods.  Order of a step, as there: count it; find the interface; KILL when over `maxsteps` or
     `maxpathlength`; EXIT when the interface is the world's; else ask the container's material whether the photon is
     absorbed on the way (ABSORB, then EMIT / SCATTER and on, or NONRADIATIVE / REACT and out) or reaches the surface,
-    where the hit node's surface reflects or transmits it in that node's frame."""
+    where the hit node's surface reflects or transmits it in that node's frame.  A container whose components carry a
+    concentration field (`ConcentrationGrid`) is asked in its own frame (`Material.is_absorbed_in / component_at`); every
+    other container takes the reference's `is_absorbed / component` and their draws."""
     from pvtrace_amd.material import Luminophore, Reactor, Scatterer, index_at
 
     root = scene.root
@@ -112,10 +114,18 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
         if hit is root:
             yield ray.propagate(distance, index), Event.EXIT, names
             return
-        absorbed, depth = medium.is_absorbed(ray, distance)
+        cell = None
+        if medium.concentration_lattice is not None:
+            if container is root:
+                from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+                raise UnsupportedSceneError(f"Root node {root.name!r}: the scene's root cannot carry a concentration field.")
+            absorbed, depth, cell = medium.is_absorbed_in(ray.representation(root, container), distance)
+        else:
+            absorbed, depth = medium.is_absorbed(ray, distance)
         if absorbed:
             ray = ray.propagate(depth, index)
-            taker = medium.component(ray.wavelength)
+            taker = medium.component(ray.wavelength) if cell is None else medium.component_at(ray.wavelength, cell)
             who = {"component": taker.name, "container": container.name}
             yield ray, Event.ABSORB, dict(who)
             if not taker.is_radiative(ray):

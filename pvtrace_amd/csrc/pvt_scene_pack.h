@@ -339,6 +339,10 @@ struct PackedScene {
     std::vector<int> gi;
     int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, n_ptab = 0, lazy_root = 0;
     int rough_d = -1;   // where the nodes' GGX widths start in the double blob (-1: no node is rough)
+    // concentration fields (PvtFieldTables): their own buffer of doubles, read from global memory alone (empty: none).
+    // fd[n] = where node n's lattice record starts (-1: none), then the records (kFr* words and one value-table offset
+    // per component), then the pooled value tables
+    std::vector<double> fd;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     int grid_dims[3] = {0, 0, 0};
@@ -349,7 +353,8 @@ struct PackedScene {
 
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
-int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs) {
+int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+                    const PvtFieldTables* fr) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -467,6 +472,56 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
     }
     // runs [start, start + count) into a table of `size` rows
     auto bad_run = [](long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; };
+    // concentration fields (PvtFieldTables, pvt_scene_create_field): lattices, value tables and who uses which
+    if (fr && fr->n_nodes != 0) {
+        const int F = fr->n_fields, V = fr->n_values;
+        if (fr->n_nodes != N || !fr->node_field) return fail(PVT_ERR_INVALID, "field tables: need one lattice index per node");
+        if (F < 0 || (F > 0 && (!fr->field_shape || !fr->field_lower || !fr->field_upper)))
+            return fail(PVT_ERR_INVALID, "field tables: lattice arrays missing");
+        for (int n = 0; n < N; n++)
+            if (fr->node_field[n] < -1 || fr->node_field[n] >= F) return fail(PVT_ERR_INVALID, "field tables: lattice index out of range");
+        if (fr->node_field[t->root_id] >= 0) return fail(PVT_ERR_INVALID, "field tables: the root node cannot carry a lattice");
+        for (int f = 0; f < F; f++)
+            for (int a = 0; a < 3; a++) {
+                if (fr->field_shape[f * 3 + a] < 1) return fail(PVT_ERR_INVALID, "field tables: lattice shape must be >= 1 on each axis");
+                const double lo = fr->field_lower[f * 3 + a], hi = fr->field_upper[f * 3 + a];
+                if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(PVT_ERR_INVALID, "field tables: lattice bounds must be finite");
+                if (!(lo < hi)) return fail(PVT_ERR_INVALID, "field tables: lattice lower must be < upper on each axis");
+            }
+        if (fr->n_components != C || (C > 0 && !fr->comp_values))
+            return fail(PVT_ERR_INVALID, "field tables: need one value-table index per component");
+        if (V < 0 || fr->n_points < 0 || (V > 0 && (!fr->values_start || !fr->values_count)) || (fr->n_points > 0 && !fr->values))
+            return fail(PVT_ERR_INVALID, "field tables: value-table arrays missing");
+        for (int c = 0; c < C; c++)
+            if (fr->comp_values[c] < -1 || fr->comp_values[c] >= V) return fail(PVT_ERR_INVALID, "field tables: value-table index out of range");
+        for (int v = 0; v < V; v++)
+            if (bad_run(fr->values_start[v], fr->values_count[v], fr->n_points) || fr->values_count[v] < 1)
+                return fail(PVT_ERR_INVALID, "field tables: value-table run out of range");
+        for (int i = 0; i < fr->n_points; i++)
+            if (!std::isfinite(fr->values[i])) return fail(PVT_ERR_INVALID, "field tables: values must be finite");
+        for (int i = 0; i < fr->n_points; i++)
+            if (fr->values[i] < 0.0) return fail(PVT_ERR_INVALID, "field tables: values must be >= 0");
+        // every component of a node with a lattice names a value table of exactly that lattice's size; the buffer the
+        // kernel indexes with int stays within int32
+        long long words = N;
+        for (int n = 0; n < N; n++) {
+            const int f = fr->node_field[n];
+            if (f < 0) continue;
+            const long long cells = (long long)fr->field_shape[f * 3] * fr->field_shape[f * 3 + 1] * fr->field_shape[f * 3 + 2];
+            if (cells > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: a lattice of more than 2^31 - 1 cells");
+            words += kFrComp + t->comp_count[n];
+            for (int k = 0; k < t->comp_count[n]; k++) {
+                const int c = t->comp_start[n] + k;
+                if (c < 0 || c >= C) return fail(PVT_ERR_INVALID, "component run out of range");
+                const int v = fr->comp_values[c];
+                if (v < 0) return fail(PVT_ERR_INVALID, "field tables: every component of a node with a lattice needs values");
+                if (fr->values_count[v] != cells)
+                    return fail(PVT_ERR_INVALID, "field tables: a value table's length must equal its node's lattice size");
+            }
+        }
+        words += fr->n_points;
+        if (words > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: more doubles than int32 offsets can index");
+    }
     for (int n = 0; n < N; n++) {
         if (bad_run(t->comp_start[n], t->comp_count[n], C)) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
         if (K > 0 && bad_run(t->coat_start[n], t->coat_count[n], K)) return fail(PVT_ERR_INVALID, "coating range of a node out of bounds");
@@ -1014,11 +1069,58 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
     }
 }
 
+// The field buffer p->fd (validated tables; left empty when no node carries a lattice): per node where its record starts,
+// then per fielded node its record -- shape, lower, cell widths h = (upper - lower) / n, the world->local rotation and
+// translation of world_to_local (the doubles the node record and rotation classes hold) and, per component in the node's
+// order, where its value table starts -- then each value table once.
+void pack_fields(const PvtSceneTables* t, const PvtFieldTables* fr, PackedScene* p) {
+    p->fd.clear();
+    if (!fr || fr->n_nodes == 0) return;
+    const int N = t->n_nodes;
+    bool any = false;
+    for (int n = 0; n < N; n++) any = any || fr->node_field[n] >= 0;
+    if (!any) return;
+    std::vector<double>& fd = p->fd;
+    fd.assign((size_t)N, -1.0);
+    for (int n = 0; n < N; n++) {
+        const int f = fr->node_field[n];
+        if (f < 0) continue;
+        fd[(size_t)n] = (double)fd.size();
+        const size_t at = fd.size();
+        fd.resize(at + kFrComp + (size_t)t->comp_count[n], 0.0);
+        double* r = fd.data() + at;
+        for (int a = 0; a < 3; a++) {
+            const double lo = fr->field_lower[f * 3 + a], hi = fr->field_upper[f * 3 + a];
+            const int na = fr->field_shape[f * 3 + a];
+            r[kFrShape + a] = (double)na;
+            r[kFrLower + a] = lo;
+            r[kFrH + a] = (hi - lo) / (double)na;
+            for (int c = 0; c < 3; c++) r[kFrRot + a * 3 + c] = t->world_to_local[n * 16 + a * 4 + c];
+            r[kFrT + a] = t->world_to_local[n * 16 + a * 4 + 3];
+        }
+    }
+    std::vector<long long> value_at((size_t)fr->n_values, -1);
+    for (int n = 0; n < N; n++) {
+        if (fr->node_field[n] < 0) continue;
+        const size_t at = (size_t)fd[(size_t)n];
+        for (int k = 0; k < t->comp_count[n]; k++) {
+            const int v = fr->comp_values[t->comp_start[n] + k];
+            if (value_at[(size_t)v] < 0) {
+                value_at[(size_t)v] = (long long)fd.size();
+                const double* src = fr->values + fr->values_start[v];
+                fd.insert(fd.end(), src, src + fr->values_count[v]);
+            }
+            fd[at + kFrComp + (size_t)k] = (double)value_at[(size_t)v];
+        }
+    }
+}
+
 // The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the
-// phase-function tables (ph, NULL = none) and the nodes' surface roughness (rs, NULL = none) -> *p.  No HIP call.
+// phase-function tables (ph, NULL = none), the nodes' surface roughness (rs, NULL = none) and the concentration fields
+// (fr, NULL = none) -> *p.  No HIP call.
 int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-               PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs);
+               const PvtFieldTables* fr, PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs, fr);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
@@ -1043,6 +1145,7 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     const std::vector<int> ctab_at = lay_out(t, x, ph, classes, spectra, records, grid, p, &rtab_at, &ptab_at);
     rc = fill(t, x, ph, rs, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
     if (rc != PVT_OK) return rc;
+    pack_fields(t, fr, p);
     prove_shortcuts(t, p);
     return PVT_OK;
 }

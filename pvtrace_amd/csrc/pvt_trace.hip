@@ -98,6 +98,7 @@ struct PvtScene {
     int nd_small = 0, ni_small = 0;   // ... of which everything but the spectra / their guide tables (the blobs' heads)
     int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
     int rough_d = -1;                   // where the nodes' GGX widths start in the double blob (-1: no rough node)
+    double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_gd = nullptr;
     int* d_gi = nullptr;
     double* d_ed = nullptr;
@@ -195,6 +196,7 @@ void pvt_scene_destroy(PvtScene* s) {
 #endif
     (void)hipSetDevice(s->device);
     if (s->d_gd) (void)hipFree(s->d_gd);
+    if (s->d_fd) (void)hipFree(s->d_fd);
     if (s->d_gi) (void)hipFree(s->d_gi);
     if (s->d_ed) (void)hipFree(s->d_ed);
     if (s->d_ei) (void)hipFree(s->d_ei);
@@ -225,6 +227,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.n_nodes = s->n_nodes; a.root = s->root; a.n_rec = s->n_rec; a.total_bins = s->total_bins;
     a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_rtab = s->n_rtab; a.n_lights = s->n_lights;
     a.rough_d = s->rough_d;
+    a.fd = s->d_fd;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -239,7 +242,8 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
 #ifndef PVT_DEV_VARIANTS
 #define PVT_DEV_VARIANTS 0   // developer builds: only the analytic, array-input, <=64-recorder variants (fast compile)
 #endif
-// Scenes with a rough node (KArgs::rough_d >= 0) run the trace_kernel_rough* families: the same choice of variant.
+// Scenes with a rough node (KArgs::rough_d >= 0) or a concentration field (KArgs::fd) run the trace_kernel_rough*
+// families: the same choice of variant.
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
 #if PVT_DEV_VARIANTS
@@ -269,7 +273,7 @@ hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st,
 
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-    if (a.rough_d >= 0) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
+    if (a.rough_d >= 0 || a.fd != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
     const bool mesh = a.bvh != nullptr;
     if constexpr (TAB_LDS == 1 && (!PVT_DEV_VARIANTS || SEENW == 1) && PVT_DEV_VARIANTS != 2) {
         if (a.lay.grid_d >= 0 && !mesh && (!PVT_DEV_VARIANTS || !emit)) {   // many nodes: per-lane walk of the node grid
@@ -630,6 +634,11 @@ int pvt_scene_create_phase(const PvtSceneTables* t, const PvtIndexTables* x, con
 
 int pvt_scene_create_rough(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                            const PvtSurfaceTables* rs, int device, PvtScene** out) {
+    return pvt_scene_create_field(t, x, ph, rs, nullptr, device, out);
+}
+
+int pvt_scene_create_field(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                           const PvtSurfaceTables* rs, const PvtFieldTables* fr, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -637,7 +646,7 @@ int pvt_scene_create_rough(const PvtSceneTables* t, const PvtIndexTables* x, con
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -712,6 +721,10 @@ int pvt_scene_create_rough(const PvtSceneTables* t, const PvtIndexTables* x, con
     }
     HIP_TRY(hipMemcpy(s->d_gd, packed.gd.data(), packed.gd.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_gi, packed.gi.data(), packed.gi.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!packed.fd.empty()) {   // (global memory only: no launch stages it in LDS)
+        HIP_TRY(hipMalloc(&s->d_fd, packed.fd.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(s->d_fd, packed.fd.data(), packed.fd.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     owner.p = nullptr;
     *out = s;
     return PVT_OK;

@@ -64,6 +64,9 @@ enum { NI_SURF = 0, NI_CSTART, NI_CCOUNT, NI_CREC, NI_KSTART, NI_KCOUNT, NI_MESH
                                                                  // the recorder candidate tables, -1 = nobody listens to the node;
                                                                  // NI_NCLS: refractive-index class)
 enum { RT_W2L = 0, RT_L2W = 9, RT = 18 };                         // Lay::rot_d records: the 3x3 blocks of world->local and local->world
+enum { kFrShape = 0, kFrLower = 3, kFrH = 6, kFrRot = 9, kFrT = 18, kFrComp = 21 };   // a fielded node's record in KArgs::fd:
+                                                                 // shape, lower, cell widths, world->local rotation (row-major)
+                                                                 // and translation, then one value-table offset per component
 enum { CD_QY = 0, CD_TAU_RAD, CD_TAU_NR, CD_PHASE, CD_ABS_SCALE, CD_EMS_SCALE_X, CD_EMS_SCALE_C,
        CD_ABS_RCP, CD_EMS_RCP_X, CD_EMS_RCP_C, CD_ABS_W, CD_EMS_W, CD };   // component doubles (*_RCP: RN(1/spacing) of an evenly spaced table, else NaN;
                                                             // *_W: the spacing w when additionally xs[i] == xs[0] + i*w bit for bit, else NaN)
@@ -208,6 +211,9 @@ struct KArgs {
     // Rough interfaces (pvt_scene_create_rough): where the nodes' GGX widths alpha start in the double blob, read from
     // where the spectra are read; -1 = no node is rough (UF_ROUGH off)
     int rough_d;
+    // Concentration fields (pvt_scene_create_field): the field buffer in global memory -- fd[n] = where node n's lattice
+    // record starts (-1: none), the records (kFr*), the value tables; null = no node carries a lattice (UF_FIELD off)
+    const double* fd;
 };
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
 constexpr int kCarryBase = 14;     // u64 words of a parked photon before its seen-mask
@@ -594,6 +600,87 @@ __device__ __attribute__((noinline)) RoughEvent rough_event_call(double alpha, d
     e.dx = t.x; e.dy = t.y; e.dz = t.z;
     e.s0 = rng.s0; e.s1 = rng.s1; e.s2 = rng.s2; e.s3 = rng.s3;
     return e;
+}
+
+// Concentration fields (PvtFieldTables; include/pvtrace_hip.h states the contract, the Python ConcentrationGrid marches
+// the same way): the free path of a lane whose container carries a lattice (UF_FIELD).  From the photon's position, cell
+// by cell along its direction up to the surface distance t0, the optical depth sum alpha_cell * segment grows until it
+// reaches tau* = `tau`; alpha_cell = sum_k alpha_k(wl) c_k[cell] in component order.  The node's world->local transform
+// and lattice come from its record at fd + frec; the components' coefficients are looked up as the caller looks them up
+// (ci0 / cd0: the records of the node's first component).  Returns where the photon is absorbed (INFINITY: it reaches
+// the surface) and that cell's alpha_cell, first partial sum and index, for the component pick.  A 1 x 1 x 1 lattice of
+// value 1 gives the caller's alpha and depth bit for bit.  A FUNCTION, called only from the trace_kernel_rough* variants.
+struct FieldMarch {
+    double depth;   // where the photon is absorbed, INFINITY = not before t0
+    double alpha;   // alpha_cell of the cell it is absorbed in ...
+    double pre0;    // ... the first partial sum of that cell's coefficients ...
+    int cell;       // ... and the cell's index into the value tables
+};
+template <int TAB_LDS>
+__device__ __attribute__((noinline)) FieldMarch field_march_call(Tables<TAB_LDS> T, const double* __restrict__ fd, int frec, int ci0,
+                                                                 int cd0, int ccount, double wl, double px, double py, double pz,
+                                                                 double dx, double dy, double dz, double tau, double t0) {
+    const double* __restrict__ r = fd + frec;
+    auto coef = [&](int k) -> double {
+        const int ci = ci0 + k * CI, cd = cd0 + k * CD;
+        return interp_clamped<TAB_LDS>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N), T.iv(ci + CI_ABS_G),
+                                       T.dv(cd + CD_ABS_SCALE), T.iv(ci + CI_ABS_HIST), T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
+    };
+    // the first two components' coefficients and value tables are held; further ones are looked up per cell
+    const double a0 = ccount > 0 ? coef(0) : 0.0, a1 = ccount > 1 ? coef(1) : 0.0;
+    const int v0 = ccount > 0 ? (int)r[kFrComp] : 0, v1 = ccount > 1 ? (int)r[kFrComp + 1] : 0;
+    // one axis of the lattice in the node's frame: the photon's coordinate and direction, the cell it starts in (clamped
+    // into the lattice) and the distance to the next interior plane ahead (INFINITY: none)
+    struct Axis {
+        double p, d, lo, h, t;
+        int n, c, step;
+        __device__ double next() const {
+            const int i = step > 0 ? c + 1 : c;   // the plane ahead: lower + i h, interior when 1 <= i <= n - 1
+            if (step == 0 || i < 1 || i > n - 1) return INFINITY;
+            return (lo + (double)i * h - p) / d;
+        }
+    };
+    auto axis = [&](int a) -> Axis {
+        Axis x;
+        x.p = r[kFrRot + 3 * a] * px + r[kFrRot + 3 * a + 1] * py + r[kFrRot + 3 * a + 2] * pz + r[kFrT + a];
+        x.d = r[kFrRot + 3 * a] * dx + r[kFrRot + 3 * a + 1] * dy + r[kFrRot + 3 * a + 2] * dz;
+        x.lo = r[kFrLower + a];
+        x.h = r[kFrH + a];
+        x.n = (int)r[kFrShape + a];
+        const double f = __builtin_floor((x.p - x.lo) / x.h);
+        x.c = (int)__builtin_fmin(__builtin_fmax(f, 0.0), (double)(x.n - 1));   // (NaN: cell 0)
+        x.step = x.d > 0.0 ? 1 : (x.d < 0.0 ? -1 : 0);
+        x.t = x.next();
+        return x;
+    };
+    Axis X = axis(0), Y = axis(1), Z = axis(2);
+    double s = 0.0, tin = 0.0;
+    for (;;) {
+        const int cell = (X.c * Y.n + Y.c) * Z.n + Z.c;
+        double ac = 0.0, p0 = 0.0;
+        for (int k = 0; k < ccount; k++) {
+            const double ak = k == 0 ? a0 : (k == 1 ? a1 : coef(k));
+            const int vk = k == 0 ? v0 : (k == 1 ? v1 : (int)r[kFrComp + k]);
+            ac += ak * fd[vk + cell];
+            if (k == 0) p0 = ac;
+        }
+        // (a plane that rounding puts a hair behind the photon is crossed at zero length)
+        const double tmin = __builtin_fmin(__builtin_fmin(X.t, Y.t), Z.t);
+        const double sout = __builtin_fmax(__builtin_fmin(tmin, t0), s);
+        if (ac > 0.0) {
+            const double q = __builtin_fmax(tau - tin, 0.0);
+            const double d = s + (ac > 1e-250 ? div_normal(q, ac) : q / ac);
+            if (d < sout) return FieldMarch{d, ac, p0, cell};
+            tin += ac * (sout - s);
+        }
+        if (!(sout < t0)) break;
+        // the nearest plane is crossed (ties: one axis per pass, the others at zero length)
+        if (X.t == tmin) { X.c += X.step; X.t = X.next(); }
+        else if (Y.t == tmin) { Y.c += Y.step; Y.t = Y.next(); }
+        else { Z.c += Z.step; Z.t = Z.next(); }
+        s = sout;
+    }
+    return FieldMarch{INFINITY, 0.0, 0.0, 0};
 }
 
 // same, tables in global memory (emitter spectra)
@@ -1007,14 +1094,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
         (A.emit_method == PVT_EMIT_FULL ? 1u << UF_EMIT_FULL : 0u) | (A.emit_method == PVT_EMIT_KT ? 1u << UF_EMIT_KT : 0u) |
         (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u) |
         (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u) |
-        (ROUGH && A.rough_d >= 0 ? 1u << UF_ROUGH : 0u);   // (only the rough variants read rough_d)
+        (ROUGH && A.rough_d >= 0 ? 1u << UF_ROUGH : 0u) |   // (only the rough variants read rough_d ...
+        (ROUGH && A.fd != nullptr ? 1u << UF_FIELD : 0u);   // ... and fd)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
@@ -2335,11 +2423,30 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             }
         }
         int comp = -1;
+        int frec = -1, fcell = 0;   // (scenes with a lattice) the container's field record, the cell absorbed in
         if (pend) {
             // free path in the container (no draw when the photon leaves the scene or the medium is clear), then
             // ONE advance for all three outcomes: to the absorption point if that comes first, else to the surface
             double depth = INFINITY;
-            if (hit != k_root && alpha > kAlphaZero) depth = div_normal(-pvt_log(1.0 - rng_uniform(rng)), alpha);
+            if constexpr (!ROUGH) {
+                if (hit != k_root && alpha > kAlphaZero) depth = div_normal(-pvt_log(1.0 - rng_uniform(rng)), alpha);
+            } else {
+                // (the variants of scenes with a rough node or a lattice) the same draw on the unscaled sum; a container
+                // with a lattice marches its cells to tau* (PvtFieldTables), and the pick below divides that cell's
+                // coefficients.  (The tail's alpha cache holds the unscaled sums, which stay right for the draw.)
+                if (hit != k_root && alpha > kAlphaZero) {
+                    const double tau = -pvt_log(1.0 - rng_uniform(rng));
+                    if (uf(UF_FIELD)) frec = (int)A.fd[container];
+                    if (frec >= 0) {
+                        const FieldMarch fm = field_march_call<TAB_LDS>(T, A.fd, frec, L.comp_i + crec * CI, L.comp_d + crec * CD, ccount,
+                                                                        wl, pos.x, pos.y, pos.z, dir.x, dir.y, dir.z, tau, t0);
+                        depth = fm.depth;
+                        if (fm.depth < t0) { alpha = fm.alpha; pre0 = fm.pre0; fcell = fm.cell; }
+                    } else {
+                        depth = div_normal(tau, alpha);
+                    }
+                }
+            }
             {
                 const double adv = __builtin_fmin(depth, t0);   // (depth == t0 is a surface event: same value)
                 pos.x = pos.x + dir.x * adv; pos.y = pos.y + dir.y * adv; pos.z = pos.z + dir.z * adv;
@@ -2363,9 +2470,13 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         double running = 0.0;
                         for (int k = 0; k < ccount; k++) {
                             const int ci = L.comp_i + (crec + k) * CI, cd = L.comp_d + (crec + k) * CD;
-                            running += interp_clamped<TAB_LDS>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N),
-                                                                      T.iv(ci + CI_ABS_G), T.dv(cd + CD_ABS_SCALE), T.iv(ci + CI_ABS_HIST),
-                                                                      T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
+                            double term = interp_clamped<TAB_LDS>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N),
+                                                                  T.iv(ci + CI_ABS_G), T.dv(cd + CD_ABS_SCALE), T.iv(ci + CI_ABS_HIST),
+                                                                  T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
+                            if constexpr (ROUGH) {   // (a lattice: the cell's concentration of the component)
+                                if (frec >= 0) term = term * A.fd[(int)A.fd[frec + kFrComp + k] + fcell];
+                            }
+                            running += term;
                             if (target <= running) { comp = cbase + k; break; }
                         }
                     }
@@ -2981,8 +3092,9 @@ template <bool RECORD, int SEENW, bool EMIT>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_grid(KArgs A) {
     trace_body<RECORD, 1, SEENW, EMIT, false, true>(A);
 }
-// The same three families for scenes with a rough node (KArgs::rough_d >= 0): the microfacet sampler of the surface branch
-// is compiled into these alone, so the smooth variants keep their registers, spills and text bit for bit.  (A call of
+// The same three families for scenes with a rough node (KArgs::rough_d >= 0) or a concentration field (KArgs::fd): the
+// microfacet sampler of the surface branch and the field march of the volume branch are compiled into these alone, so the
+// smooth variants keep their registers, spills and text bit for bit.  (A call of
 // the sampler from the smooth loop spilled 20-30 vector registers of every variant: the surface branch holds more values
 // than the callee-saved registers take.)
 template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH>

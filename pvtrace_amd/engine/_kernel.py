@@ -33,7 +33,7 @@ def _host_outputs(compiled, n_rays, record_every, max_events):
 
 def _host_buffer_scene(compiled):
     """PvtSceneTables of `compiled` for the host-buffer entries, which keep the reference's interface: that has no
-    place for refractive-index or phase-function tables or surface roughness, and tracing the scalar column instead
+    place for refractive-index or phase-function tables, surface roughness or concentration fields, and tracing the scalar column instead
     would silently drop the dispersion (the library itself refuses a component tagged with a table phase function)."""
     if int(getattr(compiled, "n_phase_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
@@ -48,6 +48,13 @@ def _host_buffer_scene(compiled):
         raise UnsupportedSceneError(
             "The scene has rough interfaces (a surface delegate with roughness > 0), which the host-buffer trace_bundle "
             "entry (the reference's interface) cannot take; trace it with engine.simulate."
+        )
+    if getattr(compiled, "has_fields", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has concentration fields (a component with a ConcentrationGrid), which the host-buffer "
+            "trace_bundle entry (the reference's interface) cannot take; trace it with engine.simulate."
         )
     if int(getattr(compiled, "n_ri_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError

@@ -90,6 +90,18 @@ class PvtSurfaceTables(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_roughness", _p_f64)]
 
 
+class PvtFieldTables(C.Structure):
+    """Concentration fields of a scene (include/pvtrace_hip.h; pvt_scene_create_field)."""
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_fields", C.c_int32),
+        ("node_field", _p_i32), ("field_shape", _p_i32), ("field_lower", _p_f64), ("field_upper", _p_f64),
+        ("n_components", C.c_int32), ("n_values", C.c_int32),
+        ("comp_values", _p_i32), ("values_start", _p_i32), ("values_count", _p_i32),
+        ("n_points", C.c_int32), ("reserved", C.c_int32),
+        ("values", _p_f64),
+    ]
+
+
 class PvtEmitterTables(C.Structure):
     _fields_ = [
         ("n_lights", C.c_int32), ("n_spec", C.c_int32),
@@ -246,6 +258,36 @@ def surface_tables_struct(compiled):
     return st, {"node_roughness": arr}
 
 
+def field_tables_struct(compiled):
+    """PvtFieldTables over the concentration fields of a CompiledScene -> (struct or None, keepalive); None when no node
+    carries a lattice (the scene is then created exactly as before)."""
+    node_field = getattr(compiled, "node_field", None)
+    if node_field is None or not np.any(np.asarray(node_field) >= 0):
+        return None, {}
+    keep = {}
+
+    def arr(name, dtype):
+        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
+        keep[name] = a
+        return np_ptr(a)
+
+    st = PvtFieldTables()
+    st.n_nodes = int(len(node_field))
+    st.n_fields = int(compiled.n_fields)
+    st.node_field = arr("node_field", np.int32)
+    st.field_shape = arr("field_shape", np.int32)
+    st.field_lower = arr("field_lower", np.float64)
+    st.field_upper = arr("field_upper", np.float64)
+    st.n_components = int(len(compiled.comp_values))
+    st.n_values = int(compiled.n_value_tables)
+    st.comp_values = arr("comp_values", np.int32)
+    st.values_start = arr("values_start", np.int32)
+    st.values_count = arr("values_count", np.int32)
+    st.n_points = int(len(compiled.field_values))
+    st.values = arr("field_values", np.float64)
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -319,6 +361,9 @@ def declare_signatures(lib, names):
                                     C.POINTER(vp)], C.c_int),
         "pvt_scene_create_rough": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
                                     C.POINTER(PvtSurfaceTables), C.c_int, C.POINTER(vp)], C.c_int),
+        "pvt_scene_create_field": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                    C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.c_int, C.POINTER(vp)],
+                                   C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
@@ -372,7 +417,7 @@ ABI_SYMBOLS = (
     "pvt_trace_bundle_multi", "pvt_shard_range", "pvt_trace_device_records", "pvt_unpack_records_device",
     "pvt_scene_carry_pending", "pvt_last_multi_reduce", "pvt_node_grid_plan", "pvt_scene_carry_discard", "pvt_scene_trim",
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
-    "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough",
+    "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
 )
 
 _lib = None
@@ -525,8 +570,14 @@ class DeviceScene:
         xt, xkeep = index_tables_struct(compiled)
         pt, pkeep = phase_tables_struct(compiled)
         rt, rkeep = surface_tables_struct(compiled)
+        ft, fkeep = field_tables_struct(compiled)
         handle = C.c_void_p()
-        if rt is not None:
+        if ft is not None:
+            check(self.lib.pvt_scene_create_field(C.byref(st), None if xt is None else C.byref(xt),
+                                                  None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
+                                                  C.byref(ft), self.device, C.byref(handle)),
+                  "pvt_scene_create_field")
+        elif rt is not None:
             check(self.lib.pvt_scene_create_rough(C.byref(st), None if xt is None else C.byref(xt),
                                                   None if pt is None else C.byref(pt), C.byref(rt), self.device,
                                                   C.byref(handle)),

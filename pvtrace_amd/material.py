@@ -920,9 +920,128 @@ def _spectrum(value, x, hist, what):
     raise ValueError(f"{what}: expected a number, an (n, 2) array or a list of callables, got {type(value).__name__}.")
 
 
+class ConcentrationGrid(object):
+    """A relative-concentration field c(cell) on a voxel lattice, for one volume component: the component's attenuation
+    coefficient at a point is alpha(lambda) * c(cell of the point).
+
+    values : finite values >= 0, shape (nx, ny, nz), each axis >= 1 (stored as float64).
+    lower, upper : finite 3-vectors, lower < upper on each axis: the lattice's box.
+
+    Anything else raises `ValueError`.  The contract, the same on the host and on the device (include/pvtrace_hip.h):
+
+    1. Frame and cells.  The lattice lies in the frame of the node whose material holds the component (the frame of a
+       `Histogram`'s x, y, z).  Cell widths h = (upper - lower) / n per axis; a point p lies in cell
+       clamp(floor((p - lower) / h), 0, n - 1) per axis, so a point outside the box takes the nearest edge cell.  Only
+       the interior planes lower + i h, i = 1 .. n - 1, are ever crossed.
+    2. Lattices.  The components of one material that carry a field share its lattice: the same shape, `lower` and
+       `upper` equal bit for bit (their values may differ); a component without a field has c = 1 everywhere.  The
+       scene's root node carries no field (`UnsupportedSceneError`).
+    3. Free path.  tau* = -ln(1 - u) is drawn where and when an unfielded container draws, on the unscaled sum
+       sum_k alpha_k(lambda).  From the photon's position, the march crosses the cells along its direction up to the
+       surface distance t0 and accumulates alpha_cell * segment, alpha_cell = sum_k alpha_k(lambda) c_k[cell] in
+       component order.  In a cell entered at s_in with accumulated depth tau_in, the photon is absorbed at
+       s_in + (tau* - tau_in) / alpha_cell if that lies before the cell's end; cells with alpha_cell = 0 add nothing.
+       Otherwise it reaches the surface.
+    4. Component.  The same draw and cumulative rule as an unfielded container, over alpha_k c_k[cell] of the cell the
+       march absorbed in.
+
+    A 1 x 1 x 1 field of value 1 has no interior planes: the march is (tau* - 0) / alpha with the same alpha, and the
+    scene traces draw for draw, bit for bit, as the same scene without fields.
+    """
+
+    def __init__(self, values, lower, upper):
+        try:
+            vals = np.array(values, dtype=np.float64)
+            lo = np.array(lower, dtype=np.float64)
+            hi = np.array(upper, dtype=np.float64)
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"ConcentrationGrid: values, lower and upper must be numeric arrays ({exc})") from None
+        if vals.ndim != 3 or min(vals.shape) < 1:
+            raise ValueError(f"values must have shape (nx, ny, nz), each axis >= 1, got {vals.shape}")
+        if not np.all(np.isfinite(vals)):
+            raise ValueError("values must be finite")
+        if np.any(vals < 0.0):
+            raise ValueError("values must be >= 0")
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("lower and upper must be 3-vectors")
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+            raise ValueError("lower and upper must be finite")
+        if not np.all(lo < hi):
+            raise ValueError("lower must be < upper on each axis")
+        self.values = vals
+        self.lower = lo
+        self.upper = hi
+
+    @property
+    def shape(self):
+        return self.values.shape
+
+    @property
+    def h(self):
+        """Cell widths (upper - lower) / n per axis."""
+        return (self.upper - self.lower) / np.array(self.shape, dtype=np.float64)
+
+    def same_lattice(self, other):
+        """Same shape and bounds bit for bit (values may differ)."""
+        return (self.shape == other.shape and self.lower.tobytes() == other.lower.tobytes()
+                and self.upper.tobytes() == other.upper.tobytes())
+
+    def cell_of(self, point):
+        """(ix, iy, iz) of a point in the node's frame, clamped into the lattice."""
+        p = np.asarray(point, dtype=np.float64)
+        h = self.h
+        return tuple(int(min(max(np.floor((p[a] - self.lower[a]) / h[a]), 0.0), self.shape[a] - 1)) for a in range(3))
+
+
+def _march(lattice, position, direction, tau, t0, alpha_of_cell):
+    """The free-path march of `ConcentrationGrid` (step 3) in the lattice's frame -> (absorbed, depth, cell): the
+    device's sequence of operations (pvt_trace_kernel.h, field_march_call).  `alpha_of_cell(cell)` is alpha_cell."""
+    h = lattice.h
+    n = lattice.shape
+    lo = lattice.lower
+    p = [float(v) for v in position]
+    d = [float(v) for v in direction]
+    c, step, t = [0, 0, 0], [0, 0, 0], [np.inf, np.inf, np.inf]
+
+    def ahead(a):   # distance to the interior plane ahead on axis a, inf when there is none
+        i = c[a] + 1 if step[a] > 0 else c[a]
+        if step[a] == 0 or i < 1 or i > n[a] - 1:
+            return np.inf
+        return (lo[a] + float(i) * h[a] - p[a]) / d[a]
+
+    for a in range(3):
+        f = np.floor((p[a] - lo[a]) / h[a])
+        c[a] = int(min(max(f, 0.0), float(n[a] - 1))) if np.isfinite(f) else 0
+        step[a] = 1 if d[a] > 0.0 else (-1 if d[a] < 0.0 else 0)
+        t[a] = ahead(a)
+    s, tin = 0.0, 0.0
+    while True:
+        cell = (c[0], c[1], c[2])
+        ac = alpha_of_cell(cell)
+        tmin = min(t)
+        sout = max(min(tmin, t0), s)
+        if ac > 0.0:
+            depth = s + max(tau - tin, 0.0) / ac
+            if depth < sout:
+                return True, depth, cell
+            tin += ac * (sout - s)
+        if not sout < t0:
+            return False, np.inf, None
+        a = t.index(tmin)
+        c[a] += step[a]
+        t[a] = ahead(a)
+        s = sout
+
+
 class Component:
     def __init__(self, name="Component"):
         self.name = name
+        self.concentration = None
+
+    def concentration_at(self, cell):
+        """Relative concentration in lattice cell `cell` (1 without a field)."""
+        grid = getattr(self, "concentration", None)
+        return 1.0 if grid is None else float(grid.values[cell])
 
     def is_radiative(self, ray):
         return False
@@ -935,8 +1054,11 @@ class Scatterer(Component):
     """Scattering centre with attenuation coefficient (cm^-1), constant or spectral."""
 
     def __init__(self, coefficient, x=None, quantum_yield=1.0, tau_rad=None, tau_nr=None, phase_function=None,
-                 hist=False, name="Scatterer"):
+                 hist=False, name="Scatterer", concentration=None):
         super().__init__(name=name)
+        if concentration is not None and not isinstance(concentration, ConcentrationGrid):
+            raise ValueError(f"concentration: expected None or a ConcentrationGrid, got {type(concentration).__name__}")
+        self.concentration = concentration
         if coefficient is None:
             raise ValueError("A component needs an attenuation coefficient.")
         if isinstance(coefficient, (int, np.integer, np.floating)) and not isinstance(coefficient, bool):
@@ -973,8 +1095,9 @@ class Scatterer(Component):
 class Absorber(Scatterer):
     """Non-radiative absorber (quantum yield 0)."""
 
-    def __init__(self, coefficient, x=None, tau_nr=None, name="Absorber", hist=False):
-        super().__init__(coefficient, x=x, quantum_yield=0.0, tau_rad=0.0, tau_nr=tau_nr, hist=hist, name=name)
+    def __init__(self, coefficient, x=None, tau_nr=None, name="Absorber", hist=False, concentration=None):
+        super().__init__(coefficient, x=x, quantum_yield=0.0, tau_rad=0.0, tau_nr=tau_nr, hist=hist, name=name,
+                         concentration=concentration)
 
     def is_radiative(self, ray):
         return False   # (and no draw, as in the reference, component.py:236-239)
@@ -983,17 +1106,17 @@ class Absorber(Scatterer):
 class Reactor(Absorber):
     """Absorber whose absorptions are tallied as photochemical reactions."""
 
-    def __init__(self, coefficient, x=None, name="Reactor", hist=False):
-        super().__init__(coefficient, x=x, hist=hist, name=name)
+    def __init__(self, coefficient, x=None, name="Reactor", hist=False, concentration=None):
+        super().__init__(coefficient, x=x, hist=hist, name=name, concentration=concentration)
 
 
 class Luminophore(Scatterer):
     """Absorbs and re-emits with a new wavelength drawn from `emission`."""
 
     def __init__(self, coefficient, emission=None, x=None, hist=False, quantum_yield=1.0, tau_rad=None, tau_nr=None,
-                 phase_function=None, name="Luminophore"):
+                 phase_function=None, name="Luminophore", concentration=None):
         super().__init__(coefficient, x=x, quantum_yield=quantum_yield, tau_rad=tau_rad, tau_nr=tau_nr,
-                         phase_function=phase_function, hist=hist, name=name)
+                         phase_function=phase_function, hist=hist, name=name, concentration=concentration)
         self._emission = emission
         if emission is None:   # the reference's default line: a Gaussian at 600 nm, 40 nm wide (component.py:330-335)
             emission = [lambda v: gaussian(v, 1.0, 600.0, 40.0)]
@@ -1057,6 +1180,50 @@ class Material(object):
     def component(self, wavelength):
         """Which component took the photon: each in proportion to its coefficient at this wavelength."""
         weights = np.array([c.coefficient(wavelength) for c in self.components])
+        if np.any(weights < 0.0):
+            raise ValueError("Must be positive.")
+        steps = np.cumsum(weights)
+        ladder = np.hstack([0, steps / max(steps)])
+        at = np.interp(np.random.uniform(), ladder, list(range(len(self.components) + 1)))
+        return self.components[int(np.floor(at))]
+
+    # Concentration fields (`ConcentrationGrid`): the same decisions over the cells of the components' lattice, asked
+    # with the ray in the frame of the node that holds this material.  Only a container with a field takes these.
+    @property
+    def concentration_lattice(self):
+        """The lattice the components' fields share (a `ConcentrationGrid`), None when no component has one; ValueError
+        when two fields of this material differ in shape or bounds."""
+        grids = [c.concentration for c in self.components if getattr(c, "concentration", None) is not None]
+        if not grids:
+            return None
+        for g in grids[1:]:
+            if not grids[0].same_lattice(g):
+                raise ValueError("the concentration fields of one material must share their lattice: the same shape, "
+                                 "lower and upper bit for bit")
+        return grids[0]
+
+    def cell_coefficients(self, wavelength, cell):
+        """alpha_k(wavelength) c_k[cell] of every component, in component order."""
+        return [c.coefficient(wavelength) * c.concentration_at(cell) for c in self.components]
+
+    def is_absorbed_in(self, local_ray, distance):
+        """(absorbed before `distance`?, the depth, the lattice cell absorbed in or None): tau* = -ln(1 - u) drawn when
+        and as `penetration_depth` draws, on the unscaled sum, then the march of `ConcentrationGrid` from the ray's
+        position and direction given in this material's node frame."""
+        lattice = self.concentration_lattice
+        alpha = self.total_attenutation_coefficient(local_ray.wavelength)
+        if np.isclose(alpha, 0.0):
+            return False, float("inf"), None
+        if not np.isfinite(alpha):
+            return 0.0 < distance, 0.0, lattice.cell_of(local_ray.position)
+        tau = -np.log(1 - np.random.uniform())
+        wl = local_ray.wavelength
+        return _march(lattice, local_ray.position, local_ray.direction, tau, distance,
+                      lambda cell: float(np.sum(self.cell_coefficients(wl, cell))))
+
+    def component_at(self, wavelength, cell):
+        """Which component took the photon in lattice cell `cell`: `component`'s draw and rule over alpha_k c_k[cell]."""
+        weights = np.array(self.cell_coefficients(wavelength, cell))
         if np.any(weights < 0.0):
             raise ValueError("Must be positive.")
         steps = np.cumsum(weights)
