@@ -282,6 +282,51 @@ typedef struct PvtFieldTables {
     const double* values;           /* (n_points) pooled relative concentrations, finite and >= 0 */
 } PvtFieldTables;
 
+/* ---- volume maps (extension within v13, passed to pvt_scene_create_maps) -------------------------------------------
+ * Per-voxel integer tallies of the volume events of a node: maps [node_map_start[n], + node_map_count[n]) belong to node
+ * n (the runs tile the maps in node order; the root carries none).  A map counts EVERY event of its kind whose container
+ * is its node (the `crossings` rule of a recorder, not first-per-ray): map_kind is PVT_EV_ABSORB, PVT_EV_EMIT,
+ * PVT_EV_SCATTER, PVT_EV_NONRADIATIVE or PVT_EV_REACT; map_component >= 0 keeps only the events whose component column is
+ * that component (one of the node's own).  The contract (the Python VolumeMap and engine.tally.map_histories are the same):
+ *  1. The local point is p = R x + t, x the event's world position, bit for bit the `position` of its log row.
+ *  2. R and t are the node's rows of PvtSceneTables.world_to_local (what a concentration field's record copies).
+ *  3. Each coordinate is evaluated as ((R[a][0] x + R[a][1] y) + R[a][2] z) + t[a], without FMA.
+ *  4. Per axis h = (upper - lower) / n (map_h, computed once by whoever fills the tables) and
+ *     i = floor((p - lower) / h).
+ *  5. The event is inside when 0 <= i <= n - 1 on all three axes and the wavelength bin, if any (map_nw > 0), is in
+ *     range: iw = trunc((w - start) / (stop - start) * nw), a Histogram's rule, inside when 0 <= iw <= nw - 1; w is the
+ *     wavelength column of the event's row (the incoming wavelength for ABSORB / NONRADIATIVE / REACT / SCATTER, the new
+ *     one for EMIT).
+ *  6. The slot is ((ix ny + iy) nz + iz) nw' + iw, nw' = max(nw, 1), iw = 0 without a wavelength axis.
+ *  7. Every other matching event adds one to the map's single `outside` slot, slot nx ny nz nw' of the map.
+ *  8. No clamping: a map may be a region of interest smaller than its node.
+ *  9. Hence the sum of a map's slots, `outside` included, is the number of matching events in the node.
+ * Where the counts live: map m owns the nx ny nz nw' + 1 int64 slots from map_offset[m] (the maps packed one after the
+ * other in map order, map_slots in all, at most PVT_MAX_MAP_SLOTS) of a block that FOLLOWS the recorders' bins:
+ * PvtTallies.rec_bins of a scene with maps has total_bins + map_slots elements (pvt_scene_map_slots), the maps' block
+ * starting at element total_bins; total_bins keeps the reference's meaning, and tally sets, carried launches and
+ * reductions move the maps with the bins.  The kernel adds one to a slot per event with a 64-bit integer atomic in
+ * global memory (never staged in LDS, whatever the recorders' bins do), so the counts are exact and independent of
+ * summation order, launch geometry, carrying and GPU count.  Map records live in global memory of their own, outside the
+ * tables a launch stages in LDS.  A NULL struct, n_nodes 0 or n_maps 0 is exactly pvt_scene_create_field. */
+#define PVT_MAX_MAP_SLOTS (1LL << 26)
+typedef struct PvtMapTables {
+    int32_t n_nodes;                /* 0 = none (as a NULL struct), else the scene's n_nodes */
+    int32_t n_maps;
+    const int32_t* node_map_start;  /* (n_nodes) first map of each node */
+    const int32_t* node_map_count;  /* (n_nodes) its maps; the runs tile [0, n_maps) in node order */
+    const int32_t* map_kind;        /* (n_maps) PVT_EV_ABSORB / EMIT / SCATTER / NONRADIATIVE / REACT */
+    const int32_t* map_component;   /* (n_maps) component id (one of the node's), -1 = any */
+    const int32_t* map_shape;       /* (n_maps, 3) nx, ny, nz, each >= 1 */
+    const double* map_lower;        /* (n_maps, 3) finite */
+    const double* map_h;            /* (n_maps, 3) cell widths (upper - lower) / n, finite and > 0 */
+    const int32_t* map_nw;          /* (n_maps) wavelength bins, 0 = no wavelength axis */
+    const double* map_wl_start;     /* (n_maps) finite, < map_wl_stop where map_nw > 0 */
+    const double* map_wl_stop;      /* (n_maps) */
+    const int64_t* map_offset;      /* (n_maps) first slot of each map in the maps' block */
+    int64_t map_slots;              /* slots of all maps, `outside` slots included */
+} PvtMapTables;
+
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
@@ -369,7 +414,7 @@ typedef struct PvtTallies {
     int64_t* rec_distinct;   /* (n_recorders)       */
     int64_t* rec_crossings;  /* (n_recorders)       */
     double* rec_sums;        /* (n_recorders,4,2)   */
-    int64_t* rec_bins;       /* (total_bins)        */
+    int64_t* rec_bins;       /* (total_bins), then the volume maps' slots (pvt_scene_map_slots) */
 } PvtTallies;
 
 /* event log: rows = ceil(n/record_every)*max_events; row of event k of
@@ -431,6 +476,13 @@ int pvt_scene_create_rough(const PvtSceneTables* tables, const PvtIndexTables* i
 int pvt_scene_create_field(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                            const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
                            const PvtFieldTables* field_tables, int device, PvtScene** out);
+/* The same with volume maps (NULL, n_nodes 0 or n_maps 0 = none: then exactly pvt_scene_create_field). */
+int pvt_scene_create_maps(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                          const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                          const PvtFieldTables* field_tables, const PvtMapTables* map_tables, int device, PvtScene** out);
+/* Slots of the scene's volume maps (PvtMapTables.map_slots; 0 without maps): PvtTallies.rec_bins of a launch on the
+ * scene holds total_bins + this many elements (per tally set: tally_stride_i64 is at least that). */
+int64_t pvt_scene_map_slots(const PvtScene* scene);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);

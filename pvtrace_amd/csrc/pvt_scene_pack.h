@@ -343,6 +343,12 @@ struct PackedScene {
     // fd[n] = where node n's lattice record starts (-1: none), then the records (kFr* words and one value-table offset
     // per component), then the pooled value tables
     std::vector<double> fd;
+    // volume maps (PvtMapTables): their own buffer of doubles, read from global memory alone (empty: none).
+    // md[n] = where node n's block starts (-1: the node has no map), then the blocks: kMn* words (the node's map count and
+    // its world->local rotation and translation) and one record of kMr words (kMr*) per map.  map_slots: the int64 slots
+    // the maps add behind the recorders' bins
+    std::vector<double> md;
+    long long map_slots = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     int grid_dims[3] = {0, 0, 0};
@@ -354,7 +360,7 @@ struct PackedScene {
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
 int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-                    const PvtFieldTables* fr) {
+                    const PvtFieldTables* fr, const PvtMapTables* mp) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -521,6 +527,54 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
         }
         words += fr->n_points;
         if (words > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: more doubles than int32 offsets can index");
+    }
+    // volume maps (PvtMapTables, pvt_scene_create_maps): whose maps they are, what they count and where
+    if (mp && mp->n_nodes != 0 && mp->n_maps != 0) {
+        const int M = mp->n_maps;
+        if (mp->n_nodes != N || !mp->node_map_start || !mp->node_map_count)
+            return fail(PVT_ERR_INVALID, "map tables: need one map run per node");
+        if (M < 0 || !mp->map_kind || !mp->map_component || !mp->map_shape || !mp->map_lower || !mp->map_h || !mp->map_nw ||
+            !mp->map_wl_start || !mp->map_wl_stop || !mp->map_offset)
+            return fail(PVT_ERR_INVALID, "map tables: map arrays missing");
+        long long next = 0;
+        for (int n = 0; n < N; n++) {
+            if (bad_run(mp->node_map_start[n], mp->node_map_count[n], M)) return fail(PVT_ERR_INVALID, "map tables: map run of a node out of range");
+            if (mp->node_map_start[n] != next) return fail(PVT_ERR_INVALID, "map tables: the nodes' map runs must tile the maps in node order");
+            next += mp->node_map_count[n];
+        }
+        if (next != M) return fail(PVT_ERR_INVALID, "map tables: the nodes' map runs must tile the maps in node order");
+        if (mp->node_map_count[t->root_id] > 0) return fail(PVT_ERR_INVALID, "map tables: the root node cannot carry a map");
+        long long slots = 0;
+        for (int n = 0; n < N; n++)
+            for (int m = mp->node_map_start[n]; m < mp->node_map_start[n] + mp->node_map_count[n]; m++) {
+                const int kind = mp->map_kind[m];
+                if (kind != PVT_EV_ABSORB && kind != PVT_EV_EMIT && kind != PVT_EV_SCATTER && kind != PVT_EV_NONRADIATIVE && kind != PVT_EV_REACT)
+                    return fail(PVT_ERR_INVALID, "map tables: map kind must be ABSORB, EMIT, SCATTER, NONRADIATIVE or REACT");
+                const int c = mp->map_component[m];
+                if (c < -1 || (c >= 0 && (bad_run(t->comp_start[n], t->comp_count[n], C) || c < t->comp_start[n] || c >= t->comp_start[n] + t->comp_count[n])))
+                    return fail(PVT_ERR_INVALID, "map tables: map component must be -1 or a component of the map's node");
+                long long cells = 1;
+                for (int a = 0; a < 3; a++) {
+                    if (mp->map_shape[m * 3 + a] < 1) return fail(PVT_ERR_INVALID, "map tables: map shape must be >= 1 on each axis");
+                    if (!std::isfinite(mp->map_lower[m * 3 + a])) return fail(PVT_ERR_INVALID, "map tables: map lower bounds must be finite");
+                    const double h = mp->map_h[m * 3 + a];
+                    if (!(std::isfinite(h) && h > 0.0)) return fail(PVT_ERR_INVALID, "map tables: map cell widths must be finite and > 0");
+                    cells *= mp->map_shape[m * 3 + a];
+                    if (cells > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
+                }
+                const int nw = mp->map_nw[m];
+                if (nw < 0) return fail(PVT_ERR_INVALID, "map tables: wavelength bins must be >= 0");
+                if (nw > 0) {
+                    const double lo = mp->map_wl_start[m], hi = mp->map_wl_stop[m];
+                    if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(PVT_ERR_INVALID, "map tables: wavelength range must be finite");
+                    if (!(lo < hi)) return fail(PVT_ERR_INVALID, "map tables: wavelength range needs start < stop");
+                    cells *= nw;
+                }
+                if (mp->map_offset[m] != slots) return fail(PVT_ERR_INVALID, "map tables: map offsets must pack the maps one after the other");
+                slots += cells + 1;
+                if (slots > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
+            }
+        if (mp->map_slots != slots) return fail(PVT_ERR_INVALID, "map tables: map_slots must be the sum of the maps' slots");
     }
     for (int n = 0; n < N; n++) {
         if (bad_run(t->comp_start[n], t->comp_count[n], C)) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
@@ -1115,12 +1169,53 @@ void pack_fields(const PvtSceneTables* t, const PvtFieldTables* fr, PackedScene*
     }
 }
 
+// The map buffer p->md (validated tables; left empty without maps): per node where its block starts, then per node with
+// maps its block -- the map count, the world->local rotation and translation of world_to_local (the doubles a field
+// record holds) -- and per map its record: kind, component, shape, lower, cell widths, wavelength bins and range, first slot.
+void pack_maps(const PvtSceneTables* t, const PvtMapTables* mp, PackedScene* p) {
+    p->md.clear();
+    p->map_slots = 0;
+    if (!mp || mp->n_nodes == 0 || mp->n_maps == 0) return;
+    const int N = t->n_nodes;
+    std::vector<double>& md = p->md;
+    md.assign((size_t)N, -1.0);
+    for (int n = 0; n < N; n++) {
+        const int count = mp->node_map_count[n];
+        if (count == 0) continue;
+        md[(size_t)n] = (double)md.size();
+        const size_t at = md.size();
+        md.resize(at + kMnRec + (size_t)count * kMr, 0.0);
+        double* r = md.data() + at;
+        r[kMnCount] = (double)count;
+        for (int a = 0; a < 3; a++) {
+            for (int c = 0; c < 3; c++) r[kMnRot + a * 3 + c] = t->world_to_local[n * 16 + a * 4 + c];
+            r[kMnT + a] = t->world_to_local[n * 16 + a * 4 + 3];
+        }
+        for (int k = 0; k < count; k++) {
+            const int m = mp->node_map_start[n] + k;
+            double* q = r + kMnRec + k * kMr;
+            q[kMrKind] = (double)mp->map_kind[m];
+            q[kMrComp] = (double)mp->map_component[m];
+            for (int a = 0; a < 3; a++) {
+                q[kMrShape + a] = (double)mp->map_shape[m * 3 + a];
+                q[kMrLower + a] = mp->map_lower[m * 3 + a];
+                q[kMrH + a] = mp->map_h[m * 3 + a];
+            }
+            q[kMrNw] = (double)mp->map_nw[m];
+            q[kMrWlo] = mp->map_wl_start[m];
+            q[kMrWhi] = mp->map_wl_stop[m];
+            q[kMrOff] = (double)mp->map_offset[m];   // (< 2^26: exact)
+        }
+    }
+    p->map_slots = mp->map_slots;
+}
+
 // The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the
 // phase-function tables (ph, NULL = none), the nodes' surface roughness (rs, NULL = none) and the concentration fields
-// (fr, NULL = none) -> *p.  No HIP call.
+// (fr, NULL = none) and the volume maps (mp, NULL = none) -> *p.  No HIP call.
 int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-               const PvtFieldTables* fr, PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs, fr);
+               const PvtFieldTables* fr, const PvtMapTables* mp, PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs, fr, mp);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
@@ -1146,6 +1241,7 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     rc = fill(t, x, ph, rs, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
     if (rc != PVT_OK) return rc;
     pack_fields(t, fr, p);
+    pack_maps(t, mp, p);
     prove_shortcuts(t, p);
     return PVT_OK;
 }

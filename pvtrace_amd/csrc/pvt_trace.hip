@@ -99,6 +99,8 @@ struct PvtScene {
     int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
     int rough_d = -1;                   // where the nodes' GGX widths start in the double blob (-1: no rough node)
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
+    double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
+    long long map_slots = 0;            // int64 slots the maps add behind the recorders' bins (pvt_scene_map_slots)
     double* d_gd = nullptr;
     int* d_gi = nullptr;
     double* d_ed = nullptr;
@@ -197,6 +199,7 @@ void pvt_scene_destroy(PvtScene* s) {
     (void)hipSetDevice(s->device);
     if (s->d_gd) (void)hipFree(s->d_gd);
     if (s->d_fd) (void)hipFree(s->d_fd);
+    if (s->d_md) (void)hipFree(s->d_md);
     if (s->d_gi) (void)hipFree(s->d_gi);
     if (s->d_ed) (void)hipFree(s->d_ed);
     if (s->d_ei) (void)hipFree(s->d_ei);
@@ -228,6 +231,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_rtab = s->n_rtab; a.n_lights = s->n_lights;
     a.rough_d = s->rough_d;
     a.fd = s->d_fd;
+    a.md = s->d_md;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -242,8 +246,8 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
 #ifndef PVT_DEV_VARIANTS
 #define PVT_DEV_VARIANTS 0   // developer builds: only the analytic, array-input, <=64-recorder variants (fast compile)
 #endif
-// Scenes with a rough node (KArgs::rough_d >= 0) or a concentration field (KArgs::fd) run the trace_kernel_rough*
-// families: the same choice of variant.
+// Scenes with a rough node (KArgs::rough_d >= 0), a concentration field (KArgs::fd) or a volume map (KArgs::md) run the
+// trace_kernel_rough* families: the same choice of variant.
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
 #if PVT_DEV_VARIANTS
@@ -273,7 +277,7 @@ hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st,
 
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-    if (a.rough_d >= 0 || a.fd != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
+    if (a.rough_d >= 0 || a.fd != nullptr || a.md != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
     const bool mesh = a.bvh != nullptr;
     if constexpr (TAB_LDS == 1 && (!PVT_DEV_VARIANTS || SEENW == 1) && PVT_DEV_VARIANTS != 2) {
         if (a.lay.grid_d >= 0 && !mesh && (!PVT_DEV_VARIANTS || !emit)) {   // many nodes: per-lane walk of the node grid
@@ -411,6 +415,8 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
         if (p->tally_bundle > 0x7fffffffLL || n_sets > kMaxSets)
             return fail(PVT_ERR_INVALID, "at most 1024 tally sets per launch");
         if (p->tally_stride_i64 < 0 || p->tally_stride_f64 < 0) return fail(PVT_ERR_INVALID, "negative tally stride");
+        if (s->map_slots > 0 && n_sets > 1 && p->tally_stride_i64 < (long long)s->total_bins + s->map_slots)
+            return fail(PVT_ERR_INVALID, "tally stride shorter than the bins and the volume maps' slots of a set");
     }
     HIP_TRY(hipSetDevice(s->device));
 
@@ -639,6 +645,14 @@ int pvt_scene_create_rough(const PvtSceneTables* t, const PvtIndexTables* x, con
 
 int pvt_scene_create_field(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                            const PvtSurfaceTables* rs, const PvtFieldTables* fr, int device, PvtScene** out) {
+    return pvt_scene_create_maps(t, x, ph, rs, fr, nullptr, device, out);
+}
+
+int64_t pvt_scene_map_slots(const PvtScene* s) { return s ? (int64_t)s->map_slots : 0; }
+
+int pvt_scene_create_maps(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                          const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp, int device,
+                          PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -646,7 +660,7 @@ int pvt_scene_create_field(const PvtSceneTables* t, const PvtIndexTables* x, con
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -724,6 +738,11 @@ int pvt_scene_create_field(const PvtSceneTables* t, const PvtIndexTables* x, con
     if (!packed.fd.empty()) {   // (global memory only: no launch stages it in LDS)
         HIP_TRY(hipMalloc(&s->d_fd, packed.fd.size() * sizeof(double)));
         HIP_TRY(hipMemcpy(s->d_fd, packed.fd.data(), packed.fd.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!packed.md.empty()) {   // (global memory only, like the fields)
+        HIP_TRY(hipMalloc(&s->d_md, packed.md.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(s->d_md, packed.md.data(), packed.md.size() * sizeof(double), hipMemcpyHostToDevice));
+        s->map_slots = packed.map_slots;
     }
     owner.p = nullptr;
     *out = s;

@@ -67,6 +67,11 @@ enum { RT_W2L = 0, RT_L2W = 9, RT = 18 };                         // Lay::rot_d 
 enum { kFrShape = 0, kFrLower = 3, kFrH = 6, kFrRot = 9, kFrT = 18, kFrComp = 21 };   // a fielded node's record in KArgs::fd:
                                                                  // shape, lower, cell widths, world->local rotation (row-major)
                                                                  // and translation, then one value-table offset per component
+enum { kMnCount = 0, kMnRot = 1, kMnT = 10, kMnRec = 13 };         // a mapped node's block in KArgs::md: its map count, world->local
+                                                                 // rotation (row-major) and translation, then its map records
+enum { kMrKind = 0, kMrComp, kMrShape, kMrLower = 5, kMrH = 8, kMrNw = 11, kMrWlo, kMrWhi, kMrOff, kMr = 16 };   // a map record: event
+                                                                 // kind, component (-1: any), shape, lower, cell widths,
+                                                                 // wavelength bins (0: no axis) and range, first slot
 enum { CD_QY = 0, CD_TAU_RAD, CD_TAU_NR, CD_PHASE, CD_ABS_SCALE, CD_EMS_SCALE_X, CD_EMS_SCALE_C,
        CD_ABS_RCP, CD_EMS_RCP_X, CD_EMS_RCP_C, CD_ABS_W, CD_EMS_W, CD };   // component doubles (*_RCP: RN(1/spacing) of an evenly spaced table, else NaN;
                                                             // *_W: the spacing w when additionally xs[i] == xs[0] + i*w bit for bit, else NaN)
@@ -214,6 +219,10 @@ struct KArgs {
     // Concentration fields (pvt_scene_create_field): the field buffer in global memory -- fd[n] = where node n's lattice
     // record starts (-1: none), the records (kFr*), the value tables; null = no node carries a lattice (UF_FIELD off)
     const double* fd;
+    // Volume maps (pvt_scene_create_maps): the map buffer in global memory -- md[n] = where node n's block starts (-1: no
+    // map), the blocks (kMn*, kMr*); null = the scene has no map (UF_VMAP off).  The counts are the int64 slots behind the
+    // recorders' bins: rec_bins[total_bins ...] of the lane's tally set
+    const double* md;
 };
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
 constexpr int kCarryBase = 14;     // u64 words of a parked photon before its seen-mask
@@ -683,6 +692,51 @@ __device__ __attribute__((noinline)) FieldMarch field_march_call(Tables<TAB_LDS>
     return FieldMarch{INFINITY, 0.0, 0.0, 0};
 }
 
+// Volume maps (PvtMapTables; include/pvtrace_hip.h states the contract, the Python VolumeMap and tally.map_histories bin the
+// same way): the tally of a lane that has just been absorbed in `container` (UF_VMAP).  The ABSORB event and the one
+// event that followed it -- `kind`: EMIT, SCATTER, NONRADIATIVE or REACT, decided by component `comp` -- lie at the same
+// point (px, py, pz), so the local point p = R x + t is formed once, as ((R0 x + R1 y) + R2 z) + t without FMA, from the
+// node's block at md[container].  Every map of the node whose kind and component match takes ONE no-return 64-bit integer
+// atomic in global memory: on slot ((ix ny + iy) nz + iz) nw + iw when floor((p - lower) / h) lies in 0 .. n - 1 on the
+// three axes and the wavelength bin (w_in, the wavelength the photon arrived with; w_out, the emitted one, for EMIT) in
+// 0 .. nw - 1, else on the map's `outside` slot, the one behind its cells.  `slots`: where the maps' block of the lane's
+// tally set starts.  A FUNCTION, called only from the trace_kernel_rough* variants.
+__device__ __attribute__((noinline)) void volume_map_call(const double* __restrict__ md, unsigned long long* __restrict__ slots,
+                                                          int container, int comp, int kind, double px, double py, double pz,
+                                                          double w_in, double w_out) {
+    const int at = (int)md[container];
+    if (at < 0) return;
+    const double* __restrict__ r = md + at;
+    const int count = (int)r[kMnCount];
+    const double lx = ((r[kMnRot + 0] * px + r[kMnRot + 1] * py) + r[kMnRot + 2] * pz) + r[kMnT + 0];
+    const double ly = ((r[kMnRot + 3] * px + r[kMnRot + 4] * py) + r[kMnRot + 5] * pz) + r[kMnT + 1];
+    const double lz = ((r[kMnRot + 6] * px + r[kMnRot + 7] * py) + r[kMnRot + 8] * pz) + r[kMnT + 2];
+    for (int m = 0; m < count; m++) {
+        const double* __restrict__ q = r + kMnRec + m * kMr;
+        const int mk = (int)q[kMrKind], mc = (int)q[kMrComp];
+        if ((mk != PVT_EV_ABSORB && mk != kind) || (mc >= 0 && mc != comp)) continue;
+        const double nx = q[kMrShape], ny = q[kMrShape + 1], nz = q[kMrShape + 2];
+        const double fx = __builtin_floor((lx - q[kMrLower]) / q[kMrH]);
+        const double fy = __builtin_floor((ly - q[kMrLower + 1]) / q[kMrH + 1]);
+        const double fz = __builtin_floor((lz - q[kMrLower + 2]) / q[kMrH + 2]);
+        // (a NaN coordinate fails every comparison: outside)
+        bool inside = fx >= 0.0 && fx <= nx - 1.0 && fy >= 0.0 && fy <= ny - 1.0 && fz >= 0.0 && fz <= nz - 1.0;
+        const int nw = (int)q[kMrNw];
+        const long long nwc = nw > 0 ? nw : 1;
+        long long iw = 0;
+        if (nw > 0) {   // a Histogram's rule: truncation of (w - start) / (stop - start) * bins, in range 0 .. bins - 1
+            const double w = mk == PVT_EV_EMIT ? w_out : w_in;
+            const double qw = (w - q[kMrWlo]) / (q[kMrWhi] - q[kMrWlo]) * (double)nw;
+            inside = inside && qw > -1.0 && qw < (double)nw;
+            if (inside) iw = (long long)qw;
+        }
+        const long long cells = (long long)nx * (long long)ny * (long long)nz * nwc;
+        long long slot = cells;   // (`outside`)
+        if (inside) slot = (((long long)fx * (long long)ny + (long long)fy) * (long long)nz + (long long)fz) * nwc + iw;
+        atomicAdd(slots + (long long)q[kMrOff] + slot, 1ull);
+    }
+}
+
 // same, tables in global memory (emitter spectra)
 __device__ __forceinline__ double interp_global(const double* xs, const double* ys, int n, double x) {
     if (n == 1) return ys[0];
@@ -1094,7 +1148,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1102,7 +1156,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (A.lazy_root == 1 ? 1u << UF_LAZY1 : 0u) | (A.lazy_root == 2 ? 1u << UF_LAZY2 : 0u) | (L.by_node ? 1u << UF_BY_NODE : 0u) |
         (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u) |
         (ROUGH && A.rough_d >= 0 ? 1u << UF_ROUGH : 0u) |   // (only the rough variants read rough_d ...
-        (ROUGH && A.fd != nullptr ? 1u << UF_FIELD : 0u);   // ... and fd)
+        (ROUGH && A.fd != nullptr ? 1u << UF_FIELD : 0u) |  // ... and fd ...
+        (ROUGH && A.md != nullptr ? 1u << UF_VMAP : 0u);    // ... and md)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
@@ -2500,6 +2555,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         }
         // ---- the absorbing component decides (:783-832): one pass per distinct component of the wave,
         // its record in SGPRs
+        const double wl_abs = wl;   // (volume maps: the wavelength the ABSORB row holds; unused in the smooth variants)
         {
             const int cu = comp;                       // the component's id (what the event and `source` name) ...
             const bool mine = cls == CLS_ABS;
@@ -2594,6 +2650,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             }
         }
 
+        if constexpr (ROUGH) {
+            // ---- volume maps (PvtMapTables): the ABSORB event and the one the component decided on, both at `pos` in
+            // `container`, are counted in the node's maps -- every event, in the maps' block of the lane's tally set
+            if (uf(UF_VMAP)) {
+                if (cls == CLS_ABS)
+                    volume_map_call(A.md, reinterpret_cast<unsigned long long*>(A.rec_bins) + (long long)set * A.set_stride_i + A.total_bins,
+                                    container, comp, ev_kind, pos.x, pos.y, pos.z, wl_abs, wl);
+            }
+        }
         PVT_MARK(2);  // classification + absorption + emission draws
         PVT_COUNT(1, alive && ev_component >= 0);            // absorbed
         PVT_COUNT(2, em);                                    // re-emitted

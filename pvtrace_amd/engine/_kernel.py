@@ -56,6 +56,13 @@ def _host_buffer_scene(compiled):
             "The scene has concentration fields (a component with a ConcentrationGrid), which the host-buffer "
             "trace_bundle entry (the reference's interface) cannot take; trace it with engine.simulate."
         )
+    if getattr(compiled, "has_maps", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has volume maps (a node with a VolumeMap), which the host-buffer trace_bundle entry (the "
+            "reference's interface) cannot take: its tallies have no place for them; trace it with engine.simulate."
+        )
     if int(getattr(compiled, "n_ri_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 

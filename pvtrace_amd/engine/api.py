@@ -18,7 +18,7 @@ import numpy as np
 
 from pvtrace_amd.engine import native
 from pvtrace_amd.engine.compiler import EMIT_METHODS, compile_scene
-from pvtrace_amd.engine.recorder import Heatmap
+from pvtrace_amd.engine.recorder import Heatmap, VolumeMapResult
 from pvtrace_amd.light import Event, Ray
 
 # moment accumulators kept for every recorder, in kernel order
@@ -195,6 +195,12 @@ class EngineResult:
         return out
 
     @property
+    def volume_maps(self):
+        """{map name: VolumeMapResult} of the scene's `VolumeMap`s (`data["map_bins"]`: the maps' slots, which follow the
+        recorders' bins in the device's tally buffer)."""
+        return maps_from_slots(self.compiled, self.data.get("map_bins"))
+
+    @property
     def packed(self):
         """True when the event log holds only the rows that were written (`simulate(packed_log=True)`):
         the rows of recorded ray j are ``row_start[j] : row_start[j+1]`` instead of the reference's
@@ -262,6 +268,19 @@ class EngineResult:
             yield steps
 
 
+def maps_from_slots(compiled, slots):
+    """The maps' block of a tally buffer (`map_slots` int64) -> {map name: VolumeMapResult}."""
+    if not compiled.has_maps:
+        return {}
+    if slots is None or len(slots) != compiled.map_slots:
+        raise ValueError(f"the scene's volume maps hold {compiled.map_slots} slots; the result carries "
+                         f"{'none' if slots is None else len(slots)} (data['map_bins'])")
+    out = {}
+    for spec, lo in zip(compiled.map_specs, compiled.map_offset):
+        out[spec.name] = VolumeMapResult(spec, slots[int(lo):int(lo) + spec.size])
+    return out
+
+
 GROUP_PHOTONS = 1_000_000   # photons one launch of simulate_stream traces in tally mode (bundles grouped)
 _WORKERS_WARNED = False
 
@@ -319,10 +338,14 @@ def download(compiled, tallies, log, n_rays, record_every, max_events, packed=Fa
         data["rec_distinct"] = ints[:nrec]
         data["rec_crossings"] = ints[pad:pad + nrec]
         data["rec_bins"] = ints[2 * pad: 2 * pad + int(compiled.total_bins)]
+        if compiled.has_maps:   # (the maps' slots follow the bins)
+            data["map_bins"] = ints[2 * pad + int(compiled.total_bins): 2 * pad + int(compiled.total_bins) + compiled.map_slots]
     else:
         data["rec_distinct"] = tallies["rec_distinct"][:nrec].cpu().numpy()
         data["rec_crossings"] = tallies["rec_crossings"][:nrec].cpu().numpy()
         data["rec_bins"] = tallies["rec_bins"][: int(compiled.total_bins)].cpu().numpy()
+        if compiled.has_maps:
+            data["map_bins"] = tallies["rec_bins"][int(compiled.total_bins): int(compiled.total_bins) + compiled.map_slots].cpu().numpy()
     data["rec_sums"] = tallies["rec_sums"][: nrec * 8].cpu().numpy().reshape(nrec, 4, 2)
     if log is None or rows == 0:
         for name, dtype, width in native.EVENT_LOG_COLUMNS:
@@ -400,7 +423,7 @@ def _scene_key(compiled, emitter, device):
 
     h = hashlib.blake2b(digest_size=16)
     h.update(repr(int(device)).encode())
-    for name in compiled.TABLE_FIELDS:
+    for name in compiled.TABLE_FIELDS + (compiled.MAP_TABLE_FIELDS if compiled.has_maps else ()):
         a = np.ascontiguousarray(getattr(compiled, name))
         h.update(a.dtype.str.encode()); h.update(repr(a.shape).encode()); h.update(a.data if a.size else b"")
     h.update(repr((int(compiled.root_id), int(compiled.total_bins))).encode())
@@ -631,6 +654,8 @@ class Session:
             data["rec_distinct"] = ints[j, :nrec]
             data["rec_crossings"] = ints[j, pad:pad + nrec]
             data["rec_bins"] = ints[j, 2 * pad: 2 * pad + nbins]
+            if c.has_maps:
+                data["map_bins"] = ints[j, 2 * pad + nbins: 2 * pad + nbins + c.map_slots]
             data["rec_sums"] = sums[j, : nrec * 8].reshape(nrec, 4, 2)
             results.append(EngineResult(c, data, sources[lo:hi], pending["max_events"], 0,
                                         kernel_ms * 1e-3 * (hi - lo) / n, kernel_ms=kernel_ms * (hi - lo) / n))
@@ -709,7 +734,7 @@ def merge_shards(results):
     concatenate in shard order."""
     first = results[0]
     data = {}
-    for key in ("rec_distinct", "rec_crossings", "rec_sums", "rec_bins"):
+    for key in ("rec_distinct", "rec_crossings", "rec_sums", "rec_bins") + (("map_bins",) if "map_bins" in first.data else ()):
         total = np.array(first.data[key], copy=True)
         for r in results[1:]:
             total += r.data[key]

@@ -20,6 +20,8 @@ import numpy as np
 
 from pvtrace_amd.engine.recorder import (
     EVENTS,
+    MAP_EVENTS,
+    MAX_MAP_SLOTS,
     PROPERTIES,
     SOURCE_COMPONENT,
     SOURCE_COMPONENTS,
@@ -27,6 +29,7 @@ from pvtrace_amd.engine.recorder import (
     VOLUME_EVENTS,
     Heatmap,
     Recorder,
+    VolumeMap,
 )
 from pvtrace_amd.geometry import Box, Cylinder, Mesh, Sphere
 from pvtrace_amd.material import (
@@ -267,6 +270,7 @@ class CompiledScene:
         del self._mesh_pool
 
         self._lower_recorders(nodes)
+        self._lower_maps(root, nodes)
 
     # -- geometry & pose -------------------------------------------------
     def _lower_geometry(self, i, geometry):
@@ -590,6 +594,83 @@ class CompiledScene:
         self.hist_offset = np.array(hist["off"], dtype=_I32)
         self.total_bins = int(offset)
 
+    # -- volume maps -----------------------------------------------------
+    def _lower_maps(self, root, nodes):
+        """VolumeMap specs -> per-node runs (node_map_start / node_map_count) and one record per map, in node order:
+        the event kind, the component id (-1: any), shape, lower, cell widths h = (upper - lower) / n, wavelength bins
+        (0: no axis) and range, and the map's first slot in the maps' block, which follows the recorders' bins in the
+        int64 tally buffer (`map_slots` slots in all; `total_bins` keeps the reference's meaning)."""
+        for node in root.preorder():
+            if node.geometry is None and getattr(node, "volume_maps", None):
+                raise UnsupportedSceneError(
+                    f"Node {node.name!r} has no geometry: a volume map tallies the events inside a node's volume.")
+        count = len(nodes)
+        self.node_map_start = np.zeros(count, dtype=_I32)
+        self.node_map_count = np.zeros(count, dtype=_I32)
+        self.map_specs, self.map_names = [], []
+        cols = {k: [] for k in ("kind", "component", "shape", "lower", "h", "nw", "wl_start", "wl_stop", "offset")}
+        slots = 0
+        for i, node in enumerate(nodes):
+            self.node_map_start[i] = len(self.map_specs)
+            for spec in getattr(node, "volume_maps", None) or ():
+                if not isinstance(spec, VolumeMap):
+                    raise UnsupportedSceneError(f"Node {node.name!r} volume_maps must be VolumeMap objects.")
+                if node is root:
+                    raise UnsupportedSceneError(
+                        f"Root node {node.name!r}: the scene's root cannot carry a volume map (VolumeMap {spec.name!r}).")
+                if spec.event not in MAP_EVENTS:
+                    raise UnsupportedSceneError(
+                        f"VolumeMap {spec.name!r}: unknown event {spec.event!r}; use one of {sorted(MAP_EVENTS)}.")
+                component = -1
+                if spec.component is not None:
+                    first, n = int(self.comp_start[i]), int(self.comp_count[i])
+                    own = self.component_names[first:first + n]
+                    if own.count(spec.component) != 1:
+                        raise UnsupportedSceneError(
+                            f"VolumeMap {spec.name!r}: unknown component {spec.component!r}; node {node.name!r} has "
+                            f"{own} (the filter names exactly one of the node's own components).")
+                    component = first + own.index(spec.component)
+                if spec.name in self.map_names:
+                    raise UnsupportedSceneError(f"Volume map names must be unique; {spec.name!r} is used twice.")
+                if spec.name in self.recorder_names:
+                    raise UnsupportedSceneError(
+                        f"VolumeMap {spec.name!r}: a recorder has the same name; maps and recorders share one namespace.")
+                h = spec.cell_widths
+                if not all(math.isfinite(v) and v > 0.0 for v in h):
+                    raise UnsupportedSceneError(f"VolumeMap {spec.name!r}: cell widths {h} must be finite and > 0.")
+                if slots + spec.size > MAX_MAP_SLOTS:
+                    raise UnsupportedSceneError(
+                        f"The scene's volume maps hold more than {MAX_MAP_SLOTS} slots (2^26: cells x wavelength bins, plus "
+                        f"one per map), reached at VolumeMap {spec.name!r}.")
+                self.map_specs.append(spec)
+                self.map_names.append(spec.name)
+                cols["kind"].append(MAP_EVENTS[spec.event])
+                cols["component"].append(component)
+                cols["shape"].append(list(spec.shape))
+                cols["lower"].append(list(spec.lower))
+                cols["h"].append(list(h))
+                cols["nw"].append(spec.wavelength_bins)
+                cols["wl_start"].append(spec.wavelength.start if spec.wavelength is not None else 0.0)
+                cols["wl_stop"].append(spec.wavelength.stop if spec.wavelength is not None else 1.0)
+                cols["offset"].append(slots)
+                slots += spec.size
+            self.node_map_count[i] = len(self.map_specs) - self.node_map_start[i]
+        self.n_maps = len(self.map_specs)
+        self.map_kind = np.array(cols["kind"], dtype=_I32)
+        self.map_component = np.array(cols["component"], dtype=_I32)
+        self.map_shape = np.array(cols["shape"], dtype=_I32).reshape(-1, 3)
+        self.map_lower = np.array(cols["lower"], dtype=_F64).reshape(-1, 3)
+        self.map_h = np.array(cols["h"], dtype=_F64).reshape(-1, 3)
+        self.map_nw = np.array(cols["nw"], dtype=_I32)
+        self.map_wl_start = np.array(cols["wl_start"], dtype=_F64)
+        self.map_wl_stop = np.array(cols["wl_stop"], dtype=_F64)
+        self.map_offset = np.array(cols["offset"], dtype=np.int64)
+        self.map_slots = int(slots)
+
+    @property
+    def has_maps(self):
+        return self.n_maps > 0
+
     # -- introspection ----------------------------------------------------
     TABLE_FIELDS = (
         "geom_type", "geom_params", "local_to_world", "world_to_local",
@@ -614,11 +695,21 @@ class CompiledScene:
         "field_values",
     )
 
+    # the volume maps' tables: part of `tables()` only when the scene has a map, so that a scene without maps lowers to
+    # the same tables, key for key, as before there were maps
+    MAP_TABLE_FIELDS = (
+        "node_map_start", "node_map_count", "map_kind", "map_component", "map_shape", "map_lower", "map_h", "map_nw",
+        "map_wl_start", "map_wl_stop", "map_offset",
+    )
+
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""
         out = {name: getattr(self, name) for name in self.TABLE_FIELDS}
         out["root_id"] = np.int32(self.root_id)
         out["total_bins"] = np.int32(self.total_bins)
+        if self.has_maps:
+            out.update({name: getattr(self, name) for name in self.MAP_TABLE_FIELDS})
+            out["map_slots"] = np.int64(self.map_slots)
         return out
 
     @property

@@ -102,6 +102,17 @@ class PvtFieldTables(C.Structure):
     ]
 
 
+class PvtMapTables(C.Structure):
+    """Volume maps of a scene (include/pvtrace_hip.h; pvt_scene_create_maps)."""
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_maps", C.c_int32),
+        ("node_map_start", _p_i32), ("node_map_count", _p_i32), ("map_kind", _p_i32), ("map_component", _p_i32),
+        ("map_shape", _p_i32), ("map_lower", _p_f64), ("map_h", _p_f64), ("map_nw", _p_i32),
+        ("map_wl_start", _p_f64), ("map_wl_stop", _p_f64), ("map_offset", C.POINTER(C.c_int64)),
+        ("map_slots", C.c_int64),
+    ]
+
+
 class PvtEmitterTables(C.Structure):
     _fields_ = [
         ("n_lights", C.c_int32), ("n_spec", C.c_int32),
@@ -288,6 +299,30 @@ def field_tables_struct(compiled):
     return st, keep
 
 
+def map_tables_struct(compiled):
+    """PvtMapTables over the volume maps of a CompiledScene -> (struct or None, keepalive); None when the scene has no
+    map (it is then created exactly as before)."""
+    if int(getattr(compiled, "n_maps", 0)) == 0:
+        return None, {}
+    keep = {}
+
+    def arr(name, dtype):
+        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
+        keep[name] = a
+        return np_ptr(a)
+
+    st = PvtMapTables()
+    st.n_nodes = int(len(compiled.node_map_start))
+    st.n_maps = int(compiled.n_maps)
+    for name in ("node_map_start", "node_map_count", "map_kind", "map_component", "map_shape", "map_nw"):
+        setattr(st, name, arr(name, np.int32))
+    for name in ("map_lower", "map_h", "map_wl_start", "map_wl_stop"):
+        setattr(st, name, arr(name, np.float64))
+    st.map_offset = arr("map_offset", np.int64)
+    st.map_slots = int(compiled.map_slots)
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -364,6 +399,10 @@ def declare_signatures(lib, names):
         "pvt_scene_create_field": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
                                     C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.c_int, C.POINTER(vp)],
                                    C.c_int),
+        "pvt_scene_create_maps": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                   C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables), C.c_int,
+                                   C.POINTER(vp)], C.c_int),
+        "pvt_scene_map_slots": ([vp], C.c_int64),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
@@ -418,6 +457,7 @@ ABI_SYMBOLS = (
     "pvt_scene_carry_pending", "pvt_last_multi_reduce", "pvt_node_grid_plan", "pvt_scene_carry_discard", "pvt_scene_trim",
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
+    "pvt_scene_create_maps", "pvt_scene_map_slots",
 )
 
 _lib = None
@@ -571,8 +611,15 @@ class DeviceScene:
         pt, pkeep = phase_tables_struct(compiled)
         rt, rkeep = surface_tables_struct(compiled)
         ft, fkeep = field_tables_struct(compiled)
+        mt, mkeep = map_tables_struct(compiled)
         handle = C.c_void_p()
-        if ft is not None:
+        if mt is not None:
+            check(self.lib.pvt_scene_create_maps(C.byref(st), None if xt is None else C.byref(xt),
+                                                 None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
+                                                 None if ft is None else C.byref(ft), C.byref(mt), self.device,
+                                                 C.byref(handle)),
+                  "pvt_scene_create_maps")
+        elif ft is not None:
             check(self.lib.pvt_scene_create_field(C.byref(st), None if xt is None else C.byref(xt),
                                                   None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
                                                   C.byref(ft), self.device, C.byref(handle)),
@@ -670,7 +717,7 @@ class DeviceScene:
         dev = torch.device("cuda", self.device)
         c = self.compiled
         nrec = max(int(c.rec_node.shape[0]), 1)
-        nbins = max(int(c.total_bins), 1)
+        nbins = max(int(c.total_bins) + int(getattr(c, "map_slots", 0)), 1)   # (the volume maps' slots follow the bins)
         ints = torch.zeros(sets * (2 * nrec + nbins), dtype=torch.int64, device=dev)
         sums = torch.zeros(sets * nrec * 8, dtype=torch.float64, device=dev)
         return {

@@ -236,11 +236,14 @@ class BundlePipeline:
         nrec = max(int(c.rec_node.shape[0]), 1)
         ints, sums = ints.cpu().numpy(), sums.cpu().numpy()
         r = int(c.rec_node.shape[0])
-        return {
+        data = {
             "rec_distinct": ints[:nrec][:r], "rec_crossings": ints[nrec:2 * nrec][:r],
             "rec_bins": ints[2 * nrec:][: int(c.total_bins)],
             "rec_sums": sums[: r * 8].reshape(r, 4, 2),
         }
+        if c.has_maps:   # (the volume maps' slots follow the bins: engine.api.maps_from_slots)
+            data["map_bins"] = ints[2 * nrec + int(c.total_bins):][: c.map_slots]
+        return data
 
     def kernel_ms(self):
         self.synchronize()

@@ -122,3 +122,130 @@ class Recorder:
 
     def __repr__(self):
         return "Recorder(%r, event=%r)" % (self.name, self.event)
+
+
+# volume-map selector -> the event-log kind it counts (include/pvtrace_hip.h PVT_EV_*; light.Event has the same values)
+MAP_EVENTS = {"absorbed": 3, "emitted": 6, "scattered": 5, "lost": 4, "reacted": 8}
+# slots (cells x wavelength bins, plus one `outside` slot per map) the maps of one scene may hold: 512 MiB of int64
+# counts per tally set (include/pvtrace_hip.h PVT_MAX_MAP_SLOTS)
+MAX_MAP_SLOTS = 1 << 26
+
+
+class VolumeMap:
+    """Per-voxel integer tally of one kind of volume event inside a node: attach as ``node.volume_maps = [...]``,
+    beside ``node.recorders``; the result is ``EngineResult.volume_maps[name]``, a `VolumeMapResult`.
+
+    name        key of the result
+    shape       (nx, ny, nz), each >= 1
+    lower,upper the lattice's box in the NODE's own frame, finite, lower < upper on each axis (both required, as for a
+                `ConcentrationGrid`; `VolumeMap.like(grid, name, ...)` copies a grid's lattice).  The root carries no map.
+    event       "absorbed", "emitted", "scattered", "lost" or "reacted": the event-log kinds ABSORB, EMIT, SCATTER,
+                NONRADIATIVE, REACT, restricted to events whose `container` is this node
+    component   None, or the name of one of the node's components: only events whose `component` column names it
+    wavelength  None, or (start, stop, bins): a fourth axis binned by `Histogram`'s rule on the wavelength column of the
+                event's row (the incoming wavelength for absorbed / lost / reacted / scattered, the new one for emitted)
+
+    A map counts EVERY matching event (the `crossings` rule of a recorder, not its first-per-ray rule): deposition needs
+    every event.  All slots are integers, so results are exact and independent of summation order, launch geometry,
+    carrying and GPU count.  The contract (include/pvtrace_hip.h, PvtMapTables, states the same; the kernel and
+    `engine.tally.map_histories` both follow it):
+
+    1. The local point is p = R x + t, x the event's world position, bit for bit the `position` of its log row.
+    2. R and t are the node's world->local rows as the flattener lowers them (`CompiledScene.world_to_local`).
+    3. Each coordinate is evaluated as ((R[a][0] x + R[a][1] y) + R[a][2] z) + t[a], without FMA.
+    4. Per axis h = (upper - lower) / n and i = floor((p - lower) / h).
+    5. The event is inside when 0 <= i <= n - 1 on all three axes and the wavelength bin, if any, is in range:
+       iw = trunc((w - start) / (stop - start) * bins), inside when 0 <= iw <= bins - 1.
+    6. The slot is ((ix ny + iy) nz + iz) nw + iw.
+    7. Every other matching event adds one to the map's single `outside` slot.
+    8. No clamping: unlike a concentration field a map may be a region of interest smaller than its node, and clamping
+       would pile the rest into its edge cells.
+    9. Hence ``counts.sum() + outside`` is the number of matching events in the node.
+    """
+
+    def __init__(self, name, shape, lower, upper, event="absorbed", component=None, wavelength=None):
+        import math
+
+        _require(event in MAP_EVENTS, f"Unknown volume-map event {event!r}; use one of {sorted(MAP_EVENTS)}")
+        try:
+            dims = tuple(int(n) for n in shape)
+        except TypeError:
+            dims = ()
+        _require(len(dims) == 3 and all(float(n) == float(m) for n, m in zip(dims, shape)),
+                 f"VolumeMap {name!r}: shape must be three integers (nx, ny, nz), got {shape!r}")
+        _require(all(n >= 1 for n in dims), f"VolumeMap {name!r}: shape must be >= 1 on each axis, got {dims}")
+        lo, hi = tuple(float(v) for v in lower), tuple(float(v) for v in upper)
+        _require(len(lo) == 3 and len(hi) == 3, f"VolumeMap {name!r}: lower and upper must have three coordinates")
+        _require(all(math.isfinite(v) for v in lo + hi), f"VolumeMap {name!r}: lower and upper must be finite, got {lo} {hi}")
+        _require(all(a < b for a, b in zip(lo, hi)), f"VolumeMap {name!r}: needs lower < upper on each axis, got {lo} {hi}")
+        if wavelength is not None:
+            start, stop, bins = wavelength
+            wavelength = Histogram("wavelength", start, stop, bins)
+            _require(math.isfinite(wavelength.start) and math.isfinite(wavelength.stop),
+                     f"VolumeMap {name!r}: the wavelength range must be finite")
+        self.name, self.shape, self.lower, self.upper = name, dims, lo, hi
+        self.event, self.component, self.wavelength = event, component, wavelength
+
+    @classmethod
+    def like(cls, grid, name, **kwargs):
+        """A map on the lattice (shape, lower, upper) of a `ConcentrationGrid`."""
+        return cls(name, tuple(grid.shape), tuple(float(v) for v in grid.lower), tuple(float(v) for v in grid.upper), **kwargs)
+
+    @property
+    def cell_widths(self):
+        """h = (upper - lower) / n per axis, the widths the binning divides by."""
+        return tuple((b - a) / float(n) for a, b, n in zip(self.lower, self.upper, self.shape))
+
+    @property
+    def wavelength_bins(self):
+        return self.wavelength.bins if self.wavelength is not None else 0
+
+    @property
+    def size(self):
+        """Number of slots, the `outside` slot included."""
+        cells = self.shape[0] * self.shape[1] * self.shape[2] * max(self.wavelength_bins, 1)
+        return cells + 1
+
+    def __repr__(self):
+        return "VolumeMap(%r, %r, event=%r)" % (self.name, self.shape, self.event)
+
+
+class VolumeMapResult:
+    """Counts of one `VolumeMap`: `counts` (int64, shape (nx, ny, nz) or (nx, ny, nz, nw)), `outside` (matching events
+    of the node that fell outside the lattice or the wavelength range), `total` = counts.sum() + outside, and the
+    lattice: `shape`, `lower`, `upper`, `cell_volume`."""
+
+    def __init__(self, spec, slots):
+        import numpy as np
+
+        slots = np.asarray(slots, dtype=np.int64)
+        if slots.shape != (spec.size,):
+            raise ValueError(f"VolumeMap {spec.name!r} has {spec.size} slots, got {slots.shape}")
+        self.spec = spec
+        nw = spec.wavelength_bins
+        self.counts = slots[:-1].reshape(spec.shape + ((nw,) if nw else ()))
+        self.outside = int(slots[-1])
+
+    @property
+    def total(self):
+        return int(self.counts.sum()) + self.outside
+
+    @property
+    def shape(self):
+        return self.spec.shape
+
+    @property
+    def lower(self):
+        return self.spec.lower
+
+    @property
+    def upper(self):
+        return self.spec.upper
+
+    @property
+    def cell_volume(self):
+        h = self.spec.cell_widths
+        return h[0] * h[1] * h[2]
+
+    def __repr__(self):
+        return f"VolumeMapResult({self.spec.name!r}, total={self.total}, outside={self.outside})"

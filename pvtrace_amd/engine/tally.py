@@ -130,3 +130,69 @@ def tally_histories(scene, histories):
                 probe.offer(ray, meta or {}, incoming or ray)
             incoming = ray
     return {probe.recorder.name: probe.result() for probe in probes}
+
+
+def map_histories(scene, histories):
+    """{map name: VolumeMapResult} from one history per ray: the scene's `VolumeMap`s binned on the host, in numpy, by
+    the contract stated in the `VolumeMap` docstring -- every event of the map's kind whose container is the map's node,
+    local point ((R0 x + R1 y) + R2 z) + t from the COMPILED scene's `world_to_local` rows (the tables the kernel reads,
+    not a second composition of the node tree), i = floor((p - lower) / h), no clamping, one `outside` slot.  The host
+    path for `follow(backend="host")` users, and the referee of the kernel's maps."""
+    from pvtrace_amd.engine.api import maps_from_slots
+    from pvtrace_amd.engine.compiler import compile_scene
+
+    compiled = scene if hasattr(scene, "map_specs") else compile_scene(scene)
+    if not compiled.has_maps:
+        return {}
+    kinds = sorted(set(int(k) for k in compiled.map_kind))
+    mapped = {compiled.node_names[i]: i for i in range(len(compiled.node_names)) if compiled.node_map_count[i] > 0}
+    # the events a map can count, per node: kind, component name, world position, wavelength
+    rows = {i: ([], [], [], []) for i in mapped.values()}
+    for history in histories:
+        for ray, event, meta in history:
+            code = int(getattr(event, "value", event))
+            if code not in kinds:
+                continue
+            i = mapped.get((meta or {}).get("container"))
+            if i is None:
+                continue
+            kind, comp, pos, wl = rows[i]
+            kind.append(code)
+            comp.append(meta.get("component"))
+            pos.append(tuple(float(v) for v in ray.position))
+            wl.append(float(ray.wavelength))
+    slots = np.zeros(compiled.map_slots, dtype=np.int64)
+    for i, (kind, comp, pos, wl) in rows.items():
+        kind = np.array(kind, dtype=np.int64)
+        x = np.array(pos, dtype=np.float64).reshape(len(pos), 3)
+        wl = np.array(wl, dtype=np.float64)
+        w2l = compiled.world_to_local[i]
+        # (element-wise products and sums in the contract's order: no matrix product, whose summation order is BLAS's)
+        local = [((w2l[a, 0] * x[:, 0] + w2l[a, 1] * x[:, 1]) + w2l[a, 2] * x[:, 2]) + w2l[a, 3] for a in range(3)]
+        first = int(compiled.node_map_start[i])
+        for m in range(first, first + int(compiled.node_map_count[i])):
+            spec = compiled.map_specs[m]
+            match = kind == int(compiled.map_kind[m])
+            if spec.component is not None:
+                match &= np.array([c == spec.component for c in comp], dtype=bool)
+            inside = np.ones(len(kind), dtype=bool)
+            cell = np.zeros(len(kind), dtype=np.int64)
+            with np.errstate(invalid="ignore"):
+                for a in range(3):
+                    n = int(compiled.map_shape[m, a])
+                    f = np.floor((local[a] - compiled.map_lower[m, a]) / compiled.map_h[m, a])
+                    ok = (f >= 0.0) & (f <= n - 1.0)
+                    inside &= ok
+                    cell = cell * n + np.where(ok, f, 0.0).astype(np.int64)
+                nw = int(compiled.map_nw[m])
+                if nw > 0:
+                    lo, hi = compiled.map_wl_start[m], compiled.map_wl_stop[m]
+                    q = (wl - lo) / (hi - lo) * float(nw)
+                    ok = (q > -1.0) & (q < float(nw))   # (truncation, a Histogram's rule: bin 0 reaches down to -1 exclusive)
+                    inside &= ok
+                    cell = cell * nw + np.trunc(np.where(ok, q, 0.0)).astype(np.int64)
+            size = spec.size
+            index = np.where(inside, cell, size - 1)[match]
+            at = int(compiled.map_offset[m])
+            slots[at:at + size] += np.bincount(index, minlength=size).astype(np.int64)
+    return maps_from_slots(compiled, slots)

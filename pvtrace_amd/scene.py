@@ -57,6 +57,7 @@ class Node(Transformable):
         self.geometry = geometry
         self.light = light
         self.recorders = [] if recorders is None else list(recorders)
+        self.volume_maps = []   # engine.VolumeMap specs: per-voxel tallies of the node's volume events
 
     def __repr__(self):
         return "Node({})".format(self.name)
