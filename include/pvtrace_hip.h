@@ -598,6 +598,25 @@ int pvt_scene_launch_span(PvtScene* scene, void* stream, uint64_t* out);
 /* Launch geometry actually used by the last trace on this scene (diagnostics). */
 int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_t* lds_bytes);
 
+/* The kernel family the scene's launches run (diagnostics; additive under ABI 13).  PVT_VARIANT_LEAN: the scene was
+ * proven plain when it was created -- unrotated boxes only (the root may be a sphere), per container at most two components,
+ * each an absorber or an isotropic luminophore, spectra on even grids (not histograms), no coating, no index / reflectivity / phase
+ * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
+ * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
+ * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
+enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
+/* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */
+int pvt_scene_variant(PvtScene* scene);
+/* Host-only (no GPU needed): *lean = 0 when the tables are not proven plain in the sense above, 2 when they are and every
+ * spectrum is a constant or an even grid bit for bit (the family's kernels without table searches), 1 when some grid is
+ * even only up to rounding (np.linspace: the family's kernels that search) -- the proof alone, on the packed tables;
+ * whether a launch then runs PVT_VARIANT_LEAN also needs the tables to fit in LDS. */
+int pvt_scene_lean_check(const PvtSceneTables* tables, const PvtIndexTables* index_tables, const PvtPhaseTables* phase_tables,
+                         const PvtSurfaceTables* surface_tables, const PvtFieldTables* field_tables,
+                         const PvtMapTables* map_tables, int32_t* lean);
+
 /* Host-only check of the triangle BVH the library builds for mesh node `node` (no GPU needed):
  * every face appears in exactly one leaf, lies inside the boxes of its leaf and of all its
  * ancestors, the children of a record are a pair on one 64-byte line, a left child's skip link is its

@@ -351,6 +351,8 @@ struct PackedScene {
     long long map_slots = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
+    bool lean_ok = false;   // see prove_lean: the scene may run the trace_kernel_lean family ...
+    bool lean_even = false; // ... and every spectrum its loop reads is a constant or on a proven even grid (its EVEN kernels)
     int grid_dims[3] = {0, 0, 0};
     std::vector<pvt::BvhNode> bvh_nodes;
     std::vector<pvt::MeshTri> bvh_tris;
@@ -1123,6 +1125,74 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
     }
 }
 
+// Lean scenes (kernel: trace_body's LEAN, the trace_kernel_lean family): every fact that variant holds as a constant,
+// read back from the PACKED tables -- the words the kernel itself would have asked -- so that whoever fills them, Python
+// or a C caller, gets the same answer.  One clause per fact; tests/test_lean_variant.py breaks each in turn.
+//   * no extension: no coating (so no reflectivity table), no index table, no phase table, no rough node, no
+//     concentration field, no volume map; no mesh, no node grid;
+//   * few nodes (Lay::by_node), every one of them unrotated, hence one rotation class, and a box -- but for the root,
+//     which may be a sphere as well (the reference's test and benchmark scenes stand in a spherical world);
+//   * per container at most two components, each an absorber or a luminophore with the isotropic phase function;
+//   * no spectrum the loop reads is a histogram, and each is sampled on an even grid: absorption x -> y of every
+//     component, emission x -> cdf and cdf -> x of every luminophore.  Two kinds.  Where every one of them is a constant
+//     (one point) or even BIT FOR BIT (even_w: CD_*_W a number) the scene is `lean_even` and runs the EVEN kernels
+//     (interp_clamped's kInterpEven / kInterpByGuide: no guide bracket, no bisection).  A grid that is even only up to
+//     rounding -- np.linspace(300, 1000, 200), the reference's benchmark slab: the spacing is no double -- cannot take the
+//     arithmetic path (the divisor of its intervals is not one known number), so its scene runs the family's other
+//     kernels, which search the tables as the generic ones do (kInterpNoHist).  A grid that is not even at all
+//     (abscissae off x0 + i (xl - x0) / (n - 1) by more than 1e-9 of the spacing) is not the plain kind: generic family.
+//     That last clause is the definition of the class, not something the kernel relies on;
+//   * at most 64 recorders, and every entry of the candidate tables carries kRecPlain (no source filter, nothing to
+//     compare with the normal).
+void prove_lean(const PvtSceneTables* t, PackedScene* p) {
+    const Lay& lay = p->lay;
+    const std::vector<double>& gd = p->gd;
+    const std::vector<int>& gi = p->gi;
+    const int N = t->n_nodes, R = t->n_recorders;
+    bool all_even = true;
+    // n abscissae stored at gd[at ...]: an even grid up to rounding
+    auto nearly_even = [&](int at, int n) {
+        const double x0 = gd[(size_t)at], step = (gd[(size_t)at + n - 1] - x0) / (double)(n - 1);
+        if (!(step > 0.0) || !std::isfinite(step)) return false;
+        for (int i = 0; i < n; i++)
+            if (!(std::fabs(gd[(size_t)at + i] - (x0 + (double)i * step)) <= 1e-9 * step)) return false;
+        return true;
+    };
+    // a searched table (CI_*_X, n points, its even_w in `w`): 2 = a constant or even bit for bit, 1 = even up to rounding, 0
+    auto grid_kind = [&](int at, int n, double w) { return (n == 1 || w == w) ? 2 : (nearly_even(at, n) ? 1 : 0); };
+    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && p->fd.empty() &&
+              p->md.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
+    for (int n = 0; n < N && ok; n++) {
+        unsigned long long bits;
+        std::memcpy(&bits, &gd[(size_t)n * ND + ND_BITS], 8);
+        const bool ident = (bits & 1ull) != 0;
+        const int geom = (int)(((unsigned int)bits >> 8) & 0xffu), rot_class = (int)(unsigned int)(bits >> 32);
+        const int* q = gi.data() + n * NI;
+        const bool shape_ok = geom == PVT_GEOM_BOX || (geom == PVT_GEOM_SPHERE && n == t->root_id);
+        if (!ident || !shape_ok || rot_class != 0 || q[NI_KCOUNT] != 0 || q[NI_CCOUNT] > 2) ok = false;
+        for (int k = 0; k < q[NI_CCOUNT] && ok; k++) {
+            const int* ci = gi.data() + lay.comp_i + (q[NI_CREC] + k) * CI;
+            const double* cd = gd.data() + lay.comp_d + (q[NI_CREC] + k) * CD;
+            const bool luminophore = ci[CI_TYPE] == PVT_COMP_LUMINOPHORE;
+            if (!luminophore && ci[CI_TYPE] != PVT_COMP_ABSORBER) ok = false;
+            if (ci[CI_PHASE] != PVT_PHASE_ISOTROPIC) ok = false;
+            const int ka = ci[CI_ABS_HIST] != 0 ? 0 : grid_kind(ci[CI_ABS_X], ci[CI_ABS_N], cd[CD_ABS_W]);
+            const int ke = !luminophore ? 2 : (ci[CI_EMS_HIST] != 0 ? 0 : grid_kind(ci[CI_EMS_X], ci[CI_EMS_N], cd[CD_EMS_W]));
+            if (ka == 0 || ke == 0) ok = false;
+            if (ka != 2 || ke != 2) all_even = false;
+        }
+    }
+    for (int block = 0; block < N * 7 && ok; block++) {   // (by_node: one candidate block per node and selector)
+        const int* rec = gi.data() + lay.cand_i + block * 8;
+        for (int b = 0; b < 6; b++)
+            if (rec[2 + b] >= 0 && !(rec[2 + b] & kRecPlain)) ok = false;
+        for (int j = 0; j < rec[1]; j++)
+            if (!(gi[(size_t)lay.cand_list + rec[0] + j] & kRecPlain)) ok = false;
+    }
+    p->lean_ok = ok;
+    p->lean_even = ok && all_even;
+}
+
 // The field buffer p->fd (validated tables; left empty when no node carries a lattice): per node where its record starts,
 // then per fielded node its record -- shape, lower, cell widths h = (upper - lower) / n, the world->local rotation and
 // translation of world_to_local (the doubles the node record and rotation classes hold) and, per component in the node's
@@ -1243,6 +1313,7 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     pack_fields(t, fr, p);
     pack_maps(t, mp, p);
     prove_shortcuts(t, p);
+    prove_lean(t, p);
     return PVT_OK;
 }
 

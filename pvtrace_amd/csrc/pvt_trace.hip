@@ -147,6 +147,9 @@ struct PvtScene {
     int grid_dims[3] = {0, 0, 0};
     bool fuse_exit = false;         // see prove_shortcuts: photons leaving the only child's surface outwards are done
     bool hist_reads_position = false;   // a histogram axis is x, y or z
+    bool lean_ok = false;           // see prove_lean: launches with the tables in LDS run the trace_kernel_lean family ...
+    bool lean_even = false;         // ... its EVEN kernels (every spectrum a constant or on a proven even grid)
+    int last_variant = -1;          // PVT_VARIANT_* of the last launch (-1: none yet)
 };
 
 extern "C" {
@@ -275,6 +278,34 @@ hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st,
 #endif
 }
 
+// Which family a launch runs (PVT_VARIANT_*): the same questions, in the same order, as launch_variant below asks.
+int variant_of(const PvtScene* s, bool tab_lds) {
+    if (s->rough_d >= 0 || s->d_fd || s->d_md) return PVT_VARIANT_ROUGH;
+    if (s->d_bvh) return PVT_VARIANT_MESH;
+    if (tab_lds && s->lay.grid_d >= 0) return PVT_VARIANT_GRID;
+    if (tab_lds && s->lean_ok && s->n_rec <= 64) return PVT_VARIANT_LEAN;
+    return PVT_VARIANT_W4;
+}
+
+// Plain scenes (PvtScene::lean_ok, proven by prove_lean) with their tables in LDS: the lean family.
+template <bool RECORD>
+hipError_t launch_lean_variant(bool even, bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
+#if PVT_DEV_VARIANTS
+    if (emit || RECORD) return hipErrorNotSupported;
+    if (even) hipLaunchKernelGGL((trace_kernel_lean_w4<false, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
+    else hipLaunchKernelGGL((trace_kernel_lean_w4<false, false, false>), dim3(grid), dim3(kBlock), lds, st, a);
+#else
+    if (even) {
+        if (emit) hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, true, true>), dim3(grid), dim3(kBlock), lds, st, a);
+        else hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
+    } else {
+        if (emit) hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, true, false>), dim3(grid), dim3(kBlock), lds, st, a);
+        else hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, false, false>), dim3(grid), dim3(kBlock), lds, st, a);
+    }
+#endif
+    return hipGetLastError();
+}
+
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
     if (a.rough_d >= 0 || a.fd != nullptr || a.md != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
@@ -313,7 +344,10 @@ hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const
 }
 
 template <bool RECORD, int TAB_LDS>
-hipError_t launch_seen(int n_rec, bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
+hipError_t launch_seen(int n_rec, int lean, bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
+    if constexpr (TAB_LDS == 1 && PVT_DEV_VARIANTS != 2) {
+        if (lean) return launch_lean_variant<RECORD>(lean == kLeanEven, emit, grid, lds, st, a);
+    }
     if (n_rec <= 64) return launch_variant<RECORD, TAB_LDS, 1>(emit, grid, lds, st, a);
     return launch_variant<RECORD, TAB_LDS, 4>(emit, grid, lds, st, a);
 }
@@ -545,14 +579,16 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
         a.emit_pool = s->emit_pool[(size_t)slot];
     }
     hipError_t e;
+    s->last_variant = variant_of(s, tab_lds);
+    const int lean = s->last_variant != PVT_VARIANT_LEAN ? kLeanOff : (s->lean_even ? kLeanEven : kLeanSearched);   // (trace_body's LEAN)
     if (record) {
-        e = tab_lds ? launch_seen<true, 1>(s->n_rec, emit, (int)grid, lds, st, a)
-            : lp.small_lds ? launch_seen<true, 2>(s->n_rec, emit, (int)grid, lds, st, a)
-                           : launch_seen<true, 0>(s->n_rec, emit, (int)grid, lds, st, a);
+        e = tab_lds ? launch_seen<true, 1>(s->n_rec, lean, emit, (int)grid, lds, st, a)
+            : lp.small_lds ? launch_seen<true, 2>(s->n_rec, lean, emit, (int)grid, lds, st, a)
+                           : launch_seen<true, 0>(s->n_rec, lean, emit, (int)grid, lds, st, a);
     } else {
-        e = tab_lds ? launch_seen<false, 1>(s->n_rec, emit, (int)grid, lds, st, a)
-            : lp.small_lds ? launch_seen<false, 2>(s->n_rec, emit, (int)grid, lds, st, a)
-                           : launch_seen<false, 0>(s->n_rec, emit, (int)grid, lds, st, a);
+        e = tab_lds ? launch_seen<false, 1>(s->n_rec, lean, emit, (int)grid, lds, st, a)
+            : lp.small_lds ? launch_seen<false, 2>(s->n_rec, lean, emit, (int)grid, lds, st, a)
+                           : launch_seen<false, 0>(s->n_rec, lean, emit, (int)grid, lds, st, a);
     }
     if (e != hipSuccess) return fail(PVT_ERR_HIP, std::string("trace_kernel launch: ") + hipGetErrorString(e));
     if (!n_sets) carry.phase = (carry.phase + 1) % 3;
@@ -681,6 +717,8 @@ int pvt_scene_create_maps(const PvtSceneTables* t, const PvtIndexTables* x, cons
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
     s->grid = packed.grid;
+    s->lean_ok = packed.lean_ok && !getenv("PVT_NO_LEAN");   // (PVT_NO_LEAN: the generic family, for parity tests and A/B runs)
+    s->lean_even = s->lean_ok && packed.lean_even;
     for (int a = 0; a < 3; a++) s->grid_dims[a] = packed.grid_dims[a];
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -944,6 +982,23 @@ int pvt_scene_launch_info(PvtScene* s, int32_t* grid, int32_t* block, int32_t* l
     if (grid) *grid = s->last_grid;
     if (block) *block = kBlock;
     if (lds_bytes) *lds_bytes = s->last_lds;
+    return PVT_OK;
+}
+
+int pvt_scene_variant(PvtScene* s) {
+    if (!s) return fail(PVT_ERR_INVALID, "null scene");
+    if (s->last_variant >= 0) return s->last_variant;
+    return variant_of(s, plan_lds(s, false).tab_lds);
+}
+
+int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+                         const PvtFieldTables* fr, const PvtMapTables* mp, int32_t* lean) {
+    if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
+    if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
+    PackedScene packed;
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, &packed);
+    if (rc != PVT_OK) return rc;
+    *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     return PVT_OK;
 }
 

@@ -369,17 +369,25 @@ constexpr double kRcpCcm = 1.0 / kCcm;   // correctly rounded by the compiler
 // of w (both checked by the host), so the reference's index is found by arithmetic — no table
 // walk, no dependent LDS reads — and validated against the (computed) neighbours.  `yw` likewise for
 // the ordinates (the inverse-CDF lookup returns wavelengths of an evenly spaced grid).
-template <int TAB_LDS>
+// `KIND` (the lean variants, whose host has proven it of every table of the scene): kInterpAny = decided here, per call, by
+// `hist`, `w` and `yw`; kInterpEven = not a histogram, and w is a number unless n == 1 (a constant); kInterpByGuide = not
+// a histogram, w NaN, and yw a number unless n == 1 (the inverse-CDF lookup of an emission table whose wavelengths are an
+// even grid).  A known kind is the same path with its run-time tests and the other paths left out.
+enum { kInterpAny = 0, kInterpEven, kInterpByGuide, kInterpNoHist };   // (kInterpNoHist: kInterpAny of a table that is no histogram)
+enum { kLeanOff = 0, kLeanSearched, kLeanEven };   // trace_body's LEAN
+template <int TAB_LDS, int KIND = kInterpAny>
 __device__ __forceinline__ double interp_clamped(const Tables<TAB_LDS>& T, double x, int xs, int ys, int n,
                                                  int guide, double scale, int hist, double rcp,
                                                  double w = __builtin_nan(""), double yw = __builtin_nan("")) {
     auto end = [&](int i) { return T.sd(i); };
     if (n == 1) return end(ys);
+    constexpr bool kAny = KIND == kInterpAny;   // (the generic variants: every test below stands where and as it always stood)
     // a table on a proven even grid (w, yw) is stored as its first value: the last one is computed, same bits
-    const bool even = !hist && w == w;
+    constexpr bool kNoHist = KIND == kInterpNoHist;
+    const bool even = KIND == kInterpEven || (kAny && !hist && w == w) || (kNoHist && w == w);
     const double x0 = end(xs), xl = even ? x0 + (double)(n - 1) * w : end(xs + n - 1);
     if (x <= x0) return end(ys);
-    if (hist ? x > xl : x >= xl) return yw == yw ? end(ys) + (double)(n - 1) * yw : end(ys + n - 1);  // step tables search x == xl (plateaus)
+    if ((kAny && hist) ? x > xl : x >= xl) return (KIND == kInterpByGuide || ((kAny || kNoHist) && yw == yw)) ? end(ys) + (double)(n - 1) * yw : end(ys + n - 1);  // step tables search x == xl (plateaus)
     if (even) {
         // the host has checked, with this very sequence of operations, that it lands on the reference's
         // bisection index for every x of the table (pvt_trace.hip: even_w)
@@ -400,7 +408,7 @@ __device__ __forceinline__ double interp_clamped(const Tables<TAB_LDS>& T, doubl
     if (hi > n - 1) hi = n - 1;
     // the abscissae travel with the indices, so nothing is re-read after the search
     double xlo = T.sd(xs + lo), xhi = T.sd(xs + hi);
-    if (hist) {
+    if (kAny && hist) {
         // histogram-sampled table (extension; Python Distribution's hist branch): the value of
         // the first abscissa >= x, i.e. ys[#{xs_i < x}] — same bracket, strict comparison
         if (!(xlo < x)) lo = 0;          // xs[0] < x is known here
@@ -421,7 +429,7 @@ __device__ __forceinline__ double interp_clamped(const Tables<TAB_LDS>& T, doubl
         if (xm <= x) { lo = mid; xlo = xm; } else { hi = mid; xhi = xm; }
     }
     double ylo, yhi;
-    if (yw == yw) {   // ordinates of an evenly spaced grid: computed, same bits as the table's
+    if (KIND == kInterpByGuide || ((kAny || kNoHist) && yw == yw)) {   // ordinates of an evenly spaced grid: computed, same bits as the table's
         const double y0 = end(ys);
         ylo = y0 + (double)lo * yw; yhi = y0 + (double)hi * yw;
     } else {
@@ -1046,7 +1054,7 @@ struct Seen {
 // GRID: scenes of many nodes -- every lane finds the nodes its ray can cross through a uniform grid (see the node loop).
 // TAIL: the same loop as a FUNCTION for the last wave of a draining workgroup (`tail_run`, below): no rays to claim, no
 // rendezvous -- it takes the `tail_total` photons its caller left in the exchange buffer and steps them until none is left.
-template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH = false>
+template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH = false, int LEAN = 0>
 __device__ void tail_run(const KArgs* kernel_args, int total, unsigned int lds);
 
 // A wave leaves its workgroup: the LAST one to do so adds the workgroup's accumulators (LDS) to the launch's outputs -- one
@@ -1117,8 +1125,15 @@ __device__ __attribute__((noinline)) void leave_workgroup(const KArgs* kernel_ar
         }
 }
 
-template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, bool ROUGH = false>
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, bool ROUGH = false,
+          int LEAN = 0>
 __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, unsigned int tail_lds = 0u) {
+    // LEAN (the trace_kernel_lean family): the scene is of the plain kind the host proves at its creation (pvt_scene_pack.h:
+    // prove_lean) -- unrotated boxes (in a world that is a box or a sphere) holding absorbers and isotropic luminophores, spectra on even grids, no coating, no
+    // extension table, every recorder entry plain.  What those facts decide is a constant here instead of a question
+    // asked of the tables in every trip: the code they make unreachable is left out, everything that remains is the
+    // generic variant's, operation for operation.
+    static_assert(!LEAN || (!MESH && !GRID && !ROUGH && TAB_LDS == 1 && SEENW == 1), "the lean variants: plain scenes only");
     extern __shared__ double smem_of_kernel[];
     // (In a called function the address of the kernel's dynamic LDS is looked up in a table in memory wherever it is used --
     // six scalar loads and waits per step of the tail function, measured in its ISA; the kernel hands it over instead.)
@@ -1127,6 +1142,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // A wave alone waits out every scalar-cache round trip too: what the loop asks of the kernel's arguments time and again
     // is held in registers by the tail function (the kernels' own loop re-reads them where it needs them: a scalar load
     // costs it nothing, a register does).
+    // (interp_clamped; LEAN: kLeanSearched = no histogram, kLeanEven = moreover every spectrum constant or on a proven even grid)
+    constexpr int kAbsKind = LEAN == kLeanEven ? kInterpEven : LEAN ? kInterpNoHist : kInterpAny;
+    constexpr int kCdfKind = LEAN == kLeanEven ? kInterpByGuide : LEAN ? kInterpNoHist : kInterpAny;
     auto held = [](int v) __attribute__((always_inline)) -> int {
         if constexpr (TAIL) asm volatile("" : "+s"(v));
         return v;
@@ -1163,6 +1181,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
+        if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP) return false;
+            if (bit == UF_BY_NODE) return true;
+        }
         unsigned int f = uflags;
         asm volatile("" : "+s"(f));
         return ((f >> bit) & 1u) != 0u;
@@ -1222,8 +1244,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
 
     // a node's flag word, read by the lane (see ND_BITS)
     auto node_bits = [&](int node) -> unsigned long long { return pvt_d2u(T.dv(node * ND + ND_BITS)); };
-    auto node_ident = [](unsigned long long bits) -> bool { return (bits & 1ull) != 0; };
-    auto node_geom = [](unsigned long long bits) -> int { return (int)(((unsigned int)bits >> 8) & 0xffu); };
+    auto node_ident = [](unsigned long long bits) -> bool { return LEAN || (bits & 1ull) != 0; };
+    // (lean: boxes, and a root that may be a sphere -- whatever is not a sphere is a box)
+    auto node_geom = [](unsigned long long bits) -> int {
+        const int g = (int)(((unsigned int)bits >> 8) & 0xffu);
+        return LEAN ? (g == PVT_GEOM_SPHERE ? (int)PVT_GEOM_SPHERE : (int)PVT_GEOM_BOX) : g;
+    };
     auto node_rot = [&](unsigned long long bits) -> int { return L.rot_d + (int)(unsigned int)(bits >> 32) * RT; };
 
     // Forward crossings (t > kEps) of one analytic shape by the ray (o, d) in the shape's own frame, each handed to
@@ -2048,8 +2074,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const double tx = T.du(hn + ND_T), ty = T.du(hn + ND_T + 1), tz = T.du(hn + ND_T + 2);
                     const double gpar[3] = {T.du(hn + ND_PARAMS), T.du(hn + ND_PARAMS + 1), T.du(hn + ND_PARAMS + 2)};
                     const unsigned long long hbits = pvt_d2u(T.du(hn + ND_BITS));
-                    const bool ident = (hbits & 1ull) != 0;   // wave-uniform
-                    const int rc = (int)(unsigned int)(hbits >> 32);   // rotation class
+                    const bool ident = node_ident(hbits);   // wave-uniform
+                    const int rc = LEAN ? 0 : (int)(unsigned int)(hbits >> 32);   // rotation class (lean: the identity is the only one)
                     V3 o;
                     if (ident) {
                         o.x = pos.x + tx; o.y = pos.y + ty; o.z = pos.z + tz;
@@ -2073,7 +2099,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         rot = rc;
                         inv_ok = false;
                     }
-                const int gt = (int)(((unsigned int)hbits >> 8) & 0xffu);
+                const int gt = node_geom(hbits);
                 // Hits are folded as they are found, in the reference's (node, k)
                 // order, so no per-ray hit list exists; the tie-breaks equal the
                 // reference's argmin scans over its hit arrays (:684-714).
@@ -2463,7 +2489,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             if (hit != k_root && !known) {
                 for (int k = 0; k < ccount; k++) {
                     const int ci = L.comp_i + (crec + k) * CI, cd = L.comp_d + (crec + k) * CD;
-                    alpha += interp_clamped<TAB_LDS>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N),
+                    alpha += interp_clamped<TAB_LDS, kAbsKind>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N),
                                                             T.iv(ci + CI_ABS_G), T.dv(cd + CD_ABS_SCALE), T.iv(ci + CI_ABS_HIST),
                                                             T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
                     if (k == 0) pre0 = alpha;
@@ -2517,7 +2543,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if (depth < t0) {  // absorbed (:762-832)
                     const double target = rng_uniform(rng) * alpha;
                     comp = cbase;
-                    if (ccount <= 2) {
+                    if (LEAN || ccount <= 2) {   // (lean: at most two, proven)
                         // (the reference walks the cumulative coefficients; with two components the first
                         // partial sum decides, and the last component takes what is left, :768-781)
                         comp = (ccount == 2 && !(target <= pre0)) ? cbase + 1 : cbase;
@@ -2564,7 +2590,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             const int ctype = T.iv(ci + CI_TYPE);
             if (mine) {
                 bool radiative = false;
-                if (ctype == PVT_COMP_SCATTERER || ctype == PVT_COMP_LUMINOPHORE)
+                // (lean: absorbers and luminophores only, isotropic, no table)
+                if ((!LEAN && ctype == PVT_COMP_SCATTERER) || ctype == PVT_COMP_LUMINOPHORE)
                     radiative = rng_uniform(rng) < T.dv(cd + CD_QY);
                 double tau = 0.0;
                 if (radiative) {
@@ -2578,17 +2605,17 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     // a tabulated phase function: CD_PHASE is where its record starts, with the spectra.  (A
                     // wave-uniform "the scene has tables" flag in front of the lane test put a vector register of the
                     // 256-recorder tally variants in scratch; without it the headline variant keeps its registers.)
-                    const bool tabled = pt == PVT_PHASE_TABLE;
+                    const bool tabled = !LEAN && pt == PVT_PHASE_TABLE;
                     const double* ptab = (TAB_LDS == 1 ? T.ld : T.hd) + (tabled ? (int)pp : 0);
                     double u1 = 0.0, u3 = 0.0;
-                    if (pt == PVT_PHASE_HG && pvt_fabs(pp) >= kEps) {
+                    if (!LEAN && pt == PVT_PHASE_HG && pvt_fabs(pp) >= kEps) {
                         double g1 = rng_uniform(rng);
                         double sg = 2.0 * g1 - 1.0;
                         double q = (1.0 - pp * pp) / (1.0 + pp * sg);
                         em_c = 1.0 / (2.0 * pp) * (1.0 + pp * pp - q * q);
                         em_turn = rng_uniform(rng);
                         em_s = sqrt1m2_normal(em_c);
-                    } else if (pt == PVT_PHASE_CONE) {
+                    } else if (!LEAN && pt == PVT_PHASE_CONE) {
                         double g1 = rng_uniform(rng), g2 = rng_uniform(rng);
                         em_s = pvt_sqrt(g1) * pvt_sin(pp);
                         em_turn = g2;
@@ -2613,7 +2640,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                     em = true;
                     source = cu;
-                    if (ctype == PVT_COMP_LUMINOPHORE) {
+                    if (LEAN || ctype == PVT_COMP_LUMINOPHORE) {
                         const int ex = T.iv(ci + CI_EMS_X), ec = T.iv(ci + CI_EMS_CDF), en = T.iv(ci + CI_EMS_N);
                         const int eh = T.iv(ci + CI_EMS_HIST);
                         const double ew = T.dv(cd + CD_EMS_W);
@@ -2627,11 +2654,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                                 double e_ev = div_normal(1240.0, e_nm) + 1.5 * kb_ev * 300.0;
                                 e_nm = div_normal(1240.0, e_ev);
                             }
-                            p1 = interp_clamped<TAB_LDS>(T, e_nm, ex, ec, en, T.iv(ci + CI_EMS_GX), T.dv(cd + CD_EMS_SCALE_X),
+                            p1 = interp_clamped<TAB_LDS, kAbsKind>(T, e_nm, ex, ec, en, T.iv(ci + CI_EMS_GX), T.dv(cd + CD_EMS_SCALE_X),
                                                                               eh, T.dv(cd + CD_EMS_RCP_X), ew);
                         }
                         double gamma = p1 + (1.0 - p1) * rng_uniform(rng);
-                        wl = interp_clamped<TAB_LDS>(T, gamma, ec, ex, en, T.iv(ci + CI_EMS_GC), T.dv(cd + CD_EMS_SCALE_C), eh,
+                        wl = interp_clamped<TAB_LDS, kCdfKind>(T, gamma, ec, ex, en, T.iv(ci + CI_EMS_GC), T.dv(cd + CD_EMS_SCALE_C), eh,
                                                                     T.dv(cd + CD_EMS_RCP_C), __builtin_nan(""), eh ? __builtin_nan("") : ew);
                         tau = T.dv(cd + CD_TAU_RAD);
                         ev_kind = PVT_EV_EMIT;
@@ -2640,7 +2667,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                 } else {
                     tau = T.dv(cd + CD_TAU_NR);
-                    if (ctype == PVT_COMP_REACTOR) { ev_kind = PVT_EV_REACT; t_sel = PVT_REC_REACTED; }
+                    if (!LEAN && ctype == PVT_COMP_REACTOR) { ev_kind = PVT_EV_REACT; t_sel = PVT_REC_REACTED; }
                     else { ev_kind = PVT_EV_NONRADIATIVE; t_sel = PVT_REC_LOST; }
                     t_node = container;
                     terminal = true;
@@ -2998,7 +3025,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const int r = entry & (kRecPlain - 1);
                     const int ri = L.rec_i + r * RI;
                     bool match = true;
-                    const bool plain = (entry & kRecPlain) != 0;   // nothing to check (see kRecPlain)
+                    const bool plain = LEAN || (entry & kRecPlain) != 0;   // nothing to check (see kRecPlain; lean: every entry)
                     const int smode = plain ? 0 : T.iv(ri + RI_SRC_MODE);  // source filter (extension)
                     if (smode != 0) {
                         if (smode == 1) match = source < 0;
@@ -3114,7 +3141,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // propagation would otherwise put back into the callee -- table lookups and all)
                 unsigned int lds_at = (unsigned int)(unsigned long long)(__attribute__((address_space(3))) double*)smem_of_kernel;
                 asm volatile("" : "+s"(lds_at));
-                tail_run<RECORD, TAB_LDS, SEENW, MESH, GRID, ROUGH>((const KArgs*)ak, tail_n, lds_at);
+                tail_run<RECORD, TAB_LDS, SEENW, MESH, GRID, ROUGH, LEAN>((const KArgs*)ak, tail_n, lds_at);
             }
         }
         leave_workgroup<TAB_LDS>((const KArgs*)ak);
@@ -3125,7 +3152,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
 // The last wave of a draining workgroup finishes its photons here (see the drain in trace_body): the step loop alone, as a
 // function -- the kernels' own loop keeps its registers whatever this one needs, and what is specific to a wave that runs
 // alone on its SIMD (every step is latency, nothing overlaps) can be done here without a price on the bulk.
-template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH>
+template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH, int LEAN>
 __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int total, unsigned int lds) {
     // The kernel's arguments, read where the kernel itself reads them.  The pointer arrives in vector registers: it is made
     // a scalar again (readfirstlane) and a pointer into the constant address space, so that the fields come through the
@@ -3134,7 +3161,7 @@ __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int
     const unsigned long long bits = (unsigned long long)kernel_args;
     const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)bits), hi = __builtin_amdgcn_readfirstlane((unsigned int)(bits >> 32));
     const __attribute__((address_space(4))) KArgs* ak = (const __attribute__((address_space(4))) KArgs*)(((unsigned long long)hi << 32) | lo);
-    trace_body<RECORD, TAB_LDS, SEENW, false, MESH, GRID, true, ROUGH>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
+    trace_body<RECORD, TAB_LDS, SEENW, false, MESH, GRID, true, ROUGH, LEAN>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
                                                                 __builtin_amdgcn_readfirstlane(lds));
 }
 
@@ -3173,6 +3200,14 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 template <bool RECORD, int SEENW, bool EMIT>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_rough_grid(KArgs A) {
     trace_body<RECORD, 1, SEENW, EMIT, false, true, false, true>(A);
+}
+// The lean family (trace_body's LEAN): scenes the host has proven plain -- see prove_lean.  Tables in LDS, at most 64
+// recorders, no mesh, no node grid, no rough / field / map extension.
+// EVEN: moreover every spectrum is a constant or lies on a proven even grid (the headline's kind); without it the tables
+// are searched as in the generic variants, step tables aside.
+template <bool RECORD, bool EMIT, bool EVEN>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_lean_w4(KArgs A) {
+    trace_body<RECORD, 1, 1, EMIT, false, false, false, false, EVEN ? kLeanEven : kLeanSearched>(A);
 }
 
 }  // namespace

@@ -434,6 +434,10 @@ def declare_signatures(lib, names):
              C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_launch_info": (
             [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+        "pvt_scene_variant": ([vp], C.c_int),
+        "pvt_scene_lean_check": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                  C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
+                                  C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_counters": ([vp, C.POINTER(C.c_uint64), C.c_int], C.c_int),
         "pvt_scene_clock": ([vp, C.POINTER(C.c_uint64)], C.c_int),
         "pvt_scene_launch_span": ([vp, vp, C.POINTER(C.c_uint64)], C.c_int),
@@ -457,8 +461,9 @@ ABI_SYMBOLS = (
     "pvt_scene_carry_pending", "pvt_last_multi_reduce", "pvt_node_grid_plan", "pvt_scene_carry_discard", "pvt_scene_trim",
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
-    "pvt_scene_create_maps", "pvt_scene_map_slots",
+    "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
 )
+VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 
 _lib = None
 ABI_VERSION = 13  # include/pvtrace_hip.h PVT_ABI_VERSION
@@ -571,6 +576,26 @@ def mesh_bvh_check(compiled, node):
     check(lib.pvt_mesh_bvh_check(C.byref(st), int(node), *(C.byref(v) for v in out)), "pvt_mesh_bvh_check")
     del keep
     return tuple(int(v.value) for v in out)
+
+
+def lean_check(compiled):
+    """True when the library proves the scene plain from its packed tables (host only, no GPU needed;
+    include/pvtrace_hip.h: pvt_scene_lean_check): its launches may run the lean kernel family."""
+    return lean_kind(compiled) != 0
+
+
+def lean_kind(compiled):
+    """pvt_scene_lean_check's own answer: 0 = not plain, 1 = plain with a spectrum on a grid that is even only up to
+    rounding (the family's kernels that search the tables), 2 = plain with every spectrum a constant or even bit for bit."""
+    lib = load_library()
+    st, keep = scene_tables_struct(compiled)
+    others = [f(compiled) for f in (index_tables_struct, phase_tables_struct, surface_tables_struct, field_tables_struct,
+                                    map_tables_struct)]
+    lean = C.c_int32(0)
+    check(lib.pvt_scene_lean_check(C.byref(st), *(None if s is None else C.byref(s) for s, _ in others), C.byref(lean)),
+          "pvt_scene_lean_check")
+    del keep, others
+    return int(lean.value)
 
 
 def node_grid_plan(compiled):
@@ -703,7 +728,10 @@ class DeviceScene:
         g, b, l = C.c_int32(), C.c_int32(), C.c_int32()
         check(self.lib.pvt_scene_launch_info(self.handle, C.byref(g), C.byref(b), C.byref(l)),
               "pvt_scene_launch_info")
-        return {"grid": g.value, "block": b.value, "lds_bytes": l.value}
+        variant = int(self.lib.pvt_scene_variant(self.handle))
+        if variant < 0:
+            check(variant, "pvt_scene_variant")
+        return {"grid": g.value, "block": b.value, "lds_bytes": l.value, "variant": VARIANT_NAMES[variant]}
 
     # -- device buffers (torch tensors) ----------------------------------
     def new_tallies(self, sets=1):
