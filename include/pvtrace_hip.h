@@ -327,6 +327,49 @@ typedef struct PvtMapTables {
     int64_t map_slots;              /* slots of all maps, `outside` slots included */
 } PvtMapTables;
 
+/* ---- ray capture (extension within v13, passed to pvt_scene_create_capture) -----------------------------------------
+ * The rays behind a recorder's `rays` count: recorder r with rec_capture_capacity[r] > 0 keeps one ROW for each ray's
+ * first match of that recorder -- the very event that adds to rec_distinct, the moment sums and the histograms -- up to
+ * that many rows; rec_capture_start[r] is its first row in the launch's row buffer (the captures packed one after the
+ * other in recorder order, capture_rows in all, at most PVT_MAX_CAPTURE_ROWS = 2^24: 1.5 GiB of rows per tally set).
+ * A row is a fixed-stride record of PVT_CAPTURE_ROW_WORDS = 12 uint64 words (96 bytes, little endian), written whole by
+ * the lane that follows the photon:
+ *   word 0     the global ray index, ray_offset + i (int64): the ray's RNG stream is seed + index
+ *   words 1-3  position, 4-6 direction, 7 wavelength, 8 path (travelled), 9 clock (duration): bit for bit the columns
+ *              of the event's row in the event log
+ *   word 10    source (int32, low half: the photon's current source id as the recorder `source` filter sees it, -1 = a
+ *              light) | recorder id (high half)
+ *   word 11    0
+ * Where the rows and cursors live: caller-owned DEVICE memory handed over per launch (PvtCaptures).  Tally set j of a
+ * launch owns rows [j capture_rows, (j + 1) capture_rows) and cursors [j n_recorders, (j + 1) n_recorders); cursors[r]
+ * (int64, one per recorder; those of recorders without capture stay untouched) counts the first matches of recorder r
+ * -- it equals what the launches added to rec_distinct[r].  The kernel never resets a cursor: the caller zeroes it, and
+ * a photon carried into the next launch (PVT_FLAG_CARRY_OUT) appends to the same capture when that launch is given the
+ * same buffers.  Rows are reserved per wave (one 64-bit atomic per wave, recorder and tally trip), so their order in
+ * the buffer is unspecified.  The contract (the Python CapturedRays and engine.tally.capture_histories state the same):
+ *  1. While cursors[r] <= capacity the row set is exact: sorted by index it does not depend on launch geometry,
+ *     carrying, tally-set grouping or the device list.
+ *  2. Beyond the capacity later arrivals are dropped (the cursor still counts them): min(cursor, capacity) rows are
+ *     written, every one a correct row, indices unique.
+ *  3. Which rows survive an overflow is unspecified.
+ * Capture launches run the PVT_VARIANT_ROUGH family.  A NULL struct, n_recorders 0 or capture_rows 0 is exactly
+ * pvt_scene_create_maps. */
+#define PVT_MAX_CAPTURE_ROWS (1LL << 24)
+#define PVT_CAPTURE_ROW_WORDS 12
+typedef struct PvtCaptureTables {
+    int32_t n_recorders;                  /* 0 = none (as a NULL struct), else the scene's n_recorders */
+    const int64_t* rec_capture_capacity;  /* (n_recorders) rows the recorder may keep, 0 = not captured */
+    const int64_t* rec_capture_start;     /* (n_recorders) its first row: the running sum of the capacities */
+    int64_t capture_rows;                 /* sum of the capacities */
+} PvtCaptureTables;
+
+/* capture buffers of one launch (DEVICE pointers): `rows` holds sets x capture_rows x PVT_CAPTURE_ROW_WORDS uint64,
+ * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle) */
+typedef struct PvtCaptures {
+    uint64_t* rows;
+    int64_t* cursors;
+} PvtCaptures;
+
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
@@ -483,6 +526,13 @@ int pvt_scene_create_maps(const PvtSceneTables* tables, const PvtIndexTables* in
 /* Slots of the scene's volume maps (PvtMapTables.map_slots; 0 without maps): PvtTallies.rec_bins of a launch on the
  * scene holds total_bins + this many elements (per tally set: tally_stride_i64 is at least that). */
 int64_t pvt_scene_map_slots(const PvtScene* scene);
+/* The same with captured recorders (NULL, n_recorders 0 or capture_rows 0 = none: then exactly pvt_scene_create_maps). */
+int pvt_scene_create_capture(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                             const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                             const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
+                             const PvtCaptureTables* capture_tables, int device, PvtScene** out);
+/* Rows of the scene's captures per tally set (PvtCaptureTables.capture_rows; 0 without captures). */
+int64_t pvt_scene_capture_rows(const PvtScene* scene);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);
@@ -504,6 +554,13 @@ int pvt_trace_device(PvtScene* scene, const PvtRays* rays, const PvtTraceParams*
  * `records` may be NULL when record_every == 0. */
 int pvt_trace_device_records(PvtScene* scene, const PvtRays* rays, const PvtTraceParams* params,
                              const PvtTallies* tallies, const PvtEventRecords* records, void* stream);
+
+/* pvt_trace_device_records with the capture buffers of a scene made by pvt_scene_create_capture (`captures` NULL, or a
+ * scene without captures: exactly pvt_trace_device_records -- the launch keeps no rows).  The other trace entries keep
+ * no rows either; the host-buffer entries know no captures. */
+int pvt_trace_device_capture(PvtScene* scene, const PvtRays* rays, const PvtTraceParams* params,
+                             const PvtTallies* tallies, const PvtEventRecords* records, const PvtCaptures* captures,
+                             void* stream);
 
 /* 1 when photons parked by the last launch on `stream` (PVT_FLAG_CARRY_OUT) wait to be resumed, else 0. */
 int pvt_scene_carry_pending(PvtScene* scene, void* stream);

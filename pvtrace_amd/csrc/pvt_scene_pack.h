@@ -349,6 +349,10 @@ struct PackedScene {
     // the maps add behind the recorders' bins
     std::vector<double> md;
     long long map_slots = 0;
+    // ray capture (PvtCaptureTables): per recorder the rows it may keep (0: not captured) and its first row, read from
+    // global memory alone (empty: no recorder is captured); capture_rows: the rows of all captures of one tally set
+    std::vector<long long> cd;
+    long long capture_rows = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     bool lean_ok = false;   // see prove_lean: the scene may run the trace_kernel_lean family ...
@@ -362,7 +366,7 @@ struct PackedScene {
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
 int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-                    const PvtFieldTables* fr, const PvtMapTables* mp) {
+                    const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -577,6 +581,21 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
                 if (slots > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
             }
         if (mp->map_slots != slots) return fail(PVT_ERR_INVALID, "map tables: map_slots must be the sum of the maps' slots");
+    }
+    // ray capture (PvtCaptureTables, pvt_scene_create_capture): how many rows each recorder keeps and where
+    if (cp && cp->n_recorders != 0 && cp->capture_rows != 0) {
+        if (cp->n_recorders != R) return fail(PVT_ERR_INVALID, "capture tables: need one capacity per recorder");
+        if (!cp->rec_capture_capacity || !cp->rec_capture_start) return fail(PVT_ERR_INVALID, "capture tables: capture arrays missing");
+        long long rows = 0;
+        for (int r = 0; r < R; r++) {
+            const long long cap = cp->rec_capture_capacity[r];
+            if (cap < 0) return fail(PVT_ERR_INVALID, "capture tables: a capacity must be >= 0");
+            if (cap > PVT_MAX_CAPTURE_ROWS) return fail(PVT_ERR_INVALID, "capture tables: more than 2^24 capture rows");
+            if (cp->rec_capture_start[r] != rows) return fail(PVT_ERR_INVALID, "capture tables: capture starts must pack the captures one after the other");
+            rows += cap;
+            if (rows > PVT_MAX_CAPTURE_ROWS) return fail(PVT_ERR_INVALID, "capture tables: more than 2^24 capture rows");
+        }
+        if (cp->capture_rows != rows) return fail(PVT_ERR_INVALID, "capture tables: capture_rows must be the sum of the capacities");
     }
     for (int n = 0; n < N; n++) {
         if (bad_run(t->comp_start[n], t->comp_count[n], C)) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
@@ -1161,7 +1180,7 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     // a searched table (CI_*_X, n points, its even_w in `w`): 2 = a constant or even bit for bit, 1 = even up to rounding, 0
     auto grid_kind = [&](int at, int n, double w) { return (n == 1 || w == w) ? 2 : (nearly_even(at, n) ? 1 : 0); };
     bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && p->fd.empty() &&
-              p->md.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
+              p->md.empty() && p->cd.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
     for (int n = 0; n < N && ok; n++) {
         unsigned long long bits;
         std::memcpy(&bits, &gd[(size_t)n * ND + ND_BITS], 8);
@@ -1280,12 +1299,24 @@ void pack_maps(const PvtSceneTables* t, const PvtMapTables* mp, PackedScene* p) 
     p->map_slots = mp->map_slots;
 }
 
+// The capture table p->cd (validated tables; left empty when no recorder is captured): capacity and first row per recorder.
+void pack_captures(const PvtSceneTables* t, const PvtCaptureTables* cp, PackedScene* p) {
+    p->cd.clear();
+    p->capture_rows = 0;
+    if (!cp || cp->n_recorders == 0 || cp->capture_rows == 0) return;
+    for (int r = 0; r < t->n_recorders; r++) {
+        p->cd.push_back(cp->rec_capture_capacity[r]);
+        p->cd.push_back(cp->rec_capture_start[r]);
+    }
+    p->capture_rows = cp->capture_rows;
+}
+
 // The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the
 // phase-function tables (ph, NULL = none), the nodes' surface roughness (rs, NULL = none) and the concentration fields
-// (fr, NULL = none) and the volume maps (mp, NULL = none) -> *p.  No HIP call.
+// (fr, NULL = none), the volume maps (mp, NULL = none) and the ray captures (cp, NULL = none) -> *p.  No HIP call.
 int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-               const PvtFieldTables* fr, const PvtMapTables* mp, PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs, fr, mp);
+               const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp, PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs, fr, mp, cp);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
@@ -1312,6 +1343,7 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     if (rc != PVT_OK) return rc;
     pack_fields(t, fr, p);
     pack_maps(t, mp, p);
+    pack_captures(t, cp, p);
     prove_shortcuts(t, p);
     prove_lean(t, p);
     return PVT_OK;

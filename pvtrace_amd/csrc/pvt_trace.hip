@@ -101,6 +101,8 @@ struct PvtScene {
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
     long long map_slots = 0;            // int64 slots the maps add behind the recorders' bins (pvt_scene_map_slots)
+    long long* d_cd = nullptr;          // ray capture: capacity and first row per recorder (KArgs::cap_tab), null = none captured
+    long long capture_rows = 0;         // rows of all captures of one tally set (pvt_scene_capture_rows)
     double* d_gd = nullptr;
     int* d_gi = nullptr;
     double* d_ed = nullptr;
@@ -203,6 +205,7 @@ void pvt_scene_destroy(PvtScene* s) {
     if (s->d_gd) (void)hipFree(s->d_gd);
     if (s->d_fd) (void)hipFree(s->d_fd);
     if (s->d_md) (void)hipFree(s->d_md);
+    if (s->d_cd) (void)hipFree(s->d_cd);
     if (s->d_gi) (void)hipFree(s->d_gi);
     if (s->d_ed) (void)hipFree(s->d_ed);
     if (s->d_ei) (void)hipFree(s->d_ei);
@@ -235,6 +238,8 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.rough_d = s->rough_d;
     a.fd = s->d_fd;
     a.md = s->d_md;
+    a.cap_tab = s->d_cd;
+    a.cap_total = s->capture_rows;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -249,8 +254,8 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
 #ifndef PVT_DEV_VARIANTS
 #define PVT_DEV_VARIANTS 0   // developer builds: only the analytic, array-input, <=64-recorder variants (fast compile)
 #endif
-// Scenes with a rough node (KArgs::rough_d >= 0), a concentration field (KArgs::fd) or a volume map (KArgs::md) run the
-// trace_kernel_rough* families: the same choice of variant.
+// Scenes with a rough node (KArgs::rough_d >= 0), a concentration field (KArgs::fd), a volume map (KArgs::md) or a captured
+// recorder (KArgs::cap_tab) run the trace_kernel_rough* families: the same choice of variant.
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
 #if PVT_DEV_VARIANTS
@@ -280,7 +285,7 @@ hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st,
 
 // Which family a launch runs (PVT_VARIANT_*): the same questions, in the same order, as launch_variant below asks.
 int variant_of(const PvtScene* s, bool tab_lds) {
-    if (s->rough_d >= 0 || s->d_fd || s->d_md) return PVT_VARIANT_ROUGH;
+    if (s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd) return PVT_VARIANT_ROUGH;
     if (s->d_bvh) return PVT_VARIANT_MESH;
     if (tab_lds && s->lay.grid_d >= 0) return PVT_VARIANT_GRID;
     if (tab_lds && s->lean_ok && s->n_rec <= 64) return PVT_VARIANT_LEAN;
@@ -308,7 +313,7 @@ hipError_t launch_lean_variant(bool even, bool emit, int grid, size_t lds, hipSt
 
 template <bool RECORD, int TAB_LDS, int SEENW>
 hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-    if (a.rough_d >= 0 || a.fd != nullptr || a.md != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
+    if (a.rough_d >= 0 || a.fd != nullptr || a.md != nullptr || a.cap_tab != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
     const bool mesh = a.bvh != nullptr;
     if constexpr (TAB_LDS == 1 && (!PVT_DEV_VARIANTS || SEENW == 1) && PVT_DEV_VARIANTS != 2) {
         if (a.lay.grid_d >= 0 && !mesh && (!PVT_DEV_VARIANTS || !emit)) {   // many nodes: per-lane walk of the node grid
@@ -414,7 +419,7 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     size_t lds = acc_bytes + tq_bytes + (lp.tab_lds ? tab_bytes : lp.small_lds ? small_bytes : 0);
     lp.bins_in_lds = (lds + bins_bytes <= budget) ? 1 : 0;
     if (lp.bins_in_lds) lds += bins_bytes;
-    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0);
+    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->d_cd ? 1 : 0);   // (capture: the global ray index)
     const size_t xbytes = (size_t)kXSlots * xw * 8;
     // (mesh scenes do without: measured, repacking a draining workgroup buys their launches nothing, and the 9 KB hold
     // another level of the trees' top)
@@ -427,7 +432,7 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
 }
 
 int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
-                 unsigned long long* log_rows, int* log_counts, hipStream_t st) {
+                 unsigned long long* log_rows, int* log_counts, hipStream_t st, const PvtCaptures* cap = nullptr) {
     const int slot = slot_of_stream(s, st);
     if (slot < 0)
         return fail(PVT_ERR_INVALID, "more than 64 HIP streams are tracing this scene; create one scene per group of streams");
@@ -461,6 +466,11 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     a.rec_crossings = reinterpret_cast<long long*>(tl->rec_crossings);
     a.rec_sums = tl->rec_sums;
     a.rec_bins = reinterpret_cast<long long*>(tl->rec_bins);
+    if (cap && s->d_cd) {   // (without them the launch keeps no rows; a scene without captures ignores them)
+        if (!cap->rows || !cap->cursors) return fail(PVT_ERR_INVALID, "capture buffers missing");
+        a.cap_rows = reinterpret_cast<unsigned long long*>(cap->rows);
+        a.cap_cursor = reinterpret_cast<unsigned long long*>(cap->cursors);
+    }
     const bool record = p->record_every > 0;
     // nobody looks at where a photon leaves the scene: the root's distance is only needed to ORDER crossings
     a.lazy_root = (!record && !s->exit_observed && !s->d_bvh) ? s->lazy_root : 0;
@@ -542,7 +552,7 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     if (carry_in || carry_out) {
         if (!s->carry_cap) s->carry_cap = (unsigned int)((long long)s->num_cu * 4 * kBlock);
         if (grid * kBlock > (long long)s->carry_cap) carry_out = false;   // an unusually wide launch finishes its own photons
-        const size_t bytes = (size_t)s->carry_cap * kCarryStride * 8;
+        const size_t bytes = (size_t)s->carry_cap * (s->d_cd ? kCarryStrideCap : kCarryStride) * 8;
         for (int q = 0; q < 2; q++)
             if (!carry.buf[q]) HIP_TRY(hipMalloc(&carry.buf[q], bytes));
         a.carry_cap = s->carry_cap;
@@ -689,6 +699,14 @@ int64_t pvt_scene_map_slots(const PvtScene* s) { return s ? (int64_t)s->map_slot
 int pvt_scene_create_maps(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                           const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp, int device,
                           PvtScene** out) {
+    return pvt_scene_create_capture(t, x, ph, rs, fr, mp, nullptr, device, out);
+}
+
+int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->capture_rows : 0; }
+
+int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
+                             const PvtCaptureTables* cp, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -696,7 +714,7 @@ int pvt_scene_create_maps(const PvtSceneTables* t, const PvtIndexTables* x, cons
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -782,6 +800,11 @@ int pvt_scene_create_maps(const PvtSceneTables* t, const PvtIndexTables* x, cons
         HIP_TRY(hipMemcpy(s->d_md, packed.md.data(), packed.md.size() * sizeof(double), hipMemcpyHostToDevice));
         s->map_slots = packed.map_slots;
     }
+    if (!packed.cd.empty()) {
+        HIP_TRY(hipMalloc(&s->d_cd, packed.cd.size() * sizeof(long long)));
+        HIP_TRY(hipMemcpy(s->d_cd, packed.cd.data(), packed.cd.size() * sizeof(long long), hipMemcpyHostToDevice));
+        s->capture_rows = packed.capture_rows;
+    }
     owner.p = nullptr;
     *out = s;
     return PVT_OK;
@@ -795,6 +818,16 @@ int pvt_trace_device_records(PvtScene* s, const PvtRays* rays, const PvtTracePar
         return fail(PVT_ERR_INVALID, "record_every > 0 needs event records");
     return trace_launch(s, rays, p, tl, rec ? reinterpret_cast<unsigned long long*>(rec->rows) : nullptr, rec ? rec->counts : nullptr,
                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int pvt_trace_device_capture(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
+                             const PvtEventRecords* rec, const PvtCaptures* cap, void* stream) {
+    int rc = check_trace_args(s, rays, p, tl);
+    if (rc != PVT_OK) return rc;
+    if (p->record_every > 0 && (!rec || !rec->rows || !rec->counts))
+        return fail(PVT_ERR_INVALID, "record_every > 0 needs event records");
+    return trace_launch(s, rays, p, tl, rec ? reinterpret_cast<unsigned long long*>(rec->rows) : nullptr, rec ? rec->counts : nullptr,
+                        reinterpret_cast<hipStream_t>(stream), cap);
 }
 
 int pvt_scene_carry_pending(PvtScene* s, void* stream) {
@@ -996,7 +1029,7 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, &packed);
     if (rc != PVT_OK) return rc;
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     return PVT_OK;

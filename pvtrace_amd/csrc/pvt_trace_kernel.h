@@ -223,10 +223,21 @@ struct KArgs {
     // map), the blocks (kMn*, kMr*); null = the scene has no map (UF_VMAP off).  The counts are the int64 slots behind the
     // recorders' bins: rec_bins[total_bins ...] of the lane's tally set
     const double* md;
+    // Ray capture (pvt_scene_create_capture): cap_tab[2 r] = the rows recorder r may keep (0: not captured) and
+    // cap_tab[2 r + 1] = its first row; null = no recorder of the scene is captured (UF_CAPTURE off).  cap_rows / cap_cursor:
+    // the launch's row buffer (kCapWords u64 words per row, cap_total rows per tally set) and its cursors (n_rec int64 per
+    // tally set, never reset by the kernel); null = this launch keeps no rows
+    const long long* cap_tab;
+    unsigned long long* cap_rows;
+    unsigned long long* cap_cursor;
+    long long cap_total;
 };
+constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): index, position, direction, wavelength, path, clock,
+                               // source | recorder << 32, 0
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
 constexpr int kCarryBase = 14;     // u64 words of a parked photon before its seen-mask
 constexpr int kCarryStride = 18;   // words per parked photon (room for the four-word mask of scenes with > 64 recorders)
+constexpr int kCarryStrideCap = 19;   // ... of a scene with a captured recorder: the photon's global ray index behind the mask
 
 // ------------------------------------------------------------------ RNG
 struct Rng {
@@ -944,6 +955,49 @@ __device__ __forceinline__ u32x4 pack_dd(double a, double b) {
     const unsigned long long ua = pvt_d2u(a), ub = pvt_d2u(b);
     return u32x4{(unsigned int)ua, (unsigned int)(ua >> 32), (unsigned int)ub, (unsigned int)(ub >> 32)};
 }
+// Ray capture (PvtCaptureTables / PvtCaptures; include/pvtrace_hip.h states the contract): the lanes of one tally trip whose
+// photon has just matched recorder `r` for the first time (`push`) append one row each to the recorder's capture.  Rows are
+// reserved per WAVE: the lanes are grouped by recorder, one lane of each group adds the group's size to the recorder's
+// cursor -- one 64-bit atomic per wave per recorder per trip, not one per lane on one address -- and every lane writes its
+// whole row at the rank its ballot gives it.  A row beyond the capacity is not written; the cursor counts it all the same.
+// `rows` / `cursor`: the row buffer and the cursors of the lane's tally set.  A FUNCTION, called only from the
+// trace_kernel_rough* variants, by every lane of the wave.
+__device__ __attribute__((noinline)) void capture_call(const long long* __restrict__ tab, unsigned long long* __restrict__ rows,
+                                                       unsigned long long* __restrict__ cursor, bool push, int r,
+                                                       unsigned long long index, double px, double py, double pz, double dx,
+                                                       double dy, double dz, double wl, double travelled, double duration,
+                                                       int source) {
+    long long cap = 0, start = 0;
+    if (push) { cap = tab[2 * r]; start = tab[2 * r + 1]; }
+    bool want = cap > 0;
+    for (;;) {
+        const unsigned long long todo = __ballot(want);
+        if (todo == 0ull) break;
+        const int leader = __builtin_ctzll(todo);
+        const int r0 = __builtin_amdgcn_readlane(r, leader);
+        const bool mine = want && r == r0;
+        const unsigned long long group = __ballot(mine);
+        const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(group >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)group, 0u));
+        unsigned long long base = 0ull;
+        if (mine && rank == 0u) base = atomicAdd(cursor + r0, (unsigned long long)__popcll(group));
+        const unsigned int lo = __builtin_amdgcn_readlane((unsigned int)base, leader);
+        const unsigned int hi = __builtin_amdgcn_readlane((unsigned int)(base >> 32), leader);
+        if (mine) {
+            const long long at = (long long)(((unsigned long long)hi << 32) | lo) + rank;
+            if (at < cap) {
+                u32x4* dst = reinterpret_cast<u32x4*>(rows + (start + at) * kCapWords);
+                dst[0] = u32x4{(unsigned int)index, (unsigned int)(index >> 32), (unsigned int)pvt_d2u(px), (unsigned int)(pvt_d2u(px) >> 32)};
+                dst[1] = pack_dd(py, pz);
+                dst[2] = pack_dd(dx, dy);
+                dst[3] = pack_dd(dz, wl);
+                dst[4] = pack_dd(travelled, duration);
+                dst[5] = u32x4{(unsigned int)source, (unsigned int)r, 0u, 0u};
+            }
+            want = false;
+        }
+    }
+}
+
 // (VIA_A: inside a called function -- the tail function -- the kernel-argument segment pointer is not to be had from the
 // intrinsic (measured: garbage in a callee, ROCm 7.0); the caller's `A` already IS that segment, handed down explicitly)
 template <bool RECORD, bool VIA_A = false>
@@ -1166,7 +1220,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1175,14 +1229,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (A.n_ctab > 0 ? 1u << UF_CTAB : 0u) | (A.n_rtab > 0 ? 1u << UF_DISP : 0u) |
         (ROUGH && A.rough_d >= 0 ? 1u << UF_ROUGH : 0u) |   // (only the rough variants read rough_d ...
         (ROUGH && A.fd != nullptr ? 1u << UF_FIELD : 0u) |  // ... and fd ...
-        (ROUGH && A.md != nullptr ? 1u << UF_VMAP : 0u);    // ... and md)
+        (ROUGH && A.md != nullptr ? 1u << UF_VMAP : 0u) |   // ... and md ...
+        (ROUGH && A.cap_tab != nullptr ? 1u << UF_CAPTURE : 0u);   // ... and cap_tab)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -1207,9 +1262,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // per-wave queue of first crossings awaiting their statistics: [4 (+3 with positions)][kTallyQ] doubles
     // + [kTallyQ] recorder ids
     constexpr int kXWords = 14 + SEENW + (RECORD ? 1 : 0);
+    // (scenes with a captured recorder: one more word per slot, the photon's global ray index; the rough variants alone)
+    const int x_words = ROUGH ? kXWords + (A.cap_tab != nullptr ? 1 : 0) : kXWords;
     const int tq_doubles = A.tq_pos ? 7 : 4;
-    double* const tq_d = reinterpret_cast<double*>(xbuf + kXWords * A.xslots) + (threadIdx.x >> 6) * (tq_doubles * kTallyQ);
-    int* const tq_r = reinterpret_cast<int*>(reinterpret_cast<double*>(xbuf + kXWords * A.xslots) + kWaves * tq_doubles * kTallyQ)
+    double* const tq_d = reinterpret_cast<double*>(xbuf + x_words * A.xslots) + (threadIdx.x >> 6) * (tq_doubles * kTallyQ);
+    int* const tq_r = reinterpret_cast<int*>(reinterpret_cast<double*>(xbuf + x_words * A.xslots) + kWaves * tq_doubles * kTallyQ)
                       + (threadIdx.x >> 6) * kTallyQ;
     int tq_n = 0;   // wave-uniform
     if constexpr (!TAIL) {   // (the tail function finds the workgroup's LDS as its caller left it)
@@ -1348,6 +1405,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     double wl = 0.0, travelled = 0.0, duration = 0.0;
     Rng rng{0, 0, 0, 0};
     int count = 0, source = -1, nev = 0;
+    unsigned long long gidx = 0ull;   // (rough variants, UF_CAPTURE) the photon's global ray index, ray_offset + i: travels with it
     unsigned int c_iters = 0u, c_steps = 0u, c_fused = 0u;   // this lane's share of the step counters (KArgs::counters)
     // (tail function) the absorption coefficients this lane's photon met last: container, wavelength bits, sum, first term
     // -- kept in LDS, in the exchange buffer the function was handed its photons through (free once they are read): four
@@ -1485,6 +1543,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 rec_slot = (int)(unsigned int)rn_;
                 nev = (int)(unsigned int)(rn_ >> 32);
             }
+            if constexpr (ROUGH) {
+                if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
+            }
         }
     }
     if constexpr (TAIL) ac_lds[0] = ~0ull;   // (nothing known yet; after the reads above, same wave: in order)
@@ -1528,7 +1589,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const unsigned int rank = rank_in(need);
                     if (!alive && rank < got) {
                         // photon-major records: one base address, every word at an immediate offset
-                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * kCarryStride;
+                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * (ROUGH && uf(UF_CAPTURE) ? kCarryStrideCap : kCarryStride);
                         pos = V3{pvt_u2d(src[0]), pvt_u2d(src[1]), pvt_u2d(src[2])};
                         dir = V3{pvt_u2d(src[3]), pvt_u2d(src[4]), pvt_u2d(src[5])};
                         wl = pvt_u2d(src[6]); travelled = pvt_u2d(src[7]); duration = pvt_u2d(src[8]);
@@ -1538,6 +1599,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         source = (int)(unsigned int)(cs_ >> 32);
 #pragma unroll
                         for (int w = 0; w < SEENW; w++) seen.w[w] = src[kCarryBase + w];
+                        if constexpr (ROUGH) {
+                            if (uf(UF_CAPTURE)) gidx = src[kCarryStride];
+                        }
                         nev = 0;
                         alive = true;
                     }
@@ -1639,6 +1703,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 count = 0;
                 source = -1;
                 nev = 0;
+                if constexpr (ROUGH) {
+                    if (uf(UF_CAPTURE)) gidx = A.ray_offset + (unsigned long long)i;
+                }
 #pragma unroll
                 for (int w = 0; w < SEENW; w++) seen.w[w] = 0ull;
                 alive = true;
@@ -1674,7 +1741,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     b = __builtin_amdgcn_readfirstlane(b);
                     const unsigned int at = b + rank_in(live_mask);
                     if (alive && at < ak->carry_cap) {
-                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * kCarryStride;
+                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * (ROUGH && uf(UF_CAPTURE) ? kCarryStrideCap : kCarryStride);
                         dst[0] = pvt_d2u(pos.x); dst[1] = pvt_d2u(pos.y); dst[2] = pvt_d2u(pos.z);
                         dst[3] = pvt_d2u(dir.x); dst[4] = pvt_d2u(dir.y); dst[5] = pvt_d2u(dir.z);
                         dst[6] = pvt_d2u(wl); dst[7] = pvt_d2u(travelled); dst[8] = pvt_d2u(duration);
@@ -1682,6 +1749,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         dst[13] = (unsigned long long)(unsigned int)count | ((unsigned long long)(unsigned int)source << 32);
 #pragma unroll
                         for (int w = 0; w < SEENW; w++) dst[kCarryBase + w] = seen.w[w];
+                        if constexpr (ROUGH) {
+                            if (uf(UF_CAPTURE)) dst[kCarryStride] = gidx;
+                        }
                     }
                     alive = false;   // (the wave leaves through the "nothing alive, no rays left" exit below)
                 }
@@ -1742,6 +1812,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         if constexpr (RECORD) {
                             xbuf[(14 + SEENW) * X + slot] = (unsigned long long)(unsigned int)rec_slot | ((unsigned long long)(unsigned int)nev << 32);
                         }
+                        if constexpr (ROUGH) {
+                            if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
+                        }
                     }
                     tail_n = live;   // (the call itself comes after the loop: nothing of the loop is live across it)
                     alive = false;
@@ -1760,6 +1833,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     for (int w = 0; w < SEENW; w++) xbuf[(14 + w) * X + slot] = seen.w[w];
                     if constexpr (RECORD) {
                         xbuf[(14 + SEENW) * X + slot] = (unsigned long long)(unsigned int)rec_slot | ((unsigned long long)(unsigned int)nev << 32);
+                    }
+                    if constexpr (ROUGH) {
+                        if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
                     }
                 }
                 __syncthreads();  // B
@@ -1788,6 +1864,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         const unsigned long long rn_ = xbuf[(14 + SEENW) * X + slot];
                         rec_slot = (int)(unsigned int)rn_;
                         nev = (int)(unsigned int)(rn_ >> 32);
+                    }
+                    if constexpr (ROUGH) {
+                        if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
                     }
                 }
                 // the set shrinks to its `keep` lowest members
@@ -3072,6 +3151,16 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         }
                     }
                     tq_n += __popcll(pm);
+                    if constexpr (ROUGH) {
+                        // ---- ray capture (PvtCaptureTables): the first matches of this trip, appended to their recorders' rows
+                        // with the values the event's log row holds
+                        if (uf(UF_CAPTURE)) {
+                            if (A.cap_rows != nullptr)
+                                capture_call(A.cap_tab, A.cap_rows + (long long)set * A.cap_total * kCapWords,
+                                             A.cap_cursor + (long long)set * A.n_rec, push, push_r, gidx, pos.x, pos.y, pos.z,
+                                             dir.x, dir.y, dir.z, wl, travelled, duration, source);
+                        }
+                    }
                 }
             }
         }

@@ -63,6 +63,13 @@ def _host_buffer_scene(compiled):
             "The scene has volume maps (a node with a VolumeMap), which the host-buffer trace_bundle entry (the "
             "reference's interface) cannot take: its tallies have no place for them; trace it with engine.simulate."
         )
+    if getattr(compiled, "has_captures", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has captured recorders (Recorder(..., capture=rows)), which the host-buffer trace_bundle entry (the "
+            "reference's interface) cannot take: it has no place for the rows; trace it with engine.simulate."
+        )
     if int(getattr(compiled, "n_ri_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 

@@ -18,7 +18,7 @@ import numpy as np
 
 from pvtrace_amd.engine import native
 from pvtrace_amd.engine.compiler import EMIT_METHODS, compile_scene
-from pvtrace_amd.engine.recorder import Heatmap, VolumeMapResult
+from pvtrace_amd.engine.recorder import MAX_CAPTURE_ROWS, CapturedRays, Heatmap, VolumeMapResult
 from pvtrace_amd.light import Event, Ray
 
 # moment accumulators kept for every recorder, in kernel order
@@ -155,8 +155,9 @@ class EngineResult:
     j*max_events + k)."""
 
     def __init__(self, compiled, data, sources, max_events, record_every, elapsed,
-                 kernel_ms=None):
+                 kernel_ms=None, captures=None):
         self.compiled = compiled
+        self._captures = {} if captures is None else captures
         self.data = data
         self.sources = sources
         self.max_events = max_events
@@ -199,6 +200,11 @@ class EngineResult:
         """{map name: VolumeMapResult} of the scene's `VolumeMap`s (`data["map_bins"]`: the maps' slots, which follow the
         recorders' bins in the device's tally buffer)."""
         return maps_from_slots(self.compiled, self.data.get("map_bins"))
+
+    @property
+    def captures(self):
+        """{recorder name: CapturedRays} of the recorders with ``capture=capacity``: the rays behind their `rays` count."""
+        return self._captures
 
     @property
     def packed(self):
@@ -279,6 +285,51 @@ def maps_from_slots(compiled, slots):
     for spec, lo in zip(compiled.map_specs, compiled.map_offset):
         out[spec.name] = VolumeMapResult(spec, slots[int(lo):int(lo) + spec.size])
     return out
+
+
+def download_captures(compiled, tallies, set_index=0, index_shift=0):
+    """The capture buffers of a tally set (`DeviceScene.new_tallies`: `cap_rows`, `cap_cursor`) -> {recorder name:
+    CapturedRays}.  Per captured recorder the min(cursor, capacity) rows that were written are sorted by ray index on the
+    GPU and only they are moved to the host.  `index_shift` is added to the indices (bundles of a stream that were traced
+    with the stream position folded into the seed instead of the ray offset)."""
+    if not getattr(compiled, "has_captures", False):
+        return {}
+    import torch
+
+    nrec = max(int(compiled.rec_node.shape[0]), 1)
+    cursors = tallies["cap_cursor"][set_index * nrec:(set_index + 1) * nrec].cpu().numpy()
+    out = {}
+    for r, spec in enumerate(compiled.recorder_specs):
+        capacity = int(compiled.rec_capture_capacity[r])
+        if capacity == 0:
+            continue
+        matched = int(cursors[r])
+        n = min(matched, capacity)
+        first = set_index * compiled.capture_rows + int(compiled.rec_capture_start[r])
+        block = tallies["cap_rows"][first:first + n]
+        if n > 1:
+            block = block.index_select(0, torch.argsort(block[:, 0]))
+        out[spec.name] = CapturedRays.from_rows(spec.name, capacity, matched, to_host(block.contiguous()), index_shift)
+    return out
+
+
+def merge_captures(parts):
+    """[{name: CapturedRays}] of consecutive shards / bundles / buffers -> one dict, rows concatenated and sorted."""
+    parts = [p for p in parts if p]
+    if not parts:
+        return {}
+    return {name: CapturedRays.merged([p[name] for p in parts]) for name in parts[0]}
+
+
+def warn_overflowed(captures):
+    """One warning per recorder whose capture overflowed."""
+    import warnings
+
+    for name, rays in captures.items():
+        if rays.dropped > 0:
+            warnings.warn(f"Recorder {name!r}: capture capacity {rays.capacity} exceeded; {rays.dropped} of {rays.matched} "
+                          f"matching rays were dropped (which ones is unspecified). Raise `capture` to keep them all.",
+                          stacklevel=3)
 
 
 GROUP_PHOTONS = 1_000_000   # photons one launch of simulate_stream traces in tally mode (bundles grouped)
@@ -423,7 +474,8 @@ def _scene_key(compiled, emitter, device):
 
     h = hashlib.blake2b(digest_size=16)
     h.update(repr(int(device)).encode())
-    for name in compiled.TABLE_FIELDS + (compiled.MAP_TABLE_FIELDS if compiled.has_maps else ()):
+    for name in (compiled.TABLE_FIELDS + (compiled.MAP_TABLE_FIELDS if compiled.has_maps else ())
+                 + (compiled.CAPTURE_TABLE_FIELDS if compiled.has_captures else ())):
         a = np.ascontiguousarray(getattr(compiled, name))
         h.update(a.dtype.str.encode()); h.update(repr(a.shape).encode()); h.update(a.data if a.size else b"")
     h.update(repr((int(compiled.root_id), int(compiled.total_bins))).encode())
@@ -533,13 +585,14 @@ class Session:
 
     def submit(self, num_rays, seed, maxsteps=1000, max_events=128, emit_method="kT", record_every=1,
                emit_seed=None, ray_offset=0, workgroups_per_cu=0, host_rays=None, tally_bundle=0,
-               packed_log=False):
+               packed_log=False, index_shift=0):
         """Enqueue one bundle on one of two HIP streams and return a handle for `collect`.
         Two bundles may be in flight: the next one is traced while the caller consumes the
         previous result.  `host_rays`: (positions, directions, wavelengths, sources) already emitted
         on the host (a shard of a bundle emitted once for several GPUs).  `tally_bundle` = m > 0
         (tally mode): the rays are consecutive bundles of m rays traced by ONE launch, each tallied on
-        its own (PvtTraceParams.tally_bundle); `collect_bundles` returns one result per bundle."""
+        its own (PvtTraceParams.tally_bundle); `collect_bundles` returns one result per bundle.  `index_shift`: added to
+        the ray indices of captured rows (a caller that folded a stream position into `seed` instead of `ray_offset`)."""
         import torch
 
         from pvtrace_amd.engine import emit as emit_mod
@@ -573,17 +626,20 @@ class Session:
                     streams = _SIDE_STREAMS.setdefault(device, [])
                     while len(streams) < 2:
                         streams.append(torch.cuda.Stream(device=device))
-                self._slots = [{"stream": st, "tallies": dscene.new_tallies()} for st in streams[:2]]
+                self._slots = [{"stream": st, "tallies": None} for st in streams[:2]]   # made at a slot's first launch
             slot = self._slots[self._submitted % 2]
             self._submitted += 1
             sets = -(-int(num_rays) // int(tally_bundle)) if tally_bundle else 1
-            if slot["tallies"].get("sets", 1) < sets:
+            if slot["tallies"] is None or slot["tallies"]["sets"] < sets:
+                slot["tallies"] = None   # (capture rows are large: free the old buffer before the new one is made)
                 slot["tallies"] = dscene.new_tallies(sets=sets)
             stream, tallies = slot["stream"], slot["tallies"]
             stream.wait_stream(torch.cuda.current_stream(device))   # ray upload, earlier downloads
             with torch.cuda.stream(stream):
                 tallies["_ints"].zero_()
                 tallies["_sums"].zero_()
+                if "cap_cursor" in tallies:
+                    tallies["cap_cursor"].zero_()
                 log = (dscene.new_event_log(num_rays, record_every, max_events)
                        if record_every > 0 else None)
                 start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -598,7 +654,8 @@ class Session:
                 stop.record(stream)
         return {"stream": stream, "tallies": tallies, "log": log, "events": (start, stop), "tic": tic, "launch_no": self._submitted,
                 "rays": rays, "sources": sources, "num_rays": num_rays, "record_every": record_every,
-                "max_events": max_events, "tally_bundle": int(tally_bundle), "packed_log": bool(packed_log)}
+                "max_events": max_events, "tally_bundle": int(tally_bundle), "packed_log": bool(packed_log),
+                "index_shift": int(index_shift)}
 
     def collect(self, pending, wall_clock=False):
         """Wait for a submitted bundle and bring its results to the host -> `EngineResult`.
@@ -620,9 +677,10 @@ class Session:
             with torch.cuda.stream(pending["stream"]):
                 data = download(self.compiled, pending["tallies"], pending["log"], pending["num_rays"],
                                 pending["record_every"], pending["max_events"], packed=pending.get("packed_log", False))
+                captures = download_captures(self.compiled, pending["tallies"], 0, pending.get("index_shift", 0))
         return EngineResult(self.compiled, data, pending["sources"], pending["max_events"],
                             pending["record_every"], wall if wall_clock else kernel_ms * 1e-3,
-                            kernel_ms=kernel_ms)
+                            kernel_ms=kernel_ms, captures=captures)
 
     def collect_bundles(self, pending):
         """Wait for a launch submitted with `tally_bundle` -> one `EngineResult` per bundle, in order
@@ -642,6 +700,7 @@ class Session:
             with torch.cuda.stream(pending["stream"]):
                 ints = t["_ints"][: sets * t["stride_i64"]].cpu().numpy().reshape(sets, t["stride_i64"])
                 sums = t["_sums"][: sets * t["stride_f64"]].cpu().numpy().reshape(sets, t["stride_f64"])
+                captured = [download_captures(c, t, j, pending.get("index_shift", 0)) for j in range(sets)]
         empty = {"counts": np.zeros(0, dtype=np.int32)}
         for name, dtype, width in native.EVENT_LOG_COLUMNS:
             col = np.zeros(0, dtype=dtype)
@@ -658,7 +717,8 @@ class Session:
                 data["map_bins"] = ints[j, 2 * pad + nbins: 2 * pad + nbins + c.map_slots]
             data["rec_sums"] = sums[j, : nrec * 8].reshape(nrec, 4, 2)
             results.append(EngineResult(c, data, sources[lo:hi], pending["max_events"], 0,
-                                        kernel_ms * 1e-3 * (hi - lo) / n, kernel_ms=kernel_ms * (hi - lo) / n))
+                                        kernel_ms * 1e-3 * (hi - lo) / n, kernel_ms=kernel_ms * (hi - lo) / n,
+                                        captures=captured[j]))
         return results
 
     def run(self, num_rays, seed, **kwargs):
@@ -720,12 +780,16 @@ def simulate(
             raise ValueError("give `device` or `devices`, not both")
         if packed_log:
             raise ValueError("packed_log is per device; use `device`")
-        return _simulate_on_devices(scene, num_rays, seed, list(devices), maxsteps, max_events, emit_method,
-                                    record_every, emission, emit_seed, ray_offset)
+        result = _simulate_on_devices(scene, num_rays, seed, list(devices), maxsteps, max_events, emit_method,
+                                      record_every, emission, emit_seed, ray_offset)
+        warn_overflowed(result.captures)
+        return result
     with Session(scene, device=device, emission=emission) as session:
-        return session.run(num_rays, seed, maxsteps=maxsteps, max_events=max_events,
-                           emit_method=emit_method, record_every=record_every,
-                           emit_seed=emit_seed, ray_offset=ray_offset, packed_log=packed_log)
+        result = session.run(num_rays, seed, maxsteps=maxsteps, max_events=max_events,
+                             emit_method=emit_method, record_every=record_every,
+                             emit_seed=emit_seed, ray_offset=ray_offset, packed_log=packed_log)
+    warn_overflowed(result.captures)
+    return result
 
 
 def merge_shards(results):
@@ -758,7 +822,8 @@ def merge_shards(results):
     sources = ChainedSources([r.sources for r in results])
     kernel_ms = [r.kernel_ms for r in results if r.kernel_ms is not None]
     return EngineResult(first.compiled, data, sources, first.max_events, first.record_every,
-                        max(r.elapsed for r in results), kernel_ms=max(kernel_ms) if kernel_ms else None)
+                        max(r.elapsed for r in results), kernel_ms=max(kernel_ms) if kernel_ms else None,
+                        captures=merge_captures([r.captures for r in results]))
 
 
 def _simulate_on_devices(scene, num_rays, seed, devices, maxsteps, max_events, emit_method, record_every,
@@ -856,16 +921,19 @@ def simulate_stream(scene, num_rays, bundle=50000, seed=None, **kwargs):
                                               [int(state["emit_seed"]) + traced + at for at in starts])
             host = tuple(np.concatenate([p[k] for p in parts]) for k in range(3)) + (emit_mod.ChainedSources([p[3] for p in parts]),)
             return session, session.submit(n, int(seed) + traced, ray_offset=base_offset, workgroups_per_cu=3,
-                                           host_rays=host, **group, **kwargs), n
+                                           host_rays=host, index_shift=traced, **group, **kwargs), n
         bundle_emit_seed = None if state["emit_seed"] is None else int(state["emit_seed"]) + traced
         return session, session.submit(n, int(seed) + traced, emit_seed=bundle_emit_seed, ray_offset=base_offset,
-                                       workgroups_per_cu=3, **kwargs), n
+                                       workgroups_per_cu=3, index_shift=traced, **kwargs), n
 
     in_flight = collections.deque()
     submitted, index, traced = 0, 0, 0
     try:
         for d in (devices if devices is not None else [device]):   # inside the try: a failing k-th Session must not
             sessions.append(Session(scene, device=d, emission=emission))   # leak the k-1 resident scenes before it
+        capture_rows = int(getattr(sessions[0].compiled, "capture_rows", 0))
+        if capture_rows:   # a grouped launch holds one set of capture rows per bundle: MAX_CAPTURE_ROWS (1.5 GiB) per launch
+            per_group = max(1, min(per_group, MAX_CAPTURE_ROWS // capture_rows))
         if state["emit_seed"] is None:
             # one draw from the global generator seeds the whole stream's emission (reproducible under
             # np.random.seed): device emission needs a seed anyway, and on the host the bundles of a group can then

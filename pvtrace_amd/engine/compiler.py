@@ -21,6 +21,7 @@ import numpy as np
 from pvtrace_amd.engine.recorder import (
     EVENTS,
     MAP_EVENTS,
+    MAX_CAPTURE_ROWS,
     MAX_MAP_SLOTS,
     PROPERTIES,
     SOURCE_COMPONENT,
@@ -594,6 +595,32 @@ class CompiledScene:
         self.hist_offset = np.array(hist["off"], dtype=_I32)
         self.total_bins = int(offset)
 
+        # ray capture: rows each recorder may keep (0: not captured) and its first row, the captures packed one after the
+        # other in recorder order (`capture_rows` rows per tally set)
+        self.rec_capture_capacity = np.zeros(n, dtype=np.int64)
+        self.rec_capture_start = np.zeros(n, dtype=np.int64)
+        rows = 0
+        for r, (_, recorder) in enumerate(found):
+            capacity = getattr(recorder, "capture", None)
+            self.rec_capture_start[r] = rows
+            if capacity is None:
+                continue
+            if not isinstance(capacity, numbers.Integral) or isinstance(capacity, bool) or capacity <= 0:
+                raise UnsupportedSceneError(
+                    f"Recorder {recorder.name!r}: capture must be a positive integer number of rows, got {capacity!r}.")
+            capacity = int(capacity)   # (a numpy integer assigned after construction)
+            if rows + capacity > MAX_CAPTURE_ROWS:
+                raise UnsupportedSceneError(
+                    f"The scene's captures hold more than {MAX_CAPTURE_ROWS} rows (2^24, summed over its recorders), "
+                    f"reached at Recorder {recorder.name!r}.")
+            self.rec_capture_capacity[r] = capacity
+            rows += capacity
+        self.capture_rows = int(rows)
+
+    @property
+    def has_captures(self):
+        return self.capture_rows > 0
+
     # -- volume maps -----------------------------------------------------
     def _lower_maps(self, root, nodes):
         """VolumeMap specs -> per-node runs (node_map_start / node_map_count) and one record per map, in node order:
@@ -702,6 +729,9 @@ class CompiledScene:
         "map_wl_start", "map_wl_stop", "map_offset",
     )
 
+    # the captures' tables: part of `tables()` only when a recorder is captured (a scene without lowers to its old tables)
+    CAPTURE_TABLE_FIELDS = ("rec_capture_capacity", "rec_capture_start")
+
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""
         out = {name: getattr(self, name) for name in self.TABLE_FIELDS}
@@ -710,6 +740,9 @@ class CompiledScene:
         if self.has_maps:
             out.update({name: getattr(self, name) for name in self.MAP_TABLE_FIELDS})
             out["map_slots"] = np.int64(self.map_slots)
+        if self.has_captures:
+            out.update({name: getattr(self, name) for name in self.CAPTURE_TABLE_FIELDS})
+            out["capture_rows"] = np.int64(self.capture_rows)
         return out
 
     @property

@@ -17,6 +17,9 @@ traces rays with seeds seed + traced + i" (api.py:249-264).  Both map directly:
   the photon count;
 * sampled event logs stay on the rank that traced them; shard boundaries are multiples of
   `record_every`, so together they are the single-process log.
+* captured rays (`Recorder(..., capture=rows)`) stay on the rank that traced them too: each rank holds the rows of its
+  own index range, with global indices and its own capacity; `matched` summed over the ranks is the recorder's `rays`,
+  which the all-reduce already carries.  A cross-rank gather of the rows is left to the caller.
 
 `backend="nccl"` is RCCL on ROCm.  The CPU tests run the sharding and the reduction
 (`run_sharded`) with gloo around a trace of their own.

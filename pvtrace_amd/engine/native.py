@@ -14,6 +14,8 @@ import threading
 
 import numpy as np
 
+from pvtrace_amd.engine.recorder import MAX_CAPTURE_ROWS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get(  # PVT_LIB: developer override (ablation builds); never a CPU path
     "PVT_LIB", os.path.join(os.path.dirname(_HERE), "csrc", "libpvtrace_hip.so"))
@@ -111,6 +113,23 @@ class PvtMapTables(C.Structure):
         ("map_wl_start", _p_f64), ("map_wl_stop", _p_f64), ("map_offset", C.POINTER(C.c_int64)),
         ("map_slots", C.c_int64),
     ]
+
+
+class PvtCaptureTables(C.Structure):
+    """Captured recorders of a scene (include/pvtrace_hip.h; pvt_scene_create_capture)."""
+    _fields_ = [
+        ("n_recorders", C.c_int32),
+        ("rec_capture_capacity", C.POINTER(C.c_int64)), ("rec_capture_start", C.POINTER(C.c_int64)),
+        ("capture_rows", C.c_int64),
+    ]
+
+
+class PvtCaptures(C.Structure):
+    """Capture buffers of one launch (device pointers)."""
+    _fields_ = [("rows", C.POINTER(C.c_uint64)), ("cursors", C.POINTER(C.c_int64))]
+
+
+CAPTURE_ROW_WORDS = 12   # uint64 words of a captured row (PVT_CAPTURE_ROW_WORDS)
 
 
 class PvtEmitterTables(C.Structure):
@@ -323,6 +342,21 @@ def map_tables_struct(compiled):
     return st, keep
 
 
+def capture_tables_struct(compiled):
+    """PvtCaptureTables over the captured recorders of a CompiledScene -> (struct or None, keepalive); None when no
+    recorder is captured (the scene is then created exactly as before)."""
+    if int(getattr(compiled, "capture_rows", 0)) == 0:
+        return None, {}
+    keep = {name: np.ascontiguousarray(getattr(compiled, name), dtype=np.int64)
+            for name in ("rec_capture_capacity", "rec_capture_start")}
+    st = PvtCaptureTables()
+    st.n_recorders = int(len(keep["rec_capture_capacity"]))
+    st.rec_capture_capacity = np_ptr(keep["rec_capture_capacity"])
+    st.rec_capture_start = np_ptr(keep["rec_capture_start"])
+    st.capture_rows = int(compiled.capture_rows)
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -403,6 +437,12 @@ def declare_signatures(lib, names):
                                    C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables), C.c_int,
                                    C.POINTER(vp)], C.c_int),
         "pvt_scene_map_slots": ([vp], C.c_int64),
+        "pvt_scene_create_capture": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                      C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
+                                      C.POINTER(PvtCaptureTables), C.c_int, C.POINTER(vp)], C.c_int),
+        "pvt_scene_capture_rows": ([vp], C.c_int64),
+        "pvt_trace_device_capture": ([vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
+                                      C.POINTER(PvtEventRecords), C.POINTER(PvtCaptures), vp], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
@@ -462,6 +502,7 @@ ABI_SYMBOLS = (
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
+    "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 
@@ -637,8 +678,15 @@ class DeviceScene:
         rt, rkeep = surface_tables_struct(compiled)
         ft, fkeep = field_tables_struct(compiled)
         mt, mkeep = map_tables_struct(compiled)
+        ct, ckeep = capture_tables_struct(compiled)
         handle = C.c_void_p()
-        if mt is not None:
+        if ct is not None:
+            check(self.lib.pvt_scene_create_capture(C.byref(st), None if xt is None else C.byref(xt),
+                                                    None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
+                                                    None if ft is None else C.byref(ft), None if mt is None else C.byref(mt),
+                                                    C.byref(ct), self.device, C.byref(handle)),
+                  "pvt_scene_create_capture")
+        elif mt is not None:
             check(self.lib.pvt_scene_create_maps(C.byref(st), None if xt is None else C.byref(xt),
                                                  None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
                                                  None if ft is None else C.byref(ft), C.byref(mt), self.device,
@@ -734,12 +782,15 @@ class DeviceScene:
         return {"grid": g.value, "block": b.value, "lds_bytes": l.value, "variant": VARIANT_NAMES[variant]}
 
     # -- device buffers (torch tensors) ----------------------------------
-    def new_tallies(self, sets=1):
+    def new_tallies(self, sets=1, captures=True):
         """Zeroed recorder accumulators on the GPU.  The three integer tables are
         views of ONE int64 buffer (`_ints`: distinct | crossings | bins) and the
         moment sums are `_sums`, so a whole tally set is zeroed by two memsets
         and all-reduced by two collectives.  `sets` > 1: that many consecutive sets
-        (the bundles of a stream traced by one launch, PvtTraceParams.tally_bundle)."""
+        (the bundles of a stream traced by one launch, PvtTraceParams.tally_bundle).
+        A scene with captured recorders gets `cap_rows` and `cap_cursor` as well: `sets` x `capture_rows` rows of 96 bytes
+        (up to 1.5 GiB per set), so a buffer that no launch will append to is made with `captures=False` (a launch given
+        such a buffer keeps no rows), and `sets` x `capture_rows` may not exceed MAX_CAPTURE_ROWS."""
         import torch
 
         dev = torch.device("cuda", self.device)
@@ -748,7 +799,7 @@ class DeviceScene:
         nbins = max(int(c.total_bins) + int(getattr(c, "map_slots", 0)), 1)   # (the volume maps' slots follow the bins)
         ints = torch.zeros(sets * (2 * nrec + nbins), dtype=torch.int64, device=dev)
         sums = torch.zeros(sets * nrec * 8, dtype=torch.float64, device=dev)
-        return {
+        out = {
             "rec_distinct": ints[:nrec],
             "rec_crossings": ints[nrec:2 * nrec],
             "rec_sums": sums,
@@ -757,6 +808,14 @@ class DeviceScene:
             "_sums": sums,
             "sets": sets, "stride_i64": 2 * nrec + nbins, "stride_f64": nrec * 8,
         }
+        rows = int(getattr(c, "capture_rows", 0)) if captures else 0
+        if sets * rows > MAX_CAPTURE_ROWS:
+            raise ValueError(f"{sets} tally sets of {rows} capture rows each exceed the {MAX_CAPTURE_ROWS} rows one buffer "
+                             f"may hold; lower the recorders' `capture` or trace fewer bundles per launch")
+        if rows:   # captured recorders: the rows (uninitialised: only rows below a cursor are ever read) and the cursors
+            out["cap_rows"] = torch.empty((sets * rows, CAPTURE_ROW_WORDS), dtype=torch.int64, device=dev)
+            out["cap_cursor"] = torch.zeros(sets * nrec, dtype=torch.int64, device=dev)
+        return out
 
     def new_event_log(self, n_rays, record_every, max_events):
         """Event-RECORD buffers for one bundle (PvtEventRecords): `counts` (recorded rays) and `rows`
@@ -858,6 +917,12 @@ class DeviceScene:
         if record_every > 0:
             rec_ref = C.byref(PvtEventRecords(addr_ptr(log["counts"].data_ptr(), C.c_int32),
                                               addr_ptr(log["rows"].data_ptr(), C.c_uint64)))
+        if "cap_rows" in tallies:   # captured recorders: the launch appends to the buffers' rows at their cursors
+            cap = PvtCaptures(addr_ptr(tallies["cap_rows"].data_ptr(), C.c_uint64),
+                              addr_ptr(tallies["cap_cursor"].data_ptr(), C.c_int64))
+            check(self.lib.pvt_trace_device_capture(self.handle, rays_ref, C.byref(params), C.byref(tl), rec_ref,
+                                                    C.byref(cap), C.c_void_p(stream)), "pvt_trace_device_capture")
+            return
         check(self.lib.pvt_trace_device_records(self.handle, rays_ref, C.byref(params), C.byref(tl),
                                                 rec_ref, C.c_void_p(stream)), "pvt_trace_device_records")
 

@@ -61,13 +61,16 @@ class BundlePipeline:
                 dscene.release_stream(self, h)
             self._claimed = []
             raise
-        self.slots = [dscene.new_tallies() for _ in range(self.depth)]
+        # Capture rows (Recorder(capture=...), up to 1.5 GiB per buffer) are made only on the buffers the launches are given:
+        # the slots with per-bundle all-reduces, the totals otherwise.
+        per_bundle = bool(distributed and reduce == "bundle")
+        self.slots = [dscene.new_tallies(captures=per_bundle) for _ in range(self.depth)]
         # The kernel ADDS its tallies with atomics (one per non-zero slot per workgroup), so the launches of every
         # stream can add into ONE running total: nothing to fold when the totals are read (the fold was eight tiny
         # kernels and two cross-stream waits at the end of every job).  Per-bundle all-reduces add each bundle's own
         # numbers with a plain torch `+=` on the bundle's stream, which is not atomic: they keep a total per stream.
         if distributed and reduce == "bundle":
-            self.totals = [dscene.new_tallies() for _ in range(self.depth)]
+            self.totals = [dscene.new_tallies(captures=False) for _ in range(self.depth)]
         else:
             self.totals = [dscene.new_tallies()] * self.depth
         self.events = []       # (start, stop) HIP events of every trace launch
@@ -193,6 +196,9 @@ class BundlePipeline:
             if k == 0 or t is not self.totals[0]:
                 t["_ints"].zero_()
                 t["_sums"].zero_()
+        for t in self.slots + self.totals:
+            if "cap_cursor" in t:
+                t["cap_cursor"].zero_()
         self.events = []
         self._reduced = False
         self._unordered = set()
@@ -228,7 +234,8 @@ class BundlePipeline:
         self._reduced = True
 
     def totals_host(self):
-        """Sum of every bundle submitted since the last reset -> host numpy dict."""
+        """Sum of every bundle submitted since the last reset -> host numpy dict (the tallies; a scene's captured rays
+        come from `captures_host`, so that polling the running totals never moves rows)."""
         self.reduce_totals()
         self.synchronize()
         ints, sums = self.totals[0]["_ints"], self.totals[0]["_sums"]
@@ -243,7 +250,24 @@ class BundlePipeline:
         }
         if c.has_maps:   # (the volume maps' slots follow the bins: engine.api.maps_from_slots)
             data["map_bins"] = ints[2 * nrec + int(c.total_bins):][: c.map_slots]
-        return data
+        return data   # (captured rays are not tallies: `captures_host` downloads and sorts them, once, when asked)
+
+    def captures_host(self):
+        """{recorder name: CapturedRays} of every bundle submitted since the pipeline was made or `reset_totals` was called: the rows of the buffers the
+        launches appended to (one shared total, or one per stream with per-bundle all-reduces), concatenated and sorted.
+        Carried photons append to the same captures.  The capacity applies per buffer; under `torch.distributed` the
+        rows are this rank's own."""
+        from pvtrace_amd.engine.api import download_captures, merge_captures
+
+        self.finish_parked()
+        self.synchronize()
+        per_bundle = self.distributed and self.reduce == "bundle"
+        buffers, seen = [], set()
+        for t in (self.slots if per_bundle else self.totals):
+            if id(t) not in seen:
+                seen.add(id(t))
+                buffers.append(t)
+        return merge_captures([download_captures(self.dscene.compiled, t) for t in buffers])
 
     def kernel_ms(self):
         self.synchronize()
@@ -283,6 +307,8 @@ def trace_stream(scene, num_rays, bundle, seed, emit_seed=0, maxsteps=1000, max_
                             closing=traced + n * depth >= num_rays)
                 traced += n
             data = pipe.totals_host()
+            if compiled.has_captures:   # ({recorder name: CapturedRays} of the whole job)
+                data["captures"] = pipe.captures_host()
             elapsed = time.perf_counter() - tic
     finally:
         dscene.close()

@@ -40,6 +40,14 @@ VOLUME_EVENTS = frozenset(("lost", "reacted", "killed"))
 SOURCE_ANY, SOURCE_LIGHTS, SOURCE_COMPONENTS, SOURCE_COMPONENT = 0, 1, 2, 3
 
 
+# rows the captures of one scene may hold, summed over its recorders (include/pvtrace_hip.h PVT_MAX_CAPTURE_ROWS): 1.5 GiB
+# of 96-byte rows per tally set on the device, and as much again while `download` gathers the written rows.  One buffer of
+# rows exists per launch in flight (two per `Session`, one per `BundlePipeline`, one per stream of a pipeline with
+# per-bundle all-reduces); a grouped launch of `simulate_stream` holds one set per bundle and groups no more bundles
+# than keep sets x rows within this limit (`DeviceScene.new_tallies` refuses more)
+MAX_CAPTURE_ROWS = 1 << 24
+
+
 def _require(condition, message):
     if not condition:
         raise ValueError(message)
@@ -98,13 +106,15 @@ class Recorder:
     histograms  `Histogram` / `Heatmap` specs filled by the first matching interaction of a ray
     source      None, "lights", "components" or a component name: only photons whose current
                 incarnation was emitted there (extension; splits "solar" from "luminescent")
+    capture     None, or a positive integer: keep up to that many of the rays behind `rays` as rows
+                (`EngineResult.captures[name]`, a `CapturedRays`; extension)
 
     A ray is counted once per recorder (`rays`, moments, histograms) however often it
     matches; `crossings` counts every match.
     """
 
     def __init__(self, name, event="entering", facet=None, atol=1e-6, histograms=None,
-                 source=None):
+                 source=None, capture=None):
         _require(event in EVENTS, f"Unknown event {event!r}; use one of {sorted(EVENTS)}")
         specs = list(histograms or ())
         _require(all(isinstance(spec, (Histogram, Heatmap)) for spec in specs),
@@ -115,6 +125,14 @@ class Recorder:
         self.atol = float(atol)
         self.histograms = specs
         self.source = source
+        if capture is not None:
+            import numbers
+
+            _require(isinstance(capture, numbers.Integral) and not isinstance(capture, bool),
+                     f"Recorder {name!r}: capture must be a positive integer number of rows, got {capture!r}")
+            _require(capture > 0, f"Recorder {name!r}: capture must be a positive number of rows, got {capture!r}")
+            capture = int(capture)
+        self.capture = capture
 
     @property
     def is_volume(self):
@@ -122,6 +140,82 @@ class Recorder:
 
     def __repr__(self):
         return "Recorder(%r, event=%r)" % (self.name, self.event)
+
+
+CAPTURE_COLUMNS = ("index", "position", "direction", "wavelength", "pathlength", "duration", "source")
+
+
+class CapturedRays:
+    """The rays that fired a recorder with ``capture=capacity``: one row for each ray's FIRST match of the recorder, the
+    event that increments `rays`, feeds the moments and fills the histograms.  Columns (numpy, sorted ascending by `index`):
+
+    index       int64, the global ray index `ray_offset + i`; the ray's RNG stream is `seed + index`
+    position    (n, 3) float64, bit for bit the `position` column of that event's row in the event log
+    direction   (n, 3) float64, likewise (the direction the photon leaves the event with)
+    wavelength, pathlength, duration   float64, the `wavelength`, `travelled` and `duration` columns of that row
+    source      int32, the photon's current source: a component id (`CompiledScene.component_names`), -1 for a light
+
+    and `matched` (first matches, equal to `recorders[name].rays`), `dropped` = matched - len, `capacity`.
+
+    The contract (include/pvtrace_hip.h, PvtCaptureTables, states the same; the kernel and
+    `engine.tally.capture_histories` both follow it):
+
+    1. When `dropped == 0` the row set is exact: sorted by index it does not depend on launch geometry, carrying,
+       tally-set grouping or the device list.
+    2. When the capacity is exceeded, later arrivals are dropped; every kept row is still a correct row and indices stay
+       unique.
+    3. Which rows survive an overflow is unspecified (the host path keeps the first in ray order; a GPU keeps the first
+       to arrive).  With `simulate(devices=[...])` and in pipeline totals the capacity applies per shard / per buffer.
+    4. `simulate` warns once per recorder that overflowed.
+    """
+
+    def __init__(self, name, capacity, matched, columns):
+        import numpy as np
+
+        self.name, self.capacity, self.matched = name, int(capacity), int(matched)
+        index = np.asarray(columns["index"], dtype=np.int64)
+        # (rows that come off the GPU are sorted already: nothing is copied then)
+        order = slice(None) if np.all(index[1:] >= index[:-1]) else np.argsort(index, kind="stable")
+        self.index = index[order]
+        self.position = np.asarray(columns["position"], dtype=np.float64).reshape(-1, 3)[order]
+        self.direction = np.asarray(columns["direction"], dtype=np.float64).reshape(-1, 3)[order]
+        self.wavelength = np.asarray(columns["wavelength"], dtype=np.float64)[order]
+        self.pathlength = np.asarray(columns["pathlength"], dtype=np.float64)[order]
+        self.duration = np.asarray(columns["duration"], dtype=np.float64)[order]
+        self.source = np.asarray(columns["source"], dtype=np.int32)[order]
+
+    def __len__(self):
+        return len(self.index)
+
+    @property
+    def dropped(self):
+        return self.matched - len(self)
+
+    def columns(self):
+        return {name: getattr(self, name) for name in CAPTURE_COLUMNS}
+
+    @classmethod
+    def from_rows(cls, name, capacity, matched, rows, index_shift=0):
+        """From device rows, an (n, 12) uint64 / int64 array laid out as include/pvtrace_hip.h says."""
+        import numpy as np
+
+        rows = np.ascontiguousarray(rows).reshape(-1, 12)
+        f64, i32 = rows.view(np.float64), rows.view(np.int32)
+        return cls(name, capacity, matched, {
+            "index": rows[:, 0].view(np.int64) + int(index_shift), "position": f64[:, 1:4], "direction": f64[:, 4:7],
+            "wavelength": f64[:, 7], "pathlength": f64[:, 8], "duration": f64[:, 9], "source": i32[:, 20]})
+
+    @classmethod
+    def merged(cls, parts):
+        """Captures of one recorder from consecutive shards, bundles or buffers -> one, concatenated and sorted."""
+        import numpy as np
+
+        first = parts[0]
+        columns = {name: np.concatenate([getattr(p, name) for p in parts]) for name in CAPTURE_COLUMNS}
+        return cls(first.name, first.capacity, sum(p.matched for p in parts), columns)
+
+    def __repr__(self):
+        return f"CapturedRays({self.name!r}, rows={len(self)}, matched={self.matched}, capacity={self.capacity})"
 
 
 # volume-map selector -> the event-log kind it counts (include/pvtrace_hip.h PVT_EV_*; light.Event has the same values)

@@ -132,6 +132,60 @@ def tally_histories(scene, histories):
     return {probe.recorder.name: probe.result() for probe in probes}
 
 
+def capture_histories(scene, histories, ray_offset=0, indices=None):
+    """{recorder name: CapturedRays} from one history per ray: the rays behind each captured recorder's `rays` count, built
+    on the host with the matching rule of `tally_histories` (first match per ray, facet tolerance, source filter).  The
+    row of a ray holds the values of the matching history event -- position, direction, wavelength, path, clock -- and
+    the photon's source as a component id of the compiled scene (-1: a light).  History j is ray `ray_offset + j`, or
+    `indices[j]`; the capacity is applied in ray order: the first `capacity` matching rays are kept.  The host path for
+    `follow(backend="host")` users, and the referee of the kernel's captures.
+
+    A history names a photon's source by the component's NAME, so the id is that of the first component of the name:
+    where two components share a name the `source` column may differ from the kernel's, which knows the component
+    itself.  The scene is flattened anew on every call (for the component ids); a referee's cost, not a hot path's."""
+    from pvtrace_amd.engine.compiler import compile_scene
+    from pvtrace_amd.engine.recorder import CapturedRays
+
+    root = scene.root
+    nodes = list(root.preorder())
+    component_ids = {}
+    for k, name in enumerate(compile_scene(scene).component_names):
+        component_ids.setdefault(name, k)
+    probes = [_Probe(node, recorder, root, set(component_ids))
+              for node in nodes for recorder in getattr(node, "recorders", []) if getattr(recorder, "capture", None)]
+    by_event = {}
+    for probe in probes:
+        by_event.setdefault(probe.event, []).append(probe)
+    kept = {id(probe): [] for probe in probes}
+    for j, history in enumerate(histories):
+        index = int(indices[j]) if indices is not None else int(ray_offset) + j
+        for probe in probes:
+            probe.open = True
+        incoming = None
+        for ray, event, meta in history:
+            for probe in by_event.get(event, ()):
+                before = len(probe.rows)
+                probe.offer(ray, meta or {}, incoming or ray)
+                if len(probe.rows) > before:   # this ray's first match
+                    kept[id(probe)].append((index, tuple(ray.position), tuple(ray.direction), float(ray.wavelength),
+                                            float(ray.travelled), float(ray.duration), component_ids.get(ray.source, -1)))
+            incoming = ray
+    out = {}
+    for probe in probes:
+        rows = sorted(kept[id(probe)], key=lambda row: row[0])
+        matched, capacity = len(rows), probe.recorder.capture
+        rows = rows[:capacity]
+        out[probe.recorder.name] = CapturedRays(probe.recorder.name, capacity, matched, {
+            "index": np.array([r[0] for r in rows], dtype=np.int64),
+            "position": np.array([r[1] for r in rows], dtype=np.float64).reshape(len(rows), 3),
+            "direction": np.array([r[2] for r in rows], dtype=np.float64).reshape(len(rows), 3),
+            "wavelength": np.array([r[3] for r in rows], dtype=np.float64),
+            "pathlength": np.array([r[4] for r in rows], dtype=np.float64),
+            "duration": np.array([r[5] for r in rows], dtype=np.float64),
+            "source": np.array([r[6] for r in rows], dtype=np.int32)})
+    return out
+
+
 def map_histories(scene, histories):
     """{map name: VolumeMapResult} from one history per ray: the scene's `VolumeMap`s binned on the host, in numpy, by
     the contract stated in the `VolumeMap` docstring -- every event of the map's kind whose container is the map's node,
