@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from pvtrace_amd.engine import native as N
+from pvtrace_amd.engine.tally_set import TallyLayout
 
 
 def _host_outputs(compiled, n_rays, record_every, max_events):
@@ -154,17 +155,13 @@ def trace_bundle_sets(compiled, positions, directions, wavelengths, seed, maxste
     wl = np.ascontiguousarray(wavelengths, dtype=np.float64)
     n = pos.shape[0]
     sets = -(-n // int(bundle))
-    nrec, nbins = int(compiled.rec_node.shape[0]), int(compiled.total_bins)
-    pad = max(nrec, 1)
-    stride_i, stride_d = 2 * pad + max(nbins, 1), pad * 8
-    ints = np.zeros(sets * stride_i, dtype=np.int64)
-    sums = np.zeros(sets * stride_d, dtype=np.float64)
-    tl = N.PvtTallies(N.np_ptr(ints), N.np_ptr(ints[pad:]), N.np_ptr(sums), N.np_ptr(ints[2 * pad:]))
-    params = N.trace_params(n, seed, ray_offset, 0, 0, maxsteps, 2, emit_method, 0, bundle, stride_i, stride_d)
+    layout = TallyLayout(compiled)
+    si, sf = layout.stride_i64, layout.stride_f64
+    ints = np.zeros(sets * si, dtype=np.int64)
+    sums = np.zeros(sets * sf, dtype=np.float64)
+    tl = layout.struct(ints.ctypes.data, sums.ctypes.data)
+    params = N.trace_params(n, seed, ray_offset, 0, 0, maxsteps, 2, emit_method, 0, bundle, si, sf)
     rays = N.PvtRays(N.np_ptr(pos), N.np_ptr(dirs), N.np_ptr(wl))
     N.check(lib.pvt_trace_bundle(C.byref(st), None, C.byref(rays), C.byref(params), C.byref(tl), None,
                                  int(device), None), "pvt_trace_bundle")
-    ints, sums = ints.reshape(sets, stride_i), sums.reshape(sets, stride_d)
-    return [{"rec_distinct": ints[j, :nrec], "rec_crossings": ints[j, pad:pad + nrec],
-             "rec_bins": ints[j, 2 * pad:2 * pad + nbins], "rec_sums": sums[j, :nrec * 8].reshape(nrec, 4, 2)}
-            for j in range(sets)]
+    return [layout.split(ints[j * si:(j + 1) * si], sums[j * sf:(j + 1) * sf]) for j in range(sets)]

@@ -287,32 +287,6 @@ def maps_from_slots(compiled, slots):
     return out
 
 
-def download_captures(compiled, tallies, set_index=0, index_shift=0):
-    """The capture buffers of a tally set (`DeviceScene.new_tallies`: `cap_rows`, `cap_cursor`) -> {recorder name:
-    CapturedRays}.  Per captured recorder the min(cursor, capacity) rows that were written are sorted by ray index on the
-    GPU and only they are moved to the host.  `index_shift` is added to the indices (bundles of a stream that were traced
-    with the stream position folded into the seed instead of the ray offset)."""
-    if not getattr(compiled, "has_captures", False):
-        return {}
-    import torch
-
-    nrec = max(int(compiled.rec_node.shape[0]), 1)
-    cursors = tallies["cap_cursor"][set_index * nrec:(set_index + 1) * nrec].cpu().numpy()
-    out = {}
-    for r, spec in enumerate(compiled.recorder_specs):
-        capacity = int(compiled.rec_capture_capacity[r])
-        if capacity == 0:
-            continue
-        matched = int(cursors[r])
-        n = min(matched, capacity)
-        first = set_index * compiled.capture_rows + int(compiled.rec_capture_start[r])
-        block = tallies["cap_rows"][first:first + n]
-        if n > 1:
-            block = block.index_select(0, torch.argsort(block[:, 0]))
-        out[spec.name] = CapturedRays.from_rows(spec.name, capacity, matched, to_host(block.contiguous()), index_shift)
-    return out
-
-
 def merge_captures(parts):
     """[{name: CapturedRays}] of consecutive shards / bundles / buffers -> one dict, rows concatenated and sorted."""
     parts = [p for p in parts if p]
@@ -375,29 +349,14 @@ def to_host(tensor):
 
 
 def download(compiled, tallies, log, n_rays, record_every, max_events, packed=False):
-    """Device buffers -> the reference's `data` dict (host numpy).  `packed`: keep only the written
-    rows of the event log (plus `row_start`, see `EngineResult.packed`) instead of rebuilding the
-    reference's dense `rows = recorded * max_events` arrays."""
-    nrec = int(compiled.rec_node.shape[0])
+    """Device buffers (`tallies`: the first set of a `TallySet`) -> the reference's `data` dict (host numpy).
+    `packed`: keep only the written rows of the event log (plus `row_start`, see `EngineResult.packed`) instead
+    of rebuilding the reference's dense `rows = recorded * max_events` arrays."""
     n_recorded = native.num_recorded(n_rays, record_every)
     rows = n_recorded * max_events
     data = {"counts": (to_host(log["counts"][:n_recorded]) if log is not None
                        else np.zeros(0, dtype=np.int32))}
-    if "_ints" in tallies:   # DeviceScene.new_tallies(): distinct | crossings | bins share one buffer
-        ints = tallies["_ints"].cpu().numpy()
-        pad = max(nrec, 1)
-        data["rec_distinct"] = ints[:nrec]
-        data["rec_crossings"] = ints[pad:pad + nrec]
-        data["rec_bins"] = ints[2 * pad: 2 * pad + int(compiled.total_bins)]
-        if compiled.has_maps:   # (the maps' slots follow the bins)
-            data["map_bins"] = ints[2 * pad + int(compiled.total_bins): 2 * pad + int(compiled.total_bins) + compiled.map_slots]
-    else:
-        data["rec_distinct"] = tallies["rec_distinct"][:nrec].cpu().numpy()
-        data["rec_crossings"] = tallies["rec_crossings"][:nrec].cpu().numpy()
-        data["rec_bins"] = tallies["rec_bins"][: int(compiled.total_bins)].cpu().numpy()
-        if compiled.has_maps:
-            data["map_bins"] = tallies["rec_bins"][int(compiled.total_bins): int(compiled.total_bins) + compiled.map_slots].cpu().numpy()
-    data["rec_sums"] = tallies["rec_sums"][: nrec * 8].cpu().numpy().reshape(nrec, 4, 2)
+    data.update(tallies.host(0))
     if log is None or rows == 0:
         for name, dtype, width in native.EVENT_LOG_COLUMNS:
             col = np.zeros(0, dtype=dtype)
@@ -630,16 +589,13 @@ class Session:
             slot = self._slots[self._submitted % 2]
             self._submitted += 1
             sets = -(-int(num_rays) // int(tally_bundle)) if tally_bundle else 1
-            if slot["tallies"] is None or slot["tallies"]["sets"] < sets:
+            if slot["tallies"] is None or slot["tallies"].sets < sets:
                 slot["tallies"] = None   # (capture rows are large: free the old buffer before the new one is made)
                 slot["tallies"] = dscene.new_tallies(sets=sets)
             stream, tallies = slot["stream"], slot["tallies"]
             stream.wait_stream(torch.cuda.current_stream(device))   # ray upload, earlier downloads
             with torch.cuda.stream(stream):
-                tallies["_ints"].zero_()
-                tallies["_sums"].zero_()
-                if "cap_cursor" in tallies:
-                    tallies["cap_cursor"].zero_()
+                tallies.zero_()
                 log = (dscene.new_event_log(num_rays, record_every, max_events)
                        if record_every > 0 else None)
                 start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -677,7 +633,7 @@ class Session:
             with torch.cuda.stream(pending["stream"]):
                 data = download(self.compiled, pending["tallies"], pending["log"], pending["num_rays"],
                                 pending["record_every"], pending["max_events"], packed=pending.get("packed_log", False))
-                captures = download_captures(self.compiled, pending["tallies"], 0, pending.get("index_shift", 0))
+                captures = pending["tallies"].captures(self.compiled, 0, pending.get("index_shift", 0))
         return EngineResult(self.compiled, data, pending["sources"], pending["max_events"],
                             pending["record_every"], wall if wall_clock else kernel_ms * 1e-3,
                             kernel_ms=kernel_ms, captures=captures)
@@ -691,16 +647,13 @@ class Session:
         n = pending["num_rays"]
         sets = -(-n // m)
         c = self.compiled
-        nrec = int(c.rec_node.shape[0])
-        pad, nbins = max(nrec, 1), int(c.total_bins)
         t = pending["tallies"]
         with torch.cuda.device(self.device):
             pending["stream"].synchronize()
             kernel_ms = pending["events"][0].elapsed_time(pending["events"][1])
             with torch.cuda.stream(pending["stream"]):
-                ints = t["_ints"][: sets * t["stride_i64"]].cpu().numpy().reshape(sets, t["stride_i64"])
-                sums = t["_sums"][: sets * t["stride_f64"]].cpu().numpy().reshape(sets, t["stride_f64"])
-                captured = [download_captures(c, t, j, pending.get("index_shift", 0)) for j in range(sets)]
+                tallied = t.host(sets=sets)
+                captured = [t.captures(c, j, pending.get("index_shift", 0)) for j in range(sets)]
         empty = {"counts": np.zeros(0, dtype=np.int32)}
         for name, dtype, width in native.EVENT_LOG_COLUMNS:
             col = np.zeros(0, dtype=dtype)
@@ -709,13 +662,7 @@ class Session:
         sources = pending["sources"]
         for j in range(sets):
             lo, hi = j * m, min((j + 1) * m, n)
-            data = dict(empty)
-            data["rec_distinct"] = ints[j, :nrec]
-            data["rec_crossings"] = ints[j, pad:pad + nrec]
-            data["rec_bins"] = ints[j, 2 * pad: 2 * pad + nbins]
-            if c.has_maps:
-                data["map_bins"] = ints[j, 2 * pad + nbins: 2 * pad + nbins + c.map_slots]
-            data["rec_sums"] = sums[j, : nrec * 8].reshape(nrec, 4, 2)
+            data = dict(empty, **tallied[j])
             results.append(EngineResult(c, data, sources[lo:hi], pending["max_events"], 0,
                                         kernel_ms * 1e-3 * (hi - lo) / n, kernel_ms=kernel_ms * (hi - lo) / n,
                                         captures=captured[j]))

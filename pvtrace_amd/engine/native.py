@@ -14,8 +14,6 @@ import threading
 
 import numpy as np
 
-from pvtrace_amd.engine.recorder import MAX_CAPTURE_ROWS
-
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get(  # PVT_LIB: developer override (ablation builds); never a CPU path
     "PVT_LIB", os.path.join(os.path.dirname(_HERE), "csrc", "libpvtrace_hip.so"))
@@ -680,36 +678,10 @@ class DeviceScene:
         mt, mkeep = map_tables_struct(compiled)
         ct, ckeep = capture_tables_struct(compiled)
         handle = C.c_void_p()
-        if ct is not None:
-            check(self.lib.pvt_scene_create_capture(C.byref(st), None if xt is None else C.byref(xt),
-                                                    None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
-                                                    None if ft is None else C.byref(ft), None if mt is None else C.byref(mt),
-                                                    C.byref(ct), self.device, C.byref(handle)),
-                  "pvt_scene_create_capture")
-        elif mt is not None:
-            check(self.lib.pvt_scene_create_maps(C.byref(st), None if xt is None else C.byref(xt),
-                                                 None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
-                                                 None if ft is None else C.byref(ft), C.byref(mt), self.device,
-                                                 C.byref(handle)),
-                  "pvt_scene_create_maps")
-        elif ft is not None:
-            check(self.lib.pvt_scene_create_field(C.byref(st), None if xt is None else C.byref(xt),
-                                                  None if pt is None else C.byref(pt), None if rt is None else C.byref(rt),
-                                                  C.byref(ft), self.device, C.byref(handle)),
-                  "pvt_scene_create_field")
-        elif rt is not None:
-            check(self.lib.pvt_scene_create_rough(C.byref(st), None if xt is None else C.byref(xt),
-                                                  None if pt is None else C.byref(pt), C.byref(rt), self.device,
-                                                  C.byref(handle)),
-                  "pvt_scene_create_rough")
-        elif pt is None:   # (scenes without phase-function tables or rough nodes are created exactly as before)
-            check(self.lib.pvt_scene_create_ex(C.byref(st), None if xt is None else C.byref(xt), self.device,
-                                               C.byref(handle)),
-                  "pvt_scene_create_ex")
-        else:
-            check(self.lib.pvt_scene_create_phase(C.byref(st), None if xt is None else C.byref(xt), C.byref(pt),
-                                                  self.device, C.byref(handle)),
-                  "pvt_scene_create_phase")
+        # (the older pvt_scene_create* entries only forward here, with NULL for the tables they lack)
+        others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct))
+        check(self.lib.pvt_scene_create_capture(C.byref(st), *others, self.device, C.byref(handle)),
+              "pvt_scene_create_capture")
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a
@@ -783,39 +755,15 @@ class DeviceScene:
 
     # -- device buffers (torch tensors) ----------------------------------
     def new_tallies(self, sets=1, captures=True):
-        """Zeroed recorder accumulators on the GPU.  The three integer tables are
-        views of ONE int64 buffer (`_ints`: distinct | crossings | bins) and the
-        moment sums are `_sums`, so a whole tally set is zeroed by two memsets
-        and all-reduced by two collectives.  `sets` > 1: that many consecutive sets
-        (the bundles of a stream traced by one launch, PvtTraceParams.tally_bundle).
-        A scene with captured recorders gets `cap_rows` and `cap_cursor` as well: `sets` x `capture_rows` rows of 96 bytes
-        (up to 1.5 GiB per set), so a buffer that no launch will append to is made with `captures=False` (a launch given
-        such a buffer keeps no rows), and `sets` x `capture_rows` may not exceed MAX_CAPTURE_ROWS."""
+        """Zeroed recorder accumulators on the GPU -> `TallySet` (tally_set.py owns their layout).  `sets` > 1: that many
+        consecutive sets (the bundles of a stream traced by one launch, PvtTraceParams.tally_bundle).  A scene with captured
+        recorders gets its capture rows as well: a buffer that no launch will append to is made with `captures=False`,
+        and `sets` x `capture_rows` may not exceed MAX_CAPTURE_ROWS."""
         import torch
 
-        dev = torch.device("cuda", self.device)
-        c = self.compiled
-        nrec = max(int(c.rec_node.shape[0]), 1)
-        nbins = max(int(c.total_bins) + int(getattr(c, "map_slots", 0)), 1)   # (the volume maps' slots follow the bins)
-        ints = torch.zeros(sets * (2 * nrec + nbins), dtype=torch.int64, device=dev)
-        sums = torch.zeros(sets * nrec * 8, dtype=torch.float64, device=dev)
-        out = {
-            "rec_distinct": ints[:nrec],
-            "rec_crossings": ints[nrec:2 * nrec],
-            "rec_sums": sums,
-            "rec_bins": ints[2 * nrec:],
-            "_ints": ints,
-            "_sums": sums,
-            "sets": sets, "stride_i64": 2 * nrec + nbins, "stride_f64": nrec * 8,
-        }
-        rows = int(getattr(c, "capture_rows", 0)) if captures else 0
-        if sets * rows > MAX_CAPTURE_ROWS:
-            raise ValueError(f"{sets} tally sets of {rows} capture rows each exceed the {MAX_CAPTURE_ROWS} rows one buffer "
-                             f"may hold; lower the recorders' `capture` or trace fewer bundles per launch")
-        if rows:   # captured recorders: the rows (uninitialised: only rows below a cursor are ever read) and the cursors
-            out["cap_rows"] = torch.empty((sets * rows, CAPTURE_ROW_WORDS), dtype=torch.int64, device=dev)
-            out["cap_cursor"] = torch.zeros(sets * nrec, dtype=torch.int64, device=dev)
-        return out
+        from pvtrace_amd.engine.tally_set import TallySet
+
+        return TallySet(self.compiled, torch.device("cuda", self.device), sets=sets, captures=captures)
 
     def new_event_log(self, n_rays, record_every, max_events):
         """Event-RECORD buffers for one bundle (PvtEventRecords): `counts` (recorded rays) and `rows`
@@ -879,21 +827,14 @@ class DeviceScene:
             need = -(-int(n_rays) // int(tally_bundle))
             if record_every > 0:
                 raise ValueError("tally_bundle needs record_every == 0")
-            if tallies.get("sets", 1) < need:
-                raise ValueError(f"{need} tally sets needed, the buffers hold {tallies.get('sets', 1)}")
-            if need > 1 and not ("stride_i64" in tallies and "stride_f64" in tallies):
-                raise ValueError("tally_bundle needs the buffers of new_tallies(sets=...) (stride_i64 / stride_f64)")
+            if tallies.sets < need:
+                raise ValueError(f"{need} tally sets needed, the buffers hold {tallies.sets}")
         params = trace_params(n_rays, seed, ray_offset, emit_seed, record_every, maxsteps,
                               max_events, emit_method, workgroups_per_cu, tally_bundle,
-                              tallies.get("stride_i64", 0) if tally_bundle else 0,
-                              tallies.get("stride_f64", 0) if tally_bundle else 0,
+                              tallies.layout.stride_i64 if tally_bundle else 0,
+                              tallies.layout.stride_f64 if tally_bundle else 0,
                               (0 if log_prefill else FLAG_NO_LOG_PREFILL) | (FLAG_CARRY_OUT if carry_out else 0))
-        tl = PvtTallies(
-            addr_ptr(tallies["rec_distinct"].data_ptr(), C.c_int64),
-            addr_ptr(tallies["rec_crossings"].data_ptr(), C.c_int64),
-            addr_ptr(tallies["rec_sums"].data_ptr(), C.c_double),
-            addr_ptr(tallies["rec_bins"].data_ptr(), C.c_int64),
-        )
+        tl = tallies.struct
         rays_ref = None
         if rays is not None:
             pos, direc, wl = rays
@@ -917,14 +858,11 @@ class DeviceScene:
         if record_every > 0:
             rec_ref = C.byref(PvtEventRecords(addr_ptr(log["counts"].data_ptr(), C.c_int32),
                                               addr_ptr(log["rows"].data_ptr(), C.c_uint64)))
-        if "cap_rows" in tallies:   # captured recorders: the launch appends to the buffers' rows at their cursors
-            cap = PvtCaptures(addr_ptr(tallies["cap_rows"].data_ptr(), C.c_uint64),
-                              addr_ptr(tallies["cap_cursor"].data_ptr(), C.c_int64))
-            check(self.lib.pvt_trace_device_capture(self.handle, rays_ref, C.byref(params), C.byref(tl), rec_ref,
-                                                    C.byref(cap), C.c_void_p(stream)), "pvt_trace_device_capture")
-            return
-        check(self.lib.pvt_trace_device_records(self.handle, rays_ref, C.byref(params), C.byref(tl),
-                                                rec_ref, C.c_void_p(stream)), "pvt_trace_device_records")
+        # a set with captured recorders: the launch appends to its rows at their cursors (NULL: exactly pvt_trace_device_records)
+        cap = tallies.capture_struct
+        check(self.lib.pvt_trace_device_capture(self.handle, rays_ref, C.byref(params), C.byref(tl), rec_ref,
+                                                None if cap is None else C.byref(cap), C.c_void_p(stream)),
+              "pvt_trace_device_capture")
 
     def carry_pending(self, stream=None):
         """True when photons parked by the last launch on `stream` (`carry_out=True`) wait to be resumed."""

@@ -108,8 +108,7 @@ class BundlePipeline:
         per_bundle = self.distributed and self.reduce == "bundle"
         with torch.cuda.stream(stream):
             if per_bundle:
-                tallies["_ints"].zero_()
-                tallies["_sums"].zero_()
+                tallies.zero_(captures=False)   # (its captured rows are the job's: `captures_host`)
             ev = None
             if timed:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -131,8 +130,7 @@ class BundlePipeline:
                 from pvtrace_amd.engine.distributed import all_reduce_tallies
 
                 all_reduce_tallies(tallies, group=self.group)
-                total["_ints"] += tallies["_ints"]
-                total["_sums"] += tallies["_sums"]
+                total.add_(tallies)
         return k
 
     def wait_for_inputs(self):
@@ -189,16 +187,18 @@ class BundlePipeline:
         self.close()
         return False
 
+    @staticmethod
+    def _distinct(buffers):
+        """`buffers` without repeats (the streams of a pipeline may share one total)."""
+        return list({id(t): t for t in buffers}.values())
+
     def reset_totals(self):
         self.finish_parked()      # photons of earlier bundles must not be tallied into what follows
         self.synchronize()
-        for k, t in enumerate(self.totals):
-            if k == 0 or t is not self.totals[0]:
-                t["_ints"].zero_()
-                t["_sums"].zero_()
-        for t in self.slots + self.totals:
-            if "cap_cursor" in t:
-                t["cap_cursor"].zero_()
+        for t in self._distinct(self.totals):
+            t.zero_()
+        for t in self.slots:
+            t.zero_(tallies=False)   # (zeroed per bundle where they are used; their captured rows are the job's)
         self.events = []
         self._reduced = False
         self._unordered = set()
@@ -220,10 +220,8 @@ class BundlePipeline:
             for t in self.totals[1:]:
                 if t is self.totals[0]:
                     continue
-                self.totals[0]["_ints"] += t["_ints"]
-                self.totals[0]["_sums"] += t["_sums"]
-                t["_ints"].zero_()
-                t["_sums"].zero_()
+                self.totals[0].add_(t)
+                t.zero_()
                 folded = True
             if folded:
                 self._unordered = set(range(1, self.depth))
@@ -238,36 +236,20 @@ class BundlePipeline:
         come from `captures_host`, so that polling the running totals never moves rows)."""
         self.reduce_totals()
         self.synchronize()
-        ints, sums = self.totals[0]["_ints"], self.totals[0]["_sums"]
-        c = self.dscene.compiled
-        nrec = max(int(c.rec_node.shape[0]), 1)
-        ints, sums = ints.cpu().numpy(), sums.cpu().numpy()
-        r = int(c.rec_node.shape[0])
-        data = {
-            "rec_distinct": ints[:nrec][:r], "rec_crossings": ints[nrec:2 * nrec][:r],
-            "rec_bins": ints[2 * nrec:][: int(c.total_bins)],
-            "rec_sums": sums[: r * 8].reshape(r, 4, 2),
-        }
-        if c.has_maps:   # (the volume maps' slots follow the bins: engine.api.maps_from_slots)
-            data["map_bins"] = ints[2 * nrec + int(c.total_bins):][: c.map_slots]
-        return data   # (captured rays are not tallies: `captures_host` downloads and sorts them, once, when asked)
+        return self.totals[0].host(0)
 
     def captures_host(self):
         """{recorder name: CapturedRays} of every bundle submitted since the pipeline was made or `reset_totals` was called: the rows of the buffers the
         launches appended to (one shared total, or one per stream with per-bundle all-reduces), concatenated and sorted.
         Carried photons append to the same captures.  The capacity applies per buffer; under `torch.distributed` the
         rows are this rank's own."""
-        from pvtrace_amd.engine.api import download_captures, merge_captures
+        from pvtrace_amd.engine.api import merge_captures
 
         self.finish_parked()
         self.synchronize()
         per_bundle = self.distributed and self.reduce == "bundle"
-        buffers, seen = [], set()
-        for t in (self.slots if per_bundle else self.totals):
-            if id(t) not in seen:
-                seen.add(id(t))
-                buffers.append(t)
-        return merge_captures([download_captures(self.dscene.compiled, t) for t in buffers])
+        buffers = self._distinct(self.slots if per_bundle else self.totals)
+        return merge_captures([t.captures(self.dscene.compiled) for t in buffers])
 
     def kernel_ms(self):
         self.synchronize()

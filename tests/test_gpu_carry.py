@@ -13,14 +13,6 @@ pytestmark = pytest.mark.gpu
 INT_KEYS = ("rec_distinct", "rec_crossings", "rec_bins")
 
 
-def _host(t, compiled):
-    nrec, pad = int(compiled.rec_node.shape[0]), max(int(compiled.rec_node.shape[0]), 1)
-    ints = t["_ints"].cpu().numpy()
-    return {"rec_distinct": ints[:nrec], "rec_crossings": ints[pad:pad + nrec],
-            "rec_bins": ints[2 * pad:2 * pad + int(compiled.total_bins)],
-            "rec_sums": t["_sums"].cpu().numpy()[: nrec * 8].reshape(nrec, 4, 2)}
-
-
 @pytest.mark.parametrize("name", ["lsc_equivalent", "nested_cylinders", "kitchen_sink", "coated_slab"])
 def test_parked_photons_are_finished_by_the_next_launch_bit_for_bit(name):
     import torch
@@ -41,7 +33,7 @@ def test_parked_photons_are_finished_by_the_next_launch_bit_for_bit(name):
             dscene.trace(part, b - a, seed, tallies, ray_offset=a, carry_out=True)
         torch.cuda.synchronize()
         assert dscene.carry_pending()
-        partial = _host(tallies, compiled)
+        partial = tallies.host(0)
         # something was left for later (every scene here has histories of several steps) ...
         assert partial["rec_crossings"].sum() < cpu["rec_crossings"].sum()
         # ... a history launch cannot take it over ...
@@ -52,14 +44,14 @@ def test_parked_photons_are_finished_by_the_next_launch_bit_for_bit(name):
         dscene.trace(None, 0, 0, tallies)
         torch.cuda.synchronize()
         assert not dscene.carry_pending()
-        got = _host(tallies, compiled)
+        got = tallies.host(0)
         for key in INT_KEYS:
             assert np.array_equal(got[key], cpu[key]), (name, key)
         assert np.allclose(got["rec_sums"], cpu["rec_sums"], rtol=1e-11)
         # nothing waiting: a launch of zero rays is a no-op
         dscene.trace(None, 0, 0, tallies)
         torch.cuda.synchronize()
-        assert np.array_equal(_host(tallies, compiled)["rec_distinct"], cpu["rec_distinct"])
+        assert np.array_equal(tallies.host(0)["rec_distinct"], cpu["rec_distinct"])
     finally:
         dscene.close()
 
@@ -121,7 +113,7 @@ def test_a_narrower_launch_still_resumes_every_parked_photon():
         dscene.trace(tuple(t[cut:] for t in rays), n - cut, seed, tallies, ray_offset=cut, carry_out=False, workgroups_per_cu=1)
         assert dscene.launch_info()["grid"] >= wide
         torch.cuda.synchronize()
-        got = _host(tallies, compiled)
+        got = tallies.host(0)
         for key in INT_KEYS:
             assert np.array_equal(got[key], cpu[key]), key
     finally:

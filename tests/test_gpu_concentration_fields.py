@@ -260,7 +260,7 @@ def _carried(scene, n, seed):
             dscene.trace(tuple(t[a:b] for t in rays), b - a, seed, parts, ray_offset=a, carry_out=True)
         dscene.trace(None, 0, 0, parts)
         torch.cuda.synchronize()
-        return whole["_ints"].cpu().numpy(), parts["_ints"].cpu().numpy()
+        return whole.ints.cpu().numpy(), parts.ints.cpu().numpy()
     finally:
         dscene.close()
 

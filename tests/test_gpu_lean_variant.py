@@ -35,13 +35,6 @@ def _worker(out_path):
     out = {}
     dev = torch.device("cuda", 0)
 
-    def _host(t, compiled):
-        nrec, pad = int(compiled.rec_node.shape[0]), max(int(compiled.rec_node.shape[0]), 1)
-        ints = t["_ints"].cpu().numpy()
-        return {"rec_distinct": ints[:nrec], "rec_crossings": ints[pad:pad + nrec],
-                "rec_bins": ints[2 * pad:2 * pad + int(compiled.total_bins)],
-                "rec_sums": t["_sums"].cpu().numpy()[: nrec * 8].reshape(nrec, 4, 2)}
-
     def launch(tag, scene, n, seed, device_emission=False, **kw):
         compiled = compile_scene(scene)
         dscene = native.DeviceScene(compiled, device=0, emitter=EmitterTables(scene) if device_emission else None)
@@ -54,7 +47,7 @@ def _worker(out_path):
                 rays = tuple(torch.from_numpy(a).to(dev) for a in (pos, dirs, wl))
                 dscene.trace(rays, n, seed, tallies, **kw)
             counters = dscene.counters()
-            for key, value in _host(tallies, compiled).items():
+            for key, value in tallies.host(0).items():
                 out[f"{tag}/{key}"] = value
             out[f"{tag}/steps"] = np.int64(counters["steps"])
             out[f"{tag}/wave_iterations"] = np.int64(counters["wave_iterations"])

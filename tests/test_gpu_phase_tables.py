@@ -214,7 +214,7 @@ def test_carried_launches_give_the_totals_of_one_launch():
             dscene.trace(tuple(t[a:b] for t in rays), b - a, seed, parts, ray_offset=a, carry_out=True)
         dscene.trace(None, 0, 0, parts)
         torch.cuda.synchronize()
-        ints_a, ints_b = whole["_ints"].cpu().numpy(), parts["_ints"].cpu().numpy()
+        ints_a, ints_b = whole.ints.cpu().numpy(), parts.ints.cpu().numpy()
         assert np.array_equal(ints_a, ints_b)
         assert ints_a.sum() > 0
     finally:

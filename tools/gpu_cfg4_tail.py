@@ -33,7 +33,7 @@ for n in ((10_000_000,) if quick else (1_000_000, 10_000_000)):
             b.record()
             torch.cuda.synchronize()
             times.append(a.elapsed_time(b))
-            distinct = tallies["rec_distinct"].cpu().numpy()
+            distinct = tallies.host(0)["rec_distinct"]
             killed.append(sum(int(distinct[names.index(k)]) for k in ("A-killed", "B-killed")))
         print(f"n {n:.0e} maxsteps {maxsteps:5d}: launch ms {' '.join(f'{t:.3f}' for t in times[1:])}   killed {killed[1:]}   "
               f"mean {np.mean(times[1:]):.3f} median {np.median(times[1:]):.3f}", flush=True)
