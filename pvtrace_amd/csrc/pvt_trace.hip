@@ -45,6 +45,7 @@
 #include <dlfcn.h>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <mutex>
 #include <vector>
 
@@ -251,123 +252,14 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     return a;
 }
 
-#ifndef PVT_DEV_VARIANTS
-#define PVT_DEV_VARIANTS 0   // developer builds: only the analytic, array-input, <=64-recorder variants (fast compile)
-#endif
-// Scenes with a rough node (KArgs::rough_d >= 0), a concentration field (KArgs::fd), a volume map (KArgs::md) or a captured
-// recorder (KArgs::cap_tab) run the trace_kernel_rough* families: the same choice of variant.
-template <bool RECORD, int TAB_LDS, int SEENW>
-hipError_t launch_rough_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-#if PVT_DEV_VARIANTS
-    (void)emit; (void)grid; (void)lds; (void)st; (void)a;
-    return hipErrorNotSupported;
-#else
-    const bool mesh = a.bvh != nullptr;
-    if constexpr (TAB_LDS == 1) {
-        if (a.lay.grid_d >= 0 && !mesh) {
-            if (emit) hipLaunchKernelGGL((trace_kernel_rough_grid<RECORD, SEENW, true>), dim3(grid), dim3(kBlock), lds, st, a);
-            else hipLaunchKernelGGL((trace_kernel_rough_grid<RECORD, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    constexpr int MESH_TAB = TAB_LDS == 2 ? 0 : TAB_LDS;
-    if (mesh && TAB_LDS == 2) return hipErrorNotSupported;
-    if (emit) {
-        if (mesh) hipLaunchKernelGGL((trace_kernel_rough<RECORD, MESH_TAB, SEENW, true, true>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_rough_w4<RECORD, TAB_LDS, SEENW, true>), dim3(grid), dim3(kBlock), lds, st, a);
-    } else {
-        if (mesh) hipLaunchKernelGGL((trace_kernel_rough<RECORD, MESH_TAB, SEENW, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_rough_w4<RECORD, TAB_LDS, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
-    }
-    return hipGetLastError();
-#endif
-}
-
-// Which family a launch runs (PVT_VARIANT_*): the same questions, in the same order, as launch_variant below asks.
-int variant_of(const PvtScene* s, bool tab_lds) {
-    if (s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd) return PVT_VARIANT_ROUGH;
-    if (s->d_bvh) return PVT_VARIANT_MESH;
-    if (tab_lds && s->lay.grid_d >= 0) return PVT_VARIANT_GRID;
-    if (tab_lds && s->lean_ok && s->n_rec <= 64) return PVT_VARIANT_LEAN;
-    return PVT_VARIANT_W4;
-}
-
-// Plain scenes (PvtScene::lean_ok, proven by prove_lean) with their tables in LDS: the lean family.
-template <bool RECORD>
-hipError_t launch_lean_variant(bool even, bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-#if PVT_DEV_VARIANTS
-    if (emit || RECORD) return hipErrorNotSupported;
-    if (even) hipLaunchKernelGGL((trace_kernel_lean_w4<false, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL((trace_kernel_lean_w4<false, false, false>), dim3(grid), dim3(kBlock), lds, st, a);
-#else
-    if (even) {
-        if (emit) hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, true, true>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
-    } else {
-        if (emit) hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, true, false>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_lean_w4<RECORD, false, false>), dim3(grid), dim3(kBlock), lds, st, a);
-    }
-#endif
-    return hipGetLastError();
-}
-
-template <bool RECORD, int TAB_LDS, int SEENW>
-hipError_t launch_variant(bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-    if (a.rough_d >= 0 || a.fd != nullptr || a.md != nullptr || a.cap_tab != nullptr) return launch_rough_variant<RECORD, TAB_LDS, SEENW>(emit, grid, lds, st, a);
-    const bool mesh = a.bvh != nullptr;
-    if constexpr (TAB_LDS == 1 && (!PVT_DEV_VARIANTS || SEENW == 1) && PVT_DEV_VARIANTS != 2) {
-        if (a.lay.grid_d >= 0 && !mesh && (!PVT_DEV_VARIANTS || !emit)) {   // many nodes: per-lane walk of the node grid
-            if (emit && !PVT_DEV_VARIANTS) hipLaunchKernelGGL((trace_kernel_grid<RECORD, SEENW, !PVT_DEV_VARIANTS>), dim3(grid), dim3(kBlock), lds, st, a);
-            else hipLaunchKernelGGL((trace_kernel_grid<RECORD, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-#if PVT_DEV_VARIANTS == 2   // developer builds of the MESH variants only (tables in LDS, <= 64 recorders, array input)
-    if (emit || !mesh || TAB_LDS != 1 || SEENW != 1) return hipErrorNotSupported;
-    if constexpr (TAB_LDS == 1 && SEENW == 1) hipLaunchKernelGGL((trace_kernel<RECORD, 1, 1, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
-#elif PVT_DEV_VARIANTS
-    if (emit || mesh || TAB_LDS != 1 || SEENW != 1) return hipErrorNotSupported;
-    if constexpr (TAB_LDS == 1 && SEENW == 1) {
-        if constexpr (RECORD) hipLaunchKernelGGL((trace_kernel_w4<true, 1, 1, false>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_w4<false, 1, 1, false>), dim3(grid), dim3(kBlock), lds, st, a);
-    }
-#else
-    // (mesh scenes stage all their tables or none: plan_lds never asks for the heads alone there)
-    constexpr int MESH_TAB = TAB_LDS == 2 ? 0 : TAB_LDS;
-    if (mesh && TAB_LDS == 2) return hipErrorNotSupported;
-    if (emit) {
-        if (mesh) hipLaunchKernelGGL((trace_kernel<RECORD, MESH_TAB, SEENW, true, true>), dim3(grid), dim3(kBlock), lds, st, a);
-        else if constexpr (RECORD) hipLaunchKernelGGL((trace_kernel_w4<true, TAB_LDS, SEENW, true>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_w4<false, TAB_LDS, SEENW, true>), dim3(grid), dim3(kBlock), lds, st, a);
-    } else {
-        if (mesh) hipLaunchKernelGGL((trace_kernel<RECORD, MESH_TAB, SEENW, false, true>), dim3(grid), dim3(kBlock), lds, st, a);
-        else if constexpr (RECORD) hipLaunchKernelGGL((trace_kernel_w4<true, TAB_LDS, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((trace_kernel_w4<false, TAB_LDS, SEENW, false>), dim3(grid), dim3(kBlock), lds, st, a);
-    }
-#endif
-    return hipGetLastError();
-}
-
-template <bool RECORD, int TAB_LDS>
-hipError_t launch_seen(int n_rec, int lean, bool emit, int grid, size_t lds, hipStream_t st, const KArgs& a) {
-    if constexpr (TAB_LDS == 1 && PVT_DEV_VARIANTS != 2) {
-        if (lean) return launch_lean_variant<RECORD>(lean == kLeanEven, emit, grid, lds, st, a);
-    }
-    if (n_rec <= 64) return launch_variant<RECORD, TAB_LDS, 1>(emit, grid, lds, st, a);
-    return launch_variant<RECORD, TAB_LDS, 4>(emit, grid, lds, st, a);
-}
-
-}  // namespace
-
-namespace {
-
-// cursor / staging slot of a stream (launches on one stream are ordered and share it)
+// cursor / staging slot of a stream (launches on one stream are ordered and share it); -1, and the error said, when all are taken
 int slot_of_stream(PvtScene* s, hipStream_t st) {
     std::lock_guard<std::mutex> lock(s->slot_mutex);
     size_t slot = 0;
     while (slot < s->slot_of.size() && s->slot_of[slot] != st) slot++;
     if (slot == s->slot_of.size()) {
-        if (slot >= (size_t)kCursorSlots) return -1;
+        if (slot >= (size_t)kCursorSlots)
+            return fail(-1, "more than 64 HIP streams are tracing this scene; create one scene per group of streams");
         s->slot_of.push_back(st);
         s->stage.push_back(nullptr);
         s->stage_bytes.push_back(0);
@@ -390,14 +282,16 @@ int check_trace_args(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, 
     return PVT_OK;
 }
 
-// Enqueue ONE trace kernel.  `log_rows` / `log_counts`: the event records of the recorded rays (device memory,
-// null when record_every == 0); counts are cleared here.
-// LDS of a launch, before what mesh walks add: recorder accumulators + control words, tables if they fit, bins if
-// they fit, then the drain-phase consolidation buffer (kXSlots photon states, also the seed pools) within 40 KB.
-// `s->meshq` and `s->top_n` (mesh scenes) are reserved first, so that what is decided here still fits with them.
-struct LdsPlan { size_t bytes; bool tab_lds, small_lds; int bins_in_lds, xslots, tq_pos; bool ok; };
+// Where a launch reads the scene tables from (the kernels' TAB_LDS): global memory, LDS, or LDS for the blobs' heads only.
+enum class Tab { Global = 0, Lds = 1, Heads = 2 };
+
+// LDS of a launch: recorder accumulators + control words, tables if they fit, bins if they fit, then the drain-phase
+// consolidation buffer (kXSlots photon states, also the seed pools) within 40 KB: `bytes`.  Mesh walks add the lanes'
+// noted leaves (at `meshq_off`), then the copy of the trees' top levels (at `top_off`): `total`.  These two
+// (`s->meshq`, `s->top_n`) are reserved first, so that what is decided here still fits with them.
+struct LdsPlan { size_t bytes; Tab tab; int bins_in_lds, xslots, tq_pos; bool ok; int meshq_off, top_off; size_t total; };
 LdsPlan plan_lds(const PvtScene* s, bool record) {
-    LdsPlan lp{0, false, false, 0, 0, 0, true};
+    LdsPlan lp{0, Tab::Global, 0, 0, 0, true, -1, 0, 0};
     const size_t reserved = (size_t)s->meshq * kBlock * 4 + (size_t)s->top_n * sizeof(pvt::BvhNode);
     const size_t acc_bytes = (size_t)s->n_rec * (8 * 8 + 8) + (size_t)((s->n_rec + 1) & ~1) * 4 + CTL_WORDS * 4;
     const size_t tab_bytes = (size_t)s->nd * 8 + (size_t)((s->ni + 1) & ~1) * 4;
@@ -410,13 +304,13 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     if (acc_bytes + tq_bytes > lds_limit) { lp.ok = false; return lp; }
     // (PVT_TABLES: developer / test switch -- "global": no tables in LDS, "heads": never the spectra)
     const char* force = getenv("PVT_TABLES");
-    lp.tab_lds = acc_bytes + tq_bytes + tab_bytes <= budget && !force;
     // spectra too large for LDS: everything else -- node, component and recorder records, class tables -- still is staged
-    // (the blobs' heads; the spectra and their guide tables are read from global memory)
+    // (the blobs' heads; the spectra and their guide tables are read from global memory; mesh scenes stage all or none)
     const size_t small_bytes = (size_t)s->nd_small * 8 + (size_t)((s->ni_small + 1) & ~1) * 4;
-    lp.small_lds = !lp.tab_lds && s->meshq == 0 && acc_bytes + tq_bytes + small_bytes <= 40 * 1024 && acc_bytes + tq_bytes + small_bytes <= budget &&
-                   !(force && force[0] == 'g');
-    size_t lds = acc_bytes + tq_bytes + (lp.tab_lds ? tab_bytes : lp.small_lds ? small_bytes : 0);
+    if (acc_bytes + tq_bytes + tab_bytes <= budget && !force) lp.tab = Tab::Lds;
+    else if (s->meshq == 0 && acc_bytes + tq_bytes + small_bytes <= 40 * 1024 && acc_bytes + tq_bytes + small_bytes <= budget &&
+             !(force && force[0] == 'g')) lp.tab = Tab::Heads;
+    size_t lds = acc_bytes + tq_bytes + (lp.tab == Tab::Lds ? tab_bytes : lp.tab == Tab::Heads ? small_bytes : 0);
     lp.bins_in_lds = (lds + bins_bytes <= budget) ? 1 : 0;
     if (lp.bins_in_lds) lds += bins_bytes;
     const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->d_cd ? 1 : 0);   // (capture: the global ray index)
@@ -427,36 +321,202 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
         lp.xslots = kXSlots;
         lds += xbytes;
     }
-    lp.bytes = (lds + 15) & ~(size_t)15;
+    lp.total = lp.bytes = (lds + 15) & ~(size_t)15;
+    if (s->meshq) {
+        lp.meshq_off = (int)lp.total;
+        lp.total += (size_t)s->meshq * kBlock * 4;
+        lp.top_off = (int)lp.total;
+        lp.total += (size_t)s->top_n * sizeof(pvt::BvhNode);
+    }
     return lp;
 }
 
-int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
-                 unsigned long long* log_rows, int* log_counts, hipStream_t st, const PvtCaptures* cap = nullptr) {
-    const int slot = slot_of_stream(s, st);
-    if (slot < 0)
-        return fail(PVT_ERR_INVALID, "more than 64 HIP streams are tracing this scene; create one scene per group of streams");
-    PvtScene::Carry& carry = s->carry[(size_t)slot];
-    const bool carry_in = carry.pending;
-    if (p->n_rays == 0 && !carry_in) return PVT_OK;
-    if (carry_in && (p->record_every > 0 || p->tally_bundle > 0))
+// Which kernel a launch runs: decided once, here.  `family` is what pvt_scene_variant reports; the other members are
+// the template arguments of that family's entry points.
+struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even; };
+Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit) {
+    Variant v{};
+    v.record = record; v.emit = emit; v.tab = lp.tab;
+    v.seenw = s->n_rec <= 64 ? 1 : 4;
+    v.mesh = s->d_bvh != nullptr;
+    v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
+    // a rough node, a concentration field, a volume map or a captured recorder: the extension family, split as the plain ones
+    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd;
+    const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
+    v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
+    v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
+    return v;
+}
+
+// A run-time value as a template argument: f is called with it as a std::integral_constant.
+using Kernel = void (*)(KArgs);
+template <class F> Kernel with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> Kernel with_tab(Tab t, F f) {
+    return t == Tab::Lds ? f(std::integral_constant<int, 1>{}) : t == Tab::Heads ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 0>{});
+}
+
+#ifndef PVT_DEV_VARIANTS
+#define PVT_DEV_VARIANTS 0   // developer builds (fast compile): 1 the plain-scene kernels, 2 the mesh kernels, of `narrow` launches only
+#endif
+// The entry point of a variant, null where this build has none.  A new family is a new case here (and in choose_variant).
+Kernel kernel_of(const Variant& v) {
+    return with_bool(v.record, [&](auto record) { return with_bool(v.emit, [&](auto emit) { return with_bool(v.seenw == 4, [&](auto wide) {
+    return with_tab(v.tab, [&](auto tab) -> Kernel {
+        constexpr bool R = decltype(record)::value, E = decltype(emit)::value;
+        constexpr int W = decltype(wide)::value ? 4 : 1, T = decltype(tab)::value, dev = PVT_DEV_VARIANTS;
+        constexpr bool narrow = T == 1 && W == 1 && !E;   // tables in LDS, <= 64 recorders, given rays
+        constexpr bool has_rough = dev == 0;
+        constexpr bool has_mesh = T != 2 && (dev == 0 || (dev == 2 && narrow));   // (mesh scenes stage all their tables or none)
+        constexpr bool has_grid = T == 1 && (dev == 0 || (dev == 1 && narrow));
+        constexpr bool has_lean = T == 1 && W == 1 && (dev == 0 || (dev == 1 && narrow && !R));
+        constexpr bool has_w4 = dev == 0 || (dev == 1 && narrow);
+        switch (v.family) {
+        case PVT_VARIANT_ROUGH:
+            if constexpr (has_rough) {
+                if constexpr (T == 1) if (v.grid) return trace_kernel_rough_grid<R, W, E>;
+                if constexpr (T != 2) if (v.mesh) return trace_kernel_rough<R, T, W, E, true>;
+                if (!v.mesh) return trace_kernel_rough_w4<R, T, W, E>;
+            }
+            break;
+        case PVT_VARIANT_MESH:
+            if constexpr (has_mesh) return trace_kernel<R, T, W, E, true>;
+            break;
+        case PVT_VARIANT_GRID:
+            if constexpr (has_grid) return trace_kernel_grid<R, W, E>;
+            break;
+        case PVT_VARIANT_LEAN:
+            if constexpr (has_lean) { if (v.even) return trace_kernel_lean_w4<R, E, true>; return trace_kernel_lean_w4<R, E, false>; }
+            break;
+        case PVT_VARIANT_W4:
+            if constexpr (has_w4) return trace_kernel_w4<R, T, W, E>;
+            break;
+        }
+        return nullptr;
+    }); }); }); });
+}
+
+// Photons parked by the previous launch on the stream wait for this one: it must be able to finish them, by their rules.
+int check_carried(const PvtScene::Carry& carry, const PvtTraceParams* p) {
+    if (p->record_every > 0 || p->tally_bundle > 0)
         return fail(PVT_ERR_INVALID, "photons parked by the previous launch on this stream (PVT_FLAG_CARRY_OUT) are waiting: "
                                      "finish them with a plain tally launch (n_rays may be 0) first");
-    if (carry_in && (p->maxsteps != carry.maxsteps || p->emit_method != carry.emit_method))
+    if (p->maxsteps != carry.maxsteps || p->emit_method != carry.emit_method)
         return fail(PVT_ERR_INVALID, "photons parked by the previous launch on this stream were traced with maxsteps " +
                                      std::to_string(carry.maxsteps) + ", emit_method " + std::to_string(carry.emit_method) +
                                      "; this launch asks for " + std::to_string(p->maxsteps) + ", " + std::to_string(p->emit_method) +
                                      ": finish them under their own rules first (a launch with n_rays = 0 and the old values), or drop "
                                      "them with pvt_scene_carry_discard");
-    long long n_sets = 0;
-    if (p->tally_bundle > 0) {
-        n_sets = (p->n_rays + p->tally_bundle - 1) / p->tally_bundle;
-        if (p->tally_bundle > 0x7fffffffLL || n_sets > kMaxSets)
-            return fail(PVT_ERR_INVALID, "at most 1024 tally sets per launch");
-        if (p->tally_stride_i64 < 0 || p->tally_stride_f64 < 0) return fail(PVT_ERR_INVALID, "negative tally stride");
-        if (s->map_slots > 0 && n_sets > 1 && p->tally_stride_i64 < (long long)s->total_bins + s->map_slots)
-            return fail(PVT_ERR_INVALID, "tally stride shorter than the bins and the volume maps' slots of a set");
+    return PVT_OK;
+}
+
+// The tally sets a launch asks for (0: none), PVT_OK if they are well formed.
+int check_tally_sets(const PvtScene* s, const PvtTraceParams* p, long long* n_sets) {
+    *n_sets = 0;
+    if (p->tally_bundle <= 0) return PVT_OK;
+    *n_sets = (p->n_rays + p->tally_bundle - 1) / p->tally_bundle;
+    if (p->tally_bundle > 0x7fffffffLL || *n_sets > kMaxSets) return fail(PVT_ERR_INVALID, "at most 1024 tally sets per launch");
+    if (p->tally_stride_i64 < 0 || p->tally_stride_f64 < 0) return fail(PVT_ERR_INVALID, "negative tally stride");
+    if (s->map_slots > 0 && *n_sets > 1 && p->tally_stride_i64 < (long long)s->total_bins + s->map_slots)
+        return fail(PVT_ERR_INVALID, "tally stride shorter than the bins and the volume maps' slots of a set");
+    return PVT_OK;
+}
+
+// Workgroups of the persistent grid: enough to fill every CU a few times over, never more than the rays can feed.
+// With tally sets (which it binds in `a`) a workgroup serves one set: the same total, split evenly over the sets.
+long long size_grid(const PvtScene* s, const PvtTraceParams* p, long long carried, long long n_sets, KArgs& a) {
+    long long blocks_for_rays = (p->n_rays + carried + kBlock - 1) / kBlock;
+    double per_cu = p->workgroups_per_cu > 0 ? (double)p->workgroups_per_cu : 4.0;
+    long long grid = (long long)((double)s->num_cu * per_cu);
+    if (grid > blocks_for_rays) grid = blocks_for_rays;
+    if (grid < 1) grid = 1;
+    // Every wave resumes the slice of the parked photons that its index names (64 per wave, the kernel's refill); the
+    // launch that parked them put at most 64 per wave of ITS grid: this launch must not be narrower, or slices beyond
+    // its last wave would depend on the claim cursor being asked often enough (ADVICE r3: workgroups_per_cu 4, then 1)
+    if (grid * kBlock < carried) grid = (carried + kBlock - 1) / kBlock;
+    if (n_sets) {
+        long long per_set = grid / n_sets;
+        const long long for_rays = (p->tally_bundle + kBlock - 1) / kBlock;
+        if (per_set > for_rays) per_set = for_rays;
+        if (per_set < 1) per_set = 1;
+        grid = per_set * n_sets;
+        a.set_size = (unsigned int)p->tally_bundle;
+        a.wgs_per_set = (int)per_set;
+        a.set_stride_i = p->tally_stride_i64;
+        a.set_stride_d = p->tally_stride_f64;
     }
+    return grid;
+}
+
+// Carried photons: the stream's two buffers (allocated at first use) -- this launch resumes from one and parks into
+// the other -- and where its predecessor counted what it parked.  Clears `carry_out` for a launch too wide to park.
+int bind_carry(PvtScene* s, PvtScene::Carry& carry, unsigned int* blocks, long long grid, bool carry_in, bool* carry_out, KArgs& a) {
+    if (!s->carry_cap) s->carry_cap = (unsigned int)((long long)s->num_cu * 4 * kBlock);
+    if (grid * kBlock > (long long)s->carry_cap) *carry_out = false;   // an unusually wide launch finishes its own photons
+    const size_t bytes = (size_t)s->carry_cap * (s->d_cd ? kCarryStrideCap : kCarryStride) * 8;
+    for (int q = 0; q < 2; q++)
+        if (!carry.buf[q]) HIP_TRY(hipMalloc(&carry.buf[q], bytes));
+    a.carry_cap = s->carry_cap;
+    a.carry_in = carry.buf[carry.parity ^ 1];
+    a.carry_out = carry.buf[carry.parity];
+    a.carry_in_count = blocks + 4 * ((carry.phase + 2) % 3) + 2;
+    a.carry_flags = (carry_in ? 1 : 0) | (*carry_out ? 2 : 0);
+    return PVT_OK;
+}
+
+// Device emission: the stream's pool of [7][64] doubles per wave of the launch, grown to the widest grid seen.
+int grow_emit_pool(PvtScene* s, size_t slot, long long grid, hipStream_t st, KArgs& a) {
+    const size_t need = (size_t)grid * kWaves * 7 * 64 * sizeof(double);
+    if (s->emit_pool_bytes[slot] < need) {
+        // (growth is rare -- the grid of a stream's launches is stable -- and the launch before this one on the stream may
+        // still be reading the old buffer)
+        if (s->emit_pool[slot]) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(s->emit_pool[slot]); s->emit_pool[slot] = nullptr; s->emit_pool_bytes[slot] = 0; }
+        const size_t usual = (size_t)s->num_cu * 4 * kWaves * 7 * 64 * sizeof(double);
+        const size_t bytes = need < usual ? usual : need;
+        HIP_TRY(hipMalloc(&s->emit_pool[slot], bytes));
+        s->emit_pool_bytes[slot] = bytes;
+    }
+    a.emit_pool = s->emit_pool[slot];
+    return PVT_OK;
+}
+
+#if PVT_STATS
+// developer build: waits for the launch and prints its counters (KArgs::cursor points at them)
+void dump_stats(const KArgs& a, hipStream_t st) {
+    unsigned long long c[32];
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpy(c, a.cursor, 256, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[pvt stats] waves %llu  wave-iterations %llu (drain %llu)  lane-steps %llu (drain %llu)  "
+            "mean live lanes/iter %.1f (bulk %.1f, drain %.1f)  iters/wave %.1f (drain %.1f)\n",
+            c[5], c[1], c[3], c[2], c[4], (double)c[2] / c[1], (double)(c[2] - c[4]) / (double)(c[1] - c[3] + 1e-9),
+            (double)c[4] / (c[3] + 1e-9), (double)c[1] / c[5], (double)c[3] / c[5]);
+    fprintf(stderr, "[pvt stats] solo-wave cycles: refill %llu nodes %llu absorb %llu frame %llu trig %llu surface %llu tally %llu (solo waves %llu)\n",
+            c[9], c[10], c[11], c[12], c[13], c[14], c[15], c[16]);
+    const double bi = (double)(c[1] - c[3]) + 1e-9;
+    if (a.lay.grid_d >= 0)
+        fprintf(stderr, "[pvt stats] grid walk per wave-iteration: cell rounds %.2f  node-test trips %.2f  (lanes per trip %.1f, lanes per cell round %.1f)\n",
+                (double)c[25] / c[1], (double)c[26] / c[1], (double)c[27] / (c[26] + 1e-9), (double)c[28] / (c[25] + 1e-9));
+    if (a.bvh)
+        fprintf(stderr, "[pvt stats] mesh walk per wave-iteration: box trips %.2f (lanes per trip %.1f)  triangle trips %.2f (lanes per trip %.1f);  per lane-step: boxes %.2f triangles %.2f\n",
+                (double)c[25] / c[1], (double)c[26] / (c[25] + 1e-9), (double)c[27] / c[1], (double)c[28] / (c[27] + 1e-9),
+                (double)c[26] / c[2], (double)c[28] / c[2]);
+    fprintf(stderr, "[pvt stats] bulk lanes/iteration: live %.1f absorbed %.1f re-emitted %.1f surface %.1f exit %.1f terminal-selector %.1f terminal %.1f\n",
+            c[17] / bi, c[18] / bi, c[19] / bi, c[20] / bi, c[21] / bi, c[22] / bi, c[23] / bi);
+}
+#endif
+
+// Enqueue ONE trace kernel.  `log_rows` / `log_counts`: the event records of the recorded rays (device memory,
+// null when record_every == 0); counts are cleared here.
+int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
+                 unsigned long long* log_rows, int* log_counts, hipStream_t st, const PvtCaptures* cap = nullptr) {
+    const int slot = slot_of_stream(s, st);
+    if (slot < 0) return PVT_ERR_INVALID;
+    PvtScene::Carry& carry = s->carry[(size_t)slot];
+    const bool carry_in = carry.pending;
+    if (p->n_rays == 0 && !carry_in) return PVT_OK;
+    int rc = carry_in ? check_carried(carry, p) : PVT_OK;
+    if (rc != PVT_OK) return rc;
+    long long n_sets = 0;
+    if ((rc = check_tally_sets(s, p, &n_sets)) != PVT_OK) return rc;
     HIP_TRY(hipSetDevice(s->device));
 
     KArgs a = base_args(s, p);
@@ -509,58 +569,16 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     a.tq_pos = lp.tq_pos;
     a.bins_in_lds = lp.bins_in_lds;
     a.xslots = lp.xslots;
-    const bool tab_lds = lp.tab_lds;
-    if (lp.small_lds) { a.nd_lds = s->nd_small; a.ni_lds = s->ni_small; }
-    size_t lds = lp.bytes;
-    a.meshq_off = -1;
-    a.top_off = 0; a.top_n = 0; a.bvh_top = nullptr;
-    if (a.bvh) {   // mesh walks: the lanes' noted leaves, then the copy of the trees' top levels
-        a.meshq_off = (int)lds;
-        lds += (size_t)s->meshq * kBlock * 4;
-        a.top_off = (int)lds; a.top_n = s->top_n; a.bvh_top = s->d_bvh_top;
-        lds += (size_t)s->top_n * sizeof(pvt::BvhNode);
-        if (lds > s->lds_limit) return fail(PVT_ERR_INVALID, "mesh staging exceeds LDS");
-    }
+    if (lp.tab == Tab::Heads) { a.nd_lds = s->nd_small; a.ni_lds = s->ni_small; }
+    a.meshq_off = lp.meshq_off;
+    a.top_off = lp.top_off; a.top_n = s->top_n; a.bvh_top = s->d_bvh_top;
+    if (a.bvh && lp.total > s->lds_limit) return fail(PVT_ERR_INVALID, "mesh staging exceeds LDS");
 
-    // persistent grid: enough workgroups to fill every CU a few times over,
-    // never more than the rays can feed
-    long long blocks_for_rays = (p->n_rays + (carry_in ? carry.bound : 0) + kBlock - 1) / kBlock;
-    double per_cu = p->workgroups_per_cu > 0 ? (double)p->workgroups_per_cu : 4.0;
-    long long grid = (long long)((double)s->num_cu * per_cu);
-    if (grid > blocks_for_rays) grid = blocks_for_rays;
-    if (grid < 1) grid = 1;
-    // Every wave resumes the slice of the parked photons that its index names (64 per wave, the kernel's refill); the
-    // launch that parked them put at most 64 per wave of ITS grid: this launch must not be narrower, or slices beyond
-    // its last wave would depend on the claim cursor being asked often enough (ADVICE r3: workgroups_per_cu 4, then 1)
-    if (carry_in && grid * kBlock < carry.bound) grid = (carry.bound + kBlock - 1) / kBlock;
-    if (n_sets) {   // a workgroup serves one set: the same total, split evenly over the sets
-        long long per_set = grid / n_sets;
-        const long long for_rays = (p->tally_bundle + kBlock - 1) / kBlock;
-        if (per_set > for_rays) per_set = for_rays;
-        if (per_set < 1) per_set = 1;
-        grid = per_set * n_sets;
-        a.set_size = (unsigned int)p->tally_bundle;
-        a.wgs_per_set = (int)per_set;
-        a.set_stride_i = p->tally_stride_i64;
-        a.set_stride_d = p->tally_stride_f64;
-    }
+    const long long grid = size_grid(s, p, carry_in ? carry.bound : 0, n_sets, a);
     s->last_grid = (int)grid;
-    s->last_lds = (int)lds;
-
-    // carried photons
+    s->last_lds = (int)lp.total;
     bool carry_out = (p->flags & PVT_FLAG_CARRY_OUT) != 0 && !record && !n_sets;
-    if (carry_in || carry_out) {
-        if (!s->carry_cap) s->carry_cap = (unsigned int)((long long)s->num_cu * 4 * kBlock);
-        if (grid * kBlock > (long long)s->carry_cap) carry_out = false;   // an unusually wide launch finishes its own photons
-        const size_t bytes = (size_t)s->carry_cap * (s->d_cd ? kCarryStrideCap : kCarryStride) * 8;
-        for (int q = 0; q < 2; q++)
-            if (!carry.buf[q]) HIP_TRY(hipMalloc(&carry.buf[q], bytes));
-        a.carry_cap = s->carry_cap;
-        a.carry_in = carry.buf[carry.parity ^ 1];
-        a.carry_out = carry.buf[carry.parity];
-        a.carry_in_count = blocks + 4 * ((carry.phase + 2) % 3) + 2;
-        a.carry_flags = (carry_in ? 1 : 0) | (carry_out ? 2 : 0);
-    }
+    if ((carry_in || carry_out) && (rc = bind_carry(s, carry, blocks, grid, carry_in, &carry_out, a)) != PVT_OK) return rc;
 
 #if PVT_TIMELINE
     // developer build: the first kTlLaunches launches after PVT_TIMELINE_FROM each get a region of the stamp buffer;
@@ -576,29 +594,13 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     }
 #endif
     const bool emit = rays == nullptr && s->d_ed != nullptr;
-    if (emit) {
-        const size_t need = (size_t)grid * kWaves * 7 * 64 * sizeof(double);
-        if (s->emit_pool_bytes[(size_t)slot] < need) {
-            // (growth is rare -- the grid of a stream's launches is stable -- and the launch before this one on the stream may
-            // still be reading the old buffer)
-            if (s->emit_pool[(size_t)slot]) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(s->emit_pool[(size_t)slot]); s->emit_pool[(size_t)slot] = nullptr; s->emit_pool_bytes[(size_t)slot] = 0; }
-            const size_t bytes = need < ((size_t)s->num_cu * 4 * kWaves * 7 * 64 * sizeof(double)) ? (size_t)s->num_cu * 4 * kWaves * 7 * 64 * sizeof(double) : need;
-            HIP_TRY(hipMalloc(&s->emit_pool[(size_t)slot], bytes));
-            s->emit_pool_bytes[(size_t)slot] = bytes;
-        }
-        a.emit_pool = s->emit_pool[(size_t)slot];
-    }
-    hipError_t e;
-    s->last_variant = variant_of(s, tab_lds);
-    const int lean = s->last_variant != PVT_VARIANT_LEAN ? kLeanOff : (s->lean_even ? kLeanEven : kLeanSearched);   // (trace_body's LEAN)
-    if (record) {
-        e = tab_lds ? launch_seen<true, 1>(s->n_rec, lean, emit, (int)grid, lds, st, a)
-            : lp.small_lds ? launch_seen<true, 2>(s->n_rec, lean, emit, (int)grid, lds, st, a)
-                           : launch_seen<true, 0>(s->n_rec, lean, emit, (int)grid, lds, st, a);
-    } else {
-        e = tab_lds ? launch_seen<false, 1>(s->n_rec, lean, emit, (int)grid, lds, st, a)
-            : lp.small_lds ? launch_seen<false, 2>(s->n_rec, lean, emit, (int)grid, lds, st, a)
-                           : launch_seen<false, 0>(s->n_rec, lean, emit, (int)grid, lds, st, a);
+    if (emit && (rc = grow_emit_pool(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
+    const Variant v = choose_variant(s, lp, record, emit);
+    s->last_variant = v.family;
+    hipError_t e = hipErrorNotSupported;
+    if (const Kernel kernel = kernel_of(v)) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlock), lp.total, st, a);
+        e = hipGetLastError();
     }
     if (e != hipSuccess) return fail(PVT_ERR_HIP, std::string("trace_kernel launch: ") + hipGetErrorString(e));
     if (!n_sets) carry.phase = (carry.phase + 1) % 3;
@@ -610,27 +612,7 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
         carry.parity ^= 1;
     }
 #if PVT_STATS
-    {
-        unsigned long long c[32];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(c, a.cursor, 256, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[pvt stats] waves %llu  wave-iterations %llu (drain %llu)  lane-steps %llu (drain %llu)  "
-                "mean live lanes/iter %.1f (bulk %.1f, drain %.1f)  iters/wave %.1f (drain %.1f)\n",
-                c[5], c[1], c[3], c[2], c[4], (double)c[2] / c[1], (double)(c[2] - c[4]) / (double)(c[1] - c[3] + 1e-9),
-                (double)c[4] / (c[3] + 1e-9), (double)c[1] / c[5], (double)c[3] / c[5]);
-        fprintf(stderr, "[pvt stats] solo-wave cycles: refill %llu nodes %llu absorb %llu frame %llu trig %llu surface %llu tally %llu (solo waves %llu)\n",
-                c[9], c[10], c[11], c[12], c[13], c[14], c[15], c[16]);
-        const double bi = (double)(c[1] - c[3]) + 1e-9;
-        if (a.lay.grid_d >= 0)
-            fprintf(stderr, "[pvt stats] grid walk per wave-iteration: cell rounds %.2f  node-test trips %.2f  (lanes per trip %.1f, lanes per cell round %.1f)\n",
-                    (double)c[25] / c[1], (double)c[26] / c[1], (double)c[27] / (c[26] + 1e-9), (double)c[28] / (c[25] + 1e-9));
-        if (a.bvh)
-            fprintf(stderr, "[pvt stats] mesh walk per wave-iteration: box trips %.2f (lanes per trip %.1f)  triangle trips %.2f (lanes per trip %.1f);  per lane-step: boxes %.2f triangles %.2f\n",
-                    (double)c[25] / c[1], (double)c[26] / (c[25] + 1e-9), (double)c[27] / c[1], (double)c[28] / (c[27] + 1e-9),
-                    (double)c[26] / c[2], (double)c[28] / c[2]);
-        fprintf(stderr, "[pvt stats] bulk lanes/iteration: live %.1f absorbed %.1f re-emitted %.1f surface %.1f exit %.1f terminal-selector %.1f terminal %.1f\n",
-                c[17] / bi, c[18] / bi, c[19] / bi, c[20] / bi, c[21] / bi, c[22] / bi, c[23] / bi);
-    }
+    dump_stats(a, st);
 #endif
     return PVT_OK;
 }
@@ -775,9 +757,8 @@ int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, c
         // what was planned without the copy must still hold with it (plan_lds reserves the copy first): same table
         // placement, everything inside the LDS of a workgroup
         const LdsPlan tally2 = plan_lds(s, false), hist2 = plan_lds(s, true);
-        const size_t with_top = (size_t)s->meshq * kBlock * 4 + (size_t)s->top_n * sizeof(pvt::BvhNode);
-        if (tally2.ok != tally.ok || hist2.ok != hist.ok || tally2.tab_lds != tally.tab_lds || hist2.tab_lds != hist.tab_lds ||
-            tally2.bytes + with_top > s->lds_limit || hist2.bytes + with_top > s->lds_limit)
+        if (tally2.ok != tally.ok || hist2.ok != hist.ok || tally2.tab != tally.tab || hist2.tab != hist.tab ||
+            tally2.total > s->lds_limit || hist2.total > s->lds_limit)
             return fail(PVT_ERR_INVALID, "internal: the LDS plan of a mesh scene changed when the copy of its trees' top levels was added");
         if (s->top_n > 0) {
             HIP_TRY(hipMalloc(&s->d_bvh_top, top.size() * sizeof(pvt::BvhNode)));
@@ -812,12 +793,7 @@ int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, c
 
 int pvt_trace_device_records(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
                              const PvtEventRecords* rec, void* stream) {
-    int rc = check_trace_args(s, rays, p, tl);
-    if (rc != PVT_OK) return rc;
-    if (p->record_every > 0 && (!rec || !rec->rows || !rec->counts))
-        return fail(PVT_ERR_INVALID, "record_every > 0 needs event records");
-    return trace_launch(s, rays, p, tl, rec ? reinterpret_cast<unsigned long long*>(rec->rows) : nullptr, rec ? rec->counts : nullptr,
-                        reinterpret_cast<hipStream_t>(stream));
+    return pvt_trace_device_capture(s, rays, p, tl, rec, nullptr, stream);
 }
 
 int pvt_trace_device_capture(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
@@ -888,7 +864,7 @@ int pvt_trace_device(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, 
     if (p->n_rays == 0) return PVT_OK;
     HIP_TRY(hipSetDevice(s->device));
     const int slot = slot_of_stream(s, st);
-    if (slot < 0) return fail(PVT_ERR_INVALID, "more than 64 HIP streams are tracing this scene; create one scene per group of streams");
+    if (slot < 0) return PVT_ERR_INVALID;
     const long long every = p->record_every, me = p->max_events;
     const long long nrec = (p->n_rays + every - 1) / every;
     const size_t row_bytes = (size_t)kRecWords * 8;
@@ -1021,7 +997,7 @@ int pvt_scene_launch_info(PvtScene* s, int32_t* grid, int32_t* block, int32_t* l
 int pvt_scene_variant(PvtScene* s) {
     if (!s) return fail(PVT_ERR_INVALID, "null scene");
     if (s->last_variant >= 0) return s->last_variant;
-    return variant_of(s, plan_lds(s, false).tab_lds);
+    return choose_variant(s, plan_lds(s, false), false, false).family;
 }
 
 int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
