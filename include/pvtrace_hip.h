@@ -33,7 +33,10 @@ extern "C" {
 enum {
     PVT_EV_GENERATE = 0, PVT_EV_REFLECT = 1, PVT_EV_TRANSMIT = 2, PVT_EV_ABSORB = 3,
     PVT_EV_NONRADIATIVE = 4, PVT_EV_SCATTER = 5, PVT_EV_EMIT = 6, PVT_EV_EXIT = 7,
-    PVT_EV_REACT = 8, PVT_EV_KILL = 9
+    PVT_EV_REACT = 8, PVT_EV_KILL = 9,
+    /* EXTENSION within v13 (the reference has no such event): absorbed at a surface by a coating's absorptivity
+     * (PvtCoatingAbsorbTables); a terminal surface row */
+    PVT_EV_DETECT = 10
 };
 /* geometry / surface / component / phase / emit-method tags (compiler.py:25-48) */
 enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_MESH = 3 };
@@ -52,6 +55,11 @@ enum {
     PVT_REC_ENTERING = 0, PVT_REC_ESCAPING = 1, PVT_REC_REFLECTED = 2, PVT_REC_LOST = 3,
     PVT_REC_REACTED = 4, PVT_REC_KILLED = 5, PVT_REC_EXIT = 6
 };
+/* EXTENSION within v13: the selector of a recorder that counts the photons a coating of its node absorbed (PVT_EV_DETECT),
+ * from either side; a surface selector owned by the node that was HIT.  Spelled outside the enum above, which lists the
+ * reference's selectors and nothing else (tests/test_golden_units.py holds every constant of that enum to the reference's
+ * dict): the Python side keeps it in recorder.EXTENSION_EVENTS for the same reason. */
+#define PVT_RECX_DETECTED 7
 /* error codes (negative returns) */
 enum {
     PVT_OK = 0,
@@ -363,6 +371,47 @@ typedef struct PvtCaptureTables {
     int64_t capture_rows;                 /* sum of the capacities */
 } PvtCaptureTables;
 
+/* ---- absorbing coatings (extension within v13, passed to pvt_scene_create_absorb) -----------------------------------
+ * coat_absorptivity[k] is the probability A that a photon ARRIVING at a point covered by coating row k is absorbed there
+ * -- per incident photon, like the EQE of a solar cell, not a share of what was not reflected; a row with coat_table[k] >= 0
+ * takes A(lambda, theta) of that table instead, laid out, looked up and clamped as the reflectivity tables of
+ * PvtSceneTables (ctab_*): lambda the photon's current wavelength, theta the angle of incidence.  The contract (the Python
+ * Coating docstring states the same; the kernel and the host tracer both follow it):
+ *  1. R is what the surface branch computes for the point without absorption: Fresnel, or the coating's scalar or table
+ *     value; beyond the critical angle R stays 1 unless the coating's transmission is index matched.
+ *  2. A is the coating's absorptivity at the photon's current wavelength and the angle of incidence the reflectivity table
+ *     uses (the same arc cosine of the same cosine).
+ *  3. One uniform draw u decides, the draw that decides reflection, taken when R > 0 or A > 0: u < R reflects; else
+ *     u < R + A (one double addition) absorbs; else the photon is transmitted.
+ *  4. Where R + A > 1 the absorbed share is 1 - R and nothing is transmitted (Fresnel R near grazing incidence).
+ *  5. Beyond the critical angle on a coating with Fresnel transmission R = 1: the photon is totally reflected and A never
+ *     applies.  An absorber bonded to the surface is reflectivity 0 with index-matched transmission.
+ * An absorbed photon writes one PVT_EV_DETECT row and ends, as after PVT_EV_NONRADIATIVE: hit, container and adjacent as a
+ * REFLECT or TRANSMIT row at that point would have them, the position the hit point, the direction the INCOMING one,
+ * unchanged, the normal as logged for surface events, wavelength, path and clock as at arrival.  A recorder with selector
+ * PVT_RECX_DETECTED on the node that was hit counts it, with facet, source filter, histograms and capture as for the
+ * other surface selectors (its angle from the incoming direction and the normal).  No photon draws an additional random
+ * number: a coating with A = 0 traces bit for bit as one without, and a point with A > 0 whose R is exactly 0 takes the
+ * one draw it would not take otherwise.  A covered point of a rough node behaves as a smooth one, as before.  Launches of
+ * such a scene run the PVT_VARIANT_ROUGH family; the host-buffer entries know no absorbing coatings.  A NULL struct,
+ * n_coatings 0 or every A zero with no table is exactly pvt_scene_create_capture.  A separate struct so that the other
+ * table structs keep the lengths old callers pass. */
+typedef struct PvtCoatingAbsorbTables {
+    int32_t n_coatings;                 /* 0 = none (as a NULL struct), else the scene's n_coatings */
+    int32_t n_tables;                   /* absorptivity tables */
+    const double* coat_absorptivity;    /* (n_coatings) scalar A of each coating row, finite and in [0, 1]; 0 = absorbs nothing */
+    const int32_t* coat_table;          /* (n_coatings) table of each coating row, -1 = its scalar A (NULL when n_tables is 0) */
+    int32_t n_wavelength, n_angle, n_value, reserved;   /* lengths of the three pools */
+    const int32_t* table_nw;            /* (n_tables) wavelengths of the table, >= 1 */
+    const int32_t* table_na;            /* (n_tables) angles of the table, >= 1 */
+    const int32_t* wl_start;            /* (n_tables) first wavelength in `wavelength` */
+    const int32_t* angle_start;         /* (n_tables) first angle in `angle` */
+    const int32_t* value_start;         /* (n_tables) first value in `value`: na x nw, row-major by angle */
+    const double* wavelength;           /* pooled, nm, finite and strictly increasing per table */
+    const double* angle;                /* pooled, degrees in [0, 90], strictly increasing per table */
+    const double* value;                /* pooled absorptivities, finite and in [0, 1] */
+} PvtCoatingAbsorbTables;
+
 /* capture buffers of one launch (DEVICE pointers): `rows` holds sets x capture_rows x PVT_CAPTURE_ROW_WORDS uint64,
  * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle) */
 typedef struct PvtCaptures {
@@ -533,6 +582,15 @@ int pvt_scene_create_capture(const PvtSceneTables* tables, const PvtIndexTables*
                              const PvtCaptureTables* capture_tables, int device, PvtScene** out);
 /* Rows of the scene's captures per tally set (PvtCaptureTables.capture_rows; 0 without captures). */
 int64_t pvt_scene_capture_rows(const PvtScene* scene);
+/* The same with absorbing coatings (NULL, n_coatings 0 or every A zero with no table = none: then exactly
+ * pvt_scene_create_capture).  This is the one entry that knows the recorder selector PVT_RECX_DETECTED: the entries
+ * before it refuse a recorder with it ("recorder selector out of range"), as they refused a selector 7 before it existed;
+ * here such a recorder is accepted also where no coating absorbs, and then counts nothing. */
+int pvt_scene_create_absorb(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                            const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                            const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
+                            const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables, int device,
+                            PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);
@@ -661,7 +719,7 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
  * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
  * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
  * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
- * GRID (many nodes), ROUGH (rough nodes, fields, maps), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing coatings), MESH.  The environment variable PVT_NO_LEAN, read when the scene
  * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */

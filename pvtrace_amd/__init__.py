@@ -10,7 +10,7 @@ from pvtrace_amd.light import (
     Event, Light, Ray, circular_mask, cube_mask, rectangular_mask,
 )
 from pvtrace_amd.material import (
-    Absorber, CoatedSurfaceDelegate, Coating, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
+    Absorber, AbsorptivityTable, CoatedSurfaceDelegate, Coating, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
     Luminophore, Material, NullSurfaceDelegate, PhaseFunctionTable, Reactor, ReflectivityTable,
     RefractiveIndexTable, Scatterer, Surface,
     SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian,

@@ -91,7 +91,8 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
     the objects' own methods.  Order of a step, as there: count it; find the interface; KILL when over `maxsteps` or
     `maxpathlength`; EXIT when the interface is the world's; else ask the container's material whether the photon is
     absorbed on the way (ABSORB, then EMIT / SCATTER and on, or NONRADIATIVE / REACT and out) or reaches the surface,
-    where the hit node's surface reflects or transmits it in that node's frame.  A container whose components carry a
+    where the hit node's surface reflects or transmits it in that node's frame -- or, under an absorbing coating, ends it
+    (DETECT).  A container whose components carry a
     concentration field (`ConcentrationGrid`) is asked in its own frame (`Material.is_absorbed_in / component_at`); every
     other container takes the reference's `is_absorbed / component` and their draws."""
     from pvtrace_amd.material import Luminophore, Reactor, Scatterer, index_at
@@ -140,7 +141,14 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
         skin = hit.geometry.material.surface
         local = ray.representation(root, hit)   # the surface's questions are asked in the frame of the node that is hit
         names["normal"] = hit.vector_to_node(hit.geometry.normal(local.position), root)
-        if skin.is_reflected(local, hit.geometry, container, beyond):
+        if hasattr(skin, "outcome"):   # (a surface of the caller's own answers the reference's two-way question)
+            fate = skin.outcome(local, hit.geometry, container, beyond)
+        else:
+            fate = "reflect" if skin.is_reflected(local, hit.geometry, container, beyond) else "transmit"
+        if fate == "absorb":   # an absorbing coating: the photon ends here, its direction the incoming one
+            yield ray, Event.DETECT, names
+            return
+        if fate == "reflect":
             ray, what = skin.reflect(local, hit.geometry, container, beyond).representation(hit, root), Event.REFLECT
         else:
             ray, what = skin.transmit(local, hit.geometry, container, beyond).representation(hit, root), Event.TRANSMIT
@@ -183,7 +191,7 @@ def step_forward(scene, ray, maxsteps=1000, maxpathlength=np.inf, emit_method="k
         yield from _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method)
         return
     history = _history(scene, ray, maxsteps, emit_method, seed, session)
-    closes_step = {Event.GENERATE, Event.REFLECT, Event.TRANSMIT, Event.EMIT, Event.SCATTER}
+    closes_step = {Event.GENERATE, Event.REFLECT, Event.TRANSMIT, Event.EMIT, Event.SCATTER}   # (DETECT ends the photon)
     for k, (r, event, metadata) in enumerate(history):
         yield (r, event, None if event == Event.GENERATE else metadata)
         if (event in closes_step and r.travelled > maxpathlength and k + 1 < len(history)):

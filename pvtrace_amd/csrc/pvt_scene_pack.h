@@ -339,6 +339,13 @@ struct PackedScene {
     std::vector<int> gi;
     int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, n_ptab = 0, lazy_root = 0;
     int rough_d = -1;   // where the nodes' GGX widths start in the double blob (-1: no node is rough)
+    // absorbing coatings (PvtCoatingAbsorbTables; -1: no coating absorbs).  Both blocks lie BEHIND everything the blobs of a
+    // scene without them hold, so every other offset is what it would be without them, and are read from where the
+    // spectra are read.  cabs_d: in the double blob, one record of kCa doubles (kCa*) per coating row, then the pooled
+    // tables (wavelengths, angles in radians, values).  dcand_i: in the int blob, the candidate tables of the eighth
+    // recorder selector, PVT_RECX_DETECTED -- one block {start, count, bin[6]} per candidate node (NI_CAND; the blocks of
+    // Lay::cand_i keep their seven selectors), then the walked lists; `start` is absolute in the int blob
+    int cabs_d = -1, dcand_i = -1;
     // concentration fields (PvtFieldTables): their own buffer of doubles, read from global memory alone (empty: none).
     // fd[n] = where node n's lattice record starts (-1: none), then the records (kFr* words and one value-table offset
     // per component), then the pooled value tables
@@ -366,7 +373,8 @@ struct PackedScene {
 // Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
 // else is read.
 int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-                    const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp) {
+                    const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
+                    const PvtCoatingAbsorbTables* ab, int max_selector) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -597,6 +605,40 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
         }
         if (cp->capture_rows != rows) return fail(PVT_ERR_INVALID, "capture tables: capture_rows must be the sum of the capacities");
     }
+    // absorbing coatings (PvtCoatingAbsorbTables, pvt_scene_create_absorb): a scalar A per coating row, tables for some
+    if (ab && ab->n_coatings != 0) {
+        if (ab->n_coatings != K || !ab->coat_absorptivity) return fail(PVT_ERR_INVALID, "absorb tables: need one absorptivity per coating");
+        for (int k = 0; k < K; k++) {
+            const double a = ab->coat_absorptivity[k];
+            if (!std::isfinite(a)) return fail(PVT_ERR_INVALID, "absorb tables: absorptivity must be finite");
+            if (!(a >= 0.0 && a <= 1.0)) return fail(PVT_ERR_INVALID, "absorb tables: absorptivity must be within [0, 1]");
+        }
+        const int NT = ab->n_tables;
+        if (NT < 0 || (NT > 0 && (!ab->coat_table || !ab->table_nw || !ab->table_na || !ab->wl_start || !ab->angle_start ||
+                                  !ab->value_start || !ab->wavelength || !ab->angle || !ab->value)))
+            return fail(PVT_ERR_INVALID, "absorb tables: missing arrays");
+        long long total = (long long)K * kCa;
+        for (int j = 0; j < NT; j++) {
+            const long long nw = ab->table_nw[j], na = ab->table_na[j];
+            const long long w0 = ab->wl_start[j], a0 = ab->angle_start[j], v0 = ab->value_start[j];
+            if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > ab->n_wavelength || a0 + na > ab->n_angle ||
+                v0 + nw * na > ab->n_value)
+                return fail(PVT_ERR_INVALID, "absorb tables: axis or value range out of bounds");
+            for (long long i = 0; i < nw; i++)
+                if (!std::isfinite(ab->wavelength[w0 + i]) || (i > 0 && !(ab->wavelength[w0 + i] > ab->wavelength[w0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "absorb tables: wavelengths must be finite and strictly increasing");
+            for (long long i = 0; i < na; i++)
+                if (!(ab->angle[a0 + i] >= 0.0 && ab->angle[a0 + i] <= 90.0) || (i > 0 && !(ab->angle[a0 + i] > ab->angle[a0 + i - 1])))
+                    return fail(PVT_ERR_INVALID, "absorb tables: angles must be strictly increasing, in [0, 90] degrees");
+            for (long long i = 0; i < nw * na; i++)
+                if (!(ab->value[v0 + i] >= 0.0 && ab->value[v0 + i] <= 1.0))
+                    return fail(PVT_ERR_INVALID, "absorb tables: values must be finite and within [0, 1]");
+            total += nw + na + nw * na;
+        }
+        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "absorb tables: more than 2^27 doubles");
+        for (int k = 0; k < K && NT > 0; k++)
+            if (ab->coat_table[k] < -1 || ab->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "absorb tables: coating row names a missing table");
+    }
     for (int n = 0; n < N; n++) {
         if (bad_run(t->comp_start[n], t->comp_count[n], C)) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
         if (K > 0 && bad_run(t->coat_start[n], t->coat_count[n], K)) return fail(PVT_ERR_INVALID, "coating range of a node out of bounds");
@@ -609,7 +651,7 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
     }
     for (int r = 0; r < R; r++) {
         if (t->rec_node[r] < 0 || t->rec_node[r] >= N) return fail(PVT_ERR_INVALID, "recorder on a missing node");
-        if (t->rec_event[r] < 0 || t->rec_event[r] > PVT_REC_EXIT) return fail(PVT_ERR_INVALID, "recorder selector out of range");
+        if (t->rec_event[r] < 0 || t->rec_event[r] > max_selector) return fail(PVT_ERR_INVALID, "recorder selector out of range");
         if (bad_run(t->rec_hist_start[r], t->rec_hist_n[r], H)) return fail(PVT_ERR_INVALID, "histogram range of a recorder out of bounds");
     }
     for (int h = 0; h < H; h++) {   // bins hist_offset + [0, na) (1-D) or + [0, na * nb) (2-D) of the tally
@@ -853,7 +895,9 @@ std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const
 // Recorders grouped by the (node, selector) they listen to.  A facet recorder whose facet has a clearly dominant
 // component, alone in its (axis, sign) bin, goes to the bin table; the rest (no facet, oblique facets, bin collisions)
 // to the walked list, ascending id.
-void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* p) {
+// (`detected`: the blocks and lists of the eighth selector, PVT_RECX_DETECTED, at PackedScene::dcand_i instead -- one block
+// per candidate node, the lists behind the blocks, `start` absolute in the int blob.)
+void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* p, bool detected = false) {
     const int N = t->n_nodes, R = t->n_recorders;
     auto bin_of = [&](int r) -> int {
         if (!t->rec_has_facet[r]) return -1;
@@ -872,15 +916,18 @@ void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* 
             if (f[a] != (a == b / 2 ? (b % 2 ? 1.0 : -1.0) : 0.0)) return false;
         return t->rec_atol[r] >= 0.0;
     };
-    int at = 0;
+    const int sel0 = detected ? PVT_RECX_DETECTED : 0, sel1 = detected ? PVT_RECX_DETECTED + 1 : 7;
+    const int list0 = detected ? p->dcand_i + recs.n_cand * 8 : p->lay.cand_list;
+    int at = detected ? list0 : 0;   // (the lists of Lay::cand_list count from its start)
     for (int node = 0; node < N; node++) {
         if (recs.node_cand[node] < 0) continue;
         // kRecPlain on an entry: the lane need not read the recorder's row at all -- no source filter, and either no
         // facet, or a facet that IS the bin's axis (exactly +-1 on it, zeros elsewhere) on an unrotated box, whose
         // world normals are exactly such unit vectors: |facet - normal| is exactly 0 for every normal of the bin
         const bool exact_normals = t->geom_type[node] == PVT_GEOM_BOX && unrotated(t, node);
-        for (int sel = 0; sel < 7; sel++) {
-            int* rec = p->gi.data() + p->lay.cand_i + (recs.node_cand[node] * 7 + sel) * 8;
+        for (int sel = sel0; sel < sel1; sel++) {
+            int* rec = detected ? p->gi.data() + p->dcand_i + recs.node_cand[node] * 8
+                                : p->gi.data() + p->lay.cand_i + (recs.node_cand[node] * 7 + sel) * 8;
             rec[0] = at;
             int owner[6] = {-1, -1, -1, -1, -1, -1};
             bool clash[6] = {false, false, false, false, false, false};
@@ -897,7 +944,7 @@ void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* 
                 if (!listens(r)) continue;
                 const int b = bin_of(r);
                 if (b >= 0 && !clash[b]) continue;  // served by the bin table
-                p->gi[p->lay.cand_list + at++] = r | ((unfiltered(r) && !t->rec_has_facet[r]) ? kRecPlain : 0);
+                p->gi[(detected ? 0 : list0) + at++] = r | ((unfiltered(r) && !t->rec_has_facet[r]) ? kRecPlain : 0);
             }
             rec[1] = at - rec[0];
         }
@@ -1311,12 +1358,53 @@ void pack_captures(const PvtSceneTables* t, const PvtCaptureTables* cp, PackedSc
     p->capture_rows = cp->capture_rows;
 }
 
+// Absorbing coatings (validated tables; nothing is placed when no coating absorbs): the records and tables of
+// PackedScene::cabs_d appended to the double blob, the candidate tables of the `detected` selector (PackedScene::dcand_i)
+// to the int blob -- behind everything the scene holds without them, so no other offset moves.
+void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, const Records& recs, PackedScene* p) {
+    p->cabs_d = -1;
+    p->dcand_i = -1;
+    if (!ab || ab->n_coatings == 0) return;
+    const int K = t->n_coatings, NT = ab->n_tables;
+    bool any = false;
+    for (int k = 0; k < K; k++) any = any || ab->coat_absorptivity[k] > 0.0 || (NT > 0 && ab->coat_table[k] >= 0);
+    if (!any) return;
+    std::vector<double>& gd = p->gd;
+    p->cabs_d = (int)gd.size();
+    gd.resize(gd.size() + (size_t)K * kCa, 0.0);
+    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
+    std::vector<int> tab_at((size_t)(NT > 0 ? NT : 0), -1);
+    for (int k = 0; k < K; k++) {
+        const int j = NT > 0 ? ab->coat_table[k] : -1;
+        if (j >= 0 && tab_at[(size_t)j] < 0) {   // wavelengths (nm), angles (radians), values: a reflectivity table's layout
+            tab_at[(size_t)j] = (int)gd.size();
+            const int nw = ab->table_nw[j], na = ab->table_na[j];
+            for (int i = 0; i < nw; i++) gd.push_back(ab->wavelength[ab->wl_start[j] + i]);
+            for (int i = 0; i < na; i++) gd.push_back(ab->angle[ab->angle_start[j] + i] * kRadPerDeg);
+            for (int i = 0; i < na * nw; i++) gd.push_back(ab->value[ab->value_start[j] + i]);
+        }
+        double* d = gd.data() + p->cabs_d + (size_t)k * kCa;
+        d[kCaA] = ab->coat_absorptivity[k];
+        d[kCaNw] = j >= 0 ? ab->table_nw[j] : 0;   // 0: no table
+        d[kCaNa] = j >= 0 ? ab->table_na[j] : 0;
+        d[kCaTab] = j >= 0 ? tab_at[(size_t)j] : 0;
+    }
+    gd.push_back(0.0);   // (the blob's spare last element, as before)
+    std::vector<int>& gi = p->gi;
+    p->dcand_i = (int)gi.size();
+    gi.resize(gi.size() + (size_t)recs.n_cand * 8 + (size_t)t->n_recorders + 1, 0);
+    fill_candidates(t, recs, p, true);
+}
+
 // The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the
 // phase-function tables (ph, NULL = none), the nodes' surface roughness (rs, NULL = none) and the concentration fields
-// (fr, NULL = none), the volume maps (mp, NULL = none) and the ray captures (cp, NULL = none) -> *p.  No HIP call.
+// (fr, NULL = none), the volume maps (mp, NULL = none), the ray captures (cp, NULL = none) and the coatings' absorptivities
+// (ab, NULL = none) -> *p.  max_selector: the last recorder selector the calling entry knows (PVT_REC_EXIT before
+// pvt_scene_create_absorb, PVT_RECX_DETECTED there); a recorder beyond it is refused.  No HIP call.
 int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-               const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp, PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs, fr, mp, cp);
+               const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab,
+               int max_selector, PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs, fr, mp, cp, ab, max_selector);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
@@ -1344,6 +1432,7 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     pack_fields(t, fr, p);
     pack_maps(t, mp, p);
     pack_captures(t, cp, p);
+    pack_absorb(t, ab, records, p);
     prove_shortcuts(t, p);
     prove_lean(t, p);
     return PVT_OK;

@@ -99,6 +99,7 @@ struct PvtScene {
     int nd_small = 0, ni_small = 0;   // ... of which everything but the spectra / their guide tables (the blobs' heads)
     int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
     int rough_d = -1;                   // where the nodes' GGX widths start in the double blob (-1: no rough node)
+    int cabs_d = -1, dcand_i = -1;      // absorbing coatings: their records in the double blob, the `detected` candidate tables in the int blob (-1: none)
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
     long long map_slots = 0;            // int64 slots the maps add behind the recorders' bins (pvt_scene_map_slots)
@@ -237,6 +238,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.n_nodes = s->n_nodes; a.root = s->root; a.n_rec = s->n_rec; a.total_bins = s->total_bins;
     a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_rtab = s->n_rtab; a.n_lights = s->n_lights;
     a.rough_d = s->rough_d;
+    a.cabs_d = s->cabs_d; a.dcand_i = s->dcand_i;
     a.fd = s->d_fd;
     a.md = s->d_md;
     a.cap_tab = s->d_cd;
@@ -340,8 +342,9 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.seenw = s->n_rec <= 64 ? 1 : 4;
     v.mesh = s->d_bvh != nullptr;
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
-    // a rough node, a concentration field, a volume map or a captured recorder: the extension family, split as the plain ones
-    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd;
+    // a rough node, a concentration field, a volume map, a captured recorder or an absorbing coating: the extension family,
+    // split as the plain ones
+    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
@@ -650,6 +653,12 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
     return PVT_OK;
 }
 
+// What every pvt_scene_create* entry does.  max_selector: the last recorder selector the entry knows -- PVT_RECX_DETECTED
+// for pvt_scene_create_absorb, PVT_REC_EXIT for the entries from before it, which refuse an eighth selector as they did.
+int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+                 const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
+                 const PvtCoatingAbsorbTables* ab, int max_selector, int device, PvtScene** out);
+
 }  // namespace
 
 extern "C" {
@@ -689,6 +698,22 @@ int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->captu
 int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                              const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                              const PvtCaptureTables* cp, int device, PvtScene** out) {
+    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, PVT_REC_EXIT, device, out);
+}
+
+int pvt_scene_create_absorb(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                            const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
+                            const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, device, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+                 const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
+                 const PvtCoatingAbsorbTables* ab, int max_selector, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -696,7 +721,7 @@ int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, c
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -714,6 +739,7 @@ int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, c
     s->n_nodes = t->n_nodes; s->root = t->root_id; s->n_rec = t->n_recorders;
     s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab; s->n_rtab = packed.n_rtab;
     s->rough_d = packed.rough_d;
+    s->cabs_d = packed.cabs_d; s->dcand_i = packed.dcand_i;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
     s->grid = packed.grid;
@@ -790,6 +816,10 @@ int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, c
     *out = s;
     return PVT_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int pvt_trace_device_records(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, const PvtTallies* tl,
                              const PvtEventRecords* rec, void* stream) {
@@ -1005,7 +1035,7 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, nullptr, PVT_RECX_DETECTED, &packed);
     if (rc != PVT_OK) return rc;
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     return PVT_OK;

@@ -86,6 +86,10 @@ enum { KI_RMODE = 0, KI_TMODE, KI_TNW, KI_TNA, KI_TW, KI_TA, KI_TV, KI };   // K
                                                                  // its axis lengths (KI_TNW = 0: none) and where its wavelengths,
                                                                  // angles (radians) and values (row-major by angle) start in
                                                                  // the double blob, after the spectra
+enum { kCaA = 0, kCaNw, kCaNa, kCaTab, kCa };   // an absorbing scene's record per coating row at KArgs::cabs_d: the scalar
+                                                                 // absorptivity, its table's axis lengths (kCaNw = 0: none) and
+                                                                 // where the table starts in the double blob (wavelengths, angles
+                                                                 // in radians, values row-major by angle)
 
 struct Lay {  // record bases (elements) inside the blobs; spectra follow the records and are
               // addressed by absolute offsets stored in the component records
@@ -161,6 +165,10 @@ struct KArgs {
     // The root is visited LAST and only by the lanes that need its exact distance (0 = off; 1 = box root,
     // 2 = sphere root, `lazy_k` = 1/(2 radius)); see the node loop
     int lazy_root;
+    // Absorbing coatings (pvt_scene_create_absorb): where the coating rows' absorptivity records (kCa*) and tables start in
+    // the double blob, read from where the spectra are read; -1 = no coating absorbs (UF_CABS off).  (It and `dcand_i`
+    // below stand where the struct had four bytes of padding: no other member moves and the argument block keeps its size.)
+    int cabs_d;
     double lazy_k;
     // 1: the scene is one unrotated box inside a lazy root with an empty, unobserved medium; a photon that leaves
     // the box's surface outwards, provably clear of it, is finished (see the surface branch)
@@ -189,6 +197,9 @@ struct KArgs {
     // Mesh walks: the TOP of every tree (pvt_bvh.h: stage_top) is copied to LDS when a launch starts -- `top_n` records
     // from `bvh_top` to byte offset `top_off`; cursors with pvt::kTopFlag set index that copy
     int top_off, top_n;
+    // Absorbing coatings: where the candidate tables of the PVT_RECX_DETECTED selector start in the int blob, behind the
+    // guide tables and read from where those are read; -1 with cabs_d
+    int dcand_i;
     const pvt::BvhNode* bvh_top;
     // Step counters of the scene, always on (pvt_scene_counters): 64 rows (blockIdx & 63) of eight u64 words
     //   [0] wave-iterations: trips of the photon loop in which a wave stepped its lanes
@@ -487,6 +498,19 @@ __device__ __forceinline__ double coat_table_r(const double* wls, int nw, const 
 __device__ __attribute__((noinline)) double coat_table_r_call(const double* wls, int nw, const double* angs, int na,
                                                               const double* vals, double wl, double c1) {
     return coat_table_r(wls, nw, angs, na, vals, wl, c1);
+}
+
+// Absorbing coatings (PvtCoatingAbsorbTables; the Python Coating docstring states the rule): A of coating row `coat` at
+// wavelength `wl` and incidence cosine `c1` -- the row's scalar, or its table walked as coat_table_r walks a reflectivity
+// table.  `tab` is the blob the spectra are read from, `recs` the rows' records (kCa*) in it.  A FUNCTION, like
+// rough_event_call: inlined, the table walk would live in the step loop of every extension variant.
+__device__ __attribute__((noinline)) double coat_absorb_call(const double* tab, const double* recs, int coat, double wl, double c1) {
+    const double* r = recs + coat * kCa;
+    const int nw = (int)r[kCaNw];
+    if (nw == 0) return r[kCaA];
+    const int na = (int)r[kCaNa];
+    const double* wls = tab + (int)r[kCaTab];
+    return coat_table_r(wls, nw, wls + nw, na, wls + nw + na, wl, c1);
 }
 
 // Refractive-index tables n(lambda) (the Python RefractiveIndexTable.at is the same arithmetic): `np` wavelengths, then
@@ -1220,7 +1244,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1230,14 +1254,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.rough_d >= 0 ? 1u << UF_ROUGH : 0u) |   // (only the rough variants read rough_d ...
         (ROUGH && A.fd != nullptr ? 1u << UF_FIELD : 0u) |  // ... and fd ...
         (ROUGH && A.md != nullptr ? 1u << UF_VMAP : 0u) |   // ... and md ...
-        (ROUGH && A.cap_tab != nullptr ? 1u << UF_CAPTURE : 0u);   // ... and cap_tab)
+        (ROUGH && A.cap_tab != nullptr ? 1u << UF_CAPTURE : 0u) |   // ... and cap_tab ...
+        (ROUGH && A.cabs_d >= 0 ? 1u << UF_CABS : 0u);   // ... and cabs_d)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -2979,8 +3004,18 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 }
               }
             }
+            // (scenes with an absorbing coating) A of the coating that covers the point (PvtCoatingAbsorbTables): the draw is
+            // taken when R > 0 or A > 0, and u in [R, R + A) ends the photon here.  Beyond the critical angle on a coating
+            // with Fresnel transmission R is 1 and no u reaches A.
+            double ab = 0.0;
+            if constexpr (ROUGH) {
+                if (uf(UF_CABS) && coat >= 0) {
+                    const double* tab = TAB_LDS == 1 ? T.ld : T.hd;   // (where the spectra are read from)
+                    ab = coat_absorb_call(tab, tab + A.cabs_d, coat, wl, c1);
+                }
+            }
             double u = 1.0;
-            if (r > 0.0 && !rough) u = rng_uniform(rng);
+            if ((r > 0.0 || (ROUGH && ab > 0.0)) && !rough) u = rng_uniform(rng);
             if (rough ? rough_reflect : u < r) {
                 bool lamb = false;
                 if (coat >= 0) lamb = T.iv(L.coat_i + coat * KI + KI_RMODE) == 1;
@@ -3010,6 +3045,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 }
                 ev_kind = PVT_EV_REFLECT;
                 t_sel = (container != hit) ? PVT_REC_REFLECTED : -1;
+            } else if (ROUGH && ab > 0.0 && u < r + ab) {
+                // absorbed by the coating: a terminal surface row with the incoming direction, tallied by the hit node's
+                // `detected` recorders; the lane ends as after NONRADIATIVE
+                ev_kind = PVT_EV_DETECT;
+                t_sel = PVT_RECX_DETECTED;
+                terminal = true;
             } else {
                 bool matched = false;
                 if (coat >= 0) matched = T.iv(L.coat_i + coat * KI + KI_TMODE) == 1;
@@ -3036,7 +3077,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             // g / dn -- below kEps, hence ignored (_kernel.pyx:271-276), whenever g <= kEps/2 * dn; g is formed
             // with the very operations the next step would use (o = pos + t, h = 0.5 * size).  A photon that
             // cannot be cleared this way (grazing departures) simply takes its next step.
-            if (!RECORD && !MESH && uf(UF_FUSE_EXIT) && !terminal && count < k_maxsteps &&
+            // (A photon a coating absorbed was sent nowhere: the test below names the two kinds it is written for.)
+            if (!RECORD && !MESH && uf(UF_FUSE_EXIT) && !terminal && count < k_maxsteps && (!ROUGH || ev_kind != PVT_EV_DETECT) &&
                 (ev_kind == PVT_EV_REFLECT ? container == k_root : adjacent == k_root)) {
                 const V3 lp = local_point();
                 const int gp = hit * ND + ND_PARAMS;
@@ -3077,17 +3119,20 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     listened = cb >= 0;
                     cb = listened ? cb : 0;
                 }
-                const int key = L.cand_i + (cb * 7 + t_sel) * 8;
+                // (the eighth selector, PVT_RECX_DETECTED: its blocks -- one per candidate node -- and lists lie behind the
+                // guide tables at KArgs::dcand_i, its `start` absolute in the int blob)
+                const bool det = ROUGH && t_sel == PVT_RECX_DETECTED;
+                const int key = det ? A.dcand_i + cb * 8 : L.cand_i + (cb * 7 + t_sel) * 8;
                 if (listened) {
-                    cs = T.iv(key);
-                    cn = T.iv(key + 1);
+                    cs = det ? T.si(key) - L.cand_list : T.iv(key);
+                    cn = det ? T.si(key + 1) : T.iv(key + 1);
                 }
                 if (listened && t_normal) {
                     const double ax = pvt_fabs(nrm.x), ay = pvt_fabs(nrm.y), az = pvt_fabs(nrm.z);
                     int b = (ax >= ay && ax >= az) ? (nrm.x > 0.0 ? 1 : 0)
                           : (ay >= az)             ? (nrm.y > 0.0 ? 3 : 2)
                                                    : (nrm.z > 0.0 ? 5 : 4);
-                    rbin = T.iv(key + 2 + b);
+                    rbin = det ? T.si(key + 2 + b) : T.iv(key + 2 + b);
                 }
             }
             // trip t of a lane: its bin recorder first (if any), then its list -- so lanes served by
@@ -3100,7 +3145,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 bool push = false;
                 int push_r = 0;
                 if (j < ntrips) {
-                    const int entry = j < nb ? rbin : T.iv(L.cand_list + cs + j - nb);
+                    const int entry = j < nb ? rbin : (ROUGH && t_sel == PVT_RECX_DETECTED) ? T.si(L.cand_list + cs + j - nb)
+                                                                                           : T.iv(L.cand_list + cs + j - nb);
                     const int r = entry & (kRecPlain - 1);
                     const int ri = L.rec_i + r * RI;
                     bool match = true;

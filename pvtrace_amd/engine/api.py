@@ -268,7 +268,7 @@ class EngineResult:
                     "adjacent": self._node(int(d["adjacent"][row])),
                     "component": self._component(int(d["component"][row])),
                 }
-                if event in (Event.REFLECT, Event.TRANSMIT):
+                if event in (Event.REFLECT, Event.TRANSMIT, Event.DETECT):
                     meta["normal"] = tuple(d["normal"][row].tolist())
                 steps.append((ray, event, meta))
             yield steps
@@ -434,7 +434,8 @@ def _scene_key(compiled, emitter, device):
     h = hashlib.blake2b(digest_size=16)
     h.update(repr(int(device)).encode())
     for name in (compiled.TABLE_FIELDS + (compiled.MAP_TABLE_FIELDS if compiled.has_maps else ())
-                 + (compiled.CAPTURE_TABLE_FIELDS if compiled.has_captures else ())):
+                 + (compiled.CAPTURE_TABLE_FIELDS if compiled.has_captures else ())
+                 + (compiled.ABSORB_TABLE_FIELDS if compiled.has_absorbing_coatings else ())):
         a = np.ascontiguousarray(getattr(compiled, name))
         h.update(a.dtype.str.encode()); h.update(repr(a.shape).encode()); h.update(a.data if a.size else b"")
     h.update(repr((int(compiled.root_id), int(compiled.total_bins))).encode())

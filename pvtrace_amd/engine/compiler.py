@@ -19,7 +19,7 @@ import numbers
 import numpy as np
 
 from pvtrace_amd.engine.recorder import (
-    EVENTS,
+    ALL_EVENTS,
     MAP_EVENTS,
     MAX_CAPTURE_ROWS,
     MAX_MAP_SLOTS,
@@ -246,7 +246,26 @@ class CompiledScene:
         self.coat_table = np.full(ncoat, -1, dtype=_I32)
         ctab = {"index": {}, "nw": [], "na": [], "wl_start": [], "angle_start": [], "value_start": [],
                 "wavelength": [], "angle": [], "value": []}
+        # Absorptivity A(wavelength, angle) of the coatings (Coating(absorptivity=...)): a scalar per coating (0: none) and
+        # the table of those that have one (coat_abs_table: -1 = the scalar), pooled in `atab_*` pools of their own, laid
+        # out like `ctab_*`.  All zeros / empty unless some coating has an absorptivity, and then passed to the library as
+        # PvtCoatingAbsorbTables.
+        self.coat_absorptivity = np.zeros(ncoat, dtype=_F64)
+        self.coat_abs_table = np.full(ncoat, -1, dtype=_I32)
+        atab = {"index": {}, "nw": [], "na": [], "wl_start": [], "angle_start": [], "value_start": [],
+                "wavelength": [], "angle": [], "value": []}
+        self.has_absorbing_coatings = False
         for r, coating in enumerate(coat_rows):
+            absorptivity = getattr(coating, "absorptivity", None)
+            if absorptivity is not None:
+                self.has_absorbing_coatings = True
+                if isinstance(absorptivity, ReflectivityTable):
+                    self.coat_abs_table[r] = self._pool_coating_table(absorptivity, atab)
+                else:
+                    a = float(absorptivity)   # (assigned after construction, perhaps: checked again)
+                    if not 0.0 <= a <= 1.0:
+                        raise UnsupportedSceneError(f"Coating {r}: absorptivity must be in [0, 1], got {absorptivity!r}.")
+                    self.coat_absorptivity[r] = a
             self.coat_facet[r] = coating.facet
             self.coat_lo[r] = [b[0] for b in coating.region]
             self.coat_hi[r] = [b[1] for b in coating.region]
@@ -262,6 +281,11 @@ class CompiledScene:
             setattr(self, f"ctab_{key}", np.array(ctab[key], dtype=_I32))
         for key in ("wavelength", "angle", "value"):
             setattr(self, f"ctab_{key}", np.array(ctab[key], dtype=_F64))
+        self.n_abs_tables = len(atab["nw"])
+        for key in ("nw", "na", "wl_start", "angle_start", "value_start"):
+            setattr(self, f"atab_{key}", np.array(atab[key], dtype=_I32))
+        for key in ("wavelength", "angle", "value"):
+            setattr(self, f"atab_{key}", np.array(atab[key], dtype=_F64))
 
         pool = self._mesh_pool
         self.n_mesh_vertices, self.n_mesh_faces = pool["nv"], pool["nf"]
@@ -543,7 +567,7 @@ class CompiledScene:
         offset = 0
         for r, (node_index, recorder) in enumerate(found):
             self.rec_node[r] = node_index
-            self.rec_event[r] = EVENTS[recorder.event]
+            self.rec_event[r] = ALL_EVENTS[recorder.event]
             if recorder.facet is not None:
                 self.rec_has_facet[r] = 1
                 self.rec_facet[r] = recorder.facet
@@ -732,6 +756,13 @@ class CompiledScene:
     # the captures' tables: part of `tables()` only when a recorder is captured (a scene without lowers to its old tables)
     CAPTURE_TABLE_FIELDS = ("rec_capture_capacity", "rec_capture_start")
 
+    # the absorbing coatings' tables: part of `tables()` only when a coating has an absorptivity (a scene without lowers to
+    # its old tables)
+    ABSORB_TABLE_FIELDS = (
+        "coat_absorptivity", "coat_abs_table", "atab_nw", "atab_na", "atab_wl_start", "atab_angle_start",
+        "atab_value_start", "atab_wavelength", "atab_angle", "atab_value",
+    )
+
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""
         out = {name: getattr(self, name) for name in self.TABLE_FIELDS}
@@ -743,6 +774,8 @@ class CompiledScene:
         if self.has_captures:
             out.update({name: getattr(self, name) for name in self.CAPTURE_TABLE_FIELDS})
             out["capture_rows"] = np.int64(self.capture_rows)
+        if self.has_absorbing_coatings:
+            out.update({name: getattr(self, name) for name in self.ABSORB_TABLE_FIELDS})
         return out
 
     @property

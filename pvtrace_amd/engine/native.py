@@ -122,6 +122,17 @@ class PvtCaptureTables(C.Structure):
     ]
 
 
+class PvtCoatingAbsorbTables(C.Structure):
+    """Absorptivities of a scene's coatings (include/pvtrace_hip.h; pvt_scene_create_absorb)."""
+    _fields_ = [
+        ("n_coatings", C.c_int32), ("n_tables", C.c_int32),
+        ("coat_absorptivity", _p_f64), ("coat_table", _p_i32),
+        ("n_wavelength", C.c_int32), ("n_angle", C.c_int32), ("n_value", C.c_int32), ("reserved", C.c_int32),
+        ("table_nw", _p_i32), ("table_na", _p_i32), ("wl_start", _p_i32), ("angle_start", _p_i32), ("value_start", _p_i32),
+        ("wavelength", _p_f64), ("angle", _p_f64), ("value", _p_f64),
+    ]
+
+
 class PvtCaptures(C.Structure):
     """Capture buffers of one launch (device pointers)."""
     _fields_ = [("rows", C.POINTER(C.c_uint64)), ("cursors", C.POINTER(C.c_int64))]
@@ -355,6 +366,36 @@ def capture_tables_struct(compiled):
     return st, keep
 
 
+def absorb_tables_struct(compiled):
+    """PvtCoatingAbsorbTables over the coatings' absorptivities of a CompiledScene -> (struct or None, keepalive); None when
+    no coating has one (the scene is then created exactly as before)."""
+    if not getattr(compiled, "has_absorbing_coatings", False):
+        return None, {}
+    keep = {}
+
+    def arr(name, dtype):
+        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=dtype)   # never hand out NULL for an empty table
+        keep[name] = a
+        return np_ptr(a)
+
+    st = PvtCoatingAbsorbTables()
+    st.n_coatings = int(compiled.n_coatings)
+    st.n_tables = int(compiled.n_abs_tables)
+    st.coat_absorptivity = arr("coat_absorptivity", np.float64)
+    st.coat_table = arr("coat_abs_table", np.int32)
+    st.n_wavelength = int(compiled.atab_wavelength.shape[0])
+    st.n_angle = int(compiled.atab_angle.shape[0])
+    st.n_value = int(compiled.atab_value.shape[0])
+    for field, name in (("table_nw", "atab_nw"), ("table_na", "atab_na"), ("wl_start", "atab_wl_start"),
+                        ("angle_start", "atab_angle_start"), ("value_start", "atab_value_start")):
+        setattr(st, field, arr(name, np.int32))
+    for field, name in (("wavelength", "atab_wavelength"), ("angle", "atab_angle"), ("value", "atab_value")):
+        setattr(st, field, arr(name, np.float64))
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -439,6 +480,10 @@ def declare_signatures(lib, names):
                                       C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
                                       C.POINTER(PvtCaptureTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_scene_capture_rows": ([vp], C.c_int64),
+        "pvt_scene_create_absorb": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                     C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
+                                     C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables), C.c_int, C.POINTER(vp)],
+                                    C.c_int),
         "pvt_trace_device_capture": ([vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
                                       C.POINTER(PvtEventRecords), C.POINTER(PvtCaptures), vp], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
@@ -500,7 +545,7 @@ ABI_SYMBOLS = (
     "pvt_scene_counters", "pvt_scene_clock", "pvt_scene_launch_span", "pvt_release_cached_memory",
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
-    "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture",
+    "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 
@@ -677,11 +722,13 @@ class DeviceScene:
         ft, fkeep = field_tables_struct(compiled)
         mt, mkeep = map_tables_struct(compiled)
         ct, ckeep = capture_tables_struct(compiled)
+        at, akeep = absorb_tables_struct(compiled)
         handle = C.c_void_p()
-        # (the older pvt_scene_create* entries only forward here, with NULL for the tables they lack)
-        others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct))
-        check(self.lib.pvt_scene_create_capture(C.byref(st), *others, self.device, C.byref(handle)),
-              "pvt_scene_create_capture")
+        # (the older pvt_scene_create* entries do the same with NULL for the tables they lack; this one alone takes a
+        # `detected` recorder)
+        others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct, at))
+        check(self.lib.pvt_scene_create_absorb(C.byref(st), *others, self.device, C.byref(handle)),
+              "pvt_scene_create_absorb")
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a

@@ -32,6 +32,12 @@ EVENTS = {
     )
 }
 
+# selectors the reference does not have (its `EVENTS` above stays the reference's dict, exactly):
+#   surface: detected (absorbed at the node's surface by a coating's absorptivity, from either side; include/pvtrace_hip.h
+#            PVT_RECX_DETECTED)
+EXTENSION_EVENTS = {"detected": 7}
+ALL_EVENTS = {**EVENTS, **EXTENSION_EVENTS}
+
 VOLUME_EVENTS = frozenset(("lost", "reacted", "killed"))
 
 # optional source filter (EXTENSION; the reference's recorders have none, its CLI count
@@ -100,7 +106,8 @@ class Recorder:
 
     name        key of the result in `EngineResult.recorders`
     event       one of `EVENTS`: "entering" / "escaping" / "reflected" at the node's surface,
-                "lost" / "reacted" / "killed" inside it, "exit" on the root
+                "lost" / "reacted" / "killed" inside it, "exit" on the root; or of `EXTENSION_EVENTS`: "detected",
+                absorbed at the node's surface by a coating's absorptivity (`Coating(absorptivity=...)`), from either side
     facet       optional outward world normal a surface interaction must have (each component
                 within `atol`) -- one recorder per face of a box, say
     histograms  `Histogram` / `Heatmap` specs filled by the first matching interaction of a ray
@@ -115,7 +122,7 @@ class Recorder:
 
     def __init__(self, name, event="entering", facet=None, atol=1e-6, histograms=None,
                  source=None, capture=None):
-        _require(event in EVENTS, f"Unknown event {event!r}; use one of {sorted(EVENTS)}")
+        _require(event in EVENTS or event in EXTENSION_EVENTS, f"Unknown event {event!r}; use one of {sorted(EVENTS)}")
         specs = list(histograms or ())
         _require(all(isinstance(spec, (Histogram, Heatmap)) for spec in specs),
                  "histograms must contain Histogram or Heatmap objects.")

@@ -27,6 +27,7 @@ _TRIGGERS = {
     "reacted": (Event.REACT, ("container",)),
     "killed": (Event.KILL, ("container",)),
     "exit": (Event.EXIT, ("hit",)),
+    "detected": (Event.DETECT, ("hit",)),   # absorbed by a coating of the node, from either side (extension)
 }
 _COLUMNS = ("wavelength", "angle", "duration", "pathlength", "x", "y", "z")
 

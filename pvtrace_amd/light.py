@@ -30,6 +30,7 @@ class Event(Enum):
     EXIT = 7
     REACT = 8
     KILL = 9
+    DETECT = 10   # absorbed at a surface by a coating's absorptivity (extension; the reference has no such event)
 
 
 @dataclass(frozen=True)

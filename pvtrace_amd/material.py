@@ -526,6 +526,33 @@ class ReflectivityTable(object):
         return float(r0 + ta * (r1 - r0))
 
 
+# The absorptivity of a coating A(wavelength, angle of incidence) is tabulated by the same class, with the same contract,
+# `at()` and clamping; the alias lets user code say what the numbers are.
+AbsorptivityTable = ReflectivityTable
+
+
+def _coating_sum_exceeds_one(reflectivity, absorptivity):
+    """(wavelength, angle, R, A) of a point where R + A > 1, or None.  A table on either side is evaluated with the other
+    side on the outer product of the union of the wavelength grids and the union of the angle grids: clamped bilinear
+    interpolants take their maximum at such vertices, so the check is exact."""
+    tables = [v for v in (reflectivity, absorptivity) if isinstance(v, ReflectivityTable)]
+    if not tables:
+        r, a = float(reflectivity), float(absorptivity)
+        return (None, None, r, a) if r + a > 1.0 else None
+    wavelengths = np.unique(np.concatenate([t.wavelength for t in tables]))
+    angles = np.unique(np.concatenate([t._angle_axis for t in tables]))
+
+    def at(value, wl, angle):
+        return value.at(wl, angle) if isinstance(value, ReflectivityTable) else float(value)
+
+    for angle in angles:
+        for wl in wavelengths:
+            r, a = at(reflectivity, wl, angle), at(absorptivity, wl, angle)
+            if r + a > 1.0:
+                return float(wl), float(angle), r, a
+    return None
+
+
 class RefractiveIndexTable(object):
     """Refractive index of a material as a table n(wavelength): dispersion.
 
@@ -746,10 +773,33 @@ class Coating(object):
         local frame restricting where on that face it applies (None = unbounded).
     reflectivity : probability of reflection in [0, 1], a `ReflectivityTable` R(wavelength, angle of incidence),
         or None to keep Fresnel.
+    absorptivity : None (the coating absorbs nothing, exactly as before), a probability in [0, 1], or an
+        `AbsorptivityTable` (= `ReflectivityTable`) A(wavelength, angle of incidence): the probability that a photon
+        ARRIVING at a covered point is absorbed there (extension; the reference has no such coating).  It is per
+        incident photon, like the EQE of a solar cell, not a share of the light that was not reflected.
     reflection : "specular" or "lambertian" (cosine-weighted about the outward
         facet normal, in the local frame).
     transmission : "fresnel" (Snell refraction) or "matched" (index-matched:
         direction unchanged, e.g. a perfectly coupled solar cell).
+
+    The rule of an absorbing coating, the same on the host and on the device (include/pvtrace_hip.h,
+    PvtCoatingAbsorbTables, states the same):
+
+    1. R is what the surface computes for the point without absorption: Fresnel, or the coating's scalar or table
+       value; beyond the critical angle R stays 1 unless transmission is "matched".
+    2. A is the coating's absorptivity at the photon's current wavelength and the angle of incidence the
+       reflectivity table uses.
+    3. One uniform draw u decides, the draw that decides reflection, taken when R > 0 or A > 0: u < R reflects; else
+       u < R + A (one double addition) absorbs; else the photon is transmitted.
+    4. Where R + A > 1 the absorbed share is 1 - R and nothing is transmitted (Fresnel R near grazing incidence).
+    5. Beyond the critical angle on a "fresnel" coating R = 1: the photon is totally reflected and A never applies.  An
+       absorber bonded to the surface is `reflectivity=0.0, transmission="matched"`.
+
+    An absorbed photon ends with an `Event.DETECT` row -- a surface row at the hit point, its direction the INCOMING
+    one -- which a recorder with `event="detected"` on the node that was hit counts.  A coating with
+    `absorptivity=0.0` traces bit for bit as one without, and no photon draws an additional random number; a point
+    with A > 0 whose R is exactly 0 takes the one draw it would not take otherwise.  Where both `reflectivity` and
+    `absorptivity` are given, R + A > 1 anywhere is refused.
     """
 
     REFLECTION_MODES = {"specular": 0, "lambertian": 1}
@@ -759,6 +809,7 @@ class Coating(object):
         self,
         facet,
         reflectivity=None,
+        absorptivity=None,
         region=None,
         reflection="specular",
         transmission="fresnel",
@@ -772,6 +823,18 @@ class Coating(object):
             if reflectivity is not None and not 0.0 <= float(reflectivity) <= 1.0:
                 raise ValueError("reflectivity must be in [0, 1], a ReflectivityTable or None")
             self.reflectivity = None if reflectivity is None else float(reflectivity)
+        if isinstance(absorptivity, ReflectivityTable):
+            self.absorptivity = absorptivity
+        else:
+            if absorptivity is not None and not 0.0 <= float(absorptivity) <= 1.0:   # (NaN fails both comparisons)
+                raise ValueError("absorptivity must be in [0, 1], an AbsorptivityTable or None")
+            self.absorptivity = None if absorptivity is None else float(absorptivity)
+        if self.reflectivity is not None and self.absorptivity is not None:
+            over = _coating_sum_exceeds_one(self.reflectivity, self.absorptivity)
+            if over is not None:
+                wl, angle, r, a = over
+                where = "" if wl is None else f" at {wl:g} nm, {angle:g} degrees"
+                raise ValueError(f"reflectivity + absorptivity must not exceed 1: R = {r:g}, A = {a:g}{where}")
         if reflection not in self.REFLECTION_MODES:
             raise ValueError(f"reflection must be one of {sorted(self.REFLECTION_MODES)}")
         if transmission not in self.TRANSMISSION_MODES:
@@ -838,6 +901,19 @@ class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
             return coating.reflectivity.at(ray.wavelength, math.degrees(math.acos(cosang)))
         return coating.reflectivity
 
+    def absorptivity(self, surface, ray, geometry, container, adjacent):
+        """A of the coating covering the hit point at the ray's wavelength and angle of incidence (0 where no coating
+        covers it or the coating absorbs nothing): step 2 of the rule in the `Coating` docstring."""
+        coating = self._match(ray, geometry)
+        a = None if coating is None else getattr(coating, "absorptivity", None)
+        if a is None:
+            return 0.0
+        if isinstance(a, ReflectivityTable):
+            normal = _flipped_normal(geometry, ray)
+            cosang = float(np.clip(np.dot(normal, ray.direction), -1.0, 1.0))
+            return a.at(ray.wavelength, math.degrees(math.acos(cosang)))
+        return a
+
     def transmitted_direction(self, surface, ray, geometry, container, adjacent):
         coating = self._match(ray, geometry)
         if coating is not None and coating.transmission == "matched":
@@ -887,6 +963,22 @@ class Surface(BaseSurface):
         if r == 0.0:
             return False   # (no draw: keeps a seeded sequence in step with the reference's)
         return bool(np.random.uniform() < r)
+
+    def outcome(self, ray, geometry, container, adjacent):
+        """"reflect", "absorb" or "transmit": the three-way decision of a surface whose delegate may absorb (the rule in
+        the `Coating` docstring).  One draw, the one `is_reflected` takes, when R > 0 or A > 0; a delegate without
+        `absorptivity` has A = 0 and this is `is_reflected`, draw for draw."""
+        r = self.delegate.reflectivity(self, ray, geometry, container, adjacent)
+        if not isinstance(r, (int, float)):
+            raise ValueError("Reflectivity must be a number.")
+        absorbs = getattr(self.delegate, "absorptivity", None)
+        a = 0.0 if absorbs is None else float(absorbs(self, ray, geometry, container, adjacent))
+        if r == 0.0 and not a > 0.0:
+            return "transmit"   # (no draw: keeps a seeded sequence in step with the reference's)
+        u = np.random.uniform()
+        if u < r:
+            return "reflect"
+        return "absorb" if a > 0.0 and u < r + a else "transmit"
 
     def _turned(self, ray, which, *where):
         direction = getattr(self.delegate, which)(self, ray, *where)

@@ -217,7 +217,7 @@ def is_end_ray(event, metadata):
     pvtrace/scene/scene.py:32-58) -- what `Scene.simulate(..., queue=q, end_rays=True)` sends to the queue."""
     if event in (Event.EMIT, Event.SCATTER, Event.ABSORB):
         return False
-    if event in (Event.GENERATE, Event.NONRADIATIVE, Event.REACT, Event.KILL, Event.EXIT):
+    if event in (Event.GENERATE, Event.NONRADIATIVE, Event.REACT, Event.KILL, Event.EXIT, Event.DETECT):
         return True
     if event in (Event.REFLECT, Event.TRANSMIT):
         if metadata["hit"] == metadata["adjacent"]:
