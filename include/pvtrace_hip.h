@@ -60,6 +60,36 @@ enum {
  * reference's selectors and nothing else (tests/test_golden_units.py holds every constant of that enum to the reference's
  * dict): the Python side keeps it in recorder.EXTENSION_EVENTS for the same reason. */
 #define PVT_RECX_DETECTED 7
+/* histogram properties (engine/recorder.py:33-41): what hist_prop_a / hist_prop_b name */
+enum {
+    PVT_PROP_WAVELENGTH = 0, PVT_PROP_ANGLE = 1, PVT_PROP_DURATION = 2, PVT_PROP_PATHLENGTH = 3,
+    PVT_PROP_X = 4, PVT_PROP_Y = 5, PVT_PROP_Z = 6
+};
+/* EXTENSION within v13 -- photon event counters.  Spelled outside the enum above for the reason PVT_RECX_DETECTED is; the
+ * Python side keeps them in recorder.EXTENSION_PROPERTIES.  The contract (the Python Histogram and CapturedRays docstrings
+ * state the same; the kernel and engine.tally both follow it):
+ *  1. A photon carries three counters, all zero when a light emits it: emissions, scatterings and reflections, the rows of
+ *     kind PVT_EV_EMIT, PVT_EV_SCATTER and PVT_EV_REFLECT in its history -- REFLECT at every node, from either side, whether
+ *     Fresnel, total internal, coating, rough or Lambertian.
+ *  2. At a matching event a counter's value is the number of such rows that STRICTLY PRECEDE the matching row in the ray's
+ *     full history: the counters describe the photon as it arrives.  A PVT_REC_REFLECTED recorder sees 0 at a ray's first
+ *     reflection.
+ *  3. A histogram bins the counter as the double of the same value, by the rule of every other property.  No moments are
+ *     added: rec_sums keeps its eight sums per recorder.
+ *  4. The counters draw no random number and change no other result: a scene that uses them traces the same histories and
+ *     the same other tallies, bit for bit.
+ *  5. The values do not depend on launch geometry, carrying, tally-set grouping, the device list or which code finishes a
+ *     photon.
+ * A scene COUNTS when a histogram reads a counter or a recorder is captured (word 11 of a captured row holds them).  Its
+ * launches run the PVT_VARIANT_ROUGH family; each counter is a 20-bit field and a step writes at most one row of a counted
+ * kind, so a launch of a counting scene with maxsteps > 2^20 - 1 is refused (PVT_ERR_INVALID) and the loop never
+ * saturates.  Which entry takes the ids: pvt_scene_create_absorb, whose acceptance was extended -- no entry was added.
+ * Every older pvt_scene_create* entry, and with them the host-buffer entries, refuse an id above PVT_PROP_Z ("histogram
+ * property out of range"); before this check nothing looked at the ids, and one past 6 read beyond the kernel's tally
+ * queue. */
+#define PVT_PROPX_EMISSIONS 7
+#define PVT_PROPX_SCATTERINGS 8
+#define PVT_PROPX_REFLECTIONS 9
 /* error codes (negative returns) */
 enum {
     PVT_OK = 0,
@@ -114,7 +144,7 @@ typedef struct PvtSceneTables {
     const int32_t* rec_hist_start;
     const int32_t* rec_hist_n;
     /* histograms */
-    const int32_t* hist_prop_a;
+    const int32_t* hist_prop_a;     /* PVT_PROP_*; PVT_PROPX_* through pvt_scene_create_absorb alone */
     const int32_t* hist_prop_b;     /* -1: 1-D */
     const int32_t* hist_na;
     const int32_t* hist_nb;
@@ -347,7 +377,8 @@ typedef struct PvtMapTables {
  *              of the event's row in the event log
  *   word 10    source (int32, low half: the photon's current source id as the recorder `source` filter sees it, -1 = a
  *              light) | recorder id (high half)
- *   word 11    0
+ *   word 11    the photon's event counters as it arrives at that event (PVT_PROPX_*: the rows that strictly precede the
+ *              event's row), 20 bits each: emissions | scatterings << 20 | reflections << 40
  * Where the rows and cursors live: caller-owned DEVICE memory handed over per launch (PvtCaptures).  Tally set j of a
  * launch owns rows [j capture_rows, (j + 1) capture_rows) and cursors [j n_recorders, (j + 1) n_recorders); cursors[r]
  * (int64, one per recorder; those of recorders without capture stay untouched) counts the first matches of recorder r
@@ -413,7 +444,8 @@ typedef struct PvtCoatingAbsorbTables {
 } PvtCoatingAbsorbTables;
 
 /* capture buffers of one launch (DEVICE pointers): `rows` holds sets x capture_rows x PVT_CAPTURE_ROW_WORDS uint64,
- * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle) */
+ * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle).  Word 11 of a row:
+ * emissions | scatterings << 20 | reflections << 40, the photon's event counters (PVT_PROPX_*) */
 typedef struct PvtCaptures {
     uint64_t* rows;
     int64_t* cursors;
@@ -585,7 +617,9 @@ int64_t pvt_scene_capture_rows(const PvtScene* scene);
 /* The same with absorbing coatings (NULL, n_coatings 0 or every A zero with no table = none: then exactly
  * pvt_scene_create_capture).  This is the one entry that knows the recorder selector PVT_RECX_DETECTED: the entries
  * before it refuse a recorder with it ("recorder selector out of range"), as they refused a selector 7 before it existed;
- * here such a recorder is accepted also where no coating absorbs, and then counts nothing. */
+ * here such a recorder is accepted also where no coating absorbs, and then counts nothing.  By the same rule it is the
+ * one entry that knows the histogram properties PVT_PROPX_* (the photon event counters): the entries before it refuse
+ * them ("histogram property out of range"). */
 int pvt_scene_create_absorb(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                             const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
                             const PvtFieldTables* field_tables, const PvtMapTables* map_tables,

@@ -362,6 +362,7 @@ struct PackedScene {
     long long capture_rows = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
+    bool hist_reads_counter = false;   // a histogram axis is a photon event counter (PVT_PROPX_*)
     bool lean_ok = false;   // see prove_lean: the scene may run the trace_kernel_lean family ...
     bool lean_even = false; // ... and every spectrum its loop reads is a constant or on a proven even grid (its EVEN kernels)
     int grid_dims[3] = {0, 0, 0};
@@ -654,6 +655,12 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
         if (t->rec_event[r] < 0 || t->rec_event[r] > max_selector) return fail(PVT_ERR_INVALID, "recorder selector out of range");
         if (bad_run(t->rec_hist_start[r], t->rec_hist_n[r], H)) return fail(PVT_ERR_INVALID, "histogram range of a recorder out of bounds");
     }
+    // (the kernel reads column `prop` of its tally queue: an id beyond the ones it parks would read past the queue.  The entry
+    // that knows the eighth selector is the one that knows the event counters, PVT_PROPX_*: the newest, as the header says)
+    const int max_prop = max_selector >= PVT_RECX_DETECTED ? PVT_PROPX_REFLECTIONS : PVT_PROP_Z;
+    for (int h = 0; h < H; h++)
+        if (t->hist_prop_a[h] < 0 || t->hist_prop_a[h] > max_prop || t->hist_prop_b[h] < -1 || t->hist_prop_b[h] > max_prop)
+            return fail(PVT_ERR_INVALID, "histogram property out of range");
     for (int h = 0; h < H; h++) {   // bins hist_offset + [0, na) (1-D) or + [0, na * nb) (2-D) of the tally
         const long long bins = (long long)std::max(t->hist_na[h], 0) * (t->hist_prop_b[h] >= 0 ? std::max(t->hist_nb[h], 0) : 1);
         if (bins > 0 && bad_run(t->hist_offset[h], bins, t->total_bins)) return fail(PVT_ERR_INVALID, "histogram bins out of range of total_bins");
@@ -1108,7 +1115,10 @@ int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables*
         int* q = gi.data() + lay.hist_i + h * HI;
         q[HI_PA] = t->hist_prop_a[h]; q[HI_PB] = t->hist_prop_b[h];
         q[HI_NA] = t->hist_na[h]; q[HI_NB] = t->hist_nb[h]; q[HI_OFF] = t->hist_offset[h];
-        if (t->hist_prop_a[h] >= 4 || t->hist_prop_b[h] >= 4) p->hist_reads_position = true;
+        for (const int prop : {t->hist_prop_a[h], t->hist_prop_b[h]}) {
+            if (prop >= PVT_PROP_X && prop <= PVT_PROP_Z) p->hist_reads_position = true;
+            if (prop >= PVT_PROPX_EMISSIONS) p->hist_reads_counter = true;
+        }
     }
     for (int c = 0; c < K; c++) {
         double* d = gd.data() + lay.coat_d + c * KD;

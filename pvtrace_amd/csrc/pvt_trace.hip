@@ -151,6 +151,10 @@ struct PvtScene {
     int grid_dims[3] = {0, 0, 0};
     bool fuse_exit = false;         // see prove_shortcuts: photons leaving the only child's surface outwards are done
     bool hist_reads_position = false;   // a histogram axis is x, y or z
+    bool hist_reads_counter = false;    // a histogram axis is a photon event counter
+    // KArgs::count: 0 the scene counts nothing, 1 its photons carry their event counters (a captured recorder), 2 a histogram
+    // reads one as well
+    int counting() const { return hist_reads_counter ? 2 : d_cd ? 1 : 0; }
     bool lean_ok = false;           // see prove_lean: launches with the tables in LDS run the trace_kernel_lean family ...
     bool lean_even = false;         // ... its EVEN kernels (every spectrum a constant or on a proven even grid)
     int last_variant = -1;          // PVT_VARIANT_* of the last launch (-1: none yet)
@@ -243,6 +247,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.md = s->d_md;
     a.cap_tab = s->d_cd;
     a.cap_total = s->capture_rows;
+    a.count = s->counting();
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -281,6 +286,11 @@ int check_trace_args(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, 
     if ((p->flags & PVT_FLAG_CARRY_OUT) && (p->record_every > 0 || p->tally_bundle > 0))
         return fail(PVT_ERR_INVALID, "PVT_FLAG_CARRY_OUT is for plain tally launches (record_every == 0, no tally sets)");
     if (p->tally_bundle > 0 && p->record_every > 0) return fail(PVT_ERR_INVALID, "tally_bundle needs record_every == 0");
+    // (photon event counters: kCountBits each, no saturation in the loop -- a step writes at most kCountRowsPerStep rows of one
+    // counted kind, a photon takes at most maxsteps steps)
+    if (s->counting() && (long long)p->maxsteps * kCountRowsPerStep > (1LL << kCountBits) - 1)
+        return fail(PVT_ERR_INVALID, "maxsteps too large for the photon event counters of this scene (a counter histogram or a "
+                                     "captured recorder): at most " + std::to_string(((1LL << kCountBits) - 1) / kCountRowsPerStep));
     return PVT_OK;
 }
 
@@ -302,7 +312,8 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     const size_t budget = (64 * 1024 < s->lds_limit ? 64 * 1024 : s->lds_limit) - reserved;  // keep >= 2 workgroups per CU
     // per-wave queues of first crossings awaiting their statistics (kernel: tally_flush)
     lp.tq_pos = s->hist_reads_position ? 1 : 0;
-    const size_t tq_bytes = (size_t)kWaves * kTallyQ * ((lp.tq_pos ? 7 : 4) * 8 + 4);
+    // (a histogram that reads an event counter: one more column, the packed counters)
+    const size_t tq_bytes = (size_t)kWaves * kTallyQ * (((lp.tq_pos ? 7 : 4) + (s->hist_reads_counter ? 1 : 0)) * 8 + 4);
     if (acc_bytes + tq_bytes > lds_limit) { lp.ok = false; return lp; }
     // (PVT_TABLES: developer / test switch -- "global": no tables in LDS, "heads": never the spectra)
     const char* force = getenv("PVT_TABLES");
@@ -315,7 +326,8 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     size_t lds = acc_bytes + tq_bytes + (lp.tab == Tab::Lds ? tab_bytes : lp.tab == Tab::Heads ? small_bytes : 0);
     lp.bins_in_lds = (lds + bins_bytes <= budget) ? 1 : 0;
     if (lp.bins_in_lds) lds += bins_bytes;
-    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->d_cd ? 1 : 0);   // (capture: the global ray index)
+    // (a scene that counts: the global ray index, which captures read, and the event counters)
+    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->counting() ? 2 : 0);
     const size_t xbytes = (size_t)kXSlots * xw * 8;
     // (mesh scenes do without: measured, repacking a draining workgroup buys their launches nothing, and the 9 KB hold
     // another level of the trees' top)
@@ -342,9 +354,9 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.seenw = s->n_rec <= 64 ? 1 : 4;
     v.mesh = s->d_bvh != nullptr;
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
-    // a rough node, a concentration field, a volume map, a captured recorder or an absorbing coating: the extension family,
-    // split as the plain ones
-    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0;
+    // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
+    // photon event counter: the extension family, split as the plain ones
+    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting();
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
@@ -455,7 +467,7 @@ long long size_grid(const PvtScene* s, const PvtTraceParams* p, long long carrie
 int bind_carry(PvtScene* s, PvtScene::Carry& carry, unsigned int* blocks, long long grid, bool carry_in, bool* carry_out, KArgs& a) {
     if (!s->carry_cap) s->carry_cap = (unsigned int)((long long)s->num_cu * 4 * kBlock);
     if (grid * kBlock > (long long)s->carry_cap) *carry_out = false;   // an unusually wide launch finishes its own photons
-    const size_t bytes = (size_t)s->carry_cap * (s->d_cd ? kCarryStrideCap : kCarryStride) * 8;
+    const size_t bytes = (size_t)s->carry_cap * (s->counting() ? kCarryStrideCount : kCarryStride) * 8;
     for (int q = 0; q < 2; q++)
         if (!carry.buf[q]) HIP_TRY(hipMalloc(&carry.buf[q], bytes));
     a.carry_cap = s->carry_cap;
@@ -742,6 +754,7 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     s->cabs_d = packed.cabs_d; s->dcand_i = packed.dcand_i;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
+    s->hist_reads_counter = packed.hist_reads_counter;
     s->grid = packed.grid;
     s->lean_ok = packed.lean_ok && !getenv("PVT_NO_LEAN");   // (PVT_NO_LEAN: the generic family, for parity tests and A/B runs)
     s->lean_even = s->lean_ok && packed.lean_even;

@@ -146,6 +146,11 @@ struct KArgs {
     unsigned long long emit_seed;  // + nothing; global index added per ray
     unsigned long long ray_offset;
     int maxsteps, max_events, emit_method;
+    // Photon event counters (see `hcount` in trace_body): 0 = the scene counts nothing (UF_COUNT off); 1 = every photon
+    // carries its counters -- a recorder is captured, a histogram reads one; 2 = moreover a histogram reads one, and queued
+    // first crossings carry the packed word in one more column.  (It stands where the struct had four bytes of padding:
+    // no other member moves and the argument block keeps its size.)
+    int count;
     long long record_every;
     // outputs
     long long* rec_distinct;
@@ -244,11 +249,16 @@ struct KArgs {
     long long cap_total;
 };
 constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): index, position, direction, wavelength, path, clock,
-                               // source | recorder << 32, 0
+                               // source | recorder << 32, the photon's event counters (kCountBits each)
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
 constexpr int kCarryBase = 14;     // u64 words of a parked photon before its seen-mask
 constexpr int kCarryStride = 18;   // words per parked photon (room for the four-word mask of scenes with > 64 recorders)
-constexpr int kCarryStrideCap = 19;   // ... of a scene with a captured recorder: the photon's global ray index behind the mask
+constexpr int kCarryStrideCount = 20;   // ... of a scene that counts (KArgs::count; a captured recorder makes it one): behind the
+                                        // mask the photon's global ray index (captures read it), then its event counters
+constexpr int kCountBits = 20;   // one event counter in the packed word: emissions | scatterings << 20 | reflections << 40.  A step
+                                 // writes at most ONE row of a counted kind (kCountRowsPerStep), so no counter passes `maxsteps`;
+                                 // the host refuses a launch whose maxsteps could overflow a field: the loop never saturates
+constexpr int kCountRowsPerStep = 1;
 
 // ------------------------------------------------------------------ RNG
 struct Rng {
@@ -990,7 +1000,7 @@ __device__ __attribute__((noinline)) void capture_call(const long long* __restri
                                                        unsigned long long* __restrict__ cursor, bool push, int r,
                                                        unsigned long long index, double px, double py, double pz, double dx,
                                                        double dy, double dz, double wl, double travelled, double duration,
-                                                       int source) {
+                                                       int source, unsigned long long counters) {
     long long cap = 0, start = 0;
     if (push) { cap = tab[2 * r]; start = tab[2 * r + 1]; }
     bool want = cap > 0;
@@ -1015,7 +1025,7 @@ __device__ __attribute__((noinline)) void capture_call(const long long* __restri
                 dst[2] = pack_dd(dx, dy);
                 dst[3] = pack_dd(dz, wl);
                 dst[4] = pack_dd(travelled, duration);
-                dst[5] = u32x4{(unsigned int)source, (unsigned int)r, 0u, 0u};
+                dst[5] = u32x4{(unsigned int)source, (unsigned int)r, (unsigned int)counters, (unsigned int)(counters >> 32)};
             }
             want = false;
         }
@@ -1244,7 +1254,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1255,14 +1265,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.fd != nullptr ? 1u << UF_FIELD : 0u) |  // ... and fd ...
         (ROUGH && A.md != nullptr ? 1u << UF_VMAP : 0u) |   // ... and md ...
         (ROUGH && A.cap_tab != nullptr ? 1u << UF_CAPTURE : 0u) |   // ... and cap_tab ...
-        (ROUGH && A.cabs_d >= 0 ? 1u << UF_CABS : 0u);   // ... and cabs_d)
+        (ROUGH && A.cabs_d >= 0 ? 1u << UF_CABS : 0u) |   // ... and cabs_d ...
+        (ROUGH && A.count >= 1 ? 1u << UF_COUNT : 0u) | (ROUGH && A.count >= 2 ? 1u << UF_TQ_COUNT : 0u);   // ... and count)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -1287,9 +1298,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // per-wave queue of first crossings awaiting their statistics: [4 (+3 with positions)][kTallyQ] doubles
     // + [kTallyQ] recorder ids
     constexpr int kXWords = 14 + SEENW + (RECORD ? 1 : 0);
-    // (scenes with a captured recorder: one more word per slot, the photon's global ray index; the rough variants alone)
-    const int x_words = ROUGH ? kXWords + (A.cap_tab != nullptr ? 1 : 0) : kXWords;
-    const int tq_doubles = A.tq_pos ? 7 : 4;
+    // (scenes that count, KArgs::count -- a captured recorder makes a scene one: two more words per slot, the photon's global ray
+    // index, which captures read, and its event counters; the rough variants alone)
+    const int x_words = ROUGH ? kXWords + (A.count != 0 ? 2 : 0) : kXWords;
+    // (a histogram reads a counter: one more column, the packed word, behind the positions' or in their place)
+    const int tq_doubles = (A.tq_pos ? 7 : 4) + (ROUGH && A.count >= 2 ? 1 : 0);
+    const int tq_count_at = (A.tq_pos ? 7 : 4) * kTallyQ;
     double* const tq_d = reinterpret_cast<double*>(xbuf + x_words * A.xslots) + (threadIdx.x >> 6) * (tq_doubles * kTallyQ);
     int* const tq_r = reinterpret_cast<int*>(reinterpret_cast<double*>(xbuf + x_words * A.xslots) + kWaves * tq_doubles * kTallyQ)
                       + (threadIdx.x >> 6) * kTallyQ;
@@ -1431,6 +1445,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     Rng rng{0, 0, 0, 0};
     int count = 0, source = -1, nev = 0;
     unsigned long long gidx = 0ull;   // (rough variants, UF_CAPTURE) the photon's global ray index, ray_offset + i: travels with it
+    // (rough variants, UF_COUNT) the photon's event counters, kCountBits each: the EMIT | SCATTER << 20 | REFLECT << 40 rows of its
+    // history so far.  Zero at the claim, it travels with the photon wherever `gidx` does and is advanced AFTER a step's
+    // tally, from the kind of the row the step wrote last: a recorder sees the photon as it arrives (include/pvtrace_hip.h)
+    unsigned long long hcount = 0ull;
     unsigned int c_iters = 0u, c_steps = 0u, c_fused = 0u;   // this lane's share of the step counters (KArgs::counters)
     // (tail function) the absorption coefficients this lane's photon met last: container, wavelength bits, sum, first term
     // -- kept in LDS, in the exchange buffer the function was handed its photons through (free once they are read): four
@@ -1526,6 +1544,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 const int na = T.iv(hi_ + HI_NA), nb = T.iv(hi_ + HI_NB);
                 auto prop = [&](int pr) -> double {
                     if (pr < 4) return pr == 0 ? q_wl : pr == 1 ? q_angle : pr == 2 ? q_duration : q_travelled;
+                    if constexpr (ROUGH) {   // an event counter (ids 7-9; the host lets none in unless UF_TQ_COUNT): its field of the packed word
+                        if (pr >= 7)
+                            return (double)(unsigned int)((pvt_d2u(tq_d[tq_count_at + lane]) >> ((pr - 7) * kCountBits)) & ((1u << kCountBits) - 1u));
+                    }
                     return tq_d[pr * kTallyQ + lane];   // x, y, z in the recorder node's frame (A.tq_pos)
                 };
                 const double la = T.dv(hd_ + HD_LO_A), ha = T.dv(hd_ + HD_HI_A);
@@ -1570,6 +1592,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             }
             if constexpr (ROUGH) {
                 if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
+                if (uf(UF_COUNT)) hcount = xbuf[(kXWords + 1) * X + slot];
             }
         }
     }
@@ -1614,7 +1637,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const unsigned int rank = rank_in(need);
                     if (!alive && rank < got) {
                         // photon-major records: one base address, every word at an immediate offset
-                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * (ROUGH && uf(UF_CAPTURE) ? kCarryStrideCap : kCarryStride);
+                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * (ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride);
                         pos = V3{pvt_u2d(src[0]), pvt_u2d(src[1]), pvt_u2d(src[2])};
                         dir = V3{pvt_u2d(src[3]), pvt_u2d(src[4]), pvt_u2d(src[5])};
                         wl = pvt_u2d(src[6]); travelled = pvt_u2d(src[7]); duration = pvt_u2d(src[8]);
@@ -1626,6 +1649,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         for (int w = 0; w < SEENW; w++) seen.w[w] = src[kCarryBase + w];
                         if constexpr (ROUGH) {
                             if (uf(UF_CAPTURE)) gidx = src[kCarryStride];
+                            if (uf(UF_COUNT)) hcount = src[kCarryStride + 1];
                         }
                         nev = 0;
                         alive = true;
@@ -1730,6 +1754,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 nev = 0;
                 if constexpr (ROUGH) {
                     if (uf(UF_CAPTURE)) gidx = A.ray_offset + (unsigned long long)i;
+                    if (uf(UF_COUNT)) hcount = 0ull;
                 }
 #pragma unroll
                 for (int w = 0; w < SEENW; w++) seen.w[w] = 0ull;
@@ -1766,7 +1791,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     b = __builtin_amdgcn_readfirstlane(b);
                     const unsigned int at = b + rank_in(live_mask);
                     if (alive && at < ak->carry_cap) {
-                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * (ROUGH && uf(UF_CAPTURE) ? kCarryStrideCap : kCarryStride);
+                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * (ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride);
                         dst[0] = pvt_d2u(pos.x); dst[1] = pvt_d2u(pos.y); dst[2] = pvt_d2u(pos.z);
                         dst[3] = pvt_d2u(dir.x); dst[4] = pvt_d2u(dir.y); dst[5] = pvt_d2u(dir.z);
                         dst[6] = pvt_d2u(wl); dst[7] = pvt_d2u(travelled); dst[8] = pvt_d2u(duration);
@@ -1776,6 +1801,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         for (int w = 0; w < SEENW; w++) dst[kCarryBase + w] = seen.w[w];
                         if constexpr (ROUGH) {
                             if (uf(UF_CAPTURE)) dst[kCarryStride] = gidx;
+                            if (uf(UF_COUNT)) dst[kCarryStride + 1] = hcount;
                         }
                     }
                     alive = false;   // (the wave leaves through the "nothing alive, no rays left" exit below)
@@ -1839,6 +1865,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         }
                         if constexpr (ROUGH) {
                             if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
+                            if (uf(UF_COUNT)) xbuf[(kXWords + 1) * X + slot] = hcount;
                         }
                     }
                     tail_n = live;   // (the call itself comes after the loop: nothing of the loop is live across it)
@@ -1861,6 +1888,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                     if constexpr (ROUGH) {
                         if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
+                        if (uf(UF_COUNT)) xbuf[(kXWords + 1) * X + slot] = hcount;
                     }
                 }
                 __syncthreads();  // B
@@ -1892,6 +1920,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                     if constexpr (ROUGH) {
                         if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
+                        if (uf(UF_COUNT)) hcount = xbuf[(kXWords + 1) * X + slot];
                     }
                 }
                 // the set shrinks to its `keep` lowest members
@@ -3195,6 +3224,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                             const V3 lpos = local_point();   // position in the recorder node's frame
                             tq_d[4 * kTallyQ + at] = lpos.x; tq_d[5 * kTallyQ + at] = lpos.y; tq_d[6 * kTallyQ + at] = lpos.z;
                         }
+                        if constexpr (ROUGH) {
+                            if (uf(UF_TQ_COUNT)) tq_d[tq_count_at + at] = pvt_u2d(hcount);   // (the counters before this step's row)
+                        }
                     }
                     tq_n += __popcll(pm);
                     if constexpr (ROUGH) {
@@ -3204,13 +3236,22 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                             if (A.cap_rows != nullptr)
                                 capture_call(A.cap_tab, A.cap_rows + (long long)set * A.cap_total * kCapWords,
                                              A.cap_cursor + (long long)set * A.n_rec, push, push_r, gidx, pos.x, pos.y, pos.z,
-                                             dir.x, dir.y, dir.z, wl, travelled, duration, source);
+                                             dir.x, dir.y, dir.z, wl, travelled, duration, source, hcount);
                         }
                     }
                 }
             }
         }
 
+        if constexpr (ROUGH) {
+            // ---- photon event counters: the row this step wrote last, counted now that the tally has seen the photon as it
+            // arrived (an ABSORB row before it is of no counted kind: at most one counted row per step, kCountRowsPerStep)
+            if (uf(UF_COUNT)) {
+                if (alive && ev_kind == PVT_EV_EMIT) hcount += 1ull;
+                if (alive && ev_kind == PVT_EV_SCATTER) hcount += 1ull << kCountBits;
+                if (alive && ev_kind == PVT_EV_REFLECT) hcount += 1ull << (2 * kCountBits);
+            }
+        }
         PVT_MARK(6);  // log + tally
         if (alive && terminal) {
             if constexpr (RECORD) {

@@ -20,10 +20,11 @@ import numpy as np
 
 from pvtrace_amd.engine.recorder import (
     ALL_EVENTS,
+    ALL_PROPERTIES,
+    EXTENSION_PROPERTIES,
     MAP_EVENTS,
     MAX_CAPTURE_ROWS,
     MAX_MAP_SLOTS,
-    PROPERTIES,
     SOURCE_COMPONENT,
     SOURCE_COMPONENTS,
     SOURCE_LIGHTS,
@@ -597,10 +598,10 @@ class CompiledScene:
             for spec in recorder.histograms:
                 if isinstance(spec, Heatmap):
                     a, b = spec.a, spec.b
-                    row = (PROPERTIES[a.prop], PROPERTIES[b.prop], a.bins, b.bins,
+                    row = (ALL_PROPERTIES[a.prop], ALL_PROPERTIES[b.prop], a.bins, b.bins,
                            a.start, a.stop, b.start, b.stop)
                 else:
-                    row = (PROPERTIES[spec.prop], -1, spec.bins, 1,
+                    row = (ALL_PROPERTIES[spec.prop], -1, spec.bins, 1,
                            spec.start, spec.stop, 0.0, 1.0)
                 for key, value in zip(("pa", "pb", "na", "nb", "loa", "hia", "lob", "hib"), row):
                     hist[key].append(value)
@@ -644,6 +645,12 @@ class CompiledScene:
     @property
     def has_captures(self):
         return self.capture_rows > 0
+
+    @property
+    def has_counter_histograms(self):
+        """A histogram axis is a photon event counter (`recorder.EXTENSION_PROPERTIES`)."""
+        first = min(EXTENSION_PROPERTIES.values())
+        return bool(np.any(self.hist_prop_a >= first) or np.any(self.hist_prop_b >= first))
 
     # -- volume maps -----------------------------------------------------
     def _lower_maps(self, root, nodes):

@@ -20,6 +20,12 @@ PROPERTIES = {
     )
 }
 
+# properties the reference does not have (its `PROPERTIES` above stays the reference's dict, exactly): the photon's event
+# counters as it ARRIVES at the matching event -- the EMIT / SCATTER / REFLECT rows that strictly precede the matching row
+# in the ray's history (include/pvtrace_hip.h, "photon event counters"; `Histogram` states the contract)
+EXTENSION_PROPERTIES = {"emissions": 7, "scatterings": 8, "reflections": 9}
+ALL_PROPERTIES = {**PROPERTIES, **EXTENSION_PROPERTIES}
+
 # selector id -> which interaction fires the recorder.
 #   surface: entering (transmit in from outside), escaping (transmit out from
 #            inside), reflected (bounced off the outside)
@@ -64,12 +70,26 @@ class Histogram:
 
     Same constructor and attributes (`prop`, `start`, `stop`, `bins`) as the reference's
     Histogram (pvtrace/engine/recorder.py:56-72); the flattener turns it into one row of the
-    `hist_*` tables."""
+    `hist_*` tables.
+
+    Besides the reference's properties `prop` may be one of `EXTENSION_PROPERTIES`, the photon's event counters.  The contract
+    (include/pvtrace_hip.h, "photon event counters", states the same; the kernel and `engine.tally` both follow it):
+
+    1. A photon carries three counters, all zero when a light emits it: `emissions`, `scatterings` and `reflections`, the
+       rows of kind `Event.EMIT`, `Event.SCATTER` and `Event.REFLECT` in its history -- REFLECT at every node, from either
+       side, whether Fresnel, total internal, coating, rough or Lambertian.
+    2. At a matching event a counter's value is the number of such rows that STRICTLY PRECEDE the matching row in the ray's
+       full history: the counters describe the photon as it arrives.  A `reflected` recorder sees 0 at a ray's first
+       reflection.
+    3. They are integers, binned as the doubles of the same value by the rule of every other property.
+    4. They draw no random number: a scene that uses them traces the same histories and the same other tallies, bit for bit.
+    5. They do not depend on launch geometry, carrying, tally-set grouping, the device list or which code finishes a photon.
+    6. They add no moments: the eight sums of a recorder stay those of wavelength, angle, duration and pathlength."""
 
     __slots__ = ("prop", "start", "stop", "bins")
 
     def __init__(self, prop, start, stop, bins):
-        _require(prop in PROPERTIES, f"Unknown property {prop!r}; use one of {sorted(PROPERTIES)}")
+        _require(prop in ALL_PROPERTIES, f"Unknown property {prop!r}; use one of {sorted(PROPERTIES)}")
         lo, hi, count = float(start), float(stop), int(bins)
         _require(hi > lo, "Histogram range requires stop > start.")
         _require(count >= 1, "Histogram requires at least one bin.")
@@ -149,7 +169,9 @@ class Recorder:
         return "Recorder(%r, event=%r)" % (self.name, self.event)
 
 
-CAPTURE_COLUMNS = ("index", "position", "direction", "wavelength", "pathlength", "duration", "source")
+CAPTURE_COLUMNS = ("index", "position", "direction", "wavelength", "pathlength", "duration", "source",
+                   "emissions", "scatterings", "reflections")
+COUNTER_BITS = 20   # width of one counter in word 11 of a captured row: emissions | scatterings << 20 | reflections << 40
 
 
 class CapturedRays:
@@ -161,6 +183,9 @@ class CapturedRays:
     direction   (n, 3) float64, likewise (the direction the photon leaves the event with)
     wavelength, pathlength, duration   float64, the `wavelength`, `travelled` and `duration` columns of that row
     source      int32, the photon's current source: a component id (`CompiledScene.component_names`), -1 for a light
+    emissions, scatterings, reflections   int32, the photon's event counters as it arrives at that event: the EMIT, SCATTER
+                and REFLECT rows that strictly precede the event's row in the ray's history (`Histogram` states the
+                contract).  Columns built from a dict without them are zeros.
 
     and `matched` (first matches, equal to `recorders[name].rays`), `dropped` = matched - len, `capacity`.
 
@@ -190,6 +215,10 @@ class CapturedRays:
         self.pathlength = np.asarray(columns["pathlength"], dtype=np.float64)[order]
         self.duration = np.asarray(columns["duration"], dtype=np.float64)[order]
         self.source = np.asarray(columns["source"], dtype=np.int32)[order]
+        for counter in EXTENSION_PROPERTIES:
+            values = columns.get(counter)
+            setattr(self, counter, np.zeros(len(self.index), dtype=np.int32) if values is None
+                    else np.asarray(values, dtype=np.int32)[order])
 
     def __len__(self):
         return len(self.index)
@@ -208,9 +237,12 @@ class CapturedRays:
 
         rows = np.ascontiguousarray(rows).reshape(-1, 12)
         f64, i32 = rows.view(np.float64), rows.view(np.int32)
+        packed, mask = rows[:, 11].view(np.int64), (1 << COUNTER_BITS) - 1
         return cls(name, capacity, matched, {
             "index": rows[:, 0].view(np.int64) + int(index_shift), "position": f64[:, 1:4], "direction": f64[:, 4:7],
-            "wavelength": f64[:, 7], "pathlength": f64[:, 8], "duration": f64[:, 9], "source": i32[:, 20]})
+            "wavelength": f64[:, 7], "pathlength": f64[:, 8], "duration": f64[:, 9], "source": i32[:, 20],
+            "emissions": packed & mask, "scatterings": (packed >> COUNTER_BITS) & mask,
+            "reflections": (packed >> (2 * COUNTER_BITS)) & mask})
 
     @classmethod
     def merged(cls, parts):

@@ -9,7 +9,9 @@ the kernel's accumulators exact on sampled runs.
 Organisation: every recorder becomes a `_Probe` bound to its node.  Probes are filed under the
 event kind that can fire them, each history is streamed once through the probes of its events,
 a probe keeps the property values of the FIRST qualifying event of each ray, and moments and
-histograms are computed from those columns with numpy at the end.
+histograms are computed from those columns with numpy at the end.  The stream counts the EMIT, SCATTER
+and REFLECT events of a history as it goes; a probe is offered an event with the counts of the events
+BEFORE it (the photon as it arrives: the contract in `recorder.Histogram`).
 """
 import math
 
@@ -29,7 +31,9 @@ _TRIGGERS = {
     "exit": (Event.EXIT, ("hit",)),
     "detected": (Event.DETECT, ("hit",)),   # absorbed by a coating of the node, from either side (extension)
 }
-_COLUMNS = ("wavelength", "angle", "duration", "pathlength", "x", "y", "z")
+_COLUMNS = ("wavelength", "angle", "duration", "pathlength", "x", "y", "z", "emissions", "scatterings", "reflections")
+# the photon's event counters (recorder.EXTENSION_PROPERTIES): history event -> its place among the three
+_COUNTED = {Event.EMIT: 0, Event.SCATTER: 1, Event.REFLECT: 2}
 
 
 class _Probe:
@@ -58,8 +62,9 @@ class _Probe:
     def _local(self, position):
         return tuple(position) if self.node is self.root else self.root.point_to_node(position, self.node)
 
-    def offer(self, ray, meta, incoming):
-        """Present one history event of this probe's kind; `incoming` is the ray as it arrived."""
+    def offer(self, ray, meta, incoming, counters=(0, 0, 0)):
+        """Present one history event of this probe's kind; `incoming` is the ray as it arrived, `counters` the EMIT,
+        SCATTER and REFLECT events of its history before this one."""
         name = self.node.name
         if any(meta.get(key) != name for key in self.keys) or not self._from_wanted_source(ray.source):
             return
@@ -79,7 +84,7 @@ class _Probe:
             along = ray.direction if self.event == Event.EXIT else incoming.direction
             angle = math.acos(min(abs(float(np.dot(along, normal))), 1.0))
         x, y, z = self._local(ray.position)
-        self.rows.append((ray.wavelength, angle, ray.duration, ray.travelled, x, y, z))
+        self.rows.append((ray.wavelength, angle, ray.duration, ray.travelled, x, y, z) + tuple(counters))
 
     # -- reduction ---------------------------------------------------------------------
     @staticmethod
@@ -125,10 +130,12 @@ def tally_histories(scene, histories):
     for history in histories:
         for probe in probes:
             probe.open = True
-        incoming = None
+        incoming, counters = None, [0, 0, 0]
         for ray, event, meta in history:
             for probe in by_event.get(event, ()):
-                probe.offer(ray, meta or {}, incoming or ray)
+                probe.offer(ray, meta or {}, incoming or ray, counters)
+            if event in _COUNTED:
+                counters[_COUNTED[event]] += 1
             incoming = ray
     return {probe.recorder.name: probe.result() for probe in probes}
 
@@ -136,8 +143,8 @@ def tally_histories(scene, histories):
 def capture_histories(scene, histories, ray_offset=0, indices=None):
     """{recorder name: CapturedRays} from one history per ray: the rays behind each captured recorder's `rays` count, built
     on the host with the matching rule of `tally_histories` (first match per ray, facet tolerance, source filter).  The
-    row of a ray holds the values of the matching history event -- position, direction, wavelength, path, clock -- and
-    the photon's source as a component id of the compiled scene (-1: a light).  History j is ray `ray_offset + j`, or
+    row of a ray holds the values of the matching history event -- position, direction, wavelength, path, clock --, the
+    photon's source as a component id of the compiled scene (-1: a light) and its event counters as it arrives.  History j is ray `ray_offset + j`, or
     `indices[j]`; the capacity is applied in ray order: the first `capacity` matching rays are kept.  The host path for
     `follow(backend="host")` users, and the referee of the kernel's captures.
 
@@ -162,14 +169,17 @@ def capture_histories(scene, histories, ray_offset=0, indices=None):
         index = int(indices[j]) if indices is not None else int(ray_offset) + j
         for probe in probes:
             probe.open = True
-        incoming = None
+        incoming, counters = None, [0, 0, 0]
         for ray, event, meta in history:
             for probe in by_event.get(event, ()):
                 before = len(probe.rows)
-                probe.offer(ray, meta or {}, incoming or ray)
+                probe.offer(ray, meta or {}, incoming or ray, counters)
                 if len(probe.rows) > before:   # this ray's first match
                     kept[id(probe)].append((index, tuple(ray.position), tuple(ray.direction), float(ray.wavelength),
-                                            float(ray.travelled), float(ray.duration), component_ids.get(ray.source, -1)))
+                                            float(ray.travelled), float(ray.duration), component_ids.get(ray.source, -1))
+                                           + tuple(counters))
+            if event in _COUNTED:
+                counters[_COUNTED[event]] += 1
             incoming = ray
     out = {}
     for probe in probes:
@@ -183,7 +193,10 @@ def capture_histories(scene, histories, ray_offset=0, indices=None):
             "wavelength": np.array([r[3] for r in rows], dtype=np.float64),
             "pathlength": np.array([r[4] for r in rows], dtype=np.float64),
             "duration": np.array([r[5] for r in rows], dtype=np.float64),
-            "source": np.array([r[6] for r in rows], dtype=np.int32)})
+            "source": np.array([r[6] for r in rows], dtype=np.int32),
+            "emissions": np.array([r[7] for r in rows], dtype=np.int32),
+            "scatterings": np.array([r[8] for r in rows], dtype=np.int32),
+            "reflections": np.array([r[9] for r in rows], dtype=np.int32)})
     return out
 
 
