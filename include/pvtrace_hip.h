@@ -90,6 +90,26 @@ enum {
 #define PVT_PROPX_EMISSIONS 7
 #define PVT_PROPX_SCATTERINGS 8
 #define PVT_PROPX_REFLECTIONS 9
+/* EXTENSION within v13 -- launch origin: the photon as it was LAUNCHED, where every property above describes it at the
+ * event.  The Python side keeps the ids in recorder.ORIGIN_PROPERTIES.  The contract (the Python Histogram docstring states
+ * the same; the kernel and engine.tally both follow it):
+ *  1. A photon carries four doubles: the wavelength and the position of its GENERATE row, bit for bit what the launch's
+ *     ray arrays (PvtRays) hold for it or what device emission sampled.  They are fixed when a lane claims the ray and
+ *     never recomputed.
+ *  2. The position is in the scene ROOT's frame, the frame lights emit in and the event log stores -- deliberately NOT in
+ *     the recorder node's frame, unlike PVT_PROP_X .. PVT_PROP_Z: bins stay exact against the launch arrays, with no
+ *     transform in between.  For an untransformed node the two frames agree.
+ *  3. A histogram bins them by the unchanged rule of every other property, at the recorder's first match.
+ *  4. They draw no random number and change no other result, bit for bit.
+ *  5. They do not depend on launch geometry, carrying, tally-set grouping, the device list or which code finishes a photon.
+ *  6. No moments are added, no capture columns (the 96-byte row stays), and no recorder filters by them.
+ * A scene that reads one runs the PVT_VARIANT_ROUGH family; reading origins alone makes a scene count nothing (no limit on
+ * maxsteps).  Which entry takes the ids: pvt_scene_create_origin alone.  Every older pvt_scene_create* entry,
+ * pvt_scene_create_absorb included, and the host-buffer entries refuse them ("histogram property out of range"). */
+#define PVT_PROPX_ORIGIN_WAVELENGTH 10
+#define PVT_PROPX_ORIGIN_X 11
+#define PVT_PROPX_ORIGIN_Y 12
+#define PVT_PROPX_ORIGIN_Z 13
 /* error codes (negative returns) */
 enum {
     PVT_OK = 0,
@@ -144,7 +164,7 @@ typedef struct PvtSceneTables {
     const int32_t* rec_hist_start;
     const int32_t* rec_hist_n;
     /* histograms */
-    const int32_t* hist_prop_a;     /* PVT_PROP_*; PVT_PROPX_* through pvt_scene_create_absorb alone */
+    const int32_t* hist_prop_a;     /* PVT_PROP_*; PVT_PROPX_* through the entries that know them */
     const int32_t* hist_prop_b;     /* -1: 1-D */
     const int32_t* hist_na;
     const int32_t* hist_nb;
@@ -621,6 +641,14 @@ int64_t pvt_scene_capture_rows(const PvtScene* scene);
  * one entry that knows the histogram properties PVT_PROPX_* (the photon event counters): the entries before it refuse
  * them ("histogram property out of range"). */
 int pvt_scene_create_absorb(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                            const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                            const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
+                            const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables, int device,
+                            PvtScene** out);
+/* The same, and the one entry that knows the histogram properties PVT_PROPX_ORIGIN_* (the launch origin): same arguments,
+ * same scene for tables without them; pvt_scene_create_absorb and every entry before it refuse those ids ("histogram
+ * property out of range"), as pvt_scene_create_absorb refused an id 10 before they existed. */
+int pvt_scene_create_origin(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                             const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
                             const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
                             const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables, int device,

@@ -362,7 +362,8 @@ struct PackedScene {
     long long capture_rows = 0;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
-    bool hist_reads_counter = false;   // a histogram axis is a photon event counter (PVT_PROPX_*)
+    bool hist_reads_counter = false;   // a histogram axis is a photon event counter (PVT_PROPX_EMISSIONS .. _REFLECTIONS)
+    int origin_mask = 0;   // bit k: a histogram axis is launch-origin property PVT_PROPX_ORIGIN_WAVELENGTH + k
     bool lean_ok = false;   // see prove_lean: the scene may run the trace_kernel_lean family ...
     bool lean_even = false; // ... and every spectrum its loop reads is a constant or on a proven even grid (its EVEN kernels)
     int grid_dims[3] = {0, 0, 0};
@@ -375,7 +376,7 @@ struct PackedScene {
 // else is read.
 int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                     const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                    const PvtCoatingAbsorbTables* ab, int max_selector) {
+                    const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
@@ -655,9 +656,9 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
         if (t->rec_event[r] < 0 || t->rec_event[r] > max_selector) return fail(PVT_ERR_INVALID, "recorder selector out of range");
         if (bad_run(t->rec_hist_start[r], t->rec_hist_n[r], H)) return fail(PVT_ERR_INVALID, "histogram range of a recorder out of bounds");
     }
-    // (the kernel reads column `prop` of its tally queue: an id beyond the ones it parks would read past the queue.  The entry
-    // that knows the eighth selector is the one that knows the event counters, PVT_PROPX_*: the newest, as the header says)
-    const int max_prop = max_selector >= PVT_RECX_DETECTED ? PVT_PROPX_REFLECTIONS : PVT_PROP_Z;
+    // (the kernel reads column `prop` of its tally queue: an id beyond the ones it parks would read past the queue.  max_prop
+    // is the calling entry's: PVT_PROP_Z, PVT_PROPX_REFLECTIONS for pvt_scene_create_absorb, PVT_PROPX_ORIGIN_Z for
+    // pvt_scene_create_origin, as the header says)
     for (int h = 0; h < H; h++)
         if (t->hist_prop_a[h] < 0 || t->hist_prop_a[h] > max_prop || t->hist_prop_b[h] < -1 || t->hist_prop_b[h] > max_prop)
             return fail(PVT_ERR_INVALID, "histogram property out of range");
@@ -1117,7 +1118,8 @@ int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables*
         q[HI_NA] = t->hist_na[h]; q[HI_NB] = t->hist_nb[h]; q[HI_OFF] = t->hist_offset[h];
         for (const int prop : {t->hist_prop_a[h], t->hist_prop_b[h]}) {
             if (prop >= PVT_PROP_X && prop <= PVT_PROP_Z) p->hist_reads_position = true;
-            if (prop >= PVT_PROPX_EMISSIONS) p->hist_reads_counter = true;
+            if (prop >= PVT_PROPX_EMISSIONS && prop <= PVT_PROPX_REFLECTIONS) p->hist_reads_counter = true;
+            if (prop >= PVT_PROPX_ORIGIN_WAVELENGTH && prop <= PVT_PROPX_ORIGIN_Z) p->origin_mask |= 1 << (prop - PVT_PROPX_ORIGIN_WAVELENGTH);
         }
     }
     for (int c = 0; c < K; c++) {
@@ -1410,11 +1412,12 @@ void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, cons
 // phase-function tables (ph, NULL = none), the nodes' surface roughness (rs, NULL = none) and the concentration fields
 // (fr, NULL = none), the volume maps (mp, NULL = none), the ray captures (cp, NULL = none) and the coatings' absorptivities
 // (ab, NULL = none) -> *p.  max_selector: the last recorder selector the calling entry knows (PVT_REC_EXIT before
-// pvt_scene_create_absorb, PVT_RECX_DETECTED there); a recorder beyond it is refused.  No HIP call.
+// pvt_scene_create_absorb, PVT_RECX_DETECTED there); a recorder beyond it is refused.  max_prop: likewise the last histogram
+// property it knows.  No HIP call.
 int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab,
-               int max_selector, PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs, fr, mp, cp, ab, max_selector);
+               int max_selector, int max_prop, PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);

@@ -140,6 +140,9 @@ struct PvtScene {
     // device emission: per stream slot, [7][64] doubles per wave of the launch (KArgs::emit_pool), grown on demand
     std::vector<double*> emit_pool;
     std::vector<size_t> emit_pool_bytes;
+    // launch origin: per stream slot, [lanes of the launch][kOriginWords] doubles (KArgs::origin_store), grown on demand
+    std::vector<double*> origin_store;
+    std::vector<size_t> origin_store_bytes;
     unsigned int carry_cap = 0;    // photons one buffer holds (a launch of more lanes than that does not park)
     int num_cu = 0;
     int last_grid = 0, last_lds = 0;
@@ -152,6 +155,7 @@ struct PvtScene {
     bool fuse_exit = false;         // see prove_shortcuts: photons leaving the only child's surface outwards are done
     bool hist_reads_position = false;   // a histogram axis is x, y or z
     bool hist_reads_counter = false;    // a histogram axis is a photon event counter
+    int origin_mask = 0;                // bit k: a histogram axis is PVT_PROPX_ORIGIN_WAVELENGTH + k (KArgs::origin)
     // KArgs::count: 0 the scene counts nothing, 1 its photons carry their event counters (a captured recorder), 2 a histogram
     // reads one as well
     int counting() const { return hist_reads_counter ? 2 : d_cd ? 1 : 0; }
@@ -225,6 +229,7 @@ void pvt_scene_destroy(PvtScene* s) {
     for (auto* b : s->stage) if (b) (void)hipFree(b);
     for (auto& c : s->carry) for (auto* b : c.buf) if (b) (void)hipFree(b);
     for (auto* b : s->emit_pool) if (b) (void)hipFree(b);
+    for (auto* b : s->origin_store) if (b) (void)hipFree(b);
     delete s;
 }
 
@@ -248,6 +253,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.cap_tab = s->d_cd;
     a.cap_total = s->capture_rows;
     a.count = s->counting();
+    a.origin = s->origin_mask;
     a.n_rays = (unsigned int)p->n_rays;
     a.cursor = s->d_cursor;
     a.counters = s->d_counters;
@@ -273,6 +279,8 @@ int slot_of_stream(PvtScene* s, hipStream_t st) {
         s->carry.emplace_back();
         s->emit_pool.push_back(nullptr);
         s->emit_pool_bytes.push_back(0);
+        s->origin_store.push_back(nullptr);
+        s->origin_store_bytes.push_back(0);
     }
     return (int)slot;
 }
@@ -313,7 +321,8 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     // per-wave queues of first crossings awaiting their statistics (kernel: tally_flush)
     lp.tq_pos = s->hist_reads_position ? 1 : 0;
     // (a histogram that reads an event counter: one more column, the packed counters)
-    const size_t tq_bytes = (size_t)kWaves * kTallyQ * (((lp.tq_pos ? 7 : 4) + (s->hist_reads_counter ? 1 : 0)) * 8 + 4);
+    // (... that reads a launch origin: one more for each origin that IS read, not kOriginWords -- LDS, as for the packed word)
+    const size_t tq_bytes = (size_t)kWaves * kTallyQ * (((lp.tq_pos ? 7 : 4) + (s->hist_reads_counter ? 1 : 0) + __builtin_popcount((unsigned)s->origin_mask)) * 8 + 4);
     if (acc_bytes + tq_bytes > lds_limit) { lp.ok = false; return lp; }
     // (PVT_TABLES: developer / test switch -- "global": no tables in LDS, "heads": never the spectra)
     const char* force = getenv("PVT_TABLES");
@@ -327,7 +336,8 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     lp.bins_in_lds = (lds + bins_bytes <= budget) ? 1 : 0;
     if (lp.bins_in_lds) lds += bins_bytes;
     // (a scene that counts: the global ray index, which captures read, and the event counters)
-    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->counting() ? 2 : 0);
+    // (one that reads a launch origin: its kOriginWords words; a buffer that no longer fits is done without, as ever)
+    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->counting() ? 2 : 0) + (s->origin_mask ? kOriginWords : 0);
     const size_t xbytes = (size_t)kXSlots * xw * 8;
     // (mesh scenes do without: measured, repacking a draining workgroup buys their launches nothing, and the 9 KB hold
     // another level of the trees' top)
@@ -355,8 +365,8 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.mesh = s->d_bvh != nullptr;
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
     // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
-    // photon event counter: the extension family, split as the plain ones
-    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting();
+    // photon event counter or of the launch origin: the extension family, split as the plain ones
+    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
@@ -467,7 +477,7 @@ long long size_grid(const PvtScene* s, const PvtTraceParams* p, long long carrie
 int bind_carry(PvtScene* s, PvtScene::Carry& carry, unsigned int* blocks, long long grid, bool carry_in, bool* carry_out, KArgs& a) {
     if (!s->carry_cap) s->carry_cap = (unsigned int)((long long)s->num_cu * 4 * kBlock);
     if (grid * kBlock > (long long)s->carry_cap) *carry_out = false;   // an unusually wide launch finishes its own photons
-    const size_t bytes = (size_t)s->carry_cap * (s->counting() ? kCarryStrideCount : kCarryStride) * 8;
+    const size_t bytes = (size_t)s->carry_cap * ((s->counting() ? kCarryStrideCount : kCarryStride) + (s->origin_mask ? kOriginWords : 0)) * 8;
     for (int q = 0; q < 2; q++)
         if (!carry.buf[q]) HIP_TRY(hipMalloc(&carry.buf[q], bytes));
     a.carry_cap = s->carry_cap;
@@ -491,6 +501,21 @@ int grow_emit_pool(PvtScene* s, size_t slot, long long grid, hipStream_t st, KAr
         s->emit_pool_bytes[slot] = bytes;
     }
     a.emit_pool = s->emit_pool[slot];
+    return PVT_OK;
+}
+
+// Launch origin: the stream's side store of [grid x kBlock][kOriginWords] doubles, grown to the widest grid seen.  The kernel
+// indexes it by the launch's own grid, so any buffer at least that large serves.
+int grow_origin_store(PvtScene* s, size_t slot, long long grid, hipStream_t st, KArgs& a) {
+    const size_t need = (size_t)grid * kBlock * kOriginWords * sizeof(double);
+    if (s->origin_store_bytes[slot] < need) {   // (rare, and the launch before this one on the stream may still use the old buffer)
+        if (s->origin_store[slot]) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(s->origin_store[slot]); s->origin_store[slot] = nullptr; s->origin_store_bytes[slot] = 0; }
+        const size_t usual = (size_t)s->num_cu * 4 * kBlock * kOriginWords * sizeof(double);
+        const size_t bytes = need < usual ? usual : need;
+        HIP_TRY(hipMalloc(&s->origin_store[slot], bytes));
+        s->origin_store_bytes[slot] = bytes;
+    }
+    a.origin_store = s->origin_store[slot];
     return PVT_OK;
 }
 
@@ -610,6 +635,7 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
 #endif
     const bool emit = rays == nullptr && s->d_ed != nullptr;
     if (emit && (rc = grow_emit_pool(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
+    if (s->origin_mask && (rc = grow_origin_store(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
     const Variant v = choose_variant(s, lp, record, emit);
     s->last_variant = v.family;
     hipError_t e = hipErrorNotSupported;
@@ -667,9 +693,11 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
 
 // What every pvt_scene_create* entry does.  max_selector: the last recorder selector the entry knows -- PVT_RECX_DETECTED
 // for pvt_scene_create_absorb, PVT_REC_EXIT for the entries from before it, which refuse an eighth selector as they did.
+// max_prop: the last histogram property it knows -- PVT_PROP_Z, PVT_PROPX_REFLECTIONS for pvt_scene_create_absorb,
+// PVT_PROPX_ORIGIN_Z for pvt_scene_create_origin.
 int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                  const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, int max_selector, int device, PvtScene** out);
+                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int device, PvtScene** out);
 
 }  // namespace
 
@@ -710,13 +738,19 @@ int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->captu
 int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                              const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                              const PvtCaptureTables* cp, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, PVT_REC_EXIT, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, PVT_REC_EXIT, PVT_PROP_Z, device, out);
 }
 
 int pvt_scene_create_absorb(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, device, out);
+}
+
+int pvt_scene_create_origin(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                            const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
+                            const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, device, out);
 }
 
 }  // extern "C"
@@ -725,7 +759,7 @@ namespace {
 
 int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                  const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, int max_selector, int device, PvtScene** out) {
+                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -733,7 +767,7 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -744,6 +778,7 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     PvtScene* s = owner.p;
     s->stage.reserve(kCursorSlots); s->stage_bytes.reserve(kCursorSlots); s->carry.reserve(kCursorSlots);   // (references stay valid)
     s->emit_pool.reserve(kCursorSlots); s->emit_pool_bytes.reserve(kCursorSlots);
+    s->origin_store.reserve(kCursorSlots); s->origin_store_bytes.reserve(kCursorSlots);
     s->device = device;
     s->lay = packed.lay;
     s->nd = (int)packed.gd.size(); s->ni = (int)packed.gi.size();
@@ -755,6 +790,7 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
     s->hist_reads_counter = packed.hist_reads_counter;
+    s->origin_mask = packed.origin_mask;
     s->grid = packed.grid;
     s->lean_ok = packed.lean_ok && !getenv("PVT_NO_LEAN");   // (PVT_NO_LEAN: the generic family, for parity tests and A/B runs)
     s->lean_even = s->lean_ok && packed.lean_even;
@@ -1048,7 +1084,7 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, nullptr, PVT_RECX_DETECTED, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, nullptr, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, &packed);
     if (rc != PVT_OK) return rc;
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     return PVT_OK;

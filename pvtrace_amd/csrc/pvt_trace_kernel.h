@@ -247,6 +247,11 @@ struct KArgs {
     unsigned long long* cap_rows;
     unsigned long long* cap_cursor;
     long long cap_total;
+    // Launch origin (pvt_scene_create_origin; see `origin_put` in trace_body): bit k = a histogram reads property
+    // PVT_PROPX_ORIGIN_WAVELENGTH + k (0 = none: UF_ORIGIN off) -- queued first crossings carry one more column per bit --
+    // and the launch's side store, [lanes of the launch][kOriginWords] doubles in global memory (null with origin == 0)
+    int origin;
+    double* origin_store;
 };
 constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): index, position, direction, wavelength, path, clock,
                                // source | recorder << 32, the photon's event counters (kCountBits each)
@@ -255,6 +260,10 @@ constexpr int kCarryBase = 14;     // u64 words of a parked photon before its se
 constexpr int kCarryStride = 18;   // words per parked photon (room for the four-word mask of scenes with > 64 recorders)
 constexpr int kCarryStrideCount = 20;   // ... of a scene that counts (KArgs::count; a captured recorder makes it one): behind the
                                         // mask the photon's global ray index (captures read it), then its event counters
+constexpr int kOriginWords = 4;    // the launch origin of a photon: wavelength, x, y, z of its GENERATE row.  A scene that reads one
+                                   // (KArgs::origin) moves them with the photon: kOriginWords more words per exchange-buffer slot
+                                   // and per parked photon, BEHIND the ray index and the counters where the scene counts too --
+                                   // a parked photon takes kCarryStride (+ 2 counting) (+ kOriginWords origin) = 18, 20, 22 or 24 words
 constexpr int kCountBits = 20;   // one event counter in the packed word: emissions | scatterings << 20 | reflections << 40.  A step
                                  // writes at most ONE row of a counted kind (kCountRowsPerStep), so no counter passes `maxsteps`;
                                  // the host refuses a launch whose maxsteps could overflow a field: the loop never saturates
@@ -1254,7 +1263,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1266,14 +1275,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.md != nullptr ? 1u << UF_VMAP : 0u) |   // ... and md ...
         (ROUGH && A.cap_tab != nullptr ? 1u << UF_CAPTURE : 0u) |   // ... and cap_tab ...
         (ROUGH && A.cabs_d >= 0 ? 1u << UF_CABS : 0u) |   // ... and cabs_d ...
-        (ROUGH && A.count >= 1 ? 1u << UF_COUNT : 0u) | (ROUGH && A.count >= 2 ? 1u << UF_TQ_COUNT : 0u);   // ... and count)
+        (ROUGH && A.count >= 1 ? 1u << UF_COUNT : 0u) | (ROUGH && A.count >= 2 ? 1u << UF_TQ_COUNT : 0u) |   // ... and count ...
+        (ROUGH && A.origin != 0 ? 1u << UF_ORIGIN : 0u);   // ... and origin)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -1300,9 +1310,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     constexpr int kXWords = 14 + SEENW + (RECORD ? 1 : 0);
     // (scenes that count, KArgs::count -- a captured recorder makes a scene one: two more words per slot, the photon's global ray
     // index, which captures read, and its event counters; the rough variants alone)
-    const int x_words = ROUGH ? kXWords + (A.count != 0 ? 2 : 0) : kXWords;
-    // (a histogram reads a counter: one more column, the packed word, behind the positions' or in their place)
-    const int tq_doubles = (A.tq_pos ? 7 : 4) + (ROUGH && A.count >= 2 ? 1 : 0);
+    // (scenes that read a launch origin, KArgs::origin: kOriginWords more behind those)
+    const int x_words = ROUGH ? kXWords + (A.count != 0 ? 2 : 0) + (A.origin != 0 ? kOriginWords : 0) : kXWords;
+    // (a histogram reads a counter: one more column, the packed word, behind the positions' or in their place; one reads a
+    // launch origin: one more column behind that for each origin that IS read, in the order of their ids)
+    const int tq_doubles = (A.tq_pos ? 7 : 4) + (ROUGH && A.count >= 2 ? 1 : 0) + (ROUGH ? __builtin_popcount((unsigned int)A.origin & 15u) : 0);
     const int tq_count_at = (A.tq_pos ? 7 : 4) * kTallyQ;
     double* const tq_d = reinterpret_cast<double*>(xbuf + x_words * A.xslots) + (threadIdx.x >> 6) * (tq_doubles * kTallyQ);
     int* const tq_r = reinterpret_cast<int*>(reinterpret_cast<double*>(xbuf + x_words * A.xslots) + kWaves * tq_doubles * kTallyQ)
@@ -1449,6 +1461,44 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // history so far.  Zero at the claim, it travels with the photon wherever `gidx` does and is advanced AFTER a step's
     // tally, from the kind of the row the step wrote last: a recorder sees the photon as it arrives (include/pvtrace_hip.h)
     unsigned long long hcount = 0ull;
+    // (rough variants, UF_ORIGIN) the photon's launch origin -- wavelength, x, y, z of its GENERATE row, the position in the root's
+    // frame as the ray arrays hold it.  Written ONCE, when the lane claims the ray, read only at a recorder's first match, and
+    // moved wherever `gidx` moves: it lives in no register across the loop but in this lane's words of a side store in global
+    // memory (KArgs::origin_store, L2-resident as the emission pool is), [lane of the launch][kOriginWords].  A lane reads back
+    // only what it wrote itself; a photon changes lanes through the exchange buffer or a carry record, which hold the words.
+    // (the kernel re-reads the pointer from its argument segment where it is used, as it does the ray pointers: held, it would
+    // cost the loop two scalar registers.  The tail function reads it through `A`, which there IS the segment, handed over by
+    // the caller: the kernel-argument intrinsic returns garbage inside a called function, see tail_run)
+    auto origin_slot = [&]() __attribute__((always_inline)) -> double* {   // this lane's kOriginWords doubles, side by side
+        double* store;
+        if constexpr (TAIL) {
+            store = A.origin_store;
+        } else {
+            const __attribute__((address_space(4))) KArgs* ak =
+                (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ak));
+            store = ak->origin_store;
+        }
+        return store + ((unsigned long long)blockIdx.x * kBlock + (unsigned long long)threadIdx.x) * kOriginWords;
+    };
+    auto origin_put = [&](double w, double x, double y, double z) __attribute__((always_inline)) {
+        double* o = origin_slot();
+        o[0] = w; o[1] = x; o[2] = y; o[3] = z;
+    };
+    // (KArgs::origin, likewise)
+    auto origin_mask = [&]() __attribute__((always_inline)) -> unsigned int {
+        if constexpr (TAIL) {
+            return (unsigned int)A.origin;
+        } else {
+            const __attribute__((address_space(4))) KArgs* ak =
+                (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ak));
+            return (unsigned int)ak->origin;
+        }
+    };
+    // where the origin words stand behind a slot's / a parked photon's other words (wave-uniform)
+    auto origin_xat = [&]() -> int { return kXWords + (uf(UF_COUNT) ? 2 : 0); };
+    auto origin_cat = [&]() -> int { return uf(UF_COUNT) ? kCarryStrideCount : kCarryStride; };
     unsigned int c_iters = 0u, c_steps = 0u, c_fused = 0u;   // this lane's share of the step counters (KArgs::counters)
     // (tail function) the absorption coefficients this lane's photon met last: container, wavelength bits, sum, first term
     // -- kept in LDS, in the exchange buffer the function was handed its photons through (free once they are read): four
@@ -1544,7 +1594,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 const int na = T.iv(hi_ + HI_NA), nb = T.iv(hi_ + HI_NB);
                 auto prop = [&](int pr) -> double {
                     if (pr < 4) return pr == 0 ? q_wl : pr == 1 ? q_angle : pr == 2 ? q_duration : q_travelled;
-                    if constexpr (ROUGH) {   // an event counter (ids 7-9; the host lets none in unless UF_TQ_COUNT): its field of the packed word
+                    if constexpr (ROUGH) {
+                        // a launch origin (ids 10-13; the host lets none in unless its bit of KArgs::origin is set): its column
+                        if (pr >= 10)
+                            return tq_d[tq_count_at + ((uf(UF_TQ_COUNT) ? 1 : 0) + __builtin_popcount(origin_mask() & ((1u << (pr - 10)) - 1u))) * kTallyQ + lane];
+                        // an event counter (ids 7-9; the host lets none in unless UF_TQ_COUNT): its field of the packed word
                         if (pr >= 7)
                             return (double)(unsigned int)((pvt_d2u(tq_d[tq_count_at + lane]) >> ((pr - 7) * kCountBits)) & ((1u << kCountBits) - 1u));
                     }
@@ -1593,6 +1647,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             if constexpr (ROUGH) {
                 if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
                 if (uf(UF_COUNT)) hcount = xbuf[(kXWords + 1) * X + slot];
+                if (uf(UF_ORIGIN)) {
+                    const int xo = origin_xat();
+                    origin_put(pvt_u2d(xbuf[xo * X + slot]), pvt_u2d(xbuf[(xo + 1) * X + slot]), pvt_u2d(xbuf[(xo + 2) * X + slot]),
+                               pvt_u2d(xbuf[(xo + 3) * X + slot]));
+                }
             }
         }
     }
@@ -1637,7 +1696,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const unsigned int rank = rank_in(need);
                     if (!alive && rank < got) {
                         // photon-major records: one base address, every word at an immediate offset
-                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * (ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride);
+                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * ((ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride) + (ROUGH && uf(UF_ORIGIN) ? kOriginWords : 0));
                         pos = V3{pvt_u2d(src[0]), pvt_u2d(src[1]), pvt_u2d(src[2])};
                         dir = V3{pvt_u2d(src[3]), pvt_u2d(src[4]), pvt_u2d(src[5])};
                         wl = pvt_u2d(src[6]); travelled = pvt_u2d(src[7]); duration = pvt_u2d(src[8]);
@@ -1650,6 +1709,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         if constexpr (ROUGH) {
                             if (uf(UF_CAPTURE)) gidx = src[kCarryStride];
                             if (uf(UF_COUNT)) hcount = src[kCarryStride + 1];
+                            if (uf(UF_ORIGIN)) {
+                                const int co = origin_cat();
+                                origin_put(pvt_u2d(src[co]), pvt_u2d(src[co + 1]), pvt_u2d(src[co + 2]), pvt_u2d(src[co + 3]));
+                            }
                         }
                         nev = 0;
                         alive = true;
@@ -1755,6 +1818,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if constexpr (ROUGH) {
                     if (uf(UF_CAPTURE)) gidx = A.ray_offset + (unsigned long long)i;
                     if (uf(UF_COUNT)) hcount = 0ull;
+                    if (uf(UF_ORIGIN)) origin_put(wl, pos.x, pos.y, pos.z);   // (as read above: the GENERATE row's values)
                 }
 #pragma unroll
                 for (int w = 0; w < SEENW; w++) seen.w[w] = 0ull;
@@ -1791,7 +1855,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     b = __builtin_amdgcn_readfirstlane(b);
                     const unsigned int at = b + rank_in(live_mask);
                     if (alive && at < ak->carry_cap) {
-                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * (ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride);
+                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * ((ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride) + (ROUGH && uf(UF_ORIGIN) ? kOriginWords : 0));
                         dst[0] = pvt_d2u(pos.x); dst[1] = pvt_d2u(pos.y); dst[2] = pvt_d2u(pos.z);
                         dst[3] = pvt_d2u(dir.x); dst[4] = pvt_d2u(dir.y); dst[5] = pvt_d2u(dir.z);
                         dst[6] = pvt_d2u(wl); dst[7] = pvt_d2u(travelled); dst[8] = pvt_d2u(duration);
@@ -1802,6 +1866,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         if constexpr (ROUGH) {
                             if (uf(UF_CAPTURE)) dst[kCarryStride] = gidx;
                             if (uf(UF_COUNT)) dst[kCarryStride + 1] = hcount;
+                            if (uf(UF_ORIGIN)) {
+                                const int co = origin_cat();
+                                const double* o = origin_slot();
+#pragma unroll
+                                for (int k = 0; k < kOriginWords; k++) dst[co + k] = pvt_d2u(o[k]);
+                            }
                         }
                     }
                     alive = false;   // (the wave leaves through the "nothing alive, no rays left" exit below)
@@ -1866,6 +1936,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         if constexpr (ROUGH) {
                             if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
                             if (uf(UF_COUNT)) xbuf[(kXWords + 1) * X + slot] = hcount;
+                            if (uf(UF_ORIGIN)) {
+                                const int xo = origin_xat();
+                                const double* o = origin_slot();
+#pragma unroll
+                                for (int k = 0; k < kOriginWords; k++) xbuf[(xo + k) * X + slot] = pvt_d2u(o[k]);
+                            }
                         }
                     }
                     tail_n = live;   // (the call itself comes after the loop: nothing of the loop is live across it)
@@ -1889,6 +1965,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     if constexpr (ROUGH) {
                         if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
                         if (uf(UF_COUNT)) xbuf[(kXWords + 1) * X + slot] = hcount;
+                        if (uf(UF_ORIGIN)) {
+                            const int xo = origin_xat();
+                            const double* o = origin_slot();
+#pragma unroll
+                            for (int k = 0; k < kOriginWords; k++) xbuf[(xo + k) * X + slot] = pvt_d2u(o[k]);
+                        }
                     }
                 }
                 __syncthreads();  // B
@@ -1921,6 +2003,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     if constexpr (ROUGH) {
                         if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
                         if (uf(UF_COUNT)) hcount = xbuf[(kXWords + 1) * X + slot];
+                        if (uf(UF_ORIGIN)) {
+                            const int xo = origin_xat();
+                            origin_put(pvt_u2d(xbuf[xo * X + slot]), pvt_u2d(xbuf[(xo + 1) * X + slot]), pvt_u2d(xbuf[(xo + 2) * X + slot]),
+                                       pvt_u2d(xbuf[(xo + 3) * X + slot]));
+                        }
                     }
                 }
                 // the set shrinks to its `keep` lowest members
@@ -3226,6 +3313,14 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         }
                         if constexpr (ROUGH) {
                             if (uf(UF_TQ_COUNT)) tq_d[tq_count_at + at] = pvt_u2d(hcount);   // (the counters before this step's row)
+                            if (uf(UF_ORIGIN)) {   // the origins that are read, each in its column behind the counters'
+                                const double* o = origin_slot();
+                                const unsigned int read = origin_mask();
+                                int col = tq_count_at + (uf(UF_TQ_COUNT) ? kTallyQ : 0);
+#pragma unroll
+                                for (int k = 0; k < kOriginWords; k++)
+                                    if ((read >> k) & 1u) { tq_d[col + at] = o[k]; col += kTallyQ; }
+                            }
                         }
                     }
                     tq_n += __popcll(pm);

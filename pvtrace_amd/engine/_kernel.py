@@ -85,6 +85,14 @@ def _host_buffer_scene(compiled):
             "The scene has a histogram of a photon event counter (emissions, scatterings, reflections), which the "
             "host-buffer trace_bundle entry (the reference's interface) cannot take; trace it with engine.simulate."
         )
+    if int(getattr(compiled, "origin_mask", 0)) != 0:
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has a histogram of a launch-origin property (origin_wavelength, origin_x, origin_y, origin_z), "
+            "which the host-buffer trace_bundle entry (the reference's interface) cannot take; trace it with "
+            "engine.simulate."
+        )
     if int(getattr(compiled, "n_ri_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 

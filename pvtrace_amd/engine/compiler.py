@@ -20,11 +20,12 @@ import numpy as np
 
 from pvtrace_amd.engine.recorder import (
     ALL_EVENTS,
-    ALL_PROPERTIES,
     EXTENSION_PROPERTIES,
+    HISTOGRAM_PROPERTIES,
     MAP_EVENTS,
     MAX_CAPTURE_ROWS,
     MAX_MAP_SLOTS,
+    ORIGIN_PROPERTIES,
     SOURCE_COMPONENT,
     SOURCE_COMPONENTS,
     SOURCE_LIGHTS,
@@ -598,10 +599,10 @@ class CompiledScene:
             for spec in recorder.histograms:
                 if isinstance(spec, Heatmap):
                     a, b = spec.a, spec.b
-                    row = (ALL_PROPERTIES[a.prop], ALL_PROPERTIES[b.prop], a.bins, b.bins,
+                    row = (HISTOGRAM_PROPERTIES[a.prop], HISTOGRAM_PROPERTIES[b.prop], a.bins, b.bins,
                            a.start, a.stop, b.start, b.stop)
                 else:
-                    row = (ALL_PROPERTIES[spec.prop], -1, spec.bins, 1,
+                    row = (HISTOGRAM_PROPERTIES[spec.prop], -1, spec.bins, 1,
                            spec.start, spec.stop, 0.0, 1.0)
                 for key, value in zip(("pa", "pb", "na", "nb", "loa", "hia", "lob", "hib"), row):
                     hist[key].append(value)
@@ -649,8 +650,19 @@ class CompiledScene:
     @property
     def has_counter_histograms(self):
         """A histogram axis is a photon event counter (`recorder.EXTENSION_PROPERTIES`)."""
-        first = min(EXTENSION_PROPERTIES.values())
-        return bool(np.any(self.hist_prop_a >= first) or np.any(self.hist_prop_b >= first))
+        first, last = min(EXTENSION_PROPERTIES.values()), max(EXTENSION_PROPERTIES.values())
+        return bool(np.any((self.hist_prop_a >= first) & (self.hist_prop_a <= last))
+                    or np.any((self.hist_prop_b >= first) & (self.hist_prop_b <= last)))
+
+    @property
+    def origin_mask(self):
+        """Which launch-origin properties (`recorder.ORIGIN_PROPERTIES`) some histogram axis reads: bit k for the k-th of
+        origin_wavelength, origin_x, origin_y, origin_z; 0 = none."""
+        first, mask = min(ORIGIN_PROPERTIES.values()), 0
+        for k in range(len(ORIGIN_PROPERTIES)):
+            if np.any(self.hist_prop_a == first + k) or np.any(self.hist_prop_b == first + k):
+                mask |= 1 << k
+        return mask
 
     # -- volume maps -----------------------------------------------------
     def _lower_maps(self, root, nodes):

@@ -484,6 +484,10 @@ def declare_signatures(lib, names):
                                      C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
                                      C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables), C.c_int, C.POINTER(vp)],
                                     C.c_int),
+        "pvt_scene_create_origin": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                     C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
+                                     C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables), C.c_int, C.POINTER(vp)],
+                                    C.c_int),
         "pvt_trace_device_capture": ([vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
                                       C.POINTER(PvtEventRecords), C.POINTER(PvtCaptures), vp], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
@@ -546,6 +550,7 @@ ABI_SYMBOLS = (
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
+    "pvt_scene_create_origin",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 
@@ -725,10 +730,10 @@ class DeviceScene:
         at, akeep = absorb_tables_struct(compiled)
         handle = C.c_void_p()
         # (the older pvt_scene_create* entries do the same with NULL for the tables they lack; this one alone takes a
-        # `detected` recorder)
+        # `detected` recorder; pvt_scene_create_origin is that entry with the launch-origin histogram properties accepted)
         others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct, at))
-        check(self.lib.pvt_scene_create_absorb(C.byref(st), *others, self.device, C.byref(handle)),
-              "pvt_scene_create_absorb")
+        check(self.lib.pvt_scene_create_origin(C.byref(st), *others, self.device, C.byref(handle)),
+              "pvt_scene_create_origin")
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a

@@ -26,6 +26,13 @@ PROPERTIES = {
 EXTENSION_PROPERTIES = {"emissions": 7, "scatterings": 8, "reflections": 9}
 ALL_PROPERTIES = {**PROPERTIES, **EXTENSION_PROPERTIES}
 
+# ... and the photon as it was LAUNCHED: the wavelength and the position of its GENERATE row, the position in the scene
+# root's frame -- the frame lights emit in and the log stores (include/pvtrace_hip.h, "launch origin"; `Histogram` states
+# the contract).  A dict of their own: the two above are pinned as they stand.  `HISTOGRAM_PROPERTIES` is every name a
+# histogram axis may carry, what `Histogram` validates against and the flattener lowers from.
+ORIGIN_PROPERTIES = {"origin_wavelength": 10, "origin_x": 11, "origin_y": 12, "origin_z": 13}
+HISTOGRAM_PROPERTIES = {**ALL_PROPERTIES, **ORIGIN_PROPERTIES}
+
 # selector id -> which interaction fires the recorder.
 #   surface: entering (transmit in from outside), escaping (transmit out from
 #            inside), reflected (bounced off the outside)
@@ -84,12 +91,27 @@ class Histogram:
     3. They are integers, binned as the doubles of the same value by the rule of every other property.
     4. They draw no random number: a scene that uses them traces the same histories and the same other tallies, bit for bit.
     5. They do not depend on launch geometry, carrying, tally-set grouping, the device list or which code finishes a photon.
-    6. They add no moments: the eight sums of a recorder stay those of wavelength, angle, duration and pathlength."""
+    6. They add no moments: the eight sums of a recorder stay those of wavelength, angle, duration and pathlength.
+
+    Or one of `ORIGIN_PROPERTIES`, the photon as it was launched: `origin_wavelength`, and `origin_x`, `origin_y`,
+    `origin_z`.  The contract (include/pvtrace_hip.h, "launch origin", states the same):
+
+    1. The four doubles are the wavelength and the position of the photon's GENERATE row, bit for bit: what the launch's
+       ray arrays hold for it, or what device emission sampled.  They are fixed when the photon is claimed and never
+       recomputed: re-emission, scattering and refraction leave them as they are.
+    2. The position is in the scene ROOT's frame, the frame lights emit in and the event log stores -- deliberately NOT
+       in the recorder node's frame, unlike `x`, `y`, `z`: the bins are then exact against the launch arrays, with no
+       transform in between.  For an untransformed node the two frames agree.
+    3. They are binned by the rule of every other property, at the recorder's first match.
+    4. They draw no random number and change no other result: histories and every other tally stay bit for bit.
+    5. They do not depend on how the job was launched: carried launches, tally sets, shards, the device list or which code
+       finishes a photon.
+    6. They add no moments and no capture columns, and no recorder filters by them."""
 
     __slots__ = ("prop", "start", "stop", "bins")
 
     def __init__(self, prop, start, stop, bins):
-        _require(prop in ALL_PROPERTIES, f"Unknown property {prop!r}; use one of {sorted(PROPERTIES)}")
+        _require(prop in HISTOGRAM_PROPERTIES, f"Unknown property {prop!r}; use one of {sorted(PROPERTIES)}")
         lo, hi, count = float(start), float(stop), int(bins)
         _require(hi > lo, "Histogram range requires stop > start.")
         _require(count >= 1, "Histogram requires at least one bin.")

@@ -11,7 +11,8 @@ event kind that can fire them, each history is streamed once through the probes 
 a probe keeps the property values of the FIRST qualifying event of each ray, and moments and
 histograms are computed from those columns with numpy at the end.  The stream counts the EMIT, SCATTER
 and REFLECT events of a history as it goes; a probe is offered an event with the counts of the events
-BEFORE it (the photon as it arrives: the contract in `recorder.Histogram`).
+BEFORE it (the photon as it arrives: the contract in `recorder.Histogram`), and with the ray of the
+history's first row, the photon as launched (the `origin_*` properties).
 """
 import math
 
@@ -31,7 +32,8 @@ _TRIGGERS = {
     "exit": (Event.EXIT, ("hit",)),
     "detected": (Event.DETECT, ("hit",)),   # absorbed by a coating of the node, from either side (extension)
 }
-_COLUMNS = ("wavelength", "angle", "duration", "pathlength", "x", "y", "z", "emissions", "scatterings", "reflections")
+_COLUMNS = ("wavelength", "angle", "duration", "pathlength", "x", "y", "z", "emissions", "scatterings", "reflections",
+            "origin_wavelength", "origin_x", "origin_y", "origin_z")
 # the photon's event counters (recorder.EXTENSION_PROPERTIES): history event -> its place among the three
 _COUNTED = {Event.EMIT: 0, Event.SCATTER: 1, Event.REFLECT: 2}
 
@@ -62,9 +64,11 @@ class _Probe:
     def _local(self, position):
         return tuple(position) if self.node is self.root else self.root.point_to_node(position, self.node)
 
-    def offer(self, ray, meta, incoming, counters=(0, 0, 0)):
+    def offer(self, ray, meta, incoming, counters=(0, 0, 0), origin=None):
         """Present one history event of this probe's kind; `incoming` is the ray as it arrived, `counters` the EMIT,
-        SCATTER and REFLECT events of its history before this one."""
+        SCATTER and REFLECT events of its history before this one, `origin` the ray of the history's FIRST row (the
+        photon as launched; None: this ray) -- its wavelength and its position, in the root's frame as the log has it,
+        are the `origin_*` columns."""
         name = self.node.name
         if any(meta.get(key) != name for key in self.keys) or not self._from_wanted_source(ray.source):
             return
@@ -84,7 +88,9 @@ class _Probe:
             along = ray.direction if self.event == Event.EXIT else incoming.direction
             angle = math.acos(min(abs(float(np.dot(along, normal))), 1.0))
         x, y, z = self._local(ray.position)
-        self.rows.append((ray.wavelength, angle, ray.duration, ray.travelled, x, y, z) + tuple(counters))
+        first = ray if origin is None else origin
+        self.rows.append((ray.wavelength, angle, ray.duration, ray.travelled, x, y, z) + tuple(counters)
+                         + (first.wavelength,) + tuple(first.position))
 
     # -- reduction ---------------------------------------------------------------------
     @staticmethod
@@ -130,10 +136,12 @@ def tally_histories(scene, histories):
     for history in histories:
         for probe in probes:
             probe.open = True
-        incoming, counters = None, [0, 0, 0]
+        incoming, counters, origin = None, [0, 0, 0], None
         for ray, event, meta in history:
+            if origin is None:
+                origin = ray   # the GENERATE row: the photon as launched
             for probe in by_event.get(event, ()):
-                probe.offer(ray, meta or {}, incoming or ray, counters)
+                probe.offer(ray, meta or {}, incoming or ray, counters, origin)
             if event in _COUNTED:
                 counters[_COUNTED[event]] += 1
             incoming = ray
