@@ -39,7 +39,29 @@ enum {
     PVT_EV_DETECT = 10
 };
 /* geometry / surface / component / phase / emit-method tags (compiler.py:25-48) */
-enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_MESH = 3 };
+enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_MESH = 3,
+       /* EXTENSION (the reference has no such shape): a truncated cone, see below */
+       PVT_GEOM_FRUSTUM = 4 };
+/* PVT_GEOM_FRUSTUM: a truncated cone along the node's z axis, centred on its origin; geom_params = (length L,
+ * radius_bottom r0 at z = -L/2, radius_top r1 at z = +L/2, 0).  L finite and > 0; r0, r1 finite and >= 0, not both 0
+ * (else PVT_ERR_INVALID).  Convex, so the container rule of the analytic shapes applies unchanged.  The arithmetic is
+ * fixed -- IEEE double, no contraction, correctly rounded division and square root -- and pvtrace_amd.geometry.Frustum
+ * performs the same operations in the same order, so host and device agree bit for bit:
+ *     half = 0.5*L;  rm = 0.5*(r0 + r1);  k = (r1 - r0)/L
+ *     e = rm + k*o.z;  f = k*d.z;  s = d.x*d.x + d.y*d.y
+ *     a = s - f*f;  b = 2.0*((o.x*d.x + o.y*d.y) - e*f);  c = (o.x*o.x + o.y*o.y) - e*e;  disc = b*b - 4.0*a*c
+ *   side, disc >= 0 and fabs(a) > 0x1p-20*(s + f*f):  sq = sqrt(disc);  t = (-b - sq)/(2.0*a), then (-b + sq)/(2.0*a)
+ *     (with r0 == r1 every intermediate is the capped cylinder's);
+ *   side, disc >= 0 otherwise (the ray runs nearly along a generator):  q = -0.5*(b + copysign(sq, b));
+ *     t = c/q where q != 0, then t = q/a where fabs(a) > 1e-300;
+ *   a root counts when z = o.z + t*d.z has -half < z < half and t > EPS;
+ *   caps, fabs(d.z) > 1e-300: t = (-half - o.z)/d.z with x*x + y*y <= r0*r0, then t = (half - o.z)/d.z with r1, t > EPS;
+ *   normal: tol = 1e-8 + 1e-5*fabs(half); fabs(p.z + half) <= tol: (0,0,-1); fabs(p.z - half) <= tol: (0,0,1); else
+ *     rz = rm + k*p.z, w = k*rz, m = sqrt((p.x*p.x + p.y*p.y) + w*w), n = (p.x/m, p.y/m, (-w)/m).
+ * Additive under ABI 13.  A scene with such a node runs the PVT_VARIANT_ROUGH family (with or without meshes), is never
+ * lean, and gets no node grid.  Which entry takes the type: pvt_scene_create_origin, pvt_scene_lean_check and the
+ * host-buffer entries; every older pvt_scene_create* entry refuses it as before ("unknown geometry type"), as they refuse
+ * the extension selectors and properties -- no entry was added. */
 enum { PVT_SURF_FRESNEL = 0, PVT_SURF_NULL = 1 };
 enum { PVT_COMP_ABSORBER = 0, PVT_COMP_SCATTERER = 1, PVT_COMP_LUMINOPHORE = 2, PVT_COMP_REACTOR = 3 };
 enum { PVT_PHASE_ISOTROPIC = 0, PVT_PHASE_HG = 1, PVT_PHASE_CONE = 2,
@@ -781,7 +803,7 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
  * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
  * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
  * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
- * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing coatings), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing coatings, truncated cones), MESH.  The environment variable PVT_NO_LEAN, read when the scene
  * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */

@@ -63,7 +63,9 @@ bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
     std::vector<double> blo((size_t)N * 3), bhi((size_t)N * 3);
     double extent = 0.0;
     for (int n = 0; n < N; n++) {
-        if (t->geom_type[n] == PVT_GEOM_MESH) return false;
+        // (a truncated cone: the plain node loop serves its scene -- the `default` cases below, and the grid walk's
+        // shape_hits in the kernel, mean "cylinder" and never see one)
+        if (t->geom_type[n] == PVT_GEOM_MESH || t->geom_type[n] == PVT_GEOM_FRUSTUM) return false;
         const double* w = t->world_to_local + n * 16;
         const double* l = t->local_to_world + n * 16;
         const double* gp = t->geom_params + n * 4;
@@ -339,6 +341,7 @@ struct PackedScene {
     std::vector<int> gi;
     int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, n_ptab = 0, lazy_root = 0;
     int rough_d = -1;   // where the nodes' GGX widths start in the double blob (-1: no node is rough)
+    bool has_frustum = false;   // a node is a truncated cone (PVT_GEOM_FRUSTUM)
     // absorbing coatings (PvtCoatingAbsorbTables; -1: no coating absorbs).  Both blocks lie BEHIND everything the blobs of a
     // scene without them hold, so every other offset is what it would be without them, and are read from where the
     // spectra are read.  cabs_d: in the double blob, one record of kCa doubles (kCa*) per coating row, then the pooled
@@ -376,12 +379,20 @@ struct PackedScene {
 // else is read.
 int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                     const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                    const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop) {
+                    const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int max_geom) {
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
         const int g = t->geom_type[n];
-        if (g < PVT_GEOM_BOX || g > PVT_GEOM_MESH) return fail(PVT_ERR_INVALID, "unknown geometry type");
+        // (max_geom: the last geometry type the entry knows -- the entries from before the truncated cone refuse type 4 as they did)
+        if (g < PVT_GEOM_BOX || g > max_geom) return fail(PVT_ERR_INVALID, "unknown geometry type");
+        if (g == PVT_GEOM_FRUSTUM) {   // (length, radius_bottom, radius_top): the kernel divides by the first
+            const double* gp = t->geom_params + n * 4;
+            if (!(std::isfinite(gp[0]) && gp[0] > 0.0)) return fail(PVT_ERR_INVALID, "frustum: length must be finite and > 0");
+            if (!(std::isfinite(gp[1]) && std::isfinite(gp[2]) && gp[1] >= 0.0 && gp[2] >= 0.0))
+                return fail(PVT_ERR_INVALID, "frustum: radii must be finite and >= 0");
+            if (gp[1] == 0.0 && gp[2] == 0.0) return fail(PVT_ERR_INVALID, "frustum: radii must not both be 0");
+        }
         if (g != PVT_GEOM_MESH) continue;
         if (!t->mesh_face_start || !t->mesh_face_count || !t->mesh_vertices || !t->mesh_faces || !t->mesh_normals)
             return fail(PVT_ERR_INVALID, "mesh node without mesh tables");
@@ -1174,6 +1185,11 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
                 case PVT_GEOM_BOX: radius = 0.5 * std::sqrt(gp[0] * gp[0] + gp[1] * gp[1] + gp[2] * gp[2]); break;
                 case PVT_GEOM_SPHERE: radius = gp[0]; break;
                 case PVT_GEOM_CYLINDER: radius = std::sqrt(gp[1] * gp[1] + 0.25 * gp[0] * gp[0]); break;
+                case PVT_GEOM_FRUSTUM: {
+                    const double rmax = std::fmax(gp[1], gp[2]);
+                    radius = std::sqrt(rmax * rmax + 0.25 * gp[0] * gp[0]);
+                    break;
+                }
                 default: radius = INFINITY; break;   // (mesh scenes never take this path)
             }
             radius *= 1.0 + 1e-12;
@@ -1238,7 +1254,7 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     };
     // a searched table (CI_*_X, n points, its even_w in `w`): 2 = a constant or even bit for bit, 1 = even up to rounding, 0
     auto grid_kind = [&](int at, int n, double w) { return (n == 1 || w == w) ? 2 : (nearly_even(at, n) ? 1 : 0); };
-    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && p->fd.empty() &&
+    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && !p->has_frustum && p->fd.empty() &&
               p->md.empty() && p->cd.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
     for (int n = 0; n < N && ok; n++) {
         unsigned long long bits;
@@ -1416,8 +1432,8 @@ void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, cons
 // property it knows.  No HIP call.
 int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab,
-               int max_selector, int max_prop, PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop);
+               int max_selector, int max_prop, int max_geom, PackedScene* p) {
+    int rc = validate_tables(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, max_geom);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(t, x);
     Spectra spectra = pool_spectra(t);
@@ -1438,6 +1454,9 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     if (rs && rs->n_nodes > 0)
         for (int n = 0; n < t->n_nodes; n++)
             if (rs->node_roughness[n] > 0.0) p->rough_d = 0;
+    p->has_frustum = false;
+    for (int n = 0; n < t->n_nodes; n++)
+        if (t->geom_type[n] == PVT_GEOM_FRUSTUM) p->has_frustum = true;
     std::vector<int> rtab_at, ptab_at;
     const std::vector<int> ctab_at = lay_out(t, x, ph, classes, spectra, records, grid, p, &rtab_at, &ptab_at);
     rc = fill(t, x, ph, rs, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);

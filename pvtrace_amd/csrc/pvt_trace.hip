@@ -99,6 +99,7 @@ struct PvtScene {
     int nd_small = 0, ni_small = 0;   // ... of which everything but the spectra / their guide tables (the blobs' heads)
     int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
     int rough_d = -1;                   // where the nodes' GGX widths start in the double blob (-1: no rough node)
+    bool has_frustum = false;           // a node is a truncated cone (PVT_GEOM_FRUSTUM): only the extension family traces one
     int cabs_d = -1, dcand_i = -1;      // absorbing coatings: their records in the double blob, the `detected` candidate tables in the int blob (-1: none)
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
@@ -365,8 +366,8 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.mesh = s->d_bvh != nullptr;
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
     // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
-    // photon event counter or of the launch origin: the extension family, split as the plain ones
-    const bool extension = s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask;
+    // photon event counter or of the launch origin, or a truncated cone: the extension family, split as the plain ones
+    const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
@@ -694,10 +695,11 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
 // What every pvt_scene_create* entry does.  max_selector: the last recorder selector the entry knows -- PVT_RECX_DETECTED
 // for pvt_scene_create_absorb, PVT_REC_EXIT for the entries from before it, which refuse an eighth selector as they did.
 // max_prop: the last histogram property it knows -- PVT_PROP_Z, PVT_PROPX_REFLECTIONS for pvt_scene_create_absorb,
-// PVT_PROPX_ORIGIN_Z for pvt_scene_create_origin.
+// PVT_PROPX_ORIGIN_Z for pvt_scene_create_origin.  max_geom: the last geometry type it knows -- PVT_GEOM_FRUSTUM for
+// pvt_scene_create_origin and the host-buffer entries, PVT_GEOM_MESH for the older ones ("unknown geometry type", as before).
 int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                  const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int device, PvtScene** out);
+                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int max_geom, int device, PvtScene** out);
 
 }  // namespace
 
@@ -738,19 +740,19 @@ int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->captu
 int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                              const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                              const PvtCaptureTables* cp, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, PVT_REC_EXIT, PVT_PROP_Z, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_MESH, device, out);
 }
 
 int pvt_scene_create_absorb(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH, device, out);
 }
 
 int pvt_scene_create_origin(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, device, out);
 }
 
 }  // extern "C"
@@ -759,7 +761,7 @@ namespace {
 
 int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                  const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int device, PvtScene** out) {
+                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int max_geom, int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -767,7 +769,7 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, max_geom, &packed);
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -786,6 +788,7 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     s->n_nodes = t->n_nodes; s->root = t->root_id; s->n_rec = t->n_recorders;
     s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab; s->n_rtab = packed.n_rtab;
     s->rough_d = packed.rough_d;
+    s->has_frustum = packed.has_frustum;
     s->cabs_d = packed.cabs_d; s->dcand_i = packed.dcand_i;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
@@ -1084,7 +1087,7 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, nullptr, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, &packed);
+    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, nullptr, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, &packed);
     if (rc != PVT_OK) return rc;
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     return PVT_OK;
@@ -1424,7 +1427,8 @@ struct HostBundle {
         tables = tb;
         params = *pp;
         params.flags &= ~(int64_t)PVT_FLAG_CARRY_OUT;   // a scene that lives for one call has no next launch to carry photons to
-        int rc = pvt_scene_create(tables, device, &scene);
+        // (pvt_scene_create, but for the geometry types: a host-buffer call takes a truncated cone)
+        int rc = create_scene(tables, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_FRUSTUM, device, &scene);
         if (rc != PVT_OK) return rc;
         if (emitter) {
             rc = pvt_scene_set_emitter(scene, emitter);

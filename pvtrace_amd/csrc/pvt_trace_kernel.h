@@ -594,6 +594,65 @@ __device__ __attribute__((noinline)) V3 phase_table_turn_call(const double* tab,
     return phase_table_turn(tab, wl, u1, u2, u3, dx, dy, dz);
 }
 
+// Truncated cones (PVT_GEOM_FRUSTUM; include/pvtrace_hip.h states the arithmetic, geometry.Frustum performs the same
+// operations in the same order): the four candidate distances of the ray (o, d) in the node's frame, in fold order -- side
+// root, side root, -z cap, +z cap -- a candidate that is no crossing being 0 (never > kEps).  With r0 == r1 every
+// intermediate of the general branch is the capped cylinder's.  A FUNCTION, called only from the trace_kernel_rough*
+// variants: the plain families carry none of it.
+struct FrustumHits { double t[4]; };
+__device__ __attribute__((noinline)) FrustumHits frustum_hits_call(double length, double r0, double r1, double ox, double oy, double oz,
+                                                                   double dx, double dy, double dz) {
+    FrustumHits h{{0.0, 0.0, 0.0, 0.0}};
+    const double half = 0.5 * length, rm = 0.5 * (r0 + r1), k = (r1 - r0) / length;
+    const double e = rm + k * oz, f = k * dz, s = dx * dx + dy * dy;
+    const double ff = f * f;
+    const double a = s - ff;
+    const double b = 2.0 * ((ox * dx + oy * dy) - e * f);
+    const double c = (ox * ox + oy * oy) - e * e;
+    const double disc = b * b - 4.0 * a * c;
+    if (disc >= 0.0) {
+        const double sq = pvt_sqrt(disc);
+        double ta = 0.0, tb = 0.0;
+        bool has_a = true, has_b = true;
+        if (pvt_fabs(a) > 0x1p-20 * (s + ff)) {
+            ta = (-b - sq) / (2.0 * a);
+            tb = (-b + sq) / (2.0 * a);
+        } else {   // the ray runs nearly along a generator: the roots without the cancellation
+            const double q = -0.5 * (b + __builtin_copysign(sq, b));
+            has_a = q != 0.0;
+            has_b = pvt_fabs(a) > 1e-300;
+            if (has_a) ta = c / q;
+            if (has_b) tb = q / a;
+        }
+        double z = oz + ta * dz;
+        if (has_a && z > -half && z < half) h.t[0] = ta;
+        z = oz + tb * dz;
+        if (has_b && z > -half && z < half) h.t[1] = tb;
+    }
+    if (pvt_fabs(dz) > 1e-300) {
+        double t = (-half - oz) / dz;
+        double x = ox + t * dx, y = oy + t * dy;
+        if (x * x + y * y <= r0 * r0) h.t[2] = t;
+        t = (half - oz) / dz;
+        x = ox + t * dx;
+        y = oy + t * dy;
+        if (x * x + y * y <= r1 * r1) h.t[3] = t;
+    }
+    return h;
+}
+// ... and the outward normal at the point p of its surface: the cylinder's cap rule, then the gradient of the side
+__device__ __attribute__((noinline)) V3 frustum_normal_call(double length, double r0, double r1, double px, double py, double pz) {
+    const double half = 0.5 * length;
+    const double tol = 1e-8 + 1e-5 * pvt_fabs(half);
+    if (pvt_fabs(pz + half) <= tol) return V3{0.0, 0.0, -1.0};
+    if (pvt_fabs(pz - half) <= tol) return V3{0.0, 0.0, 1.0};
+    const double rm = 0.5 * (r0 + r1), k = (r1 - r0) / length;
+    const double rz = rm + k * pz;
+    const double w = k * rz;
+    const double m = pvt_sqrt((px * px + py * py) + w * w);
+    return V3{px / m, py / m, (-w) / m};
+}
+
 // Rough interfaces (PvtSurfaceTables; include/pvtrace_hip.h states the contract, the Python FresnelSurfaceDelegate samples
 // the same way): one surface event of a lane whose hit node is rough where no coating covers it (UF_ROUGH) -- the draws
 // u_a, u_b, the microfacet normal m from the GGX distribution of visible normals of width `alpha` (Heitz 2018) about the
@@ -1409,7 +1468,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 t = (-b + sq) / (2.0 * a);
                 if (t > kEps) fold(t);
             }
-        } else {  // capped z cylinder (:301-345)
+        } else {  // capped z cylinder (:301-345) -- (a truncated cone never comes here: its scene gets no node grid, plan_node_grid)
             double half = 0.5 * g0, radius = g1;
             double a = d.x * d.x + d.y * d.y;
             if (a > 1e-300) {
@@ -2598,6 +2657,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         t = (-b + sq) / (2.0 * a);
                         if (t > kEps) fold(t);
                     }
+                } else if (ROUGH && gt == PVT_GEOM_FRUSTUM) {   // EXTENSION: truncated cone (frustum_hits_call; no node grid holds one)
+                    const FrustumHits fh = frustum_hits_call(gpar[0], gpar[1], gpar[2], o.x, o.y, o.z, d.x, d.y, d.z);
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if (fh.t[j] > kEps) fold(fh.t[j]);
                 } else {  // capped z cylinder (:301-345)
                     double half = 0.5 * gpar[0], radius = gpar[1];
                     double a = d.x * d.x + d.y * d.y;
@@ -2969,6 +3033,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 double mag = pvt_sqrt(dot3(lp, lp));
                 return V3{lp.x / mag, lp.y / mag, lp.z / mag};
             }
+            if (ROUGH && !GRID && gt == PVT_GEOM_FRUSTUM)   // (no node grid holds a truncated cone: plan_node_grid)
+                return frustum_normal_call(param(0), param(1), param(2), lp.x, lp.y, lp.z);
             double half = 0.5 * param(0);
             double tol = 1e-8 + 1e-5 * pvt_fabs(half);
             if (pvt_fabs(lp.z + half) <= tol) return V3{0.0, 0.0, -1.0};

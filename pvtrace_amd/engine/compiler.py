@@ -34,7 +34,7 @@ from pvtrace_amd.engine.recorder import (
     Recorder,
     VolumeMap,
 )
-from pvtrace_amd.geometry import Box, Cylinder, Mesh, Sphere
+from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Sphere
 from pvtrace_amd.material import (
     Absorber,
     CoatedSurfaceDelegate,
@@ -57,6 +57,7 @@ MAX_NODES = 128       # device limit (reference _kernel.pyx:66, :929-930)
 MAX_RECORDERS = 256   # per-photon distinct-ray bitmask width (compiler.py:23)
 
 GEOM_BOX, GEOM_SPHERE, GEOM_CYLINDER, GEOM_MESH = 0, 1, 2, 3
+GEOM_FRUSTUM = 4   # EXTENSION: truncated cone (include/pvtrace_hip.h: PVT_GEOM_FRUSTUM)
 SURF_FRESNEL, SURF_NULL = 0, 1
 COMP_ABSORBER, COMP_SCATTERER, COMP_LUMINOPHORE, COMP_REACTOR = 0, 1, 2, 3
 PHASE_ISOTROPIC, PHASE_HENYEY_GREENSTEIN, PHASE_CONE = 0, 1, 2
@@ -311,6 +312,16 @@ class CompiledScene:
             self.geom_type[i] = GEOM_CYLINDER
             self.geom_params[i, 0] = float(geometry.length)
             self.geom_params[i, 1] = float(geometry.radius)
+        elif isinstance(geometry, Frustum):
+            # EXTENSION: the reference has no truncated cone; (length, radius_bottom, radius_top), checked again here
+            # because the attributes may have been changed since construction
+            problem = Frustum.parameter_problem(geometry.length, geometry.radius_bottom, geometry.radius_top)
+            if problem:
+                raise UnsupportedSceneError(problem)
+            self.geom_type[i] = GEOM_FRUSTUM
+            self.geom_params[i, 0] = float(geometry.length)
+            self.geom_params[i, 1] = float(geometry.radius_bottom)
+            self.geom_params[i, 2] = float(geometry.radius_top)
         elif isinstance(geometry, Mesh):
             # EXTENSION: the reference engine rejects meshes (compiler.py:220-223)
             pool = self._mesh_pool
@@ -371,6 +382,10 @@ class CompiledScene:
         if not (math.isfinite(alpha) and 0.0 <= alpha <= 1.0):
             raise UnsupportedSceneError(f"Node {node.name!r}: surface roughness must satisfy 0 <= alpha <= 1, got {alpha!r}.")
         return alpha
+
+    @property
+    def has_frustum(self):
+        return bool(np.any(self.geom_type == GEOM_FRUSTUM))
 
     @property
     def has_roughness(self):

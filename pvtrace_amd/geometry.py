@@ -361,6 +361,142 @@ class Cylinder(Geometry):
         return (p[0] / r, p[1] / r, 0.0)
 
 
+_TWO_M20 = 2.0 ** -20   # (Frustum: below this share of s + f*f, `a` is taken to have cancelled)
+
+
+class Frustum(Geometry):
+    """Truncated cone along z, centred on the origin: radius `radius_bottom` at z = -length/2, `radius_top` at
+    z = +length/2.  EXTENSION (the reference has no such shape); with equal radii it is `Cylinder`, operation for operation
+    (up to the sign of one zero: the side normal's z is (-0.0)/m = -0.0 where the cylinder writes 0.0).
+
+    `length > 0`; both radii finite and >= 0, at most one of them 0 (a full cone whose apex lies on a cap plane).
+
+    The arithmetic, which the device kernel (csrc/pvt_trace_kernel.h: frustum_hits_call, frustum_normal_call) repeats operation
+    for operation in IEEE double, no contraction, correctly rounded `/` and square root:
+
+        half = 0.5*L;  rm = 0.5*(r0 + r1);  k = (r1 - r0)/L
+        e = rm + k*o.z;  f = k*d.z;  s = d.x*d.x + d.y*d.y
+        a = s - f*f;  b = 2.0*((o.x*d.x + o.y*d.y) - e*f);  c = (o.x*o.x + o.y*o.y) - e*e
+        disc = b*b - 4.0*a*c
+
+    Side, when fabs(a) > 2**-20 * (s + f*f) (the cylinder's sequence):
+        if disc >= 0:  sq = sqrt(disc);  t = (-b - sq)/(2.0*a), then t = (-b + sq)/(2.0*a)
+    Side otherwise (the ray runs nearly along a generator: the textbook roots cancel), when disc >= 0:
+        sq = sqrt(disc);  q = -0.5*(b + copysign(sq, b))
+        if q != 0:                     t = c/q
+        if fabs(a) > 1e-300:           t = q/a
+    A root t is a crossing when z = o.z + t*d.z has -half < z < half (strictly) and t > EPS_ZERO; roots are taken in the
+    order written.  Caps, the cylinder's: when fabs(d.z) > 1e-300, t = (-half - o.z)/d.z with x*x + y*y <= r0*r0, then
+    t = (half - o.z)/d.z with x*x + y*y <= r1*r1, each when t > EPS_ZERO.
+
+    Normal: tol = 1e-8 + 1e-5*fabs(half); fabs(p.z + half) <= tol gives (0, 0, -1), then fabs(p.z - half) <= tol gives
+    (0, 0, 1); otherwise rz = rm + k*p.z, w = k*rz, m = sqrt((p.x*p.x + p.y*p.y) + w*w), n = (p.x/m, p.y/m, (-w)/m).
+    """
+
+    def __init__(self, length, radius_bottom, radius_top, material=None):
+        super(Frustum, self).__init__(material=material)
+        self.length = length
+        self.radius_bottom = radius_bottom
+        self.radius_top = radius_top
+        problem = self.parameter_problem(length, radius_bottom, radius_top)
+        if problem:
+            raise ValueError(problem)
+
+    @staticmethod
+    def parameter_problem(length, radius_bottom, radius_top):
+        """What is wrong with the three parameters, or None."""
+        try:
+            L, r0, r1 = float(length), float(radius_bottom), float(radius_top)
+        except (TypeError, ValueError):
+            return "Frustum length and radii must be numbers."
+        if not (math.isfinite(L) and L > 0.0):
+            return "Frustum length must be finite and > 0."
+        if not (math.isfinite(r0) and math.isfinite(r1) and r0 >= 0.0 and r1 >= 0.0):
+            return "Frustum radii must be finite and >= 0."
+        if r0 == 0.0 and r1 == 0.0:
+            return "Frustum radii must not both be 0."
+        return None
+
+    def _constants(self):
+        L, r0, r1 = float(self.length), float(self.radius_bottom), float(self.radius_top)
+        return 0.5 * L, 0.5 * (r0 + r1), (r1 - r0) / L, r0, r1
+
+    def radius_at(self, z):
+        _, rm, k, _, _ = self._constants()
+        return rm + k * z
+
+    def _ray_distances(self, o, d):
+        half, rm, k, r0, r1 = self._constants()
+        ox, oy, oz = float(o[0]), float(o[1]), float(o[2])
+        dx, dy, dz = float(d[0]), float(d[1]), float(d[2])
+        cand = []
+        e = rm + k * oz
+        f = k * dz
+        s = dx * dx + dy * dy
+        ff = f * f
+        a = s - ff
+        b = 2.0 * ((ox * dx + oy * dy) - e * f)
+        c = (ox * ox + oy * oy) - e * e
+        disc = b * b - 4.0 * a * c
+        if disc >= 0.0:
+            roots = []
+            if abs(a) > _TWO_M20 * (s + ff):
+                sq = math.sqrt(disc)
+                roots.append((-b - sq) / (2.0 * a))
+                roots.append((-b + sq) / (2.0 * a))
+            else:
+                sq = math.sqrt(disc)
+                q = -0.5 * (b + math.copysign(sq, b))
+                if q != 0.0:
+                    roots.append(c / q)
+                if abs(a) > 1e-300:
+                    roots.append(q / a)
+            for t in roots:
+                z = oz + t * dz
+                if -half < z < half:
+                    cand.append(t)
+        if abs(dz) > 1e-300:
+            for cap, rad in ((-half, r0), (half, r1)):
+                t = (cap - oz) / dz
+                x, y = ox + t * dx, oy + t * dy
+                if x * x + y * y <= rad * rad:
+                    cand.append(t)
+        return [t for t in cand if t > EPS_ZERO]
+
+    def contains(self, point):
+        p = np.asarray(point, dtype=np.float64)
+        r = math.hypot(p[0], p[1])
+        half = 0.5 * float(self.length)
+        return bool(
+            self.radius_at(float(p[2])) - (r + EPS_ZERO) > 0.0
+            and half - (abs(p[2]) + EPS_ZERO) > 0.0
+        )
+
+    def is_on_surface(self, point):
+        p = np.asarray(point, dtype=np.float64)
+        r, half = math.hypot(p[0], p[1]), 0.5 * float(self.length)
+        rz = self.radius_at(float(p[2]))
+        on_cap = abs(abs(p[2]) - half) < EPS_ZERO and r <= rz + EPS_ZERO
+        on_side = abs(r - rz) < EPS_ZERO and abs(p[2]) <= half + EPS_ZERO
+        return bool(on_cap or on_side)
+
+    def normal(self, surface_point):
+        p = np.asarray(surface_point, dtype=np.float64)
+        half, rm, k, _, _ = self._constants()
+        tol = 1e-8 + 1e-5 * abs(half)
+        if abs(p[2] + half) <= tol:
+            return (0.0, 0.0, -1.0)
+        if abs(p[2] - half) <= tol:
+            return (0.0, 0.0, 1.0)
+        px, py = float(p[0]), float(p[1])
+        rz = rm + k * float(p[2])
+        w = k * rz
+        m = math.sqrt((px * px + py * py) + w * w)
+        if m == 0.0:
+            raise GeometryError("Point on the frustum's apex has no normal.")
+        return (px / m, py / m, (-w) / m)
+
+
 class Mesh(Geometry):
     """Closed triangle mesh (reference pvtrace/geometry/mesh.py:11-24: `Mesh(trimesh, material)`).
 

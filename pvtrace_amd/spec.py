@@ -19,7 +19,7 @@ import numpy as np
 from pvtrace_amd.data import fluro_red, lumogen_f_red_305
 from pvtrace_amd.engine.compiler import UnsupportedSceneError
 from pvtrace_amd.engine.instrument import auto_recorders, recorders_from_spec
-from pvtrace_amd.geometry import Box, Cylinder, Mesh, Sphere
+from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Sphere
 from pvtrace_amd.light import (
     CircularMask, ConstantWavelengthMask, CubeMask, Light, RectangularMask, SpectrumWavelengthMask,
 )
@@ -206,6 +206,13 @@ class _Builder:
             g = entry["cylinder"]
             return Node(name=name, geometry=Cylinder(g["length"], g["radius"],
                                                      material=self.material(g["material"])))
+        if "frustum" in entry:   # EXTENSION: a truncated cone (geometry.Frustum)
+            g = entry["frustum"]
+            try:
+                shape = Frustum(g["length"], g["radius-bottom"], g["radius-top"], material=self.material(g["material"]))
+            except ValueError as exc:
+                raise SpecError(f"node {name!r}: {exc}") from None
+            return Node(name=name, geometry=shape)
         if "mesh" in entry:   # reference: trimesh.exchange.load (cli/parse.py:130-138); here STL only
             g = entry["mesh"]
             path = g["file"] if os.path.isabs(g["file"]) else os.path.join(self.base, g["file"])
@@ -225,7 +232,7 @@ class _Builder:
                 direction = self.direction(mask["direction"])
             return Node(name=name, light=Light(wavelength=wavelength, position=position,
                                                direction=direction, name=name))
-        raise SpecError(f"node {name!r}: needs a geometry (box / sphere / cylinder) or a light")
+        raise SpecError(f"node {name!r}: needs a geometry (box / sphere / cylinder / frustum / mesh) or a light")
 
     def scene(self):
         entries = self.spec["nodes"]
