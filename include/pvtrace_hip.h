@@ -485,6 +485,42 @@ typedef struct PvtCoatingAbsorbTables {
     const double* value;                /* pooled absorptivities, finite and in [0, 1] */
 } PvtCoatingAbsorbTables;
 
+/* ---- patterned coatings (extension within v13, passed to pvt_scene_create_pattern) ----------------------------------
+ * Where a coating covers.  coat_any_facet[k] != 0 skips the normal test of coating row k (its coat_facet is ignored: a
+ * flag of the row, no magic normal); coat_pattern[k] >= 0 names the mask lattice of the row, in the node's own frame, the
+ * frame coat_lo / coat_hi are in.  The rule (the Python Coating docstring states the same; the kernel and the host
+ * delegate both follow it):
+ *  1. A coating covers a point when all three hold: its facet matches (or the row's any-facet flag is set); its region
+ *     contains the point; it has no pattern, or the point's cell is set.
+ *  2. The point is the local point the coating match already uses: pos + t on an unrotated node, the row products
+ *     ((R0 x + R1 y) + R2 z) + t otherwise, without FMA (what the volume maps' rules 1-3 state).
+ *  3. Per bounded axis h = (upper - lower) / n and i = floor((p - lower) / h).  The point is inside when
+ *     0 <= i <= n - 1 on every bounded axis.  The slot is (ix ny + iy) nz + iz.
+ *  4. A point outside the lattice is not covered.  There is no clamping: a pattern may be smaller than its face.
+ *  5. The first covering coating wins.  Several coatings with disjoint masks give a palette.
+ *  6. The decision draws no random number.  A pattern of all ones whose lattice contains the face traces bit for bit as
+ *     the same coating without a pattern; a pattern of all zeros traces bit for bit as the scene with that coating
+ *     removed.  Coverage is binary: a dot pattern is rendered into the mask at the resolution it needs.
+ *  7. Roughness keeps its rule: it applies where no coating covers, so the holes of a pattern on a rough node are rough.
+ * An axis with bounded == 0 has one cell and index 0 for every point; its lower and h are not read.  The masks live in
+ * global memory, outside what a launch stages in LDS; a covered-or-not decision is one byte load.  Launches of such a
+ * scene run the PVT_VARIANT_ROUGH family; the host-buffer entries know no patterns.  A NULL struct, n_coatings 0, or no
+ * row with a pattern or an any-facet flag is exactly pvt_scene_create_origin.  A separate struct so that the other table
+ * structs keep the lengths old callers pass. */
+typedef struct PvtCoatingPatternTables {
+    int32_t n_coatings;                 /* 0 = none (as a NULL struct), else the scene's n_coatings */
+    int32_t n_patterns;                 /* mask lattices */
+    const int32_t* coat_any_facet;      /* (n_coatings) != 0: the row's normal test is skipped */
+    const int32_t* coat_pattern;        /* (n_coatings) pattern of each coating row, -1 = none */
+    const int32_t* shape;               /* (n_patterns,3) cells per axis, >= 1 */
+    const int32_t* bounded;             /* (n_patterns,3) 0 = the axis is unbounded and has one cell */
+    const double* lower;                /* (n_patterns,3) lower bound per bounded axis, finite */
+    const double* h;                    /* (n_patterns,3) cell width per bounded axis, finite and > 0 */
+    const int64_t* mask_start;          /* (n_patterns) first byte of the pattern's mask in `mask`: nx ny nz bytes, z fastest */
+    const uint8_t* mask;                /* pooled masks, != 0 = the cell is covered */
+    int64_t n_mask;                     /* bytes in `mask`, at most 2^26 */
+} PvtCoatingPatternTables;
+
 /* capture buffers of one launch (DEVICE pointers): `rows` holds sets x capture_rows x PVT_CAPTURE_ROW_WORDS uint64,
  * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle).  Word 11 of a row:
  * emissions | scatterings << 20 | reflections << 40, the photon's event counters (PVT_PROPX_*) */
@@ -675,6 +711,13 @@ int pvt_scene_create_origin(const PvtSceneTables* tables, const PvtIndexTables* 
                             const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
                             const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables, int device,
                             PvtScene** out);
+/* The same with patterned coatings (PvtCoatingPatternTables; NULL, n_coatings 0 or no row with a pattern or an any-facet
+ * flag = none: then exactly pvt_scene_create_origin).  Every entry before it knows no patterns. */
+int pvt_scene_create_pattern(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                             const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                             const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
+                             const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables,
+                             const PvtCoatingPatternTables* pattern_tables, int device, PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);
@@ -803,7 +846,7 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
  * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
  * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
  * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
- * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing coatings, truncated cones), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones), MESH.  The environment variable PVT_NO_LEAN, read when the scene
  * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */

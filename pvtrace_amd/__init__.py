@@ -10,10 +10,10 @@ from pvtrace_amd.light import (
     Event, Light, Ray, circular_mask, cube_mask, rectangular_mask,
 )
 from pvtrace_amd.material import (
-    Absorber, AbsorptivityTable, CoatedSurfaceDelegate, Coating, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
+    Absorber, AbsorptivityTable, CoatedSurfaceDelegate, Coating, CoatingPattern, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
     Luminophore, Material, NullSurfaceDelegate, PhaseFunctionTable, Reactor, ReflectivityTable,
     RefractiveIndexTable, Scatterer, Surface,
-    SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian,
+    SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian, pattern_cell,
 )
 from pvtrace_amd.scene import Node, Scene
 from pvtrace_amd import engine

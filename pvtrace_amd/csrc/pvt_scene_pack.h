@@ -363,6 +363,13 @@ struct PackedScene {
     // global memory alone (empty: no recorder is captured); capture_rows: the rows of all captures of one tally set
     std::vector<long long> cd;
     long long capture_rows = 0;
+    // patterned coatings (PvtCoatingPatternTables): their own buffer, uploaded behind the double blob in its allocation and
+    // read from global memory alone (both empty: none).
+    // pd[2 k] = where coating row k's pattern record starts in pd (-1: the row has no pattern), pd[2 k + 1] != 0: the row's
+    // normal test is skipped; then one record of kPr doubles (kPr*) per pattern.  pmask: the pooled masks, uploaded right
+    // behind pd -- a record's kPrMask counts bytes from the start of pd
+    std::vector<double> pd;
+    std::vector<unsigned char> pmask;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     bool hist_reads_counter = false;   // a histogram axis is a photon event counter (PVT_PROPX_EMISSIONS .. _REFLECTIONS)
@@ -1422,6 +1429,66 @@ void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, cons
     p->dcand_i = (int)gi.size();
     gi.resize(gi.size() + (size_t)recs.n_cand * 8 + (size_t)t->n_recorders + 1, 0);
     fill_candidates(t, recs, p, true);
+}
+
+// Patterned coatings (PvtCoatingPatternTables, pvt_scene_create_pattern; called on a scene pack_scene has accepted, before
+// anything is uploaded): every index the kernel follows is checked, then PackedScene::pd and ::pmask are filled.  Both stay
+// empty -- the scene is then exactly the one without the struct -- when no row has a pattern or an any-facet flag.
+int pack_patterns(const PvtSceneTables* t, const PvtCoatingPatternTables* pt, PackedScene* p) {
+    p->pd.clear();
+    p->pmask.clear();
+    if (!pt || pt->n_coatings == 0) return PVT_OK;
+    const int K = t->n_coatings, P = pt->n_patterns;
+    if (pt->n_coatings != K || !pt->coat_any_facet || !pt->coat_pattern)
+        return fail(PVT_ERR_INVALID, "pattern tables: need one flag and one pattern id per coating");
+    if (P < 0 || pt->n_mask < 0 || pt->n_mask > (1ll << 26)) return fail(PVT_ERR_INVALID, "pattern tables: more than 2^26 mask cells");
+    if (P > 0 && (!pt->shape || !pt->bounded || !pt->lower || !pt->h || !pt->mask_start || !pt->mask))
+        return fail(PVT_ERR_INVALID, "pattern tables: missing arrays");
+    for (int j = 0; j < P; j++) {
+        long long cells = 1;
+        for (int a = 0; a < 3; a++) {
+            const long long n = pt->shape[j * 3 + a];
+            if (n < 1) return fail(PVT_ERR_INVALID, "pattern tables: shape must be >= 1 on each axis");
+            cells *= n;
+            if (cells > (1ll << 26)) return fail(PVT_ERR_INVALID, "pattern tables: more than 2^26 mask cells");
+            if (pt->bounded[j * 3 + a] == 0) {
+                if (n != 1) return fail(PVT_ERR_INVALID, "pattern tables: an unbounded axis has one cell");
+                continue;
+            }
+            const double h = pt->h[j * 3 + a];
+            if (!std::isfinite(pt->lower[j * 3 + a])) return fail(PVT_ERR_INVALID, "pattern tables: lower bounds must be finite");
+            if (!(std::isfinite(h) && h > 0.0)) return fail(PVT_ERR_INVALID, "pattern tables: cell widths must be finite and > 0");
+        }
+        const long long m0 = pt->mask_start[j];
+        if (m0 < 0 || m0 > pt->n_mask || cells > pt->n_mask - m0) return fail(PVT_ERR_INVALID, "pattern tables: mask range out of bounds");
+    }
+    bool any = false;
+    for (int k = 0; k < K; k++) {
+        if (pt->coat_pattern[k] < -1 || pt->coat_pattern[k] >= P) return fail(PVT_ERR_INVALID, "pattern tables: coating row names a missing pattern");
+        any = any || pt->coat_pattern[k] >= 0 || pt->coat_any_facet[k] != 0;
+    }
+    if (!any) return PVT_OK;
+    std::vector<double>& pd = p->pd;
+    pd.assign((size_t)2 * K + (size_t)P * kPr, 0.0);
+    const double mask_at = (double)(pd.size() * sizeof(double));   // (< 2^53: exact)
+    for (int k = 0; k < K; k++) {
+        pd[(size_t)2 * k] = pt->coat_pattern[k] >= 0 ? (double)(2 * K + pt->coat_pattern[k] * kPr) : -1.0;
+        pd[(size_t)2 * k + 1] = pt->coat_any_facet[k] != 0 ? 1.0 : 0.0;
+    }
+    for (int j = 0; j < P; j++) {
+        double* q = pd.data() + (size_t)2 * K + (size_t)j * kPr;
+        for (int a = 0; a < 3; a++) {
+            const bool bounded = pt->bounded[j * 3 + a] != 0;
+            q[kPrShape + a] = (double)pt->shape[j * 3 + a];
+            q[kPrBounded + a] = bounded ? 1.0 : 0.0;
+            q[kPrLower + a] = bounded ? pt->lower[j * 3 + a] : 0.0;
+            q[kPrH + a] = bounded ? pt->h[j * 3 + a] : 1.0;
+        }
+        q[kPrMask] = mask_at + (double)pt->mask_start[j];
+    }
+    p->pmask.assign(pt->mask, pt->mask + pt->n_mask);
+    if (p->pmask.empty()) p->pmask.push_back(0);   // (flags alone: the buffer still ends in a byte)
+    return PVT_OK;
 }
 
 // The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the

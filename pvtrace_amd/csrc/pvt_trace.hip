@@ -103,6 +103,7 @@ struct PvtScene {
     int cabs_d = -1, dcand_i = -1;      // absorbing coatings: their records in the double blob, the `detected` candidate tables in the int blob (-1: none)
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
+    int pd_d = -1;                      // the coating patterns' flags, records and masks: where they start behind the double blob, in its allocation (KArgs::pd_d; -1 = no coating has a pattern or covers any normal)
     long long map_slots = 0;            // int64 slots the maps add behind the recorders' bins (pvt_scene_map_slots)
     long long* d_cd = nullptr;          // ray capture: capacity and first row per recorder (KArgs::cap_tab), null = none captured
     long long capture_rows = 0;         // rows of all captures of one tally set (pvt_scene_capture_rows)
@@ -251,6 +252,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.cabs_d = s->cabs_d; a.dcand_i = s->dcand_i;
     a.fd = s->d_fd;
     a.md = s->d_md;
+    a.pd_d = s->pd_d;
     a.cap_tab = s->d_cd;
     a.cap_total = s->capture_rows;
     a.count = s->counting();
@@ -367,7 +369,7 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
     // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
     // photon event counter or of the launch origin, or a truncated cone: the extension family, split as the plain ones
-    const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask;
+    const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
@@ -699,7 +701,8 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
 // pvt_scene_create_origin and the host-buffer entries, PVT_GEOM_MESH for the older ones ("unknown geometry type", as before).
 int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                  const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int max_geom, int device, PvtScene** out);
+                 const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt, int max_selector, int max_prop, int max_geom,
+                 int device, PvtScene** out);
 
 }  // namespace
 
@@ -740,19 +743,26 @@ int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->captu
 int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                              const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                              const PvtCaptureTables* cp, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_MESH, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_MESH, device, out);
 }
 
 int pvt_scene_create_absorb(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, nullptr, PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH, device, out);
 }
 
 int pvt_scene_create_origin(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, device, out);
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, nullptr, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, device, out);
+}
+
+int pvt_scene_create_pattern(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
+                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt,
+                             int device, PvtScene** out) {
+    return create_scene(t, x, ph, rs, fr, mp, cp, ab, pt, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, device, out);
 }
 
 }  // extern "C"
@@ -761,7 +771,8 @@ namespace {
 
 int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                  const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int max_geom, int device, PvtScene** out) {
+                 const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt, int max_selector, int max_prop, int max_geom,
+                 int device, PvtScene** out) {
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -769,7 +780,9 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, max_geom, &packed);
+    int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, max_geom, &packed);
+    if (rc != PVT_OK) return rc;
+    rc = pack_patterns(t, pt, &packed);   // (validated before anything is uploaded)
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -803,7 +816,8 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     s->num_cu = prop.multiProcessorCount;
     s->lds_limit = prop.sharedMemPerBlock;
     if (const char* env = getenv("PVT_STAGE_BYTES")) s->stage_limit = (size_t)atoll(env);   // (tests: force several launches)
-    HIP_TRY(hipMalloc(&s->d_gd, packed.gd.size() * sizeof(double)));
+    // (the coating patterns' buffer, when there is one, lies behind the blob in the same allocation: beyond `nd`, never staged)
+    HIP_TRY(hipMalloc(&s->d_gd, (packed.gd.size() + packed.pd.size()) * sizeof(double) + packed.pmask.size()));
     HIP_TRY(hipMalloc(&s->d_gi, packed.gi.size() * sizeof(int)));
     HIP_TRY(hipMalloc(&s->d_cursor, 64 * kCursorSlots + 256));   // + room for the PVT_STATS counters
     HIP_TRY(hipMemset(s->d_cursor, 0, 64 * kCursorSlots + 256));
@@ -858,6 +872,13 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
         HIP_TRY(hipMalloc(&s->d_md, packed.md.size() * sizeof(double)));
         HIP_TRY(hipMemcpy(s->d_md, packed.md.data(), packed.md.size() * sizeof(double), hipMemcpyHostToDevice));
         s->map_slots = packed.map_slots;
+    }
+    if (!packed.pd.empty()) {   // (global memory only: flags and records, the masks right behind them)
+        const size_t head = packed.pd.size() * sizeof(double);
+        double* d_pd = s->d_gd + packed.gd.size();
+        HIP_TRY(hipMemcpy(d_pd, packed.pd.data(), head, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(d_pd) + head, packed.pmask.data(), packed.pmask.size(), hipMemcpyHostToDevice));
+        s->pd_d = (int)packed.gd.size();
     }
     if (!packed.cd.empty()) {
         HIP_TRY(hipMalloc(&s->d_cd, packed.cd.size() * sizeof(long long)));
@@ -1428,7 +1449,7 @@ struct HostBundle {
         params = *pp;
         params.flags &= ~(int64_t)PVT_FLAG_CARRY_OUT;   // a scene that lives for one call has no next launch to carry photons to
         // (pvt_scene_create, but for the geometry types: a host-buffer call takes a truncated cone)
-        int rc = create_scene(tables, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_FRUSTUM, device, &scene);
+        int rc = create_scene(tables, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_FRUSTUM, device, &scene);
         if (rc != PVT_OK) return rc;
         if (emitter) {
             rc = pvt_scene_set_emitter(scene, emitter);

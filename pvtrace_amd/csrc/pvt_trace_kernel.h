@@ -90,6 +90,9 @@ enum { kCaA = 0, kCaNw, kCaNa, kCaTab, kCa };   // an absorbing scene's record p
                                                                  // absorptivity, its table's axis lengths (kCaNw = 0: none) and
                                                                  // where the table starts in the double blob (wavelengths, angles
                                                                  // in radians, values row-major by angle)
+enum { kPrShape = 0, kPrBounded = 3, kPrLower = 6, kPrH = 9, kPrMask = 12, kPr = 13 };   // a coating pattern's record at KArgs::pd_d:
+                                                                 // shape, per axis 1 = bounded (else index 0), lower, cell
+                                                                 // widths, and where its mask starts, in BYTES from pd
 
 struct Lay {  // record bases (elements) inside the blobs; spectra follow the records and are
               // addressed by absolute offsets stored in the component records
@@ -251,6 +254,13 @@ struct KArgs {
     // PVT_PROPX_ORIGIN_WAVELENGTH + k (0 = none: UF_ORIGIN off) -- queued first crossings carry one more column per bit --
     // and the launch's side store, [lanes of the launch][kOriginWords] doubles in global memory (null with origin == 0)
     int origin;
+    // Patterned coatings (pvt_scene_create_pattern): where the pattern buffer pd starts, in doubles from `gd` -- it lies in
+    // the double blob's allocation but BEYOND its `nd` elements, so no launch stages it in LDS: global memory alone.
+    // pd[2 c] = where coating row c's pattern record starts (-1: the row has no pattern), pd[2 c + 1] != 0: the row covers
+    // any normal; the records (kPr*); behind them the masks, one byte per cell; -1 = no row has a pattern or the flag
+    // (UF_CPAT off).  (It stands where the struct had four bytes of padding: no other member moves and the argument block
+    // keeps its size.)
+    int pd_d;
     double* origin_store;
 };
 constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): index, position, direction, wavelength, path, clock,
@@ -530,6 +540,29 @@ __device__ __attribute__((noinline)) double coat_absorb_call(const double* tab, 
     const int na = (int)r[kCaNa];
     const double* wls = tab + (int)r[kCaTab];
     return coat_table_r(wls, nw, wls + nw, na, wls + nw + na, wl, c1);
+}
+
+// Patterned coatings (PvtCoatingPatternTables; the Python Coating docstring states the rule, pattern_cell is the same
+// arithmetic): does coating row `c`, whose region holds the local point (lx, ly, lz), cover it?  `facet_ok`: the row's
+// normal test passed -- the row's any-facet flag pd[2 c + 1] overrules a failed one.  A row without a pattern
+// (pd[2 c] < 0) then covers; else per bounded axis floor((p - lower) / h) must lie in 0 .. n - 1, or the point is outside
+// and not covered (a NaN coordinate fails every comparison), and ONE byte load from global memory answers, slot
+// (ix ny + iy) nz + iz.  A FUNCTION, like coat_absorb_call: the coating loop's register allocation does not see it.
+__device__ __attribute__((noinline)) int coat_pattern_call(const double* __restrict__ pd, int c, int facet_ok, double lx, double ly,
+                                                           double lz) {
+    if (!facet_ok && pd[2 * c + 1] == 0.0) return 0;
+    const int at = (int)pd[2 * c];
+    if (at < 0) return 1;
+    const double* __restrict__ q = pd + at;
+    double fx = 0.0, fy = 0.0, fz = 0.0;
+    if (q[kPrBounded] != 0.0) fx = __builtin_floor((lx - q[kPrLower]) / q[kPrH]);
+    if (q[kPrBounded + 1] != 0.0) fy = __builtin_floor((ly - q[kPrLower + 1]) / q[kPrH + 1]);
+    if (q[kPrBounded + 2] != 0.0) fz = __builtin_floor((lz - q[kPrLower + 2]) / q[kPrH + 2]);
+    const double nx = q[kPrShape], ny = q[kPrShape + 1], nz = q[kPrShape + 2];
+    const bool inside = fx >= 0.0 && fx <= nx - 1.0 && fy >= 0.0 && fy <= ny - 1.0 && fz >= 0.0 && fz <= nz - 1.0;
+    if (!inside) return 0;
+    const long long slot = ((long long)fx * (long long)ny + (long long)fy) * (long long)nz + (long long)fz;
+    return reinterpret_cast<const unsigned char*>(pd)[(long long)q[kPrMask] + slot] != 0 ? 1 : 0;
 }
 
 // Refractive-index tables n(lambda) (the Python RefractiveIndexTable.at is the same arithmetic): `np` wavelengths, then
@@ -1322,7 +1355,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1335,14 +1368,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.cap_tab != nullptr ? 1u << UF_CAPTURE : 0u) |   // ... and cap_tab ...
         (ROUGH && A.cabs_d >= 0 ? 1u << UF_CABS : 0u) |   // ... and cabs_d ...
         (ROUGH && A.count >= 1 ? 1u << UF_COUNT : 0u) | (ROUGH && A.count >= 2 ? 1u << UF_TQ_COUNT : 0u) |   // ... and count ...
-        (ROUGH && A.origin != 0 ? 1u << UF_ORIGIN : 0u);   // ... and origin)
+        (ROUGH && A.origin != 0 ? 1u << UF_ORIGIN : 0u) |   // ... and origin ...
+        (ROUGH && A.pd_d >= 0 ? 1u << UF_CPAT : 0u);   // ... and pd_d)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -3144,11 +3178,24 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 const double nl3[3] = {nloc.x, nloc.y, nloc.z}, pl3[3] = {lpos.x, lpos.y, lpos.z};
                 for (int c = cs; c < ce && coat < 0; c++) {
                     bool ok = true;
+                    bool okf = true;   // (the extension variants keep the facet's answer apart: a row may cover any normal)
 #pragma unroll
                     for (int a = 0; a < 3; a++) {
                         double f = T.dv(L.coat_d + c * KD + KD_FACET + a);
-                        if (pvt_fabs(nl3[a] - f) > 1e-8 + 1e-5 * pvt_fabs(f)) ok = false;
+                        if (pvt_fabs(nl3[a] - f) > 1e-8 + 1e-5 * pvt_fabs(f)) {
+                            if constexpr (ROUGH) okf = false;
+                            else ok = false;
+                        }
                         if (!(pl3[a] > T.dv(L.coat_d + c * KD + KD_LO + a) && pl3[a] < T.dv(L.coat_d + c * KD + KD_HI + a))) ok = false;
+                    }
+                    if constexpr (ROUGH) {
+                        // (scenes with a patterned coating, PvtCoatingPatternTables) a row whose region holds the point: its
+                        // any-facet flag may overrule the normal test, and its pattern, if it has one, must have the cell set
+                        if (uf(UF_CPAT)) {
+                            if (ok) ok = coat_pattern_call(A.gd + A.pd_d, c, okf ? 1 : 0, lpos.x, lpos.y, lpos.z) != 0;
+                        } else {
+                            ok = ok && okf;
+                        }
                     }
                     if (ok) coat = c;
                 }

@@ -93,6 +93,13 @@ def _host_buffer_scene(compiled):
             "which the host-buffer trace_bundle entry (the reference's interface) cannot take; trace it with "
             "engine.simulate."
         )
+    if getattr(compiled, "has_coating_patterns", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has patterned coatings (Coating(..., pattern=...) or Coating(None, ...)), which the host-buffer "
+            "trace_bundle entry (the reference's interface) cannot take; trace it with engine.simulate."
+        )
     if int(getattr(compiled, "n_ri_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 

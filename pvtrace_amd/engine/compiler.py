@@ -39,6 +39,7 @@ from pvtrace_amd.material import (
     Absorber,
     CoatedSurfaceDelegate,
     Coating,
+    CoatingPattern,
     ConcentrationGrid,
     Cone,
     FresnelSurfaceDelegate,
@@ -55,6 +56,7 @@ from pvtrace_amd.material import (
 
 MAX_NODES = 128       # device limit (reference _kernel.pyx:66, :929-930)
 MAX_RECORDERS = 256   # per-photon distinct-ray bitmask width (compiler.py:23)
+MAX_PATTERN_CELLS = 1 << 26   # cells of all coating patterns of a scene: 64 MiB of bytes, the order of MAX_MAP_SLOTS
 
 GEOM_BOX, GEOM_SPHERE, GEOM_CYLINDER, GEOM_MESH = 0, 1, 2, 3
 GEOM_FRUSTUM = 4   # EXTENSION: truncated cone (include/pvtrace_hip.h: PVT_GEOM_FRUSTUM)
@@ -258,7 +260,18 @@ class CompiledScene:
         atab = {"index": {}, "nw": [], "na": [], "wl_start": [], "angle_start": [], "value_start": [],
                 "wavelength": [], "angle": [], "value": []}
         self.has_absorbing_coatings = False
+        # Where a coating covers (Coating(pattern=..., facet=None)): coat_any_facet flags the rows whose normal test is
+        # skipped (a flag of the row, its coat_facet stays zero and is ignored); coat_pattern names the row's mask lattice
+        # (-1: none) in the `cpat_*` tables -- per pattern its shape, which axes are bounded, lower and cell widths (0 on an
+        # unbounded axis) and where its uint8 mask starts in the pool `cpat_mask`.  One CoatingPattern object shared by
+        # several coatings is stored once.  Passed to the library as PvtCoatingPatternTables, only by scenes that use them.
+        self.coat_any_facet = np.zeros(ncoat, dtype=_I32)
+        self.coat_pattern = np.full(ncoat, -1, dtype=_I32)
+        cpat = {"index": {}, "shape": [], "bounded": [], "lower": [], "h": [], "start": [], "mask": [], "cells": 0}
         for r, coating in enumerate(coat_rows):
+            self.coat_pattern[r] = self._pool_coating_pattern(r, getattr(coating, "pattern", None), cpat)
+            if coating.facet is None:
+                self.coat_any_facet[r] = 1
             absorptivity = getattr(coating, "absorptivity", None)
             if absorptivity is not None:
                 self.has_absorbing_coatings = True
@@ -269,7 +282,8 @@ class CompiledScene:
                     if not 0.0 <= a <= 1.0:
                         raise UnsupportedSceneError(f"Coating {r}: absorptivity must be in [0, 1], got {absorptivity!r}.")
                     self.coat_absorptivity[r] = a
-            self.coat_facet[r] = coating.facet
+            if coating.facet is not None:
+                self.coat_facet[r] = coating.facet
             self.coat_lo[r] = [b[0] for b in coating.region]
             self.coat_hi[r] = [b[1] for b in coating.region]
             if isinstance(coating.reflectivity, ReflectivityTable):
@@ -289,6 +303,15 @@ class CompiledScene:
             setattr(self, f"atab_{key}", np.array(atab[key], dtype=_I32))
         for key in ("wavelength", "angle", "value"):
             setattr(self, f"atab_{key}", np.array(atab[key], dtype=_F64))
+
+        self.n_coat_patterns = len(cpat["start"])
+        self.cpat_shape = np.array(cpat["shape"], dtype=_I32).reshape(-1, 3)
+        self.cpat_bounded = np.array(cpat["bounded"], dtype=_I32).reshape(-1, 3)
+        self.cpat_lower = np.array(cpat["lower"], dtype=_F64).reshape(-1, 3)
+        self.cpat_h = np.array(cpat["h"], dtype=_F64).reshape(-1, 3)
+        self.cpat_start = np.array(cpat["start"], dtype=np.int64)
+        self.cpat_mask = (cpat["mask"][0] if len(cpat["mask"]) == 1 else
+                          np.concatenate(cpat["mask"]) if cpat["mask"] else np.zeros(0, dtype=np.uint8))
 
         pool = self._mesh_pool
         self.n_mesh_vertices, self.n_mesh_faces = pool["nv"], pool["nf"]
@@ -373,6 +396,51 @@ class CompiledScene:
             "NullSurfaceDelegate and CoatedSurfaceDelegate (declarative "
             "coatings) are supported."
         )
+
+    @staticmethod
+    def _pool_coating_pattern(row, pattern, cpat):
+        """Id of a coating row's pattern in the `cpat_*` tables (-1: none), pooled by identity."""
+        if pattern is None:
+            return -1
+        if not isinstance(pattern, CoatingPattern):
+            raise UnsupportedSceneError(f"Coating {row}: pattern must be a CoatingPattern, got {type(pattern).__name__}.")
+        if id(pattern) in cpat["index"]:
+            return cpat["index"][id(pattern)][0]
+        mask = np.ascontiguousarray(pattern.mask, dtype=np.uint8)
+        if mask.ndim != 3 or min(mask.shape) < 1:
+            raise UnsupportedSceneError(f"Coating {row}: the pattern's mask must have three axes of >= 1 cells, got {mask.shape}.")
+        lower, h = [], []
+        for a in range(3):   # (assigned after construction, perhaps: checked again)
+            if not pattern.bounded[a]:
+                if mask.shape[a] != 1:
+                    raise UnsupportedSceneError(f"Coating {row}: pattern axis {a} is unbounded but has {mask.shape[a]} cells.")
+                lower.append(0.0); h.append(0.0)
+                continue
+            lo, hi = float(pattern.lower[a]), float(pattern.upper[a])
+            width = (hi - lo) / float(mask.shape[a])
+            if not (math.isfinite(lo) and math.isfinite(hi) and math.isfinite(width) and width > 0.0):
+                raise UnsupportedSceneError(
+                    f"Coating {row}: pattern axis {a} needs finite bounds with lower < upper, got {pattern.lower[a]!r}, "
+                    f"{pattern.upper[a]!r}.")
+            lower.append(lo); h.append(width)
+        if cpat["cells"] + mask.size > MAX_PATTERN_CELLS:
+            raise UnsupportedSceneError(
+                f"The scene's coating patterns hold more than {MAX_PATTERN_CELLS} cells (2^26), reached at coating {row}.")
+        k = len(cpat["start"])
+        cpat["index"][id(pattern)] = (k, pattern)   # (the object is kept: its id stays its own while the pool lives)
+        cpat["shape"].append(list(mask.shape))
+        cpat["bounded"].append([int(b) for b in pattern.bounded])
+        cpat["lower"].append(lower)
+        cpat["h"].append(h)
+        cpat["start"].append(cpat["cells"])
+        cpat["mask"].append(mask.reshape(-1))   # (bytes as they are: the kernel and the host both ask `!= 0`; no copy of a large mask)
+        cpat["cells"] += mask.size
+        return k
+
+    @property
+    def has_coating_patterns(self):
+        """A coating with a pattern or with facet=None: the scene needs pvt_scene_create_pattern's tables."""
+        return bool(np.any(self.coat_pattern >= 0) or np.any(self.coat_any_facet != 0))
 
     def _surface_roughness(self, node, material):
         delegate = material.surface.delegate
@@ -797,6 +865,12 @@ class CompiledScene:
         "atab_value_start", "atab_wavelength", "atab_angle", "atab_value",
     )
 
+    # the coating patterns' tables: part of `tables()` only when a coating has a pattern or facet=None (a scene without
+    # lowers to its old tables)
+    PATTERN_TABLE_FIELDS = (
+        "coat_any_facet", "coat_pattern", "cpat_shape", "cpat_bounded", "cpat_lower", "cpat_h", "cpat_start", "cpat_mask",
+    )
+
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""
         out = {name: getattr(self, name) for name in self.TABLE_FIELDS}
@@ -810,6 +884,8 @@ class CompiledScene:
             out["capture_rows"] = np.int64(self.capture_rows)
         if self.has_absorbing_coatings:
             out.update({name: getattr(self, name) for name in self.ABSORB_TABLE_FIELDS})
+        if self.has_coating_patterns:
+            out.update({name: getattr(self, name) for name in self.PATTERN_TABLE_FIELDS})
         return out
 
     @property

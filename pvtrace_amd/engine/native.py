@@ -133,6 +133,16 @@ class PvtCoatingAbsorbTables(C.Structure):
     ]
 
 
+class PvtCoatingPatternTables(C.Structure):
+    """Where a scene's coatings cover: any-facet flags and mask lattices (include/pvtrace_hip.h; pvt_scene_create_pattern)."""
+    _fields_ = [
+        ("n_coatings", C.c_int32), ("n_patterns", C.c_int32),
+        ("coat_any_facet", _p_i32), ("coat_pattern", _p_i32),
+        ("shape", _p_i32), ("bounded", _p_i32), ("lower", _p_f64), ("h", _p_f64),
+        ("mask_start", C.POINTER(C.c_int64)), ("mask", C.POINTER(C.c_uint8)), ("n_mask", C.c_int64),
+    ]
+
+
 class PvtCaptures(C.Structure):
     """Capture buffers of one launch (device pointers)."""
     _fields_ = [("rows", C.POINTER(C.c_uint64)), ("cursors", C.POINTER(C.c_int64))]
@@ -396,6 +406,35 @@ def absorb_tables_struct(compiled):
     return st, keep
 
 
+def pattern_tables_struct(compiled):
+    """PvtCoatingPatternTables over the coating patterns of a CompiledScene -> (struct or None, keepalive); None when no
+    coating has a pattern or facet=None (the scene is then created exactly as before)."""
+    if not getattr(compiled, "has_coating_patterns", False):
+        return None, {}
+    keep = {}
+
+    def arr(name, dtype, ctype):
+        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=dtype)   # never hand out NULL for an empty table
+        keep[name] = a
+        return a.ctypes.data_as(C.POINTER(ctype))
+
+    st = PvtCoatingPatternTables()
+    st.n_coatings = int(compiled.n_coatings)
+    st.n_patterns = int(compiled.n_coat_patterns)
+    st.coat_any_facet = arr("coat_any_facet", np.int32, C.c_int32)
+    st.coat_pattern = arr("coat_pattern", np.int32, C.c_int32)
+    st.shape = arr("cpat_shape", np.int32, C.c_int32)
+    st.bounded = arr("cpat_bounded", np.int32, C.c_int32)
+    st.lower = arr("cpat_lower", np.float64, C.c_double)
+    st.h = arr("cpat_h", np.float64, C.c_double)
+    st.mask_start = arr("cpat_start", np.int64, C.c_int64)
+    st.mask = arr("cpat_mask", np.uint8, C.c_uint8)
+    st.n_mask = int(compiled.cpat_mask.shape[0])
+    return st, keep
+
+
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
     keep = {}
@@ -488,6 +527,10 @@ def declare_signatures(lib, names):
                                      C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
                                      C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables), C.c_int, C.POINTER(vp)],
                                     C.c_int),
+        "pvt_scene_create_pattern": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
+                                      C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
+                                      C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables),
+                                      C.POINTER(PvtCoatingPatternTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_trace_device_capture": ([vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
                                       C.POINTER(PvtEventRecords), C.POINTER(PvtCaptures), vp], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
@@ -550,7 +593,7 @@ ABI_SYMBOLS = (
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
-    "pvt_scene_create_origin",
+    "pvt_scene_create_origin", "pvt_scene_create_pattern",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 
@@ -728,12 +771,14 @@ class DeviceScene:
         mt, mkeep = map_tables_struct(compiled)
         ct, ckeep = capture_tables_struct(compiled)
         at, akeep = absorb_tables_struct(compiled)
+        kt, kkeep = pattern_tables_struct(compiled)
         handle = C.c_void_p()
-        # (the older pvt_scene_create* entries do the same with NULL for the tables they lack; this one alone takes a
-        # `detected` recorder; pvt_scene_create_origin is that entry with the launch-origin histogram properties accepted)
-        others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct, at))
-        check(self.lib.pvt_scene_create_origin(C.byref(st), *others, self.device, C.byref(handle)),
-              "pvt_scene_create_origin")
+        # (the older pvt_scene_create* entries do the same with NULL for the tables they lack; pvt_scene_create_absorb alone
+        # takes a `detected` recorder, pvt_scene_create_origin is that entry with the launch-origin histogram properties
+        # accepted, and this one is that entry with the coating patterns: the only one Python ever calls)
+        others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct, at, kt))
+        check(self.lib.pvt_scene_create_pattern(C.byref(st), *others, self.device, C.byref(handle)),
+              "pvt_scene_create_pattern")
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a

@@ -759,6 +759,105 @@ def phase_direction(phase_function, ray):
     return phase_function()
 
 
+class CoatingPattern(object):
+    """Where a coating covers: a mask on a lattice in the node's own frame, the frame `Coating.region` is in.
+
+    mask : an array of three dimensions (nx, ny, nz), each >= 1, of any dtype that is all finite; stored as uint8,
+        `value != 0`.  A set cell is covered.
+    lower, upper : 3-tuples in the node's frame.  On an axis with ONE cell both entries may be None: that axis is
+        unbounded, every point has index 0 there -- a flat pattern on a face is written without bracketing the face's own
+        plane (a face at z = +h must not sit on a lattice boundary).  On every other axis both are finite and
+        lower < upper.
+
+    Anything else raises `ValueError`.  The cell of a point is `pattern_cell`'s (rule 3 in the `Coating` docstring); a
+    point outside the lattice is not covered.
+    """
+
+    def __init__(self, mask, lower, upper):
+        try:
+            raw = np.asarray(mask)
+            if raw.dtype == object or raw.dtype.kind not in "biuf":
+                raise TypeError(f"dtype {raw.dtype}")
+            finite = bool(np.all(np.isfinite(raw))) if raw.dtype.kind == "f" else True
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"CoatingPattern: mask must be a numeric array ({exc})") from None
+        if raw.ndim != 3 or min(raw.shape) < 1:
+            raise ValueError(f"mask must have shape (nx, ny, nz), each axis >= 1, got {raw.shape}")
+        if not finite:
+            raise ValueError("mask must be finite")
+        try:
+            lower, upper = tuple(lower), tuple(upper)
+        except TypeError:
+            raise ValueError("lower and upper must be 3-tuples") from None
+        if len(lower) != 3 or len(upper) != 3:
+            raise ValueError("lower and upper must be 3-tuples")
+        lo, hi, bounded = [], [], []
+        for a in range(3):
+            if lower[a] is None or upper[a] is None:
+                if not (lower[a] is None and upper[a] is None):
+                    raise ValueError(f"axis {a}: lower and upper must both be None or both be numbers")
+                if raw.shape[a] != 1:
+                    raise ValueError(f"axis {a}: only an axis with one cell may be unbounded, it has {raw.shape[a]}")
+                lo.append(-math.inf); hi.append(math.inf); bounded.append(False)
+                continue
+            try:
+                l, u = float(lower[a]), float(upper[a])
+            except (TypeError, ValueError) as exc:
+                raise ValueError(f"axis {a}: lower and upper must be numbers or None ({exc})") from None
+            if not (math.isfinite(l) and math.isfinite(u)):
+                raise ValueError(f"axis {a}: lower and upper must be finite")
+            if not l < u:
+                raise ValueError(f"axis {a}: lower must be < upper")
+            lo.append(l); hi.append(u); bounded.append(True)
+        self.mask = np.ascontiguousarray(raw != 0, dtype=np.uint8)
+        self.mask.setflags(write=False)
+        self.lower = tuple(lo)
+        self.upper = tuple(hi)
+        self.bounded = tuple(bounded)
+
+    @classmethod
+    def like(cls, grid, mask=None):
+        """The lattice of a `ConcentrationGrid`; `mask` given separately (the grid's shape), or `grid.values != 0`."""
+        if mask is None:
+            mask = grid.values != 0
+        elif np.shape(mask) != tuple(grid.shape):
+            raise ValueError(f"mask must have the grid's shape {tuple(grid.shape)}, got {np.shape(mask)}")
+        return cls(mask, tuple(float(v) for v in grid.lower), tuple(float(v) for v in grid.upper))
+
+    @property
+    def shape(self):
+        return self.mask.shape
+
+    @property
+    def cell_widths(self):
+        """h = (upper - lower) / n per axis; inf on an unbounded axis."""
+        return tuple((self.upper[a] - self.lower[a]) / float(self.shape[a]) if self.bounded[a] else math.inf
+                     for a in range(3))
+
+    @property
+    def coverage(self):
+        """The share of set cells."""
+        return float(np.count_nonzero(self.mask)) / float(self.mask.size)
+
+
+def pattern_cell(pattern, local_point):
+    """The slot (ix ny + iy) nz + iz of a point of the node's frame in `pattern`'s lattice, or None when the point is
+    outside: rule 3 of the `Coating` docstring.  Per bounded axis i = floor((p - lower) / h) with h = (upper - lower) / n,
+    each one IEEE double operation, inside when 0 <= i <= n - 1; an unbounded axis has index 0."""
+    h = pattern.cell_widths
+    slot = 0
+    for a in range(3):
+        n = pattern.shape[a]
+        i = 0
+        if pattern.bounded[a]:
+            f = math.floor((float(local_point[a]) - pattern.lower[a]) / h[a]) if math.isfinite(local_point[a]) else -1
+            if not 0 <= f <= n - 1:
+                return None
+            i = int(f)
+        slot = slot * n + i
+    return slot
+
+
 class Coating(object):
     """Declarative override of the optics on part of a node's surface.
 
@@ -768,7 +867,11 @@ class Coating(object):
     callbacks cannot run on the GPU, so the same behaviours are written as data:
 
     facet : outward face normal in the node's LOCAL frame the coating covers
-        (matched like ``np.allclose``: |n_i - facet_i| <= 1e-8 + 1e-5 |facet_i|).
+        (matched like ``np.allclose``: |n_i - facet_i| <= 1e-8 + 1e-5 |facet_i|), or None: any normal (extension) --
+        the normal test is skipped, so a pattern, a region or both can cover part of a sphere or of the slanted side of
+        a cylinder or frustum; without pattern and region it covers the whole surface.
+    pattern : None, or a `CoatingPattern`: a mask lattice in the node's frame that says where, inside facet and region,
+        the coating covers (extension).
     region : optional ((xlo, xhi), (ylo, yhi), (zlo, zhi)) open intervals in the
         local frame restricting where on that face it applies (None = unbounded).
     reflectivity : probability of reflection in [0, 1], a `ReflectivityTable` R(wavelength, angle of incidence),
@@ -800,6 +903,22 @@ class Coating(object):
     `absorptivity=0.0` traces bit for bit as one without, and no photon draws an additional random number; a point
     with A > 0 whose R is exactly 0 takes the one draw it would not take otherwise.  Where both `reflectivity` and
     `absorptivity` are given, R + A > 1 anywhere is refused.
+
+    Where a coating covers -- the rule, the same on the host and on the device (include/pvtrace_hip.h,
+    PvtCoatingPatternTables, states the same):
+
+    1. A coating covers a point when all three hold: its facet matches (or is None); its region contains the point; it
+       has no pattern, or the point's cell is set.
+    2. The point is the local point the coating match already uses: pos + t on an unrotated node, the row products
+       ((R0 x + R1 y) + R2 z) + t otherwise, without FMA (what `VolumeMap` rules 1-3 state).
+    3. Per bounded axis h = (upper - lower) / n and i = floor((p - lower) / h).  The point is inside when
+       0 <= i <= n - 1 on every bounded axis.  The slot is (ix ny + iy) nz + iz.
+    4. A point outside the lattice is not covered.  There is no clamping: a pattern may be smaller than its face.
+    5. The first covering coating wins.  Several coatings with disjoint masks give a palette.
+    6. The decision draws no random number.  A pattern of all ones whose lattice contains the face traces bit for bit as
+       the same coating without a pattern; a pattern of all zeros traces bit for bit as the scene with that coating
+       removed.  Coverage is binary: a dot pattern is rendered into the mask at the resolution it needs.
+    7. Roughness keeps its rule: it applies where no coating covers, so the holes of a pattern on a rough node are rough.
     """
 
     REFLECTION_MODES = {"specular": 0, "lambertian": 1}
@@ -813,10 +932,14 @@ class Coating(object):
         region=None,
         reflection="specular",
         transmission="fresnel",
+        pattern=None,
     ):
-        self.facet = tuple(float(v) for v in facet)
-        if len(self.facet) != 3:
-            raise ValueError("facet must be a 3-vector")
+        self.facet = None if facet is None else tuple(float(v) for v in facet)
+        if self.facet is not None and len(self.facet) != 3:
+            raise ValueError("facet must be a 3-vector or None")
+        if pattern is not None and not isinstance(pattern, CoatingPattern):
+            raise ValueError("pattern must be a CoatingPattern or None")
+        self.pattern = pattern
         if isinstance(reflectivity, ReflectivityTable):
             self.reflectivity = reflectivity
         else:
@@ -853,13 +976,18 @@ class Coating(object):
         self.region = tuple(bounds)
 
     def covers(self, normal, position):
+        """Rule 1 of "where a coating covers" in the class docstring; `position` in the node's frame."""
         for a in range(3):
-            if abs(normal[a] - self.facet[a]) > 1e-8 + 1e-5 * abs(self.facet[a]):
+            if self.facet is not None and abs(normal[a] - self.facet[a]) > 1e-8 + 1e-5 * abs(self.facet[a]):
                 return False
             lo, hi = self.region[a]
             if not (lo < position[a] < hi):
                 return False
-        return True
+        pattern = getattr(self, "pattern", None)
+        if pattern is None:
+            return True
+        slot = pattern_cell(pattern, position)
+        return slot is not None and bool(pattern.mask.reshape(-1)[slot])
 
 
 class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
