@@ -1608,6 +1608,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     int hr_surf = 0;
     double hr_n2 = 0.0, hr_rn2 = 0.0, hr_cc = 0.0;
     constexpr bool kHoist = TAIL;
+    constexpr bool kClassRegions = LEAN != kLeanOff;   // (lean) the step's class-keyed bodies: one divergent region per lane class
     // (scenes with index tables, UF_DISP) the refractive index of `node` at the photon's wavelength: its class's table
     // n(lambda), or `n`, the node's scalar index, when the class has none (a dispersive node has a class of its own)
     auto index_at = [&](int node, double n) -> double {
@@ -2852,7 +2853,24 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 travelled += adv;
                 duration += div_known(adv * n_container, kCcm, kRcpCcm);
             }
-            if (hit == k_root) {  // leaves the scene (:728-744)
+            if constexpr (kClassRegions) {
+                // (lean) the three outcomes as selects of VALUES (see fold_by_key): each nested body is a handful of
+                // moves, and a divergent `if` around it costs three scalar instructions and a branch that a wave of 64
+                // mixed photons never takes.  The absorbed lanes' draws wait for the one region of their class below.
+                const bool leaves = hit == k_root;                            // leaves the scene (:728-744)
+                const bool absorbed = !leaves && depth < t0;                  // absorbed (:762-832)
+                const bool surface = !leaves && !absorbed && adjacent >= 0;   // surface interaction (:834-895)
+                const bool malformed = !leaves && !absorbed && adjacent < 0;  // malformed scene (:840-845)
+                cls = leaves ? (int)CLS_EXIT : absorbed ? (int)CLS_ABS : surface ? (int)CLS_SURF : (int)CLS_NONE;
+                ev_kind = leaves ? (int)PVT_EV_EXIT : malformed ? (int)PVT_EV_KILL : ev_kind;
+                ev_hit = absorbed ? ev_hit : hit;
+                ev_adjacent = (leaves || surface) ? adjacent : ev_adjacent;
+                terminal = terminal || leaves || malformed;
+                t_sel = leaves ? (int)PVT_REC_EXIT : t_sel;
+                t_node = (leaves || surface) ? hit : t_node;
+                t_normal = t_normal || leaves || surface;
+                ev_normal = ev_normal || surface;
+            } else if (hit == k_root) {  // leaves the scene (:728-744)
                 ev_kind = PVT_EV_EXIT; ev_hit = hit; ev_adjacent = adjacent;
                 terminal = true;
                 t_sel = PVT_REC_EXIT; t_node = hit; t_normal = true;
@@ -2861,7 +2879,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if (depth < t0) {  // absorbed (:762-832)
                     const double target = rng_uniform(rng) * alpha;
                     comp = cbase;
-                    if (LEAN || ccount <= 2) {   // (lean: at most two, proven)
+                    if (ccount <= 2) {
                         // (the reference walks the cumulative coefficients; with two components the first
                         // partial sum decides, and the last component takes what is left, :768-781)
                         comp = (ccount == 2 && !(target <= pre0)) ? cbase + 1 : cbase;
@@ -2900,7 +2918,63 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         // ---- the absorbing component decides (:783-832): one pass per distinct component of the wave,
         // its record in SGPRs
         const double wl_abs = wl;   // (volume maps: the wavelength the ABSORB row holds; unused in the smooth variants)
-        {
+        if constexpr (kClassRegions) {
+            // (lean) ONE divergent region for the absorbed lanes: the component pick, the quantum-yield draw, the emission
+            // draws in the reference's order and the lifetime draw -- every draw under the condition it has in the
+            // generic body below, so the lane's stream is the same; the two ends of the component's decision differ
+            // in five values, which are selects; the emission method is wave-uniform and stays a scalar branch.
+            // (absorbers and luminophores only, isotropic, no table, at most two components: prove_lean)
+            if (cls == CLS_ABS) {
+                const double target = rng_uniform(rng) * alpha;
+                // (the reference walks the cumulative coefficients; with two components the first partial sum
+                // decides, and the last component takes what is left, :768-781)
+                comp = (ccount == 2 && !(target <= pre0)) ? cbase + 1 : cbase;
+                log_row<RECORD, TAIL>(A, rec_slot, nev, PVT_EV_ABSORB, -1, container, -1, comp, source, pos,
+                                dir, false, pos, wl, travelled, duration);
+                ev_component = comp;
+                const int cr = crec + (comp - cbase);
+                const int ci = L.comp_i + cr * CI, cd = L.comp_d + cr * CD;
+                bool radiative = false;
+                if (T.iv(ci + CI_TYPE) == PVT_COMP_LUMINOPHORE) radiative = rng_uniform(rng) < T.dv(cd + CD_QY);
+                const double tau = T.dv(cd + (radiative ? (int)CD_TAU_RAD : (int)CD_TAU_NR));
+                ev_kind = radiative ? (int)PVT_EV_EMIT : (int)PVT_EV_NONRADIATIVE;
+                t_sel = radiative ? t_sel : (int)PVT_REC_LOST;
+                t_node = radiative ? t_node : container;
+                terminal = terminal || !radiative;
+                if (radiative) {
+                    // isotropic (_kernel.pyx:455-476): azimuth 2 pi g1, cosine of the polar angle 2 g2 - 1
+                    const double g1 = rng_uniform(rng), g2 = rng_uniform(rng);
+                    const double em_c = 2.0 * g2 - 1.0;
+                    const double em_s = sqrt1m2_normal(em_c);
+                    double sp, cp;
+                    pvt_sincos2pi(g1, &sp, &cp);
+                    dir = V3{em_s * cp, em_s * sp, em_c};
+                    em = true;
+                    source = comp;
+                    const int ex = T.iv(ci + CI_EMS_X), ec = T.iv(ci + CI_EMS_CDF), en = T.iv(ci + CI_EMS_N);
+                    const int eh = T.iv(ci + CI_EMS_HIST);
+                    const double ew = T.dv(cd + CD_EMS_W);
+                    double p1;
+                    if (uf(UF_EMIT_FULL)) {
+                        p1 = 0.0;
+                    } else {
+                        double e_nm = wl;
+                        if (uf(UF_EMIT_KT)) {
+                            const double kb_ev = 1.380649e-23 / 1.60217662e-19;
+                            double e_ev = div_normal(1240.0, e_nm) + 1.5 * kb_ev * 300.0;
+                            e_nm = div_normal(1240.0, e_ev);
+                        }
+                        p1 = interp_clamped<TAB_LDS, kAbsKind>(T, e_nm, ex, ec, en, T.iv(ci + CI_EMS_GX), T.dv(cd + CD_EMS_SCALE_X),
+                                                                          eh, T.dv(cd + CD_EMS_RCP_X), ew);
+                    }
+                    const double gamma = p1 + (1.0 - p1) * rng_uniform(rng);
+                    wl = interp_clamped<TAB_LDS, kCdfKind>(T, gamma, ec, ex, en, T.iv(ci + CI_EMS_GC), T.dv(cd + CD_EMS_SCALE_C), eh,
+                                                                T.dv(cd + CD_EMS_RCP_C), __builtin_nan(""), eh ? __builtin_nan("") : ew);
+                }
+                // radiative / non-radiative lifetime: the last draw of either end
+                if (tau > 0.0) duration += -pvt_log(1.0 - rng_uniform(rng)) * tau;
+            }
+        } else {
             const int cu = comp;                       // the component's id (what the event and `source` name) ...
             const bool mine = cls == CLS_ABS;
             const int cr = mine ? crec + (comp - cbase) : 0;   // ... and its record
@@ -2908,8 +2982,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             const int ctype = T.iv(ci + CI_TYPE);
             if (mine) {
                 bool radiative = false;
-                // (lean: absorbers and luminophores only, isotropic, no table)
-                if ((!LEAN && ctype == PVT_COMP_SCATTERER) || ctype == PVT_COMP_LUMINOPHORE)
+                if (ctype == PVT_COMP_SCATTERER || ctype == PVT_COMP_LUMINOPHORE)
                     radiative = rng_uniform(rng) < T.dv(cd + CD_QY);
                 double tau = 0.0;
                 if (radiative) {
@@ -2923,17 +2996,17 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     // a tabulated phase function: CD_PHASE is where its record starts, with the spectra.  (A
                     // wave-uniform "the scene has tables" flag in front of the lane test put a vector register of the
                     // 256-recorder tally variants in scratch; without it the headline variant keeps its registers.)
-                    const bool tabled = !LEAN && pt == PVT_PHASE_TABLE;
+                    const bool tabled = pt == PVT_PHASE_TABLE;
                     const double* ptab = (TAB_LDS == 1 ? T.ld : T.hd) + (tabled ? (int)pp : 0);
                     double u1 = 0.0, u3 = 0.0;
-                    if (!LEAN && pt == PVT_PHASE_HG && pvt_fabs(pp) >= kEps) {
+                    if (pt == PVT_PHASE_HG && pvt_fabs(pp) >= kEps) {
                         double g1 = rng_uniform(rng);
                         double sg = 2.0 * g1 - 1.0;
                         double q = (1.0 - pp * pp) / (1.0 + pp * sg);
                         em_c = 1.0 / (2.0 * pp) * (1.0 + pp * pp - q * q);
                         em_turn = rng_uniform(rng);
                         em_s = sqrt1m2_normal(em_c);
-                    } else if (!LEAN && pt == PVT_PHASE_CONE) {
+                    } else if (pt == PVT_PHASE_CONE) {
                         double g1 = rng_uniform(rng), g2 = rng_uniform(rng);
                         em_s = pvt_sqrt(g1) * pvt_sin(pp);
                         em_turn = g2;
@@ -2958,7 +3031,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                     em = true;
                     source = cu;
-                    if (LEAN || ctype == PVT_COMP_LUMINOPHORE) {
+                    if (ctype == PVT_COMP_LUMINOPHORE) {
                         const int ex = T.iv(ci + CI_EMS_X), ec = T.iv(ci + CI_EMS_CDF), en = T.iv(ci + CI_EMS_N);
                         const int eh = T.iv(ci + CI_EMS_HIST);
                         const double ew = T.dv(cd + CD_EMS_W);
@@ -2985,7 +3058,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                 } else {
                     tau = T.dv(cd + CD_TAU_NR);
-                    if (!LEAN && ctype == PVT_COMP_REACTOR) { ev_kind = PVT_EV_REACT; t_sel = PVT_REC_REACTED; }
+                    if (ctype == PVT_COMP_REACTOR) { ev_kind = PVT_EV_REACT; t_sel = PVT_REC_REACTED; }
                     else { ev_kind = PVT_EV_NONRADIATIVE; t_sel = PVT_REC_LOST; }
                     t_node = container;
                     terminal = true;
