@@ -382,17 +382,111 @@ struct PackedScene {
     std::vector<int> bvh_roots;
 };
 
-// Every index into a table that the packer follows on the host or the kernel on the device, checked before anything
-// else is read.
-int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-                    const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                    const PvtCoatingAbsorbTables* ab, int max_selector, int max_prop, int max_geom) {
-    const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
+// ---- One record of a scene's inputs.  Every pvt_scene_create* entry, pvt_scene_lean_check and the host-buffer path fill
+// one and hand it to create_scene / pack_scene: the table structs (t always; the others NULL = the scene has none) and
+// what the calling entry KNOWS.  An entry from before an extension keeps refusing what that extension added, with the
+// message it always had: a recorder selector beyond Knows::max_selector ("recorder selector out of range"), a histogram
+// property beyond max_prop ("histogram property out of range": the kernel reads column `prop` of its tally queue, so an id
+// beyond the ones it parks would read past the queue), a geometry type beyond max_geom ("unknown geometry type").
+struct Knows {
+    int max_selector, max_prop, max_geom;   // the last recorder selector, histogram property and geometry type known
+};
+
+struct SceneInputs {
+    const PvtSceneTables* t = nullptr;             // the scene tables
+    const PvtIndexTables* x = nullptr;             // refractive-index tables n(lambda)
+    const PvtPhaseTables* ph = nullptr;            // phase-function tables
+    const PvtSurfaceTables* rs = nullptr;          // the nodes' surface roughness
+    const PvtFieldTables* fr = nullptr;            // concentration fields
+    const PvtMapTables* mp = nullptr;              // volume maps
+    const PvtCaptureTables* cp = nullptr;          // ray captures
+    const PvtCoatingAbsorbTables* ab = nullptr;    // the coatings' absorptivities
+    const PvtCoatingPatternTables* pt = nullptr;   // where the coatings cover
+    Knows knows{};
+};
+
+// The levels an entry can know, one row each.  A new entry that knows more gets a new row; nothing else names these limits.
+//                                 last selector      last property          last geometry        used by
+constexpr Knows kKnowsBeforeAbsorb{PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_MESH};     // pvt_scene_create .. pvt_scene_create_capture
+constexpr Knows kKnowsAbsorb      {PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH};     // pvt_scene_create_absorb
+constexpr Knows kKnowsOrigin      {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_FRUSTUM};  // pvt_scene_create_origin, _pattern, pvt_scene_lean_check
+constexpr Knows kKnowsHostBuffer  {PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_FRUSTUM};  // pvt_trace_bundle*: pvt_scene_create, but a truncated cone is taken
+
+// ---- validation: every index into a table that the packer follows on the host or the kernel on the device, checked
+// before anything else is read.  One function per table struct; validate_tables calls them in the order that decides
+// which refusal a scene with two faults meets.
+// n values, finite and strictly increasing
+bool increasing_finite(const double* v, long long n) {
+    for (long long i = 0; i < n; i++)
+        if (!std::isfinite(v[i]) || (i > 0 && !(v[i] > v[i - 1]))) return false;
+    return true;
+}
+// n angles in [0, 90] degrees, strictly increasing
+bool increasing_angles(const double* v, long long n) {
+    for (long long i = 0; i < n; i++)
+        if (!(v[i] >= 0.0 && v[i] <= 90.0) || (i > 0 && !(v[i] > v[i - 1]))) return false;
+    return true;
+}
+// n values in [0, 1] (a NaN is not)
+bool within_unit(const double* v, long long n) {
+    for (long long i = 0; i < n; i++)
+        if (!(v[i] >= 0.0 && v[i] <= 1.0)) return false;
+    return true;
+}
+// runs [start, start + count) into a table of `size` rows
+bool bad_run(long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; }
+
+// Tables of values on a wavelength x angle grid, pooled: the coating reflectivity tables of PvtSceneTables and the
+// absorptivity tables of PvtCoatingAbsorbTables are the same thing under different field names.
+struct GridTables {
+    int n_tables;
+    const int32_t *nw, *na, *wl_start, *angle_start, *value_start;
+    long long n_wavelength, n_angle, n_value;
+    const double *wavelength, *angle, *value;
+    long long doubles(int j) const { return (long long)nw[j] + na[j] + (long long)nw[j] * na[j]; }
+};
+GridTables grid_tables(const PvtSceneTables* t) {
+    return {t->n_coat_tables, t->ctab_nw, t->ctab_na, t->ctab_wl_start, t->ctab_angle_start, t->ctab_value_start,
+            t->n_ctab_wavelength, t->n_ctab_angle, t->n_ctab_value, t->ctab_wavelength, t->ctab_angle, t->ctab_value};
+}
+GridTables grid_tables(const PvtCoatingAbsorbTables* ab) {
+    return {ab->n_tables, ab->table_nw, ab->table_na, ab->wl_start, ab->angle_start, ab->value_start,
+            ab->n_wavelength, ab->n_angle, ab->n_value, ab->wavelength, ab->angle, ab->value};
+}
+struct GridMessages { const char *range, *wavelengths, *angles, *values, *total; };
+// Every table's ranges, axes and values, then the doubles of all of them (`total`: what the caller places besides)
+int validate_grid_tables(const GridTables& g, long long total, const GridMessages& m) {
+    for (int j = 0; j < g.n_tables; j++) {
+        const long long nw = g.nw[j], na = g.na[j];
+        const long long w0 = g.wl_start[j], a0 = g.angle_start[j], v0 = g.value_start[j];
+        if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > g.n_wavelength || a0 + na > g.n_angle ||
+            v0 + nw * na > g.n_value)
+            return fail(PVT_ERR_INVALID, m.range);
+        if (!increasing_finite(g.wavelength + w0, nw)) return fail(PVT_ERR_INVALID, m.wavelengths);
+        if (!increasing_angles(g.angle + a0, na)) return fail(PVT_ERR_INVALID, m.angles);
+        if (!within_unit(g.value + v0, nw * na)) return fail(PVT_ERR_INVALID, m.values);
+        total += nw + na + nw * na;
+    }
+    if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, m.total);
+    return PVT_OK;
+}
+// Table j where the blob keeps it, at d: wavelengths (nm), angles (radians: the kernel compares pvt_acos of the cosine),
+// values -- GridTables::doubles(j) doubles
+void put_grid_table(const GridTables& g, int j, double* d) {
+    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
+    const int nw = g.nw[j], na = g.na[j];
+    for (int i = 0; i < nw; i++) d[i] = g.wavelength[g.wl_start[j] + i];
+    for (int i = 0; i < na; i++) d[nw + i] = g.angle[g.angle_start[j] + i] * kRadPerDeg;
+    for (int i = 0; i < na * nw; i++) d[nw + na + i] = g.value[g.value_start[j] + i];
+}
+
+// the core tables, first part: the root, the geometry of every node and the meshes
+int validate_nodes(const PvtSceneTables* t, const Knows& knows) {
+    const int N = t->n_nodes;
     if (t->root_id < 0 || t->root_id >= N) return fail(PVT_ERR_INVALID, "root node out of range");
     for (int n = 0; n < N; n++) {
         const int g = t->geom_type[n];
-        // (max_geom: the last geometry type the entry knows -- the entries from before the truncated cone refuse type 4 as they did)
-        if (g < PVT_GEOM_BOX || g > max_geom) return fail(PVT_ERR_INVALID, "unknown geometry type");
+        if (g < PVT_GEOM_BOX || g > knows.max_geom) return fail(PVT_ERR_INVALID, "unknown geometry type");
         if (g == PVT_GEOM_FRUSTUM) {   // (length, radius_bottom, radius_top): the kernel divides by the first
             const double* gp = t->geom_params + n * 4;
             if (!(std::isfinite(gp[0]) && gp[0] > 0.0)) return fail(PVT_ERR_INVALID, "frustum: length must be finite and > 0");
@@ -410,60 +504,65 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
             if (t->mesh_faces[k] < 0 || t->mesh_faces[k] >= t->n_mesh_vertices)
                 return fail(PVT_ERR_INVALID, "mesh face indexes a missing vertex");
     }
-    if (K > 0 && t->n_coat_tables != 0) {   // coating reflectivity tables (the fields appended to the v13 struct)
-        const int NT = t->n_coat_tables;
-        if (NT < 0 || !t->coat_table || !t->ctab_nw || !t->ctab_na || !t->ctab_wl_start || !t->ctab_angle_start ||
-            !t->ctab_value_start || !t->ctab_wavelength || !t->ctab_angle || !t->ctab_value)
-            return fail(PVT_ERR_INVALID, "coating tables: missing arrays");
-        long long total = 0;
-        for (int j = 0; j < NT; j++) {
-            const long long nw = t->ctab_nw[j], na = t->ctab_na[j];
-            const long long w0 = t->ctab_wl_start[j], a0 = t->ctab_angle_start[j], v0 = t->ctab_value_start[j];
-            if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > t->n_ctab_wavelength ||
-                a0 + na > t->n_ctab_angle || v0 + nw * na > t->n_ctab_value)
-                return fail(PVT_ERR_INVALID, "coating tables: axis or value range out of bounds");
-            for (long long i = 0; i < nw; i++)
-                if (!std::isfinite(t->ctab_wavelength[w0 + i]) || (i > 0 && !(t->ctab_wavelength[w0 + i] > t->ctab_wavelength[w0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "coating tables: wavelengths must be finite and strictly increasing");
-            for (long long i = 0; i < na; i++)
-                if (!(t->ctab_angle[a0 + i] >= 0.0 && t->ctab_angle[a0 + i] <= 90.0) || (i > 0 && !(t->ctab_angle[a0 + i] > t->ctab_angle[a0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "coating tables: angles must be strictly increasing, in [0, 90] degrees");
-            for (long long i = 0; i < nw * na; i++)
-                if (!(t->ctab_value[v0 + i] >= 0.0 && t->ctab_value[v0 + i] <= 1.0))
-                    return fail(PVT_ERR_INVALID, "coating tables: values must be in [0, 1]");
-            total += nw + na + nw * na;
-        }
-        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "coating tables: more than 2^27 doubles");
-        for (int k = 0; k < K; k++)
-            if (t->coat_table[k] < -1 || t->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "coating row names a missing table");
-    }
-    for (int n = 0; n < N; n++) {   // (the known-divisor division is proven for these)
+    return PVT_OK;
+}
+
+// coating reflectivity tables (the fields appended to the v13 struct)
+int validate_coating_tables(const PvtSceneTables* t) {
+    const int K = t->n_coatings, NT = t->n_coat_tables;
+    if (K <= 0 || NT == 0) return PVT_OK;
+    if (NT < 0 || !t->coat_table || !t->ctab_nw || !t->ctab_na || !t->ctab_wl_start || !t->ctab_angle_start ||
+        !t->ctab_value_start || !t->ctab_wavelength || !t->ctab_angle || !t->ctab_value)
+        return fail(PVT_ERR_INVALID, "coating tables: missing arrays");
+    const int rc = validate_grid_tables(grid_tables(t), 0,
+                                        {"coating tables: axis or value range out of bounds",
+                                         "coating tables: wavelengths must be finite and strictly increasing",
+                                         "coating tables: angles must be strictly increasing, in [0, 90] degrees",
+                                         "coating tables: values must be in [0, 1]",
+                                         "coating tables: more than 2^27 doubles"});
+    if (rc != PVT_OK) return rc;
+    for (int k = 0; k < K; k++)
+        if (t->coat_table[k] < -1 || t->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "coating row names a missing table");
+    return PVT_OK;
+}
+
+// the nodes' refractive indices
+int validate_indices(const PvtSceneTables* t) {
+    for (int n = 0; n < t->n_nodes; n++) {   // (the known-divisor division is proven for these)
         const double v = t->refractive_index[n];
         if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) return fail(PVT_ERR_INVALID, "refractive indices must be finite and positive");
     }
-    if (x && x->n_tables != 0) {   // refractive-index tables n(lambda) (PvtIndexTables, pvt_scene_create_ex)
-        const int NT = x->n_tables;
-        if (NT < 0 || !x->node_table || !x->table_n || !x->table_start || !x->wavelength || !x->value)
-            return fail(PVT_ERR_INVALID, "index tables: missing arrays");
-        for (int n = 0; n < N; n++)
-            if (x->node_table[n] < -1 || x->node_table[n] >= NT) return fail(PVT_ERR_INVALID, "index tables: node names a missing table");
-        long long total = 0;
-        for (int j = 0; j < NT; j++) {
-            const long long np = x->table_n[j], p0 = x->table_start[j];
-            if (np < 1 || p0 < 0 || p0 + np > x->n_points) return fail(PVT_ERR_INVALID, "index tables: point range out of bounds");
-            for (long long i = 0; i < np; i++)
-                if (!std::isfinite(x->wavelength[p0 + i]) || (i > 0 && !(x->wavelength[p0 + i] > x->wavelength[p0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "index tables: wavelengths must be finite and strictly increasing");
-            for (long long i = 0; i < np; i++) {   // (the bounds of the scalar indices: the lanes divide by these)
-                const double v = x->value[p0 + i];
-                if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) return fail(PVT_ERR_INVALID, "index tables: values must be finite and positive, in (1e-100, 1e100)");
-            }
-            total += 2 * np;
+    return PVT_OK;
+}
+
+// refractive-index tables n(lambda) (PvtIndexTables, pvt_scene_create_ex)
+int validate_index_tables(const PvtSceneTables* t, const PvtIndexTables* x) {
+    if (!x || x->n_tables == 0) return PVT_OK;
+    const int N = t->n_nodes, NT = x->n_tables;
+    if (NT < 0 || !x->node_table || !x->table_n || !x->table_start || !x->wavelength || !x->value)
+        return fail(PVT_ERR_INVALID, "index tables: missing arrays");
+    for (int n = 0; n < N; n++)
+        if (x->node_table[n] < -1 || x->node_table[n] >= NT) return fail(PVT_ERR_INVALID, "index tables: node names a missing table");
+    long long total = 0;
+    for (int j = 0; j < NT; j++) {
+        const long long np = x->table_n[j], p0 = x->table_start[j];
+        if (np < 1 || p0 < 0 || p0 + np > x->n_points) return fail(PVT_ERR_INVALID, "index tables: point range out of bounds");
+        if (!increasing_finite(x->wavelength + p0, np))
+            return fail(PVT_ERR_INVALID, "index tables: wavelengths must be finite and strictly increasing");
+        for (long long i = 0; i < np; i++) {   // (the bounds of the scalar indices: the lanes divide by these)
+            const double v = x->value[p0 + i];
+            if (!(std::isfinite(v) && v > 1e-100 && v < 1e100)) return fail(PVT_ERR_INVALID, "index tables: values must be finite and positive, in (1e-100, 1e100)");
         }
-        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "index tables: more than 2^27 doubles");
+        total += 2 * np;
     }
-    // phase-function tables (PvtPhaseTables, pvt_scene_create_phase): a component tagged PVT_PHASE_TABLE names one, and
-    // only such a component does; without the struct the tag is refused
+    if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "index tables: more than 2^27 doubles");
+    return PVT_OK;
+}
+
+// phase-function tables (PvtPhaseTables, pvt_scene_create_phase): a component tagged PVT_PHASE_TABLE names one, and
+// only such a component does; without the struct the tag is refused
+int validate_phase_tables(const PvtSceneTables* t, const PvtPhaseTables* ph) {
+    const int C = t->n_components;
     const int NP = ph ? ph->n_tables : 0;
     if (NP < 0 || (NP > 0 && (!ph->comp_table || !ph->table_nw || !ph->table_nmu || !ph->wl_start || !ph->mu_start ||
                               !ph->cdf_start || !ph->wavelength || !ph->mu || !ph->cdf)))
@@ -476,189 +575,193 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
         if (NP > 0 && tagged != (ph->comp_table[c] >= 0))
             return fail(PVT_ERR_INVALID, "phase tables: a component names a table exactly when it is tagged PVT_PHASE_TABLE");
     }
-    if (NP > 0) {
-        long long total = 0;
-        for (int j = 0; j < NP; j++) {
-            const long long nw = ph->table_nw[j], nm = ph->table_nmu[j];
-            const long long w0 = ph->wl_start[j], m0 = ph->mu_start[j], c0 = ph->cdf_start[j];
-            if (nw < 1 || nm < 2 || w0 < 0 || m0 < 0 || c0 < 0 || w0 + nw > ph->n_wavelength || m0 + nm > ph->n_points ||
-                c0 + nw * nm > ph->n_cdf)
-                return fail(PVT_ERR_INVALID, "phase tables: wavelength, mu or CDF range out of bounds");
-            for (long long i = 0; i < nw; i++)
-                if (!std::isfinite(ph->wavelength[w0 + i]) || (i > 0 && !(ph->wavelength[w0 + i] > ph->wavelength[w0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "phase tables: wavelengths must be finite and strictly increasing");
-            const double* mu = ph->mu + m0;
-            if (mu[0] != -1.0 || mu[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "phase tables: the mu axis must run from exactly -1 to exactly 1");
+    long long total = 0;
+    for (int j = 0; j < NP; j++) {
+        const long long nw = ph->table_nw[j], nm = ph->table_nmu[j];
+        const long long w0 = ph->wl_start[j], m0 = ph->mu_start[j], c0 = ph->cdf_start[j];
+        if (nw < 1 || nm < 2 || w0 < 0 || m0 < 0 || c0 < 0 || w0 + nw > ph->n_wavelength || m0 + nm > ph->n_points ||
+            c0 + nw * nm > ph->n_cdf)
+            return fail(PVT_ERR_INVALID, "phase tables: wavelength, mu or CDF range out of bounds");
+        if (!increasing_finite(ph->wavelength + w0, nw))
+            return fail(PVT_ERR_INVALID, "phase tables: wavelengths must be finite and strictly increasing");
+        const double* mu = ph->mu + m0;
+        if (mu[0] != -1.0 || mu[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "phase tables: the mu axis must run from exactly -1 to exactly 1");
+        for (long long i = 1; i < nm; i++)
+            if (!(mu[i] > mu[i - 1])) return fail(PVT_ERR_INVALID, "phase tables: the mu axis must be strictly increasing");
+        for (long long r = 0; r < nw; r++) {
+            const double* cdf = ph->cdf + c0 + r * nm;
+            if (cdf[0] != 0.0 || cdf[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "phase tables: every CDF row must run from exactly 0 to exactly 1");
             for (long long i = 1; i < nm; i++)
-                if (!(mu[i] > mu[i - 1])) return fail(PVT_ERR_INVALID, "phase tables: the mu axis must be strictly increasing");
-            for (long long r = 0; r < nw; r++) {
-                const double* cdf = ph->cdf + c0 + r * nm;
-                if (cdf[0] != 0.0 || cdf[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "phase tables: every CDF row must run from exactly 0 to exactly 1");
-                for (long long i = 1; i < nm; i++)
-                    if (!(cdf[i] >= cdf[i - 1])) return fail(PVT_ERR_INVALID, "phase tables: every CDF row must be non-decreasing");
-            }
-            total += 2 + nw + nm + nw * nm;
+                if (!(cdf[i] >= cdf[i - 1])) return fail(PVT_ERR_INVALID, "phase tables: every CDF row must be non-decreasing");
         }
-        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "phase tables: more than 2^27 doubles");
+        total += 2 + nw + nm + nw * nm;
     }
-    // rough interfaces (PvtSurfaceTables, pvt_scene_create_rough): one finite GGX width 0 <= alpha <= 1 per node
-    if (rs && rs->n_nodes != 0) {
-        if (rs->n_nodes != N || !rs->node_roughness) return fail(PVT_ERR_INVALID, "surface tables: need one roughness per node");
-        for (int n = 0; n < N; n++) {
-            const double a = rs->node_roughness[n];
-            if (!(std::isfinite(a) && a >= 0.0 && a <= 1.0))
-                return fail(PVT_ERR_INVALID, "surface tables: roughness must be finite and within [0, 1]");
+    if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "phase tables: more than 2^27 doubles");
+    return PVT_OK;
+}
+
+// rough interfaces (PvtSurfaceTables, pvt_scene_create_rough): one finite GGX width 0 <= alpha <= 1 per node
+int validate_surface_tables(const PvtSceneTables* t, const PvtSurfaceTables* rs) {
+    if (!rs || rs->n_nodes == 0) return PVT_OK;
+    const int N = t->n_nodes;
+    if (rs->n_nodes != N || !rs->node_roughness) return fail(PVT_ERR_INVALID, "surface tables: need one roughness per node");
+    if (!within_unit(rs->node_roughness, N)) return fail(PVT_ERR_INVALID, "surface tables: roughness must be finite and within [0, 1]");
+    return PVT_OK;
+}
+
+// concentration fields (PvtFieldTables, pvt_scene_create_field): lattices, value tables and who uses which
+int validate_field_tables(const PvtSceneTables* t, const PvtFieldTables* fr) {
+    if (!fr || fr->n_nodes == 0) return PVT_OK;
+    const int N = t->n_nodes, C = t->n_components;
+    const int F = fr->n_fields, V = fr->n_values;
+    if (fr->n_nodes != N || !fr->node_field) return fail(PVT_ERR_INVALID, "field tables: need one lattice index per node");
+    if (F < 0 || (F > 0 && (!fr->field_shape || !fr->field_lower || !fr->field_upper)))
+        return fail(PVT_ERR_INVALID, "field tables: lattice arrays missing");
+    for (int n = 0; n < N; n++)
+        if (fr->node_field[n] < -1 || fr->node_field[n] >= F) return fail(PVT_ERR_INVALID, "field tables: lattice index out of range");
+    if (fr->node_field[t->root_id] >= 0) return fail(PVT_ERR_INVALID, "field tables: the root node cannot carry a lattice");
+    for (int f = 0; f < F; f++)
+        for (int a = 0; a < 3; a++) {
+            if (fr->field_shape[f * 3 + a] < 1) return fail(PVT_ERR_INVALID, "field tables: lattice shape must be >= 1 on each axis");
+            const double lo = fr->field_lower[f * 3 + a], hi = fr->field_upper[f * 3 + a];
+            if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(PVT_ERR_INVALID, "field tables: lattice bounds must be finite");
+            if (!(lo < hi)) return fail(PVT_ERR_INVALID, "field tables: lattice lower must be < upper on each axis");
+        }
+    if (fr->n_components != C || (C > 0 && !fr->comp_values))
+        return fail(PVT_ERR_INVALID, "field tables: need one value-table index per component");
+    if (V < 0 || fr->n_points < 0 || (V > 0 && (!fr->values_start || !fr->values_count)) || (fr->n_points > 0 && !fr->values))
+        return fail(PVT_ERR_INVALID, "field tables: value-table arrays missing");
+    for (int c = 0; c < C; c++)
+        if (fr->comp_values[c] < -1 || fr->comp_values[c] >= V) return fail(PVT_ERR_INVALID, "field tables: value-table index out of range");
+    for (int v = 0; v < V; v++)
+        if (bad_run(fr->values_start[v], fr->values_count[v], fr->n_points) || fr->values_count[v] < 1)
+            return fail(PVT_ERR_INVALID, "field tables: value-table run out of range");
+    for (int i = 0; i < fr->n_points; i++)
+        if (!std::isfinite(fr->values[i])) return fail(PVT_ERR_INVALID, "field tables: values must be finite");
+    for (int i = 0; i < fr->n_points; i++)
+        if (fr->values[i] < 0.0) return fail(PVT_ERR_INVALID, "field tables: values must be >= 0");
+    // every component of a node with a lattice names a value table of exactly that lattice's size; the buffer the
+    // kernel indexes with int stays within int32
+    long long words = N;
+    for (int n = 0; n < N; n++) {
+        const int f = fr->node_field[n];
+        if (f < 0) continue;
+        const long long cells = (long long)fr->field_shape[f * 3] * fr->field_shape[f * 3 + 1] * fr->field_shape[f * 3 + 2];
+        if (cells > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: a lattice of more than 2^31 - 1 cells");
+        words += kFrComp + t->comp_count[n];
+        for (int k = 0; k < t->comp_count[n]; k++) {
+            const int c = t->comp_start[n] + k;
+            if (c < 0 || c >= C) return fail(PVT_ERR_INVALID, "component run out of range");
+            const int v = fr->comp_values[c];
+            if (v < 0) return fail(PVT_ERR_INVALID, "field tables: every component of a node with a lattice needs values");
+            if (fr->values_count[v] != cells)
+                return fail(PVT_ERR_INVALID, "field tables: a value table's length must equal its node's lattice size");
         }
     }
-    // runs [start, start + count) into a table of `size` rows
-    auto bad_run = [](long long start, long long count, long long size) { return count < 0 || start < 0 || start + count > size; };
-    // concentration fields (PvtFieldTables, pvt_scene_create_field): lattices, value tables and who uses which
-    if (fr && fr->n_nodes != 0) {
-        const int F = fr->n_fields, V = fr->n_values;
-        if (fr->n_nodes != N || !fr->node_field) return fail(PVT_ERR_INVALID, "field tables: need one lattice index per node");
-        if (F < 0 || (F > 0 && (!fr->field_shape || !fr->field_lower || !fr->field_upper)))
-            return fail(PVT_ERR_INVALID, "field tables: lattice arrays missing");
-        for (int n = 0; n < N; n++)
-            if (fr->node_field[n] < -1 || fr->node_field[n] >= F) return fail(PVT_ERR_INVALID, "field tables: lattice index out of range");
-        if (fr->node_field[t->root_id] >= 0) return fail(PVT_ERR_INVALID, "field tables: the root node cannot carry a lattice");
-        for (int f = 0; f < F; f++)
+    words += fr->n_points;
+    if (words > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: more doubles than int32 offsets can index");
+    return PVT_OK;
+}
+
+// volume maps (PvtMapTables, pvt_scene_create_maps): whose maps they are, what they count and where
+int validate_map_tables(const PvtSceneTables* t, const PvtMapTables* mp) {
+    if (!mp || mp->n_nodes == 0 || mp->n_maps == 0) return PVT_OK;
+    const int N = t->n_nodes, C = t->n_components, M = mp->n_maps;
+    if (mp->n_nodes != N || !mp->node_map_start || !mp->node_map_count)
+        return fail(PVT_ERR_INVALID, "map tables: need one map run per node");
+    if (M < 0 || !mp->map_kind || !mp->map_component || !mp->map_shape || !mp->map_lower || !mp->map_h || !mp->map_nw ||
+        !mp->map_wl_start || !mp->map_wl_stop || !mp->map_offset)
+        return fail(PVT_ERR_INVALID, "map tables: map arrays missing");
+    long long next = 0;
+    for (int n = 0; n < N; n++) {
+        if (bad_run(mp->node_map_start[n], mp->node_map_count[n], M)) return fail(PVT_ERR_INVALID, "map tables: map run of a node out of range");
+        if (mp->node_map_start[n] != next) return fail(PVT_ERR_INVALID, "map tables: the nodes' map runs must tile the maps in node order");
+        next += mp->node_map_count[n];
+    }
+    if (next != M) return fail(PVT_ERR_INVALID, "map tables: the nodes' map runs must tile the maps in node order");
+    if (mp->node_map_count[t->root_id] > 0) return fail(PVT_ERR_INVALID, "map tables: the root node cannot carry a map");
+    long long slots = 0;
+    for (int n = 0; n < N; n++)
+        for (int m = mp->node_map_start[n]; m < mp->node_map_start[n] + mp->node_map_count[n]; m++) {
+            const int kind = mp->map_kind[m];
+            if (kind != PVT_EV_ABSORB && kind != PVT_EV_EMIT && kind != PVT_EV_SCATTER && kind != PVT_EV_NONRADIATIVE && kind != PVT_EV_REACT)
+                return fail(PVT_ERR_INVALID, "map tables: map kind must be ABSORB, EMIT, SCATTER, NONRADIATIVE or REACT");
+            const int c = mp->map_component[m];
+            if (c < -1 || (c >= 0 && (bad_run(t->comp_start[n], t->comp_count[n], C) || c < t->comp_start[n] || c >= t->comp_start[n] + t->comp_count[n])))
+                return fail(PVT_ERR_INVALID, "map tables: map component must be -1 or a component of the map's node");
+            long long cells = 1;
             for (int a = 0; a < 3; a++) {
-                if (fr->field_shape[f * 3 + a] < 1) return fail(PVT_ERR_INVALID, "field tables: lattice shape must be >= 1 on each axis");
-                const double lo = fr->field_lower[f * 3 + a], hi = fr->field_upper[f * 3 + a];
-                if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(PVT_ERR_INVALID, "field tables: lattice bounds must be finite");
-                if (!(lo < hi)) return fail(PVT_ERR_INVALID, "field tables: lattice lower must be < upper on each axis");
+                if (mp->map_shape[m * 3 + a] < 1) return fail(PVT_ERR_INVALID, "map tables: map shape must be >= 1 on each axis");
+                if (!std::isfinite(mp->map_lower[m * 3 + a])) return fail(PVT_ERR_INVALID, "map tables: map lower bounds must be finite");
+                const double h = mp->map_h[m * 3 + a];
+                if (!(std::isfinite(h) && h > 0.0)) return fail(PVT_ERR_INVALID, "map tables: map cell widths must be finite and > 0");
+                cells *= mp->map_shape[m * 3 + a];
+                if (cells > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
             }
-        if (fr->n_components != C || (C > 0 && !fr->comp_values))
-            return fail(PVT_ERR_INVALID, "field tables: need one value-table index per component");
-        if (V < 0 || fr->n_points < 0 || (V > 0 && (!fr->values_start || !fr->values_count)) || (fr->n_points > 0 && !fr->values))
-            return fail(PVT_ERR_INVALID, "field tables: value-table arrays missing");
-        for (int c = 0; c < C; c++)
-            if (fr->comp_values[c] < -1 || fr->comp_values[c] >= V) return fail(PVT_ERR_INVALID, "field tables: value-table index out of range");
-        for (int v = 0; v < V; v++)
-            if (bad_run(fr->values_start[v], fr->values_count[v], fr->n_points) || fr->values_count[v] < 1)
-                return fail(PVT_ERR_INVALID, "field tables: value-table run out of range");
-        for (int i = 0; i < fr->n_points; i++)
-            if (!std::isfinite(fr->values[i])) return fail(PVT_ERR_INVALID, "field tables: values must be finite");
-        for (int i = 0; i < fr->n_points; i++)
-            if (fr->values[i] < 0.0) return fail(PVT_ERR_INVALID, "field tables: values must be >= 0");
-        // every component of a node with a lattice names a value table of exactly that lattice's size; the buffer the
-        // kernel indexes with int stays within int32
-        long long words = N;
-        for (int n = 0; n < N; n++) {
-            const int f = fr->node_field[n];
-            if (f < 0) continue;
-            const long long cells = (long long)fr->field_shape[f * 3] * fr->field_shape[f * 3 + 1] * fr->field_shape[f * 3 + 2];
-            if (cells > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: a lattice of more than 2^31 - 1 cells");
-            words += kFrComp + t->comp_count[n];
-            for (int k = 0; k < t->comp_count[n]; k++) {
-                const int c = t->comp_start[n] + k;
-                if (c < 0 || c >= C) return fail(PVT_ERR_INVALID, "component run out of range");
-                const int v = fr->comp_values[c];
-                if (v < 0) return fail(PVT_ERR_INVALID, "field tables: every component of a node with a lattice needs values");
-                if (fr->values_count[v] != cells)
-                    return fail(PVT_ERR_INVALID, "field tables: a value table's length must equal its node's lattice size");
+            const int nw = mp->map_nw[m];
+            if (nw < 0) return fail(PVT_ERR_INVALID, "map tables: wavelength bins must be >= 0");
+            if (nw > 0) {
+                const double lo = mp->map_wl_start[m], hi = mp->map_wl_stop[m];
+                if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(PVT_ERR_INVALID, "map tables: wavelength range must be finite");
+                if (!(lo < hi)) return fail(PVT_ERR_INVALID, "map tables: wavelength range needs start < stop");
+                cells *= nw;
             }
+            if (mp->map_offset[m] != slots) return fail(PVT_ERR_INVALID, "map tables: map offsets must pack the maps one after the other");
+            slots += cells + 1;
+            if (slots > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
         }
-        words += fr->n_points;
-        if (words > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "field tables: more doubles than int32 offsets can index");
+    if (mp->map_slots != slots) return fail(PVT_ERR_INVALID, "map tables: map_slots must be the sum of the maps' slots");
+    return PVT_OK;
+}
+
+// ray capture (PvtCaptureTables, pvt_scene_create_capture): how many rows each recorder keeps and where
+int validate_capture_tables(const PvtSceneTables* t, const PvtCaptureTables* cp) {
+    if (!cp || cp->n_recorders == 0 || cp->capture_rows == 0) return PVT_OK;
+    const int R = t->n_recorders;
+    if (cp->n_recorders != R) return fail(PVT_ERR_INVALID, "capture tables: need one capacity per recorder");
+    if (!cp->rec_capture_capacity || !cp->rec_capture_start) return fail(PVT_ERR_INVALID, "capture tables: capture arrays missing");
+    long long rows = 0;
+    for (int r = 0; r < R; r++) {
+        const long long cap = cp->rec_capture_capacity[r];
+        if (cap < 0) return fail(PVT_ERR_INVALID, "capture tables: a capacity must be >= 0");
+        if (cap > PVT_MAX_CAPTURE_ROWS) return fail(PVT_ERR_INVALID, "capture tables: more than 2^24 capture rows");
+        if (cp->rec_capture_start[r] != rows) return fail(PVT_ERR_INVALID, "capture tables: capture starts must pack the captures one after the other");
+        rows += cap;
+        if (rows > PVT_MAX_CAPTURE_ROWS) return fail(PVT_ERR_INVALID, "capture tables: more than 2^24 capture rows");
     }
-    // volume maps (PvtMapTables, pvt_scene_create_maps): whose maps they are, what they count and where
-    if (mp && mp->n_nodes != 0 && mp->n_maps != 0) {
-        const int M = mp->n_maps;
-        if (mp->n_nodes != N || !mp->node_map_start || !mp->node_map_count)
-            return fail(PVT_ERR_INVALID, "map tables: need one map run per node");
-        if (M < 0 || !mp->map_kind || !mp->map_component || !mp->map_shape || !mp->map_lower || !mp->map_h || !mp->map_nw ||
-            !mp->map_wl_start || !mp->map_wl_stop || !mp->map_offset)
-            return fail(PVT_ERR_INVALID, "map tables: map arrays missing");
-        long long next = 0;
-        for (int n = 0; n < N; n++) {
-            if (bad_run(mp->node_map_start[n], mp->node_map_count[n], M)) return fail(PVT_ERR_INVALID, "map tables: map run of a node out of range");
-            if (mp->node_map_start[n] != next) return fail(PVT_ERR_INVALID, "map tables: the nodes' map runs must tile the maps in node order");
-            next += mp->node_map_count[n];
-        }
-        if (next != M) return fail(PVT_ERR_INVALID, "map tables: the nodes' map runs must tile the maps in node order");
-        if (mp->node_map_count[t->root_id] > 0) return fail(PVT_ERR_INVALID, "map tables: the root node cannot carry a map");
-        long long slots = 0;
-        for (int n = 0; n < N; n++)
-            for (int m = mp->node_map_start[n]; m < mp->node_map_start[n] + mp->node_map_count[n]; m++) {
-                const int kind = mp->map_kind[m];
-                if (kind != PVT_EV_ABSORB && kind != PVT_EV_EMIT && kind != PVT_EV_SCATTER && kind != PVT_EV_NONRADIATIVE && kind != PVT_EV_REACT)
-                    return fail(PVT_ERR_INVALID, "map tables: map kind must be ABSORB, EMIT, SCATTER, NONRADIATIVE or REACT");
-                const int c = mp->map_component[m];
-                if (c < -1 || (c >= 0 && (bad_run(t->comp_start[n], t->comp_count[n], C) || c < t->comp_start[n] || c >= t->comp_start[n] + t->comp_count[n])))
-                    return fail(PVT_ERR_INVALID, "map tables: map component must be -1 or a component of the map's node");
-                long long cells = 1;
-                for (int a = 0; a < 3; a++) {
-                    if (mp->map_shape[m * 3 + a] < 1) return fail(PVT_ERR_INVALID, "map tables: map shape must be >= 1 on each axis");
-                    if (!std::isfinite(mp->map_lower[m * 3 + a])) return fail(PVT_ERR_INVALID, "map tables: map lower bounds must be finite");
-                    const double h = mp->map_h[m * 3 + a];
-                    if (!(std::isfinite(h) && h > 0.0)) return fail(PVT_ERR_INVALID, "map tables: map cell widths must be finite and > 0");
-                    cells *= mp->map_shape[m * 3 + a];
-                    if (cells > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
-                }
-                const int nw = mp->map_nw[m];
-                if (nw < 0) return fail(PVT_ERR_INVALID, "map tables: wavelength bins must be >= 0");
-                if (nw > 0) {
-                    const double lo = mp->map_wl_start[m], hi = mp->map_wl_stop[m];
-                    if (!(std::isfinite(lo) && std::isfinite(hi))) return fail(PVT_ERR_INVALID, "map tables: wavelength range must be finite");
-                    if (!(lo < hi)) return fail(PVT_ERR_INVALID, "map tables: wavelength range needs start < stop");
-                    cells *= nw;
-                }
-                if (mp->map_offset[m] != slots) return fail(PVT_ERR_INVALID, "map tables: map offsets must pack the maps one after the other");
-                slots += cells + 1;
-                if (slots > PVT_MAX_MAP_SLOTS) return fail(PVT_ERR_INVALID, "map tables: more than 2^26 map slots");
-            }
-        if (mp->map_slots != slots) return fail(PVT_ERR_INVALID, "map tables: map_slots must be the sum of the maps' slots");
+    if (cp->capture_rows != rows) return fail(PVT_ERR_INVALID, "capture tables: capture_rows must be the sum of the capacities");
+    return PVT_OK;
+}
+
+// absorbing coatings (PvtCoatingAbsorbTables, pvt_scene_create_absorb): a scalar A per coating row, tables for some
+int validate_absorb_tables(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab) {
+    if (!ab || ab->n_coatings == 0) return PVT_OK;
+    const int K = t->n_coatings;
+    if (ab->n_coatings != K || !ab->coat_absorptivity) return fail(PVT_ERR_INVALID, "absorb tables: need one absorptivity per coating");
+    for (int k = 0; k < K; k++) {
+        const double a = ab->coat_absorptivity[k];
+        if (!std::isfinite(a)) return fail(PVT_ERR_INVALID, "absorb tables: absorptivity must be finite");
+        if (!(a >= 0.0 && a <= 1.0)) return fail(PVT_ERR_INVALID, "absorb tables: absorptivity must be within [0, 1]");
     }
-    // ray capture (PvtCaptureTables, pvt_scene_create_capture): how many rows each recorder keeps and where
-    if (cp && cp->n_recorders != 0 && cp->capture_rows != 0) {
-        if (cp->n_recorders != R) return fail(PVT_ERR_INVALID, "capture tables: need one capacity per recorder");
-        if (!cp->rec_capture_capacity || !cp->rec_capture_start) return fail(PVT_ERR_INVALID, "capture tables: capture arrays missing");
-        long long rows = 0;
-        for (int r = 0; r < R; r++) {
-            const long long cap = cp->rec_capture_capacity[r];
-            if (cap < 0) return fail(PVT_ERR_INVALID, "capture tables: a capacity must be >= 0");
-            if (cap > PVT_MAX_CAPTURE_ROWS) return fail(PVT_ERR_INVALID, "capture tables: more than 2^24 capture rows");
-            if (cp->rec_capture_start[r] != rows) return fail(PVT_ERR_INVALID, "capture tables: capture starts must pack the captures one after the other");
-            rows += cap;
-            if (rows > PVT_MAX_CAPTURE_ROWS) return fail(PVT_ERR_INVALID, "capture tables: more than 2^24 capture rows");
-        }
-        if (cp->capture_rows != rows) return fail(PVT_ERR_INVALID, "capture tables: capture_rows must be the sum of the capacities");
-    }
-    // absorbing coatings (PvtCoatingAbsorbTables, pvt_scene_create_absorb): a scalar A per coating row, tables for some
-    if (ab && ab->n_coatings != 0) {
-        if (ab->n_coatings != K || !ab->coat_absorptivity) return fail(PVT_ERR_INVALID, "absorb tables: need one absorptivity per coating");
-        for (int k = 0; k < K; k++) {
-            const double a = ab->coat_absorptivity[k];
-            if (!std::isfinite(a)) return fail(PVT_ERR_INVALID, "absorb tables: absorptivity must be finite");
-            if (!(a >= 0.0 && a <= 1.0)) return fail(PVT_ERR_INVALID, "absorb tables: absorptivity must be within [0, 1]");
-        }
-        const int NT = ab->n_tables;
-        if (NT < 0 || (NT > 0 && (!ab->coat_table || !ab->table_nw || !ab->table_na || !ab->wl_start || !ab->angle_start ||
-                                  !ab->value_start || !ab->wavelength || !ab->angle || !ab->value)))
-            return fail(PVT_ERR_INVALID, "absorb tables: missing arrays");
-        long long total = (long long)K * kCa;
-        for (int j = 0; j < NT; j++) {
-            const long long nw = ab->table_nw[j], na = ab->table_na[j];
-            const long long w0 = ab->wl_start[j], a0 = ab->angle_start[j], v0 = ab->value_start[j];
-            if (nw < 1 || na < 1 || w0 < 0 || a0 < 0 || v0 < 0 || w0 + nw > ab->n_wavelength || a0 + na > ab->n_angle ||
-                v0 + nw * na > ab->n_value)
-                return fail(PVT_ERR_INVALID, "absorb tables: axis or value range out of bounds");
-            for (long long i = 0; i < nw; i++)
-                if (!std::isfinite(ab->wavelength[w0 + i]) || (i > 0 && !(ab->wavelength[w0 + i] > ab->wavelength[w0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "absorb tables: wavelengths must be finite and strictly increasing");
-            for (long long i = 0; i < na; i++)
-                if (!(ab->angle[a0 + i] >= 0.0 && ab->angle[a0 + i] <= 90.0) || (i > 0 && !(ab->angle[a0 + i] > ab->angle[a0 + i - 1])))
-                    return fail(PVT_ERR_INVALID, "absorb tables: angles must be strictly increasing, in [0, 90] degrees");
-            for (long long i = 0; i < nw * na; i++)
-                if (!(ab->value[v0 + i] >= 0.0 && ab->value[v0 + i] <= 1.0))
-                    return fail(PVT_ERR_INVALID, "absorb tables: values must be finite and within [0, 1]");
-            total += nw + na + nw * na;
-        }
-        if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "absorb tables: more than 2^27 doubles");
-        for (int k = 0; k < K && NT > 0; k++)
-            if (ab->coat_table[k] < -1 || ab->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "absorb tables: coating row names a missing table");
-    }
+    const int NT = ab->n_tables;
+    if (NT < 0 || (NT > 0 && (!ab->coat_table || !ab->table_nw || !ab->table_na || !ab->wl_start || !ab->angle_start ||
+                              !ab->value_start || !ab->wavelength || !ab->angle || !ab->value)))
+        return fail(PVT_ERR_INVALID, "absorb tables: missing arrays");
+    const int rc = validate_grid_tables(grid_tables(ab), (long long)K * kCa,
+                                        {"absorb tables: axis or value range out of bounds",
+                                         "absorb tables: wavelengths must be finite and strictly increasing",
+                                         "absorb tables: angles must be strictly increasing, in [0, 90] degrees",
+                                         "absorb tables: values must be finite and within [0, 1]",
+                                         "absorb tables: more than 2^27 doubles"});
+    if (rc != PVT_OK) return rc;
+    for (int k = 0; k < K && NT > 0; k++)
+        if (ab->coat_table[k] < -1 || ab->coat_table[k] >= NT) return fail(PVT_ERR_INVALID, "absorb tables: coating row names a missing table");
+    return PVT_OK;
+}
+
+// the core tables, last part: the ranges of components, coatings, spectra, recorders and histograms
+int validate_ranges(const PvtSceneTables* t, const Knows& knows) {
+    const int N = t->n_nodes, C = t->n_components, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     for (int n = 0; n < N; n++) {
         if (bad_run(t->comp_start[n], t->comp_count[n], C)) return fail(PVT_ERR_INVALID, "component range of a node out of bounds");
         if (K > 0 && bad_run(t->coat_start[n], t->coat_count[n], K)) return fail(PVT_ERR_INVALID, "coating range of a node out of bounds");
@@ -671,20 +774,35 @@ int validate_tables(const PvtSceneTables* t, const PvtIndexTables* x, const PvtP
     }
     for (int r = 0; r < R; r++) {
         if (t->rec_node[r] < 0 || t->rec_node[r] >= N) return fail(PVT_ERR_INVALID, "recorder on a missing node");
-        if (t->rec_event[r] < 0 || t->rec_event[r] > max_selector) return fail(PVT_ERR_INVALID, "recorder selector out of range");
+        if (t->rec_event[r] < 0 || t->rec_event[r] > knows.max_selector) return fail(PVT_ERR_INVALID, "recorder selector out of range");
         if (bad_run(t->rec_hist_start[r], t->rec_hist_n[r], H)) return fail(PVT_ERR_INVALID, "histogram range of a recorder out of bounds");
     }
-    // (the kernel reads column `prop` of its tally queue: an id beyond the ones it parks would read past the queue.  max_prop
-    // is the calling entry's: PVT_PROP_Z, PVT_PROPX_REFLECTIONS for pvt_scene_create_absorb, PVT_PROPX_ORIGIN_Z for
-    // pvt_scene_create_origin, as the header says)
     for (int h = 0; h < H; h++)
-        if (t->hist_prop_a[h] < 0 || t->hist_prop_a[h] > max_prop || t->hist_prop_b[h] < -1 || t->hist_prop_b[h] > max_prop)
+        if (t->hist_prop_a[h] < 0 || t->hist_prop_a[h] > knows.max_prop || t->hist_prop_b[h] < -1 || t->hist_prop_b[h] > knows.max_prop)
             return fail(PVT_ERR_INVALID, "histogram property out of range");
     for (int h = 0; h < H; h++) {   // bins hist_offset + [0, na) (1-D) or + [0, na * nb) (2-D) of the tally
         const long long bins = (long long)std::max(t->hist_na[h], 0) * (t->hist_prop_b[h] >= 0 ? std::max(t->hist_nb[h], 0) : 1);
         if (bins > 0 && bad_run(t->hist_offset[h], bins, t->total_bins)) return fail(PVT_ERR_INVALID, "histogram bins out of range of total_bins");
     }
     return PVT_OK;
+}
+
+// The order is behaviour: the first check that fails names the refusal.  The core tables are checked in two parts, around
+// the extension structs.  (Pattern tables are checked by pack_patterns, on a scene pack_scene has accepted.)
+int validate_tables(const SceneInputs& in) {
+    const PvtSceneTables* t = in.t;
+    int rc = validate_nodes(t, in.knows);
+    if (rc == PVT_OK) rc = validate_coating_tables(t);
+    if (rc == PVT_OK) rc = validate_indices(t);
+    if (rc == PVT_OK) rc = validate_index_tables(t, in.x);
+    if (rc == PVT_OK) rc = validate_phase_tables(t, in.ph);
+    if (rc == PVT_OK) rc = validate_surface_tables(t, in.rs);
+    if (rc == PVT_OK) rc = validate_field_tables(t, in.fr);
+    if (rc == PVT_OK) rc = validate_map_tables(t, in.mp);
+    if (rc == PVT_OK) rc = validate_capture_tables(t, in.cp);
+    if (rc == PVT_OK) rc = validate_absorb_tables(t, in.ab);
+    if (rc == PVT_OK) rc = validate_ranges(t, in.knows);
+    return rc;
 }
 
 // unrotated: the 3x3 blocks of both matrices of a node are the identity, bit for bit (+0.0 off the diagonal)
@@ -706,7 +824,9 @@ struct Classes {
     bool by_node = false;                    // Lay::by_node
 };
 
-Classes classify_nodes(const PvtSceneTables* t, const PvtIndexTables* x) {
+Classes classify_nodes(const SceneInputs& in) {
+    const PvtSceneTables* t = in.t;
+    const PvtIndexTables* x = in.x;
     const int N = t->n_nodes;
     Classes k;
     // rotation classes: nodes whose two 3x3 blocks have the same bits share a record (and, in the wave-uniform
@@ -809,7 +929,9 @@ struct Records {
     int n_cand = 0;
 };
 
-Records component_records(const PvtSceneTables* t, const PvtPhaseTables* ph, const Spectra& sp, bool by_node) {
+Records component_records(const SceneInputs& in, const Spectra& sp, bool by_node) {
+    const PvtSceneTables* t = in.t;
+    const PvtPhaseTables* ph = in.ph;
     const int N = t->n_nodes, C = t->n_components, R = t->n_recorders;
     auto table_of = [&](int c) { return ph && ph->n_tables > 0 ? ph->comp_table[c] : -1; };
     auto same_component = [&](int c, int e) {
@@ -856,9 +978,11 @@ Records component_records(const PvtSceneTables* t, const PvtPhaseTables* ph, con
 // of the int blob in the same way).  Sizes p->gd / p->gi; returns where each coating reflectivity table goes, in
 // *rtab_at where each refractive-index table goes and in *ptab_at where each phase-function table goes (p->rough_d, set by
 // the caller when some node is rough, is moved to where the nodes' GGX widths go).
-std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const Classes& k,
-                         const Spectra& sp, const Records& recs, const NodeGrid& grid, PackedScene* p, std::vector<int>* rtab_at,
-                         std::vector<int>* ptab_at) {
+std::vector<int> lay_out(const SceneInputs& in, const Classes& k, const Spectra& sp, const Records& recs, const NodeGrid& grid,
+                         PackedScene* p, std::vector<int>* rtab_at, std::vector<int>* ptab_at) {
+    const PvtSceneTables* t = in.t;
+    const PvtIndexTables* x = in.x;
+    const PvtPhaseTables* ph = in.ph;
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size(), CR = (int)recs.rec_comp.size();
     Lay& lay = p->lay;
@@ -882,10 +1006,11 @@ std::vector<int> lay_out(const PvtSceneTables* t, const PvtIndexTables* x, const
     // coating reflectivity tables (KI_T*): their axes and values follow the spectra, so they go wherever the spectra go
     // (LDS with the whole blob, else global memory) and a scene without them lays out exactly as before
     int spec_end = p->nd_small + sp.len;
+    const GridTables ctabs = grid_tables(t);
     std::vector<int> ctab_at(p->n_ctab);
     for (int j = 0; j < p->n_ctab; j++) {
         ctab_at[j] = spec_end;
-        spec_end += t->ctab_nw[j] + t->ctab_na[j] + t->ctab_nw[j] * t->ctab_na[j];
+        spec_end += (int)ctabs.doubles(j);
     }
     // refractive-index tables (wavelengths, then values) likewise, after the coating tables
     rtab_at->assign(p->n_rtab, 0);
@@ -978,10 +1103,12 @@ void fill_candidates(const PvtSceneTables* t, const Records& recs, PackedScene* 
 }
 
 // ---- fill: every record, table and guide table of the two blobs, and the BVHs of the meshes
-int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-         const Classes& k, const Spectra& sp,
-         const Records& recs, const NodeGrid& grid, const std::vector<int>& ctab_at, const std::vector<int>& rtab_at,
-         const std::vector<int>& ptab_at, PackedScene* p) {
+int fill(const SceneInputs& in, const Classes& k, const Spectra& sp, const Records& recs, const NodeGrid& grid,
+         const std::vector<int>& ctab_at, const std::vector<int>& rtab_at, const std::vector<int>& ptab_at, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtIndexTables* x = in.x;
+    const PvtPhaseTables* ph = in.ph;
+    const PvtSurfaceTables* rs = in.rs;
     const int N = t->n_nodes, R = t->n_recorders, H = t->n_hists, K = t->n_coatings;
     const int M = (int)k.idx_first.size(), Q = (int)k.rot_first.size();
     const Lay& lay = p->lay;
@@ -1158,14 +1285,7 @@ int fill(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables*
         q[KI_TA] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] : 0;
         q[KI_TV] = j >= 0 ? ctab_at[j] + t->ctab_nw[j] + t->ctab_na[j] : 0;
     }
-    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
-    for (int j = 0; j < p->n_ctab; j++) {   // wavelengths (nm), angles (radians: the kernel compares pvt_acos of the cosine), values
-        const int nw = t->ctab_nw[j], na = t->ctab_na[j];
-        double* d = gd.data() + ctab_at[j];
-        for (int i = 0; i < nw; i++) d[i] = t->ctab_wavelength[t->ctab_wl_start[j] + i];
-        for (int i = 0; i < na; i++) d[nw + i] = t->ctab_angle[t->ctab_angle_start[j] + i] * kRadPerDeg;
-        for (int i = 0; i < na * nw; i++) d[nw + na + i] = t->ctab_value[t->ctab_value_start[j] + i];
-    }
+    for (int j = 0; j < p->n_ctab; j++) put_grid_table(grid_tables(t), j, gd.data() + ctab_at[j]);
     return PVT_OK;
 }
 
@@ -1298,7 +1418,9 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
 // then per fielded node its record -- shape, lower, cell widths h = (upper - lower) / n, the world->local rotation and
 // translation of world_to_local (the doubles the node record and rotation classes hold) and, per component in the node's
 // order, where its value table starts -- then each value table once.
-void pack_fields(const PvtSceneTables* t, const PvtFieldTables* fr, PackedScene* p) {
+void pack_fields(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtFieldTables* fr = in.fr;
     p->fd.clear();
     if (!fr || fr->n_nodes == 0) return;
     const int N = t->n_nodes;
@@ -1343,7 +1465,9 @@ void pack_fields(const PvtSceneTables* t, const PvtFieldTables* fr, PackedScene*
 // The map buffer p->md (validated tables; left empty without maps): per node where its block starts, then per node with
 // maps its block -- the map count, the world->local rotation and translation of world_to_local (the doubles a field
 // record holds) -- and per map its record: kind, component, shape, lower, cell widths, wavelength bins and range, first slot.
-void pack_maps(const PvtSceneTables* t, const PvtMapTables* mp, PackedScene* p) {
+void pack_maps(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtMapTables* mp = in.mp;
     p->md.clear();
     p->map_slots = 0;
     if (!mp || mp->n_nodes == 0 || mp->n_maps == 0) return;
@@ -1382,7 +1506,9 @@ void pack_maps(const PvtSceneTables* t, const PvtMapTables* mp, PackedScene* p) 
 }
 
 // The capture table p->cd (validated tables; left empty when no recorder is captured): capacity and first row per recorder.
-void pack_captures(const PvtSceneTables* t, const PvtCaptureTables* cp, PackedScene* p) {
+void pack_captures(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtCaptureTables* cp = in.cp;
     p->cd.clear();
     p->capture_rows = 0;
     if (!cp || cp->n_recorders == 0 || cp->capture_rows == 0) return;
@@ -1396,7 +1522,9 @@ void pack_captures(const PvtSceneTables* t, const PvtCaptureTables* cp, PackedSc
 // Absorbing coatings (validated tables; nothing is placed when no coating absorbs): the records and tables of
 // PackedScene::cabs_d appended to the double blob, the candidate tables of the `detected` selector (PackedScene::dcand_i)
 // to the int blob -- behind everything the scene holds without them, so no other offset moves.
-void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, const Records& recs, PackedScene* p) {
+void pack_absorb(const SceneInputs& in, const Records& recs, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtCoatingAbsorbTables* ab = in.ab;
     p->cabs_d = -1;
     p->dcand_i = -1;
     if (!ab || ab->n_coatings == 0) return;
@@ -1407,16 +1535,14 @@ void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, cons
     std::vector<double>& gd = p->gd;
     p->cabs_d = (int)gd.size();
     gd.resize(gd.size() + (size_t)K * kCa, 0.0);
-    constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
+    const GridTables atabs = grid_tables(ab);
     std::vector<int> tab_at((size_t)(NT > 0 ? NT : 0), -1);
     for (int k = 0; k < K; k++) {
         const int j = NT > 0 ? ab->coat_table[k] : -1;
-        if (j >= 0 && tab_at[(size_t)j] < 0) {   // wavelengths (nm), angles (radians), values: a reflectivity table's layout
+        if (j >= 0 && tab_at[(size_t)j] < 0) {   // (a reflectivity table's layout)
             tab_at[(size_t)j] = (int)gd.size();
-            const int nw = ab->table_nw[j], na = ab->table_na[j];
-            for (int i = 0; i < nw; i++) gd.push_back(ab->wavelength[ab->wl_start[j] + i]);
-            for (int i = 0; i < na; i++) gd.push_back(ab->angle[ab->angle_start[j] + i] * kRadPerDeg);
-            for (int i = 0; i < na * nw; i++) gd.push_back(ab->value[ab->value_start[j] + i]);
+            gd.resize(gd.size() + (size_t)atabs.doubles(j));
+            put_grid_table(atabs, j, gd.data() + tab_at[(size_t)j]);
         }
         double* d = gd.data() + p->cabs_d + (size_t)k * kCa;
         d[kCaA] = ab->coat_absorptivity[k];
@@ -1434,7 +1560,9 @@ void pack_absorb(const PvtSceneTables* t, const PvtCoatingAbsorbTables* ab, cons
 // Patterned coatings (PvtCoatingPatternTables, pvt_scene_create_pattern; called on a scene pack_scene has accepted, before
 // anything is uploaded): every index the kernel follows is checked, then PackedScene::pd and ::pmask are filled.  Both stay
 // empty -- the scene is then exactly the one without the struct -- when no row has a pattern or an any-facet flag.
-int pack_patterns(const PvtSceneTables* t, const PvtCoatingPatternTables* pt, PackedScene* p) {
+int pack_patterns(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtCoatingPatternTables* pt = in.pt;
     p->pd.clear();
     p->pmask.clear();
     if (!pt || pt->n_coatings == 0) return PVT_OK;
@@ -1491,20 +1619,18 @@ int pack_patterns(const PvtSceneTables* t, const PvtCoatingPatternTables* pt, Pa
     return PVT_OK;
 }
 
-// The tables (n_nodes and n_recorders already checked by the caller), the refractive-index tables (x, NULL = none), the
-// phase-function tables (ph, NULL = none), the nodes' surface roughness (rs, NULL = none) and the concentration fields
-// (fr, NULL = none), the volume maps (mp, NULL = none), the ray captures (cp, NULL = none) and the coatings' absorptivities
-// (ab, NULL = none) -> *p.  max_selector: the last recorder selector the calling entry knows (PVT_REC_EXIT before
-// pvt_scene_create_absorb, PVT_RECX_DETECTED there); a recorder beyond it is refused.  max_prop: likewise the last histogram
-// property it knows.  No HIP call.
-int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-               const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab,
-               int max_selector, int max_prop, int max_geom, PackedScene* p) {
-    int rc = validate_tables(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, max_geom);
+// The scene's inputs (n_nodes and n_recorders already checked by the caller; the pattern tables are pack_patterns') -> *p.
+// No HIP call.
+int pack_scene(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtIndexTables* x = in.x;
+    const PvtPhaseTables* ph = in.ph;
+    const PvtSurfaceTables* rs = in.rs;
+    int rc = validate_tables(in);
     if (rc != PVT_OK) return rc;
-    const Classes classes = classify_nodes(t, x);
+    const Classes classes = classify_nodes(in);
     Spectra spectra = pool_spectra(t);
-    const Records records = component_records(t, ph, spectra, classes.by_node);
+    const Records records = component_records(in, spectra, classes.by_node);
     NodeGrid grid;
     p->grid = plan_node_grid(t, &grid);
     for (int a = 0; a < 3; a++) p->grid_dims[a] = p->grid ? grid.n[a] : 0;
@@ -1525,13 +1651,13 @@ int pack_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseT
     for (int n = 0; n < t->n_nodes; n++)
         if (t->geom_type[n] == PVT_GEOM_FRUSTUM) p->has_frustum = true;
     std::vector<int> rtab_at, ptab_at;
-    const std::vector<int> ctab_at = lay_out(t, x, ph, classes, spectra, records, grid, p, &rtab_at, &ptab_at);
-    rc = fill(t, x, ph, rs, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
+    const std::vector<int> ctab_at = lay_out(in, classes, spectra, records, grid, p, &rtab_at, &ptab_at);
+    rc = fill(in, classes, spectra, records, grid, ctab_at, rtab_at, ptab_at, p);
     if (rc != PVT_OK) return rc;
-    pack_fields(t, fr, p);
-    pack_maps(t, mp, p);
-    pack_captures(t, cp, p);
-    pack_absorb(t, ab, records, p);
+    pack_fields(in, p);
+    pack_maps(in, p);
+    pack_captures(in, p);
+    pack_absorb(in, records, p);
     prove_shortcuts(t, p);
     prove_lean(t, p);
     return PVT_OK;

@@ -694,40 +694,34 @@ int unpack_launch(const unsigned long long* rows, const int* counts, long long n
     return PVT_OK;
 }
 
-// What every pvt_scene_create* entry does.  max_selector: the last recorder selector the entry knows -- PVT_RECX_DETECTED
-// for pvt_scene_create_absorb, PVT_REC_EXIT for the entries from before it, which refuse an eighth selector as they did.
-// max_prop: the last histogram property it knows -- PVT_PROP_Z, PVT_PROPX_REFLECTIONS for pvt_scene_create_absorb,
-// PVT_PROPX_ORIGIN_Z for pvt_scene_create_origin.  max_geom: the last geometry type it knows -- PVT_GEOM_FRUSTUM for
-// pvt_scene_create_origin and the host-buffer entries, PVT_GEOM_MESH for the older ones ("unknown geometry type", as before).
-int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-                 const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt, int max_selector, int max_prop, int max_geom,
-                 int device, PvtScene** out);
+// What every pvt_scene_create* entry does with the record of its inputs (SceneInputs and the levels an entry can know:
+// pvt_scene_pack.h).
+int create_scene(const SceneInputs& in, int device, PvtScene** out);
 
 }  // namespace
 
 extern "C" {
 
 int pvt_scene_create(const PvtSceneTables* t, int device, PvtScene** out) {
-    return pvt_scene_create_ex(t, nullptr, device, out);
+    return create_scene({t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int pvt_scene_create_ex(const PvtSceneTables* t, const PvtIndexTables* x, int device, PvtScene** out) {
-    return pvt_scene_create_phase(t, x, nullptr, device, out);
+    return create_scene({t, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int pvt_scene_create_phase(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, int device, PvtScene** out) {
-    return pvt_scene_create_rough(t, x, ph, nullptr, device, out);
+    return create_scene({t, x, ph, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int pvt_scene_create_rough(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                            const PvtSurfaceTables* rs, int device, PvtScene** out) {
-    return pvt_scene_create_field(t, x, ph, rs, nullptr, device, out);
+    return create_scene({t, x, ph, rs, nullptr, nullptr, nullptr, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int pvt_scene_create_field(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                            const PvtSurfaceTables* rs, const PvtFieldTables* fr, int device, PvtScene** out) {
-    return pvt_scene_create_maps(t, x, ph, rs, fr, nullptr, device, out);
+    return create_scene({t, x, ph, rs, fr, nullptr, nullptr, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int64_t pvt_scene_map_slots(const PvtScene* s) { return s ? (int64_t)s->map_slots : 0; }
@@ -735,7 +729,7 @@ int64_t pvt_scene_map_slots(const PvtScene* s) { return s ? (int64_t)s->map_slot
 int pvt_scene_create_maps(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                           const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp, int device,
                           PvtScene** out) {
-    return pvt_scene_create_capture(t, x, ph, rs, fr, mp, nullptr, device, out);
+    return create_scene({t, x, ph, rs, fr, mp, nullptr, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->capture_rows : 0; }
@@ -743,36 +737,34 @@ int64_t pvt_scene_capture_rows(const PvtScene* s) { return s ? (int64_t)s->captu
 int pvt_scene_create_capture(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                              const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                              const PvtCaptureTables* cp, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, nullptr, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_MESH, device, out);
+    return create_scene({t, x, ph, rs, fr, mp, cp, nullptr, nullptr, kKnowsBeforeAbsorb}, device, out);
 }
 
 int pvt_scene_create_absorb(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, nullptr, PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH, device, out);
+    return create_scene({t, x, ph, rs, fr, mp, cp, ab, nullptr, kKnowsAbsorb}, device, out);
 }
 
 int pvt_scene_create_origin(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, nullptr, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, device, out);
+    return create_scene({t, x, ph, rs, fr, mp, cp, ab, nullptr, kKnowsOrigin}, device, out);
 }
 
 int pvt_scene_create_pattern(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
                              const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
                              const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt,
                              int device, PvtScene** out) {
-    return create_scene(t, x, ph, rs, fr, mp, cp, ab, pt, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, device, out);
+    return create_scene({t, x, ph, rs, fr, mp, cp, ab, pt, kKnowsOrigin}, device, out);
 }
 
 }  // extern "C"
 
 namespace {
 
-int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
-                 const PvtFieldTables* fr, const PvtMapTables* mp, const PvtCaptureTables* cp,
-                 const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt, int max_selector, int max_prop, int max_geom,
-                 int device, PvtScene** out) {
+int create_scene(const SceneInputs& in, int device, PvtScene** out) {
+    const PvtSceneTables* t = in.t;
     if (!t || !out) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0) return fail(PVT_ERR_INVALID, "scene has no nodes");
     if (t->n_nodes > PVT_MAX_NODES) return fail(PVT_ERR_TOO_MANY_NODES, "more than 128 geometry nodes");
@@ -780,9 +772,9 @@ int create_scene(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhas
     if (pvt_device_count() <= device) return fail(PVT_ERR_NO_DEVICE, "no such HIP device");
     HIP_TRY(hipSetDevice(device));
     PackedScene packed;
-    int rc = pack_scene(t, x, ph, rs, fr, mp, cp, ab, max_selector, max_prop, max_geom, &packed);
+    int rc = pack_scene(in, &packed);
     if (rc != PVT_OK) return rc;
-    rc = pack_patterns(t, pt, &packed);   // (validated before anything is uploaded)
+    rc = pack_patterns(in, &packed);   // (validated before anything is uploaded)
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -1108,7 +1100,7 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
     if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
     PackedScene packed;
-    const int rc = pack_scene(t, x, ph, rs, fr, mp, nullptr, nullptr, PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z, PVT_GEOM_FRUSTUM, &packed);
+    const int rc = pack_scene({t, x, ph, rs, fr, mp, nullptr, nullptr, nullptr, kKnowsOrigin}, &packed);
     if (rc != PVT_OK) return rc;
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     return PVT_OK;
@@ -1448,8 +1440,7 @@ struct HostBundle {
         tables = tb;
         params = *pp;
         params.flags &= ~(int64_t)PVT_FLAG_CARRY_OUT;   // a scene that lives for one call has no next launch to carry photons to
-        // (pvt_scene_create, but for the geometry types: a host-buffer call takes a truncated cone)
-        int rc = create_scene(tables, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, PVT_REC_EXIT, PVT_PROP_Z, PVT_GEOM_FRUSTUM, device, &scene);
+        int rc = create_scene({tables, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kKnowsHostBuffer}, device, &scene);
         if (rc != PVT_OK) return rc;
         if (emitter) {
             rc = pvt_scene_set_emitter(scene, emitter);

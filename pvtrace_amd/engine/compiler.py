@@ -18,6 +18,7 @@ import numbers
 
 import numpy as np
 
+from pvtrace_amd.engine import native
 from pvtrace_amd.engine.recorder import (
     ALL_EVENTS,
     EXTENSION_PROPERTIES,
@@ -848,28 +849,14 @@ class CompiledScene:
         "field_values",
     )
 
-    # the volume maps' tables: part of `tables()` only when the scene has a map, so that a scene without maps lowers to
-    # the same tables, key for key, as before there were maps
-    MAP_TABLE_FIELDS = (
-        "node_map_start", "node_map_count", "map_kind", "map_component", "map_shape", "map_lower", "map_h", "map_nw",
-        "map_wl_start", "map_wl_stop", "map_offset",
-    )
-
-    # the captures' tables: part of `tables()` only when a recorder is captured (a scene without lowers to its old tables)
-    CAPTURE_TABLE_FIELDS = ("rec_capture_capacity", "rec_capture_start")
-
-    # the absorbing coatings' tables: part of `tables()` only when a coating has an absorptivity (a scene without lowers to
-    # its old tables)
-    ABSORB_TABLE_FIELDS = (
-        "coat_absorptivity", "coat_abs_table", "atab_nw", "atab_na", "atab_wl_start", "atab_angle_start",
-        "atab_value_start", "atab_wavelength", "atab_angle", "atab_value",
-    )
-
-    # the coating patterns' tables: part of `tables()` only when a coating has a pattern or facet=None (a scene without
-    # lowers to its old tables)
-    PATTERN_TABLE_FIELDS = (
-        "coat_any_facet", "coat_pattern", "cpat_shape", "cpat_bounded", "cpat_lower", "cpat_h", "cpat_start", "cpat_mask",
-    )
+    # The tables of the later extensions are part of `tables()` only when the scene has the extension, so that a scene
+    # without it lowers to the same tables, key for key, as before there was one: the volume maps', the captures', the
+    # absorbing coatings' (a coating has an absorptivity) and the coating patterns' (a coating has a pattern or
+    # facet=None).  Which attributes they are is what the binding reads for the extension's struct.
+    MAP_TABLE_FIELDS, CAPTURE_TABLE_FIELDS, ABSORB_TABLE_FIELDS, PATTERN_TABLE_FIELDS = (
+        tuple(attribute for attribute, _ in struct_type.POINTERS.values())
+        for struct_type in (native.PvtMapTables, native.PvtCaptureTables, native.PvtCoatingAbsorbTables,
+                            native.PvtCoatingPatternTables))
 
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""

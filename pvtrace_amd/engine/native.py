@@ -28,6 +28,15 @@ class EngineUnavailableError(RuntimeError):
     """The HIP engine cannot run here (library not built, or no MI355X visible)."""
 
 
+# How a table struct is filled from a CompiledScene (`marshal`, below) is written once, next to its fields:
+#   POINTERS  pointer field -> (the CompiledScene attribute it is read from, its numpy dtype);
+#   COUNTS    count field -> how it is derived from the CompiledScene;
+#   ABSENT    "the scene has none of this": the marshaller then answers None, which the library takes for "no such tables".
+def _same_names(fields):
+    """POINTERS of a struct whose pointer fields are named like the attributes they are read from."""
+    return {name: (name, np.int32 if ctype is _p_i32 else np.float64) for name, ctype in fields if ctype in (_p_i32, _p_f64)}
+
+
 class PvtSceneTables(C.Structure):
     _fields_ = [
         ("n_nodes", C.c_int32), ("root_id", C.c_int32), ("n_components", C.c_int32),
@@ -64,34 +73,72 @@ class PvtSceneTables(C.Structure):
         ("ctab_nw", _p_i32), ("ctab_na", _p_i32), ("ctab_wl_start", _p_i32), ("ctab_angle_start", _p_i32),
         ("ctab_value_start", _p_i32), ("ctab_wavelength", _p_f64), ("ctab_angle", _p_f64), ("ctab_value", _p_f64),
     ]
+    POINTERS = _same_names(_fields_)
+    COUNTS = {
+        "n_nodes": lambda c: c.geom_type.shape[0], "root_id": lambda c: c.root_id,
+        "n_components": lambda c: c.comp_type.shape[0], "n_abs": lambda c: c.abs_x.shape[0],
+        "n_ems": lambda c: c.ems_x.shape[0], "n_recorders": lambda c: c.rec_node.shape[0],
+        "n_hists": lambda c: c.hist_prop_a.shape[0], "total_bins": lambda c: c.total_bins,
+        "n_coatings": lambda c: getattr(c, "n_coatings", 0), "n_mesh_vertices": lambda c: getattr(c, "n_mesh_vertices", 0),
+        "n_mesh_faces": lambda c: getattr(c, "n_mesh_faces", 0), "n_coat_tables": lambda c: getattr(c, "n_coat_tables", 0),
+        "n_ctab_wavelength": lambda c: c.ctab_wavelength.shape[0] if getattr(c, "n_coat_tables", 0) else 0,
+        "n_ctab_angle": lambda c: c.ctab_angle.shape[0] if getattr(c, "n_coat_tables", 0) else 0,
+        "n_ctab_value": lambda c: c.ctab_value.shape[0] if getattr(c, "n_coat_tables", 0) else 0,
+    }
+    ABSENT = staticmethod(lambda c: False)
+
+    @staticmethod
+    def MISSING(st, field, dtype):
+        """A table the object does not have at all: `coat_table` of a flattener without coating tables names no table,
+        the tables of an engine without the coating extension are zeros."""
+        if field == "coat_table":
+            return np.full(max(st.n_coatings, 1), -1, dtype=dtype)
+        return np.zeros(max(st.n_nodes, 1) * 3, dtype=dtype)
 
 
 class PvtIndexTables(C.Structure):
-    """Refractive-index tables n(wavelength) of a scene (include/pvtrace_hip.h; pvt_scene_create_ex)."""
+    """Refractive-index tables n(wavelength) of a scene (include/pvtrace_hip.h; pvt_scene_create_ex); absent when the
+    scene has no dispersive node."""
     _fields_ = [
         ("n_tables", C.c_int32), ("n_points", C.c_int32),
         ("node_table", _p_i32), ("table_n", _p_i32), ("table_start", _p_i32),
         ("wavelength", _p_f64), ("value", _p_f64),
     ]
+    POINTERS = {"node_table": ("ri_table", np.int32), "table_n": ("rtab_n", np.int32), "table_start": ("rtab_start", np.int32),
+                "wavelength": ("rtab_wavelength", np.float64), "value": ("rtab_value", np.float64)}
+    COUNTS = {"n_tables": lambda c: c.n_ri_tables, "n_points": lambda c: c.rtab_wavelength.shape[0]}
+    ABSENT = staticmethod(lambda c: int(getattr(c, "n_ri_tables", 0)) == 0)
 
 
 class PvtPhaseTables(C.Structure):
-    """Phase-function tables of a scene (include/pvtrace_hip.h; pvt_scene_create_phase)."""
+    """Phase-function tables of a scene (include/pvtrace_hip.h; pvt_scene_create_phase); absent when no component has one."""
     _fields_ = [
         ("n_tables", C.c_int32), ("n_points", C.c_int32), ("n_wavelength", C.c_int32), ("n_cdf", C.c_int32),
         ("comp_table", _p_i32), ("table_nw", _p_i32), ("table_nmu", _p_i32),
         ("wl_start", _p_i32), ("mu_start", _p_i32), ("cdf_start", _p_i32),
         ("wavelength", _p_f64), ("mu", _p_f64), ("cdf", _p_f64),
     ]
+    POINTERS = {"comp_table": ("comp_phase_table", np.int32), "table_nw": ("ptab_nw", np.int32),
+                "table_nmu": ("ptab_nmu", np.int32), "wl_start": ("ptab_wl_start", np.int32),
+                "mu_start": ("ptab_mu_start", np.int32), "cdf_start": ("ptab_cdf_start", np.int32),
+                "wavelength": ("ptab_wavelength", np.float64), "mu": ("ptab_mu", np.float64), "cdf": ("ptab_cdf", np.float64)}
+    COUNTS = {"n_tables": lambda c: c.n_phase_tables, "n_points": lambda c: c.ptab_mu.shape[0],
+              "n_wavelength": lambda c: c.ptab_wavelength.shape[0], "n_cdf": lambda c: c.ptab_cdf.shape[0]}
+    ABSENT = staticmethod(lambda c: int(getattr(c, "n_phase_tables", 0)) == 0)
 
 
 class PvtSurfaceTables(C.Structure):
-    """Rough interfaces of a scene (include/pvtrace_hip.h; pvt_scene_create_rough)."""
+    """Rough interfaces of a scene (include/pvtrace_hip.h; pvt_scene_create_rough); absent when no node is rough."""
     _fields_ = [("n_nodes", C.c_int32), ("node_roughness", _p_f64)]
+    POINTERS = {"node_roughness": ("surface_roughness", np.float64)}
+    COUNTS = {"n_nodes": lambda c: np.shape(c.surface_roughness)[0]}
+    ABSENT = staticmethod(lambda c: getattr(c, "surface_roughness", None) is None
+                          or not np.any(np.asarray(c.surface_roughness) > 0.0))
 
 
 class PvtFieldTables(C.Structure):
-    """Concentration fields of a scene (include/pvtrace_hip.h; pvt_scene_create_field)."""
+    """Concentration fields of a scene (include/pvtrace_hip.h; pvt_scene_create_field); absent when no node carries a
+    lattice."""
     _fields_ = [
         ("n_nodes", C.c_int32), ("n_fields", C.c_int32),
         ("node_field", _p_i32), ("field_shape", _p_i32), ("field_lower", _p_f64), ("field_upper", _p_f64),
@@ -100,30 +147,46 @@ class PvtFieldTables(C.Structure):
         ("n_points", C.c_int32), ("reserved", C.c_int32),
         ("values", _p_f64),
     ]
+    POINTERS = {"node_field": ("node_field", np.int32), "field_shape": ("field_shape", np.int32),
+                "field_lower": ("field_lower", np.float64), "field_upper": ("field_upper", np.float64),
+                "comp_values": ("comp_values", np.int32), "values_start": ("values_start", np.int32),
+                "values_count": ("values_count", np.int32), "values": ("field_values", np.float64)}
+    COUNTS = {"n_nodes": lambda c: len(c.node_field), "n_fields": lambda c: c.n_fields,
+              "n_components": lambda c: len(c.comp_values), "n_values": lambda c: c.n_value_tables,
+              "n_points": lambda c: len(c.field_values)}
+    ABSENT = staticmethod(lambda c: getattr(c, "node_field", None) is None or not np.any(np.asarray(c.node_field) >= 0))
 
 
 class PvtMapTables(C.Structure):
-    """Volume maps of a scene (include/pvtrace_hip.h; pvt_scene_create_maps)."""
+    """Volume maps of a scene (include/pvtrace_hip.h; pvt_scene_create_maps); absent when the scene has no map."""
     _fields_ = [
         ("n_nodes", C.c_int32), ("n_maps", C.c_int32),
         ("node_map_start", _p_i32), ("node_map_count", _p_i32), ("map_kind", _p_i32), ("map_component", _p_i32),
         ("map_shape", _p_i32), ("map_lower", _p_f64), ("map_h", _p_f64), ("map_nw", _p_i32),
-        ("map_wl_start", _p_f64), ("map_wl_stop", _p_f64), ("map_offset", C.POINTER(C.c_int64)),
+        ("map_wl_start", _p_f64), ("map_wl_stop", _p_f64), ("map_offset", _p_i64),
         ("map_slots", C.c_int64),
     ]
+    POINTERS = {**_same_names(_fields_), "map_offset": ("map_offset", np.int64)}
+    COUNTS = {"n_nodes": lambda c: len(c.node_map_start), "n_maps": lambda c: c.n_maps, "map_slots": lambda c: c.map_slots}
+    ABSENT = staticmethod(lambda c: int(getattr(c, "n_maps", 0)) == 0)
 
 
 class PvtCaptureTables(C.Structure):
-    """Captured recorders of a scene (include/pvtrace_hip.h; pvt_scene_create_capture)."""
+    """Captured recorders of a scene (include/pvtrace_hip.h; pvt_scene_create_capture); absent when no recorder is
+    captured."""
     _fields_ = [
         ("n_recorders", C.c_int32),
-        ("rec_capture_capacity", C.POINTER(C.c_int64)), ("rec_capture_start", C.POINTER(C.c_int64)),
+        ("rec_capture_capacity", _p_i64), ("rec_capture_start", _p_i64),
         ("capture_rows", C.c_int64),
     ]
+    POINTERS = {"rec_capture_capacity": ("rec_capture_capacity", np.int64), "rec_capture_start": ("rec_capture_start", np.int64)}
+    COUNTS = {"n_recorders": lambda c: len(c.rec_capture_capacity), "capture_rows": lambda c: c.capture_rows}
+    ABSENT = staticmethod(lambda c: int(getattr(c, "capture_rows", 0)) == 0)
 
 
 class PvtCoatingAbsorbTables(C.Structure):
-    """Absorptivities of a scene's coatings (include/pvtrace_hip.h; pvt_scene_create_absorb)."""
+    """Absorptivities of a scene's coatings (include/pvtrace_hip.h; pvt_scene_create_absorb); absent when no coating has
+    one."""
     _fields_ = [
         ("n_coatings", C.c_int32), ("n_tables", C.c_int32),
         ("coat_absorptivity", _p_f64), ("coat_table", _p_i32),
@@ -131,16 +194,42 @@ class PvtCoatingAbsorbTables(C.Structure):
         ("table_nw", _p_i32), ("table_na", _p_i32), ("wl_start", _p_i32), ("angle_start", _p_i32), ("value_start", _p_i32),
         ("wavelength", _p_f64), ("angle", _p_f64), ("value", _p_f64),
     ]
+    POINTERS = {"coat_absorptivity": ("coat_absorptivity", np.float64), "coat_table": ("coat_abs_table", np.int32),
+                "table_nw": ("atab_nw", np.int32), "table_na": ("atab_na", np.int32), "wl_start": ("atab_wl_start", np.int32),
+                "angle_start": ("atab_angle_start", np.int32), "value_start": ("atab_value_start", np.int32),
+                "wavelength": ("atab_wavelength", np.float64), "angle": ("atab_angle", np.float64),
+                "value": ("atab_value", np.float64)}
+    COUNTS = {"n_coatings": lambda c: c.n_coatings, "n_tables": lambda c: c.n_abs_tables,
+              "n_wavelength": lambda c: c.atab_wavelength.shape[0], "n_angle": lambda c: c.atab_angle.shape[0],
+              "n_value": lambda c: c.atab_value.shape[0]}
+    ABSENT = staticmethod(lambda c: not getattr(c, "has_absorbing_coatings", False))
 
 
 class PvtCoatingPatternTables(C.Structure):
-    """Where a scene's coatings cover: any-facet flags and mask lattices (include/pvtrace_hip.h; pvt_scene_create_pattern)."""
+    """Where a scene's coatings cover: any-facet flags and mask lattices (include/pvtrace_hip.h; pvt_scene_create_pattern);
+    absent when no coating has a pattern or facet=None."""
     _fields_ = [
         ("n_coatings", C.c_int32), ("n_patterns", C.c_int32),
         ("coat_any_facet", _p_i32), ("coat_pattern", _p_i32),
         ("shape", _p_i32), ("bounded", _p_i32), ("lower", _p_f64), ("h", _p_f64),
-        ("mask_start", C.POINTER(C.c_int64)), ("mask", C.POINTER(C.c_uint8)), ("n_mask", C.c_int64),
+        ("mask_start", _p_i64), ("mask", _p_u8), ("n_mask", C.c_int64),
     ]
+    POINTERS = {"coat_any_facet": ("coat_any_facet", np.int32), "coat_pattern": ("coat_pattern", np.int32),
+                "shape": ("cpat_shape", np.int32), "bounded": ("cpat_bounded", np.int32), "lower": ("cpat_lower", np.float64),
+                "h": ("cpat_h", np.float64), "mask_start": ("cpat_start", np.int64), "mask": ("cpat_mask", np.uint8)}
+    COUNTS = {"n_coatings": lambda c: c.n_coatings, "n_patterns": lambda c: c.n_coat_patterns,
+              "n_mask": lambda c: c.cpat_mask.shape[0]}
+    ABSENT = staticmethod(lambda c: not getattr(c, "has_coating_patterns", False))
+
+
+# the extension structs, in the order the pvt_scene_create* entries take them behind the scene tables (each entry takes the
+# first so many of them: CREATION_ENTRIES)
+EXTENSION_TABLES = (PvtIndexTables, PvtPhaseTables, PvtSurfaceTables, PvtFieldTables, PvtMapTables, PvtCaptureTables,
+                    PvtCoatingAbsorbTables, PvtCoatingPatternTables)
+CREATION_ENTRIES = {"pvt_scene_create": 0, "pvt_scene_create_ex": 1, "pvt_scene_create_phase": 2, "pvt_scene_create_rough": 3,
+                    "pvt_scene_create_field": 4, "pvt_scene_create_maps": 5, "pvt_scene_create_capture": 6,
+                    "pvt_scene_create_absorb": 7, "pvt_scene_create_origin": 7, "pvt_scene_create_pattern": 8}
+LEAN_CHECK_TABLES = 5   # pvt_scene_lean_check takes the first five
 
 
 class PvtCaptures(C.Structure):
@@ -159,6 +248,9 @@ class PvtEmitterTables(C.Structure):
         ("dir_type", _p_i32), ("dir_param", _p_f64), ("light_to_world", _p_f64),
         ("spec_x", _p_f64), ("spec_cdf", _p_f64),
     ]
+    POINTERS = _same_names(_fields_)   # (read from an `emit.EmitterTables`)
+    COUNTS = {"n_lights": lambda e: e.n_lights, "n_spec": lambda e: e.spec_x.shape[0]}
+    ABSENT = staticmethod(lambda e: False)
 
 
 class PvtTraceParams(C.Structure):
@@ -211,247 +303,76 @@ def addr_ptr(address, ctype):
     return C.cast(C.c_void_p(int(address)), C.POINTER(ctype))
 
 
-_TABLE_POINTER_FIELDS = [
-    name for name, ctype in PvtSceneTables._fields_ if ctype in (_p_i32, _p_f64)
-]
+def marshal(struct_type, source):
+    """`struct_type` over the arrays of `source` (a CompiledScene; an `emit.EmitterTables` for PvtEmitterTables), as the
+    struct describes itself (POINTERS, COUNTS, ABSENT) -> (struct, keepalive), or (None, {}) when the source has none of it.
+    `keepalive` holds, by C field name, the contiguous arrays the pointers refer to and must outlive every use of `struct`.
+    The one place an attribute becomes a pointer."""
+    if struct_type.ABSENT(source):
+        return None, {}
+    st, keep = struct_type(), {}
+    for field, derive in struct_type.COUNTS.items():
+        setattr(st, field, int(derive(source)))
+    for field, (attribute, dtype) in struct_type.POINTERS.items():
+        missing = getattr(struct_type, "MISSING", None)   # (the scene tables alone: see PvtSceneTables.MISSING)
+        value = getattr(source, attribute) if missing is None else getattr(source, attribute, None)
+        if value is None:
+            value = missing(st, field, dtype)
+        arr = np.ascontiguousarray(value, dtype=dtype)
+        if arr.size == 0:
+            arr = np.zeros(1, dtype=dtype)  # never hand out NULL for an empty table
+        keep[field] = arr
+        setattr(st, field, np_ptr(arr))
+    return st, keep
 
 
 def scene_tables_struct(compiled):
-    """Build a PvtSceneTables over the arrays of a CompiledScene.
-
-    Returns (struct, keepalive): `keepalive` holds the contiguous arrays the
-    pointers refer to and must outlive every use of `struct`."""
-    keep = {}
-    st = PvtSceneTables()
-    st.n_nodes = int(compiled.geom_type.shape[0])
-    st.root_id = int(compiled.root_id)
-    st.n_components = int(compiled.comp_type.shape[0])
-    st.n_abs = int(compiled.abs_x.shape[0])
-    st.n_ems = int(compiled.ems_x.shape[0])
-    st.n_recorders = int(compiled.rec_node.shape[0])
-    st.n_hists = int(compiled.hist_prop_a.shape[0])
-    st.total_bins = int(compiled.total_bins)
-    st.n_coatings = int(getattr(compiled, "n_coatings", 0))
-    st.n_mesh_vertices = int(getattr(compiled, "n_mesh_vertices", 0))
-    st.n_mesh_faces = int(getattr(compiled, "n_mesh_faces", 0))
-    st.n_coat_tables = int(getattr(compiled, "n_coat_tables", 0))
-    if st.n_coat_tables:
-        st.n_ctab_wavelength = int(compiled.ctab_wavelength.shape[0])
-        st.n_ctab_angle = int(compiled.ctab_angle.shape[0])
-        st.n_ctab_value = int(compiled.ctab_value.shape[0])
-    for name in _TABLE_POINTER_FIELDS:
-        want = np.int32 if dict(PvtSceneTables._fields_)[name] is _p_i32 else np.float64
-        value = getattr(compiled, name, None)
-        if value is None and name == "coat_table":   # tables from a flattener without coating tables
-            value = np.full(max(st.n_coatings, 1), -1, dtype=want)
-        elif value is None:  # tables from an engine without the coating extension
-            value = np.zeros(max(st.n_nodes, 1) * 3, dtype=want)
-        arr = np.ascontiguousarray(value, dtype=want)
-        if arr.size == 0:
-            arr = np.zeros(1, dtype=want)  # never hand out NULL for an empty table
-        keep[name] = arr
-        setattr(st, name, np_ptr(arr))
-    return st, keep
+    """PvtSceneTables over the arrays of a CompiledScene -> (struct, keepalive)."""
+    return marshal(PvtSceneTables, compiled)
 
 
 def index_tables_struct(compiled):
-    """PvtIndexTables over the refractive-index tables of a CompiledScene -> (struct or None, keepalive); None when
-    the scene has no dispersive node (what pvt_scene_create_ex takes for "none")."""
-    if int(getattr(compiled, "n_ri_tables", 0)) == 0:
-        return None, {}
-    st = PvtIndexTables()
-    st.n_tables = int(compiled.n_ri_tables)
-    st.n_points = int(compiled.rtab_wavelength.shape[0])
-    keep = {}
-    for name, field, want in (("ri_table", "node_table", np.int32), ("rtab_n", "table_n", np.int32),
-                              ("rtab_start", "table_start", np.int32), ("rtab_wavelength", "wavelength", np.float64),
-                              ("rtab_value", "value", np.float64)):
-        arr = np.ascontiguousarray(getattr(compiled, name), dtype=want)
-        keep[field] = arr
-        setattr(st, field, np_ptr(arr))
-    return st, keep
+    return marshal(PvtIndexTables, compiled)
 
 
 def phase_tables_struct(compiled):
-    """PvtPhaseTables over the phase-function tables of a CompiledScene -> (struct or None, keepalive); None when no
-    component has a table (the scene is then created exactly as before)."""
-    if int(getattr(compiled, "n_phase_tables", 0)) == 0:
-        return None, {}
-    st = PvtPhaseTables()
-    st.n_tables = int(compiled.n_phase_tables)
-    st.n_points = int(compiled.ptab_mu.shape[0])
-    st.n_wavelength = int(compiled.ptab_wavelength.shape[0])
-    st.n_cdf = int(compiled.ptab_cdf.shape[0])
-    keep = {}
-    for name, field, want in (("comp_phase_table", "comp_table", np.int32), ("ptab_nw", "table_nw", np.int32),
-                              ("ptab_nmu", "table_nmu", np.int32), ("ptab_wl_start", "wl_start", np.int32),
-                              ("ptab_mu_start", "mu_start", np.int32), ("ptab_cdf_start", "cdf_start", np.int32),
-                              ("ptab_wavelength", "wavelength", np.float64), ("ptab_mu", "mu", np.float64),
-                              ("ptab_cdf", "cdf", np.float64)):
-        arr = np.ascontiguousarray(getattr(compiled, name), dtype=want)
-        keep[field] = arr
-        setattr(st, field, np_ptr(arr))
-    return st, keep
+    return marshal(PvtPhaseTables, compiled)
 
 
 def surface_tables_struct(compiled):
-    """PvtSurfaceTables over the surface roughness of a CompiledScene -> (struct or None, keepalive); None when no node
-    is rough (the scene is then created exactly as before)."""
-    alpha = getattr(compiled, "surface_roughness", None)
-    if alpha is None or not np.any(np.asarray(alpha) > 0.0):
-        return None, {}
-    arr = np.ascontiguousarray(alpha, dtype=np.float64)
-    st = PvtSurfaceTables()
-    st.n_nodes = int(arr.shape[0])
-    st.node_roughness = np_ptr(arr)
-    return st, {"node_roughness": arr}
+    return marshal(PvtSurfaceTables, compiled)
 
 
 def field_tables_struct(compiled):
-    """PvtFieldTables over the concentration fields of a CompiledScene -> (struct or None, keepalive); None when no node
-    carries a lattice (the scene is then created exactly as before)."""
-    node_field = getattr(compiled, "node_field", None)
-    if node_field is None or not np.any(np.asarray(node_field) >= 0):
-        return None, {}
-    keep = {}
-
-    def arr(name, dtype):
-        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
-        keep[name] = a
-        return np_ptr(a)
-
-    st = PvtFieldTables()
-    st.n_nodes = int(len(node_field))
-    st.n_fields = int(compiled.n_fields)
-    st.node_field = arr("node_field", np.int32)
-    st.field_shape = arr("field_shape", np.int32)
-    st.field_lower = arr("field_lower", np.float64)
-    st.field_upper = arr("field_upper", np.float64)
-    st.n_components = int(len(compiled.comp_values))
-    st.n_values = int(compiled.n_value_tables)
-    st.comp_values = arr("comp_values", np.int32)
-    st.values_start = arr("values_start", np.int32)
-    st.values_count = arr("values_count", np.int32)
-    st.n_points = int(len(compiled.field_values))
-    st.values = arr("field_values", np.float64)
-    return st, keep
+    return marshal(PvtFieldTables, compiled)
 
 
 def map_tables_struct(compiled):
-    """PvtMapTables over the volume maps of a CompiledScene -> (struct or None, keepalive); None when the scene has no
-    map (it is then created exactly as before)."""
-    if int(getattr(compiled, "n_maps", 0)) == 0:
-        return None, {}
-    keep = {}
-
-    def arr(name, dtype):
-        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
-        keep[name] = a
-        return np_ptr(a)
-
-    st = PvtMapTables()
-    st.n_nodes = int(len(compiled.node_map_start))
-    st.n_maps = int(compiled.n_maps)
-    for name in ("node_map_start", "node_map_count", "map_kind", "map_component", "map_shape", "map_nw"):
-        setattr(st, name, arr(name, np.int32))
-    for name in ("map_lower", "map_h", "map_wl_start", "map_wl_stop"):
-        setattr(st, name, arr(name, np.float64))
-    st.map_offset = arr("map_offset", np.int64)
-    st.map_slots = int(compiled.map_slots)
-    return st, keep
+    return marshal(PvtMapTables, compiled)
 
 
 def capture_tables_struct(compiled):
-    """PvtCaptureTables over the captured recorders of a CompiledScene -> (struct or None, keepalive); None when no
-    recorder is captured (the scene is then created exactly as before)."""
-    if int(getattr(compiled, "capture_rows", 0)) == 0:
-        return None, {}
-    keep = {name: np.ascontiguousarray(getattr(compiled, name), dtype=np.int64)
-            for name in ("rec_capture_capacity", "rec_capture_start")}
-    st = PvtCaptureTables()
-    st.n_recorders = int(len(keep["rec_capture_capacity"]))
-    st.rec_capture_capacity = np_ptr(keep["rec_capture_capacity"])
-    st.rec_capture_start = np_ptr(keep["rec_capture_start"])
-    st.capture_rows = int(compiled.capture_rows)
-    return st, keep
+    return marshal(PvtCaptureTables, compiled)
 
 
 def absorb_tables_struct(compiled):
-    """PvtCoatingAbsorbTables over the coatings' absorptivities of a CompiledScene -> (struct or None, keepalive); None when
-    no coating has one (the scene is then created exactly as before)."""
-    if not getattr(compiled, "has_absorbing_coatings", False):
-        return None, {}
-    keep = {}
-
-    def arr(name, dtype):
-        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
-        if a.size == 0:
-            a = np.zeros(1, dtype=dtype)   # never hand out NULL for an empty table
-        keep[name] = a
-        return np_ptr(a)
-
-    st = PvtCoatingAbsorbTables()
-    st.n_coatings = int(compiled.n_coatings)
-    st.n_tables = int(compiled.n_abs_tables)
-    st.coat_absorptivity = arr("coat_absorptivity", np.float64)
-    st.coat_table = arr("coat_abs_table", np.int32)
-    st.n_wavelength = int(compiled.atab_wavelength.shape[0])
-    st.n_angle = int(compiled.atab_angle.shape[0])
-    st.n_value = int(compiled.atab_value.shape[0])
-    for field, name in (("table_nw", "atab_nw"), ("table_na", "atab_na"), ("wl_start", "atab_wl_start"),
-                        ("angle_start", "atab_angle_start"), ("value_start", "atab_value_start")):
-        setattr(st, field, arr(name, np.int32))
-    for field, name in (("wavelength", "atab_wavelength"), ("angle", "atab_angle"), ("value", "atab_value")):
-        setattr(st, field, arr(name, np.float64))
-    return st, keep
+    return marshal(PvtCoatingAbsorbTables, compiled)
 
 
 def pattern_tables_struct(compiled):
-    """PvtCoatingPatternTables over the coating patterns of a CompiledScene -> (struct or None, keepalive); None when no
-    coating has a pattern or facet=None (the scene is then created exactly as before)."""
-    if not getattr(compiled, "has_coating_patterns", False):
-        return None, {}
-    keep = {}
-
-    def arr(name, dtype, ctype):
-        a = np.ascontiguousarray(getattr(compiled, name), dtype=dtype)
-        if a.size == 0:
-            a = np.zeros(1, dtype=dtype)   # never hand out NULL for an empty table
-        keep[name] = a
-        return a.ctypes.data_as(C.POINTER(ctype))
-
-    st = PvtCoatingPatternTables()
-    st.n_coatings = int(compiled.n_coatings)
-    st.n_patterns = int(compiled.n_coat_patterns)
-    st.coat_any_facet = arr("coat_any_facet", np.int32, C.c_int32)
-    st.coat_pattern = arr("coat_pattern", np.int32, C.c_int32)
-    st.shape = arr("cpat_shape", np.int32, C.c_int32)
-    st.bounded = arr("cpat_bounded", np.int32, C.c_int32)
-    st.lower = arr("cpat_lower", np.float64, C.c_double)
-    st.h = arr("cpat_h", np.float64, C.c_double)
-    st.mask_start = arr("cpat_start", np.int64, C.c_int64)
-    st.mask = arr("cpat_mask", np.uint8, C.c_uint8)
-    st.n_mask = int(compiled.cpat_mask.shape[0])
-    return st, keep
+    return marshal(PvtCoatingPatternTables, compiled)
 
 
 def emitter_tables_struct(emitter):
     """PvtEmitterTables over an `emit.EmitterTables` object -> (struct, keepalive)."""
-    keep = {}
-    st = PvtEmitterTables()
-    st.n_lights = int(emitter.n_lights)
-    st.n_spec = int(emitter.spec_x.shape[0])
-    fields = dict(PvtEmitterTables._fields_)
-    for name, ctype in fields.items():
-        if ctype not in (_p_i32, _p_f64):
-            continue
-        want = np.int32 if ctype is _p_i32 else np.float64
-        arr = np.ascontiguousarray(getattr(emitter, name), dtype=want)
-        if arr.size == 0:
-            arr = np.zeros(1, dtype=want)
-        keep[name] = arr
-        setattr(st, name, np_ptr(arr))
-    return st, keep
+    return marshal(PvtEmitterTables, emitter)
+
+
+def extension_tables(compiled, count=len(EXTENSION_TABLES)):
+    """The first `count` extension structs of a CompiledScene -> (the arguments a creation entry takes for them, NULL for
+    an absent one; what must outlive the call)."""
+    made = [marshal(struct_type, compiled) for struct_type in EXTENSION_TABLES[:count]]
+    return [None if st is None else C.byref(st) for st, _ in made], made
 
 
 def trace_params(n_rays, seed, ray_offset, emit_seed, record_every, maxsteps, max_events,
@@ -498,39 +419,16 @@ def decode_records(rows):
 def declare_signatures(lib, names):
     """Set argtypes/restype of the C-ABI entry points present in `lib`."""
     vp = C.c_void_p
+
+    def scene_inputs(count):   # the scene tables and the first `count` extension structs
+        return [C.POINTER(struct_type) for struct_type in (PvtSceneTables,) + EXTENSION_TABLES[:count]]
+
     sigs = {
         "pvt_abi_version": ([], C.c_int),
         "pvt_last_error": ([], C.c_char_p),
         "pvt_device_count": ([], C.c_int),
-        "pvt_scene_create": ([C.POINTER(PvtSceneTables), C.c_int, C.POINTER(vp)], C.c_int),
-        "pvt_scene_create_ex": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.c_int, C.POINTER(vp)], C.c_int),
-        "pvt_scene_create_phase": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables), C.c_int,
-                                    C.POINTER(vp)], C.c_int),
-        "pvt_scene_create_rough": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                    C.POINTER(PvtSurfaceTables), C.c_int, C.POINTER(vp)], C.c_int),
-        "pvt_scene_create_field": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                    C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.c_int, C.POINTER(vp)],
-                                   C.c_int),
-        "pvt_scene_create_maps": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                   C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables), C.c_int,
-                                   C.POINTER(vp)], C.c_int),
         "pvt_scene_map_slots": ([vp], C.c_int64),
-        "pvt_scene_create_capture": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                      C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
-                                      C.POINTER(PvtCaptureTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_scene_capture_rows": ([vp], C.c_int64),
-        "pvt_scene_create_absorb": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                     C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
-                                     C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables), C.c_int, C.POINTER(vp)],
-                                    C.c_int),
-        "pvt_scene_create_origin": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                     C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
-                                     C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables), C.c_int, C.POINTER(vp)],
-                                    C.c_int),
-        "pvt_scene_create_pattern": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                      C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
-                                      C.POINTER(PvtCaptureTables), C.POINTER(PvtCoatingAbsorbTables),
-                                      C.POINTER(PvtCoatingPatternTables), C.c_int, C.POINTER(vp)], C.c_int),
         "pvt_trace_device_capture": ([vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
                                       C.POINTER(PvtEventRecords), C.POINTER(PvtCaptures), vp], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
@@ -565,9 +463,7 @@ def declare_signatures(lib, names):
         "pvt_scene_launch_info": (
             [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_variant": ([vp], C.c_int),
-        "pvt_scene_lean_check": ([C.POINTER(PvtSceneTables), C.POINTER(PvtIndexTables), C.POINTER(PvtPhaseTables),
-                                  C.POINTER(PvtSurfaceTables), C.POINTER(PvtFieldTables), C.POINTER(PvtMapTables),
-                                  C.POINTER(C.c_int32)], C.c_int),
+        "pvt_scene_lean_check": (scene_inputs(LEAN_CHECK_TABLES) + [C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_counters": ([vp, C.POINTER(C.c_uint64), C.c_int], C.c_int),
         "pvt_scene_clock": ([vp, C.POINTER(C.c_uint64)], C.c_int),
         "pvt_scene_launch_span": ([vp, vp, C.POINTER(C.c_uint64)], C.c_int),
@@ -575,6 +471,8 @@ def declare_signatures(lib, names):
             [C.POINTER(PvtSceneTables), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
              C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64], C.c_int),
     }
+    for name, count in CREATION_ENTRIES.items():
+        sigs[name] = (scene_inputs(count) + [C.c_int, C.POINTER(vp)], C.c_int)
     for name in names:
         argtypes, restype = sigs[name]
         fn = getattr(lib, name)
@@ -721,12 +619,10 @@ def lean_kind(compiled):
     rounding (the family's kernels that search the tables), 2 = plain with every spectrum a constant or even bit for bit."""
     lib = load_library()
     st, keep = scene_tables_struct(compiled)
-    others = [f(compiled) for f in (index_tables_struct, phase_tables_struct, surface_tables_struct, field_tables_struct,
-                                    map_tables_struct)]
+    others, alive = extension_tables(compiled, LEAN_CHECK_TABLES)
     lean = C.c_int32(0)
-    check(lib.pvt_scene_lean_check(C.byref(st), *(None if s is None else C.byref(s) for s, _ in others), C.byref(lean)),
-          "pvt_scene_lean_check")
-    del keep, others
+    check(lib.pvt_scene_lean_check(C.byref(st), *others, C.byref(lean)), "pvt_scene_lean_check")
+    del keep, alive
     return int(lean.value)
 
 
@@ -734,8 +630,6 @@ def node_grid_plan(compiled):
     """The node grid the library files the nodes of a many-node scene under (host only, no GPU needed;
     include/pvtrace_hip.h: pvt_node_grid_plan) -> dict(dims, lo, cell, guard, odd, masks[cells, 2] uint64),
     or None when the scene is served by the plain node loop."""
-    import numpy as np
-
     lib = load_library()
     st, keep = scene_tables_struct(compiled)
     dims = (C.c_int32 * 3)()
@@ -764,21 +658,12 @@ class DeviceScene:
         self.compiled = compiled
         self.device = int(device)
         st, keep = scene_tables_struct(compiled)
-        xt, xkeep = index_tables_struct(compiled)
-        pt, pkeep = phase_tables_struct(compiled)
-        rt, rkeep = surface_tables_struct(compiled)
-        ft, fkeep = field_tables_struct(compiled)
-        mt, mkeep = map_tables_struct(compiled)
-        ct, ckeep = capture_tables_struct(compiled)
-        at, akeep = absorb_tables_struct(compiled)
-        kt, kkeep = pattern_tables_struct(compiled)
+        others, alive = extension_tables(compiled)
         handle = C.c_void_p()
-        # (the older pvt_scene_create* entries do the same with NULL for the tables they lack; pvt_scene_create_absorb alone
-        # takes a `detected` recorder, pvt_scene_create_origin is that entry with the launch-origin histogram properties
-        # accepted, and this one is that entry with the coating patterns: the only one Python ever calls)
-        others = (None if t is None else C.byref(t) for t in (xt, pt, rt, ft, mt, ct, at, kt))
+        # (the newest entry, the only one Python ever calls: the older ones do the same with NULL for the structs they lack)
         check(self.lib.pvt_scene_create_pattern(C.byref(st), *others, self.device, C.byref(handle)),
               "pvt_scene_create_pattern")
+        del keep, alive
         self.handle = handle
         self.has_emitter = False
         # HIP stream handle -> weak reference to the BundlePipeline whose job lives on it (parked photons belong to a

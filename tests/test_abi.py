@@ -38,14 +38,15 @@ def test_library_builds_loads_and_exports_every_declared_symbol(built):
 def test_ctypes_structs_match_the_header(tmp_path):
     from pvtrace_amd.engine import native as N
 
-    structs = ["PvtSceneTables", "PvtEmitterTables", "PvtTraceParams", "PvtRays", "PvtTallies",
-               "PvtEventLog", "PvtEventRecords"]
-    probes = {"PvtSceneTables": ["n_nodes", "geom_type", "comp_type", "abs_x", "rec_node",
-                                 "hist_prop_a", "coat_facet", "coat_transmit_mode", "rec_source_id", "comp_ems_hist"],
-              "PvtEmitterTables": ["wl_type", "spec_cdf"],
-              "PvtTraceParams": ["seed", "ray_offset", "record_every", "maxsteps", "emit_method"],
-              "PvtRays": ["wavelength"], "PvtTallies": ["rec_bins"], "PvtEventLog": ["kind", "duration"],
-              "PvtEventRecords": ["counts", "rows"]}
+    # every ctypes.Structure of the binding mirrors a struct of the header: its size and the offset of EVERY field
+    structs = sorted(name for name, cls in vars(N).items() if isinstance(cls, type) and issubclass(cls, C.Structure)
+                     and cls is not C.Structure)
+    header = open(HEADER).read()
+    assert set(re.findall(r"^\}\s*(Pvt\w+)\s*;", header, flags=re.M)) == set(structs)   # and the header has no other
+    assert {"PvtSceneTables", "PvtEmitterTables", "PvtTraceParams", "PvtRays", "PvtTallies", "PvtEventLog", "PvtEventRecords",
+            "PvtIndexTables", "PvtPhaseTables", "PvtSurfaceTables", "PvtFieldTables", "PvtMapTables", "PvtCaptureTables",
+            "PvtCoatingAbsorbTables", "PvtCoatingPatternTables", "PvtCaptures"} <= set(structs)
+    probes = {s: [name for name, _ in getattr(N, s)._fields_] for s in structs}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for s in structs:
         lines.append(f'printf("{s} %zu\\n", sizeof({s}));')

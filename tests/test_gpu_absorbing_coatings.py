@@ -315,9 +315,9 @@ def test_the_packer_refuses_each_malformed_absorb_table_with_its_own_message():
 
     assert attempt() is None
     messages = {"count": attempt(count), "nan": attempt(poke("coat_absorptivity", 0, float("nan"))),
-                "range": attempt(poke("coat_absorptivity", 0, 1.5)), "descending": attempt(poke("atab_wavelength", 1, 400.0)),
-                "angle": attempt(poke("atab_angle", 1, 10.0)), "value": attempt(poke("atab_value", 2, 1.25)),
-                "size": attempt(poke("atab_nw", 0, 3)), "names": attempt(poke("coat_abs_table", 1, 5))}
+                "range": attempt(poke("coat_absorptivity", 0, 1.5)), "descending": attempt(poke("wavelength", 1, 400.0)),
+                "angle": attempt(poke("angle", 1, 10.0)), "value": attempt(poke("value", 2, 1.25)),
+                "size": attempt(poke("table_nw", 0, 3)), "names": attempt(poke("coat_table", 1, 5))}
     assert all(isinstance(m, str) and "absorb tables" in m for m in messages.values()), messages
     assert len(set(messages.values())) == len(messages), messages
     assert "one absorptivity per coating" in messages["count"] and "finite" in messages["nan"] and "[0, 1]" in messages["range"]

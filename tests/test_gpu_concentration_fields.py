@@ -14,6 +14,7 @@ from pvtrace_amd.algorithm import photon_tracer
 from pvtrace_amd.engine import Histogram, Recorder, Session, compile_scene, native
 from pvtrace_amd.engine.emit import emit_bundle
 from pvtrace_amd.material import NullSurfaceDelegate
+from tests import broken_tables as BT
 from tests import laws as L
 from tests import scenes
 from tests.test_concentration_fields import chord_depth, depth_cdf
@@ -301,23 +302,12 @@ def test_fields_change_the_tallies_and_carried_launches_equal_one_launch():
 
 # -- 5. refusals ------------------------------------------------------------------------------------------------------
 def test_the_packer_refuses_each_malformed_table_with_its_own_message():
-    grid = ConcentrationGrid(np.ones((1, 1, 2)), LO, HI)
-    compiled = compile_scene(block_scene([Absorber(1.0, concentration=grid), Absorber(0.5, concentration=grid)]))
+    compiled = compile_scene(BT.field_scene())
     lib = native.load_library()
     st, keep = native.scene_tables_struct(compiled)
 
     def attempt(**change):
-        tabs = {"node_field": np.array([-1, 0], np.int32), "field_shape": np.array([[1, 1, 2]], np.int32),
-                "field_lower": np.array([LO], float), "field_upper": np.array([HI], float),
-                "comp_values": np.array([0, 0], np.int32), "values_start": np.array([0], np.int32),
-                "values_count": np.array([2], np.int32), "values": np.array([1.0, 2.0])}
-        tabs.update(change)
-        ft = native.PvtFieldTables()
-        ft.n_nodes, ft.n_fields = 2, 1
-        ft.n_components, ft.n_values, ft.n_points = 2, 1, int(tabs["values"].size)
-        for name in ("node_field", "field_shape", "field_lower", "field_upper", "comp_values", "values_start",
-                     "values_count", "values"):
-            setattr(ft, name, native.np_ptr(np.ascontiguousarray(tabs[name])))
+        ft, held = BT.field_tables(**change)
         handle = C.c_void_p()
         rc = lib.pvt_scene_create_field(C.byref(st), None, None, None, C.byref(ft), 0, C.byref(handle))
         if rc == 0:
@@ -327,19 +317,7 @@ def test_the_packer_refuses_each_malformed_table_with_its_own_message():
         return lib.pvt_last_error().decode()
 
     assert attempt() is None
-    bad = {
-        "nan": dict(values=np.array([1.0, np.nan])),
-        "negative": dict(values=np.array([1.0, -2.0])),
-        "shape": dict(field_shape=np.array([[1, 0, 2]], np.int32)),
-        "bounds": dict(field_upper=np.array([[1.0, -1.0, 1.0]])),
-        "infinite bounds": dict(field_lower=np.array([[-np.inf, -1.0, -1.0]])),
-        "lattice index": dict(node_field=np.array([-1, 3], np.int32)),
-        "value index": dict(comp_values=np.array([0, 5], np.int32)),
-        "no values": dict(comp_values=np.array([0, -1], np.int32)),
-        "size": dict(values_count=np.array([1], np.int32)),
-        "root": dict(node_field=np.array([0, 0], np.int32)),
-        "run": dict(values_start=np.array([1], np.int32)),
-    }
+    bad = BT.FIELD_BREAKS   # (the cases: tests/broken_tables.py)
     messages = {}
     for what, change in bad.items():
         msg = attempt(**change)

@@ -15,6 +15,7 @@ from pvtrace_amd.data import lumogen_f_red_305
 from pvtrace_amd.engine import Recorder, Session, UnsupportedSceneError, _kernel, compile_scene
 from pvtrace_amd.engine.emit import emit_bundle
 from pvtrace_amd.material import fresnel_reflectivity, fresnel_refraction
+from tests import broken_tables as BT
 from tests import dispersion_scene as D
 from tests import scenes
 from tests.util import assert_bundles_identical, load_golden
@@ -235,14 +236,7 @@ def _create_ex(compiled, edit):
 
     lib = N.load_library()
     st, keep = N.scene_tables_struct(compiled)
-    arrays = {"node_table": compiled.ri_table.copy(), "table_n": compiled.rtab_n.copy(),
-              "table_start": compiled.rtab_start.copy(), "wavelength": compiled.rtab_wavelength.copy(),
-              "value": compiled.rtab_value.copy()}
-    xt = N.PvtIndexTables()
-    xt.n_tables, xt.n_points = int(compiled.n_ri_tables), int(compiled.rtab_wavelength.size)
-    edit(xt, arrays)
-    for name, arr in arrays.items():
-        setattr(xt, name, N.np_ptr(arr) if arr is not None else None)
+    xt, arrays = BT.index_tables(compiled, edit)
     handle = C.c_void_p()
     rc = lib.pvt_scene_create_ex(C.byref(st), C.byref(xt), 0, C.byref(handle))
     if rc == 0:
@@ -250,41 +244,7 @@ def _create_ex(compiled, edit):
     return rc, lib.pvt_last_error().decode()
 
 
-def _set(**kw):
-    def edit(xt, arrays):
-        for key, value in kw.items():
-            if key in arrays:
-                if callable(value):
-                    value(arrays[key])
-                else:
-                    arrays[key] = value
-            else:
-                setattr(xt, key, value)
-    return edit
-
-
-def _put(i, v):
-    def f(a):
-        a[i] = v
-    return f
-
-
-BREAKS = {
-    "missing node_table": (_set(node_table=None), "index tables: missing arrays"),
-    "missing value": (_set(value=None), "index tables: missing arrays"),
-    "negative count": (_set(n_tables=-1), "index tables: missing arrays"),
-    "node table too large": (_set(node_table=_put(1, 1)), "index tables: node names a missing table"),
-    "node table below -1": (_set(node_table=_put(0, -2)), "index tables: node names a missing table"),
-    "empty table": (_set(table_n=_put(0, 0)), "index tables: point range out of bounds"),
-    "negative start": (_set(table_start=_put(0, -1)), "index tables: point range out of bounds"),
-    "past the pools": (_set(n_points=2), "index tables: point range out of bounds"),
-    "wavelengths not increasing": (_set(wavelength=_put(1, 400.0)), "index tables: wavelengths must be finite and strictly increasing"),
-    "wavelength not finite": (_set(wavelength=_put(2, np.nan)), "index tables: wavelengths must be finite and strictly increasing"),
-    "value zero": (_set(value=_put(0, 0.0)), "index tables: values must be finite and positive"),
-    "value negative": (_set(value=_put(1, -1.5)), "index tables: values must be finite and positive"),
-    "value infinite": (_set(value=_put(2, np.inf)), "index tables: values must be finite and positive"),
-    "value huge": (_set(value=_put(2, 1e101)), "index tables: values must be finite and positive"),
-}
+_set, BREAKS = BT.index_edit, BT.INDEX_BREAKS   # (the cases: tests/broken_tables.py)
 
 
 @pytest.mark.parametrize("case", sorted(BREAKS))

@@ -10,6 +10,7 @@ from oracle import oracle as O
 from pvtrace_amd.engine import _kernel, compile_scene, native
 from pvtrace_amd.engine.emit import EmitterTables, emit_bundle
 from tests import scenes
+from tests.broken_tables import BROKEN_TABLES, SCENES
 from tests.util import assert_bundles_identical, assert_same_tables, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -493,84 +494,7 @@ def test_random_scenes_gpu_equals_oracle(seed, extensions):
 
 
 # -- malformed tables: pvt_scene_create rejects them before it reads or allocates anything -----------------------------
-def _coating_table_scene():
-    from pvtrace_amd import (Box, CoatedSurfaceDelegate, Coating, Light, Luminophore, Material, Node, ReflectivityTable,
-                             Scene, Surface, rectangular_mask)
-    from pvtrace_amd.data import lumogen_f_red_305
-    from tests import coating_table_scene as S
-
-    table = ReflectivityTable(S.MIRROR_WAVELENGTH, S.MIRROR_VALUE, angle=S.MIRROR_ANGLE)
-    scene, _ = S.build(Node, Scene, Box, Material, Surface, Light, rectangular_mask, lambda: S.PUMP_NM,
-                       S.components(Luminophore, lumogen_f_red_305),
-                       delegate=CoatedSurfaceDelegate([Coating((0, 0, 1), reflectivity=table)]))
-    return scene
-
-
-def _cfg2():
-    from benchmarks.configs import cfg2_lsc
-
-    return cfg2_lsc()
-
-
-def _set(st, keep, name, index, value):
-    """Table `name` of the struct with element `index` replaced (a copy: the compiled scene is left alone)."""
-    arr = keep[name].copy()
-    arr[index] = value
-    keep[name] = arr
-    setattr(st, name, native.np_ptr(arr))
-
-
-def _many_coating_tables(st, keep, c):
-    """As many tables as make 2^27 doubles, every one of them the scene's own (same ranges of the pools)."""
-    nt = (1 << 27) // int(c.ctab_nw[0] + c.ctab_na[0] + c.ctab_nw[0] * c.ctab_na[0]) + 1
-    for name in ("ctab_nw", "ctab_na", "ctab_wl_start", "ctab_angle_start", "ctab_value_start"):
-        keep[name] = np.full(nt, keep[name][0], dtype=np.int32)
-        setattr(st, name, native.np_ptr(keep[name]))
-    st.n_coat_tables = nt
-
-
-SCENES = {"cfg2": _cfg2, "mesh_lsc": scenes.mesh_lsc, "coating_table": _coating_table_scene, "two_nodes": scenes.hello_world}
-INVALID, TOO_MANY_NODES = -1, -2
-BROKEN_TABLES = [   # (scene, how one field is broken, return code, pvt_last_error)
-    ("two_nodes", lambda st, k, c: setattr(st, "n_nodes", 0), INVALID, "scene has no nodes"),
-    ("two_nodes", lambda st, k, c: setattr(st, "n_nodes", 129), TOO_MANY_NODES, "more than 128 geometry nodes"),
-    ("cfg2", lambda st, k, c: setattr(st, "n_recorders", 257), INVALID, "more than 256 recorders"),
-    ("two_nodes", lambda st, k, c: _set(st, k, "geom_type", 1, 4), INVALID, "unknown geometry type"),
-    ("mesh_lsc", lambda st, k, c: setattr(st, "mesh_faces", None), INVALID, "mesh node without mesh tables"),
-    ("mesh_lsc", lambda st, k, c: _set(st, k, "mesh_face_count", 1, c.n_mesh_faces + 1), INVALID,
-     "mesh face range out of bounds"),
-    ("mesh_lsc", lambda st, k, c: setattr(st, "n_mesh_faces", 1 << 27), INVALID, "more than 2^27 mesh faces in one scene"),
-    ("mesh_lsc", lambda st, k, c: _set(st, k, "mesh_faces", 3 * c.mesh_face_start[1] + 2, c.n_mesh_vertices), INVALID,
-     "mesh face indexes a missing vertex"),
-    ("coating_table", lambda st, k, c: setattr(st, "ctab_angle", None), INVALID, "coating tables: missing arrays"),
-    ("coating_table", lambda st, k, c: _set(st, k, "ctab_na", 0, st.n_ctab_angle + 1), INVALID,
-     "coating tables: axis or value range out of bounds"),
-    ("coating_table", lambda st, k, c: _set(st, k, "ctab_wavelength", 2, np.inf), INVALID,
-     "coating tables: wavelengths must be finite and strictly increasing"),
-    ("coating_table", lambda st, k, c: _set(st, k, "ctab_angle", 1, 0.0), INVALID,
-     "coating tables: angles must be strictly increasing, in [0, 90] degrees"),
-    ("coating_table", lambda st, k, c: _set(st, k, "ctab_value", 3, -0.5), INVALID, "coating tables: values must be in [0, 1]"),
-    ("coating_table", _many_coating_tables, INVALID, "coating tables: more than 2^27 doubles"),
-    ("coating_table", lambda st, k, c: _set(st, k, "coat_table", 0, 1), INVALID, "coating row names a missing table"),
-    ("two_nodes", lambda st, k, c: _set(st, k, "refractive_index", 1, np.nan), INVALID,
-     "refractive indices must be finite and positive"),
-    ("cfg2", lambda st, k, c: _set(st, k, "comp_count", 1, 3), INVALID, "component range of a node out of bounds"),
-    ("cfg2", lambda st, k, c: _set(st, k, "rec_node", 9, 2), INVALID, "recorder on a missing node"),
-    # ranges the packer and the kernel follow that were not checked before
-    ("two_nodes", lambda st, k, c: setattr(st, "root_id", 2), INVALID, "root node out of range"),
-    ("cfg2", lambda st, k, c: _set(st, k, "comp_abs_n", 0, c.abs_x.shape[0] + 1), INVALID,
-     "absorption spectrum range of a component out of bounds"),
-    ("coating_table", lambda st, k, c: _set(st, k, "comp_ems_start", 0, 1), INVALID,
-     "emission spectrum range of a component out of bounds"),
-    ("coating_table", lambda st, k, c: _set(st, k, "coat_count", 1, 2), INVALID, "coating range of a node out of bounds"),
-    ("cfg2", lambda st, k, c: _set(st, k, "rec_hist_start", 0, c.hist_prop_a.shape[0]), INVALID,
-     "histogram range of a recorder out of bounds"),
-    ("mesh_lsc", lambda st, k, c: _set(st, k, "rec_event", 0, 7), INVALID, "recorder selector out of range"),
-    ("cfg2", lambda st, k, c: _set(st, k, "hist_offset", 5, c.total_bins), INVALID,
-     "histogram bins out of range of total_bins"),
-]
-
-
+# (the cases: tests/broken_tables.py, which tests/test_table_refusals.py runs through the packer without a GPU)
 @pytest.mark.parametrize("case", range(len(BROKEN_TABLES)), ids=[m for _, _, _, m in BROKEN_TABLES])
 def test_scene_create_rejects_broken_tables(case):
     """Each case copies a valid compiled scene and breaks exactly one field: pvt_scene_create refuses it with the check's

@@ -16,6 +16,7 @@ from pvtrace_amd.engine.emit import emit_bundle
 from pvtrace_amd.material import FresnelSurfaceDelegate
 from tests import laws as L
 from tests import scenes
+from tests.broken_tables import BAD_ROUGHNESS, surface_tables
 from tests.law_cases import INDEX_TABLE, rows
 from tests.test_gpu_laws import Gpu
 from tests.test_rough_surfaces import (
@@ -262,18 +263,12 @@ def test_the_packer_refuses_bad_roughness():
     compiled = compile_scene(rough_block_scene(0.2))
     lib = native.load_library()
     st, keep = native.scene_tables_struct(compiled)
-    for bad in (-0.1, 1.5, float("nan")):
-        alpha = np.array([0.0, bad])
-        rt = native.PvtSurfaceTables()
-        rt.n_nodes = 2
-        rt.node_roughness = native.np_ptr(alpha)
+    for bad in BAD_ROUGHNESS:
+        rt, alpha = surface_tables(bad)
         handle = C.c_void_p()
         rc = lib.pvt_scene_create_rough(C.byref(st), None, None, C.byref(rt), 0, C.byref(handle))
         assert rc != 0 and not handle.value, bad
-    zeros = np.zeros(2)
-    rt = native.PvtSurfaceTables()
-    rt.n_nodes = 2
-    rt.node_roughness = native.np_ptr(zeros)
+    rt, zeros = surface_tables(0.0)
     handle = C.c_void_p()
     assert lib.pvt_scene_create_rough(C.byref(st), None, None, C.byref(rt), 0, C.byref(handle)) == 0
     lib.pvt_scene_destroy(handle)

@@ -19,6 +19,7 @@ from pvtrace_amd.engine import Recorder, Session, compile_scene, map_histories, 
 from pvtrace_amd.engine.api import maps_from_slots
 from pvtrace_amd.engine.emit import emit_bundle
 from pvtrace_amd.material import NullSurfaceDelegate
+from tests import broken_tables as BT
 from tests import laws as L
 from tests import scenes
 from tests.test_volume_maps import beer_lambert_probabilities, beer_lambert_scene
@@ -315,24 +316,12 @@ def test_lost_map_follows_beer_lambert_at_a_million_photons():
 
 # -- 11. the packer ---------------------------------------------------------------------------------------------------------------
 def test_the_packer_refuses_each_malformed_table_with_its_own_message():
-    scene, body = block([Absorber(1.0, name="a"), Absorber(0.5, name="b")])
-    compiled = compile_scene(scene)
+    compiled = compile_scene(BT.map_scene())
     lib = native.load_library()
     st, keep = native.scene_tables_struct(compiled)
 
     def attempt(n_nodes=2, **change):
-        tabs = {"node_map_start": np.array([0, 0], np.int32), "node_map_count": np.array([0, 2], np.int32),
-                "map_kind": np.array([3, 4], np.int32), "map_component": np.array([-1, 1], np.int32),
-                "map_shape": np.array([[2, 2, 2], [1, 1, 3]], np.int32), "map_lower": np.array([[-1.0] * 3] * 2),
-                "map_h": np.array([[1.0, 1.0, 1.0], [2.0, 2.0, 0.5]]), "map_nw": np.array([0, 4], np.int32),
-                "map_wl_start": np.array([0.0, 400.0]), "map_wl_stop": np.array([1.0, 800.0]),
-                "map_offset": np.array([0, 9], np.int64), "map_slots": 22}
-        tabs.update(change)
-        mt = native.PvtMapTables()
-        mt.n_nodes, mt.n_maps, mt.map_slots = n_nodes, 2, int(tabs.pop("map_slots"))
-        held = {k: np.ascontiguousarray(v) for k, v in tabs.items()}
-        for name, value in held.items():
-            setattr(mt, name, native.np_ptr(value))
+        mt, held = BT.map_tables(n_nodes, **change)
         handle = C.c_void_p()
         rc = lib.pvt_scene_create_maps(C.byref(st), None, None, None, None, C.byref(mt), 0, C.byref(handle))
         if rc == 0:
@@ -343,23 +332,7 @@ def test_the_packer_refuses_each_malformed_table_with_its_own_message():
         return lib.pvt_last_error().decode()
 
     assert attempt() == 22
-    bad = {
-        "nodes": dict(n_nodes=3),
-        "run": dict(node_map_count=np.array([0, 5], np.int32)),
-        "tiling": dict(node_map_start=np.array([0, 1], np.int32), node_map_count=np.array([0, 1], np.int32)),
-        "root": dict(node_map_start=np.array([0, 1], np.int32), node_map_count=np.array([1, 1], np.int32)),
-        "kind": dict(map_kind=np.array([3, 2], np.int32)),
-        "component": dict(map_component=np.array([-1, 7], np.int32)),
-        "shape": dict(map_shape=np.array([[2, 0, 2], [1, 1, 3]], np.int32)),
-        "lower": dict(map_lower=np.array([[-1.0, np.nan, -1.0], [-1.0] * 3])),
-        "width": dict(map_h=np.array([[1.0, 1.0, 0.0], [2.0, 2.0, 0.5]])),
-        "bins": dict(map_nw=np.array([0, -1], np.int32)),
-        "infinite range": dict(map_wl_stop=np.array([1.0, np.inf])),
-        "range": dict(map_wl_stop=np.array([1.0, 400.0])),
-        "offset": dict(map_offset=np.array([0, 8], np.int64)),
-        "total": dict(map_slots=23),
-        "limit": dict(map_shape=np.array([[2, 2, 2], [4096, 4096, 8]], np.int32)),
-    }
+    bad = BT.MAP_BREAKS   # (the cases: tests/broken_tables.py)
     messages = {}
     for what, change in bad.items():
         msg = attempt(**change)
