@@ -521,6 +521,49 @@ typedef struct PvtCoatingPatternTables {
     int64_t n_mask;                     /* bytes in `mask`, at most 2^26 */
 } PvtCoatingPatternTables;
 
+/* ---- aligned components (extension within v13, passed to pvt_scene_create_aligned) -----------------------------------
+ * Uniaxial alignment of a component's transition dipoles about a director n with order parameter S = <P2>: dichroic
+ * absorption and dipole emission.  No polarisation is tracked: both laws are the average over unpolarised light, so the
+ * polarisation memory between a dipole emission and the next absorption is ignored.  With mu = d . n, the absorption of
+ * unpolarised light travelling along d and the emission density along d are f(mu; S) = 1 - S P2(mu), P2(mu) = 1.5 mu^2 - 0.5,
+ * -0.5 <= S <= 1.  comp_align[c] >= 0 names the record of component c.  The absorption rule (the Python Alignment docstring
+ * states the same; the kernel and the host tracer both follow it):
+ *  1. The flattener lowers each aligned component's director ONCE to the scene root's frame as a unit vector n_w: with
+ *     the rows R0, R1, R2 of the node's rotation to the root, n_w,i = (Ri,0 nx + Ri,1 ny) + Ri,2 nz, then divided by
+ *     sqrt((x x + y y) + z z) of the result, without FMA.  `axis` holds n_w.
+ *  2. At the free-path site mu_k = (dx nx + dy ny) + dz nz, without FMA, clamped to [-1, 1].
+ *  3. f_k = 1.0 - S_k (1.5 (mu_k mu_k) - 0.5), exactly these operations in this order.
+ *  4. A component without alignment has f_k = 1 and is not multiplied.
+ *  5. The depth draw happens where and when an unaligned container draws, on the UNSCALED sum of alpha_k(lambda) >
+ *     the clear-medium threshold (the decision of the concentration fields): S = 1 along the director does not change
+ *     who draws.
+ *  6. tau* = -ln(1 - u); the depth is tau* / sum_k alpha_k f_k through the division the site already uses.
+ *  7. The depth is +inf when the scaled sum is exactly 0.
+ *  8. The component is picked by the unaligned walk over alpha_k f_k, the two-component shortcut on the first partial
+ *     sum included.
+ *  9. The tail function's cache of coefficient sums holds UNSCALED sums keyed by container and wavelength; a container
+ *     with an aligned component forms its scaled sum anew every step, from the direction the photon has then.
+ * The emission rule: emit_table[r] >= 0 names the SINGLE-ROW phase table (PvtPhaseTables) that holds f(mu; S_e) on uniform
+ * mu nodes from exactly -1 to exactly 1; the component is tagged PVT_PHASE_TABLE and names that table, and the kernel
+ * samples it by the phase tables' rule with n_w as the axis instead of the incoming direction.  A single row draws no u1
+ * and the two isotropic draw sites serve as u2 and u3: an aligned emission consumes exactly the draws an isotropic one does.
+ * Refused: an aligned component in a node with a concentration field (the march would need the factors: out of scope) or
+ * in the root.  The records lie in global memory beside the concentration fields', outside what a launch stages in LDS.
+ * Launches of such a scene run the PVT_VARIANT_ROUGH family; the host-buffer entries know no alignment.  The older
+ * pvt_scene_create* entries cannot be handed this struct, and that is their refusal: nothing in PvtSceneTables says that a
+ * component is aligned, so a scene lowered for this entry and given to an older one is the scene WITHOUT alignment (a
+ * component tagged PVT_PHASE_TABLE is then sampled about the incoming ray, as PvtPhaseTables states); a caller that has
+ * alignment tables must call this entry.  A NULL struct, n_components 0, or no component with a record is exactly
+ * pvt_scene_create_pattern. */
+typedef struct PvtAlignTables {
+    int32_t n_components;               /* 0 = none (as a NULL struct), else the scene's n_components */
+    int32_t n_records;                  /* alignment records */
+    const int32_t* comp_align;          /* (n_components) record of each component, -1 = not aligned */
+    const double* axis;                 /* (n_records,3) the director in the root's frame, a unit vector within 1e-12 */
+    const double* abs_order;            /* (n_records) S_a, finite and in [-0.5, 1] */
+    const int32_t* emit_table;          /* (n_records) the single-row phase table of f(mu; S_e), -1 = S_e is 0 */
+} PvtAlignTables;
+
 /* capture buffers of one launch (DEVICE pointers): `rows` holds sets x capture_rows x PVT_CAPTURE_ROW_WORDS uint64,
  * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle).  Word 11 of a row:
  * emissions | scatterings << 20 | reflections << 40, the photon's event counters (PVT_PROPX_*) */
@@ -718,6 +761,14 @@ int pvt_scene_create_pattern(const PvtSceneTables* tables, const PvtIndexTables*
                              const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
                              const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables,
                              const PvtCoatingPatternTables* pattern_tables, int device, PvtScene** out);
+/* The same with aligned components (PvtAlignTables; NULL, n_components 0 or no component with a record = none: then
+ * exactly pvt_scene_create_pattern).  Every entry before it knows no alignment. */
+int pvt_scene_create_aligned(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                             const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                             const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
+                             const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables,
+                             const PvtCoatingPatternTables* pattern_tables, const PvtAlignTables* align_tables, int device,
+                             PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);
@@ -846,7 +897,7 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
  * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
  * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
  * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
- * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones, aligned components), MESH.  The environment variable PVT_NO_LEAN, read when the scene
  * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */

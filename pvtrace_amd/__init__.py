@@ -10,7 +10,7 @@ from pvtrace_amd.light import (
     Event, Light, Ray, circular_mask, cube_mask, rectangular_mask,
 )
 from pvtrace_amd.material import (
-    Absorber, AbsorptivityTable, CoatedSurfaceDelegate, Coating, CoatingPattern, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
+    Absorber, AbsorptivityTable, Alignment, CoatedSurfaceDelegate, Coating, CoatingPattern, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
     Luminophore, Material, NullSurfaceDelegate, PhaseFunctionTable, Reactor, ReflectivityTable,
     RefractiveIndexTable, Scatterer, Surface,
     SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian, pattern_cell,

@@ -93,8 +93,8 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
     absorbed on the way (ABSORB, then EMIT / SCATTER and on, or NONRADIATIVE / REACT and out) or reaches the surface,
     where the hit node's surface reflects or transmits it in that node's frame -- or, under an absorbing coating, ends it
     (DETECT).  A container whose components carry a
-    concentration field (`ConcentrationGrid`) is asked in its own frame (`Material.is_absorbed_in / component_at`); every
-    other container takes the reference's `is_absorbed / component` and their draws."""
+    concentration field (`ConcentrationGrid`) is asked in its own frame (`Material.is_absorbed_in / component_at`), and so
+    is one with an aligned component (`Alignment`: `Material.is_absorbed_along / component_along`); every other container takes the reference's `is_absorbed / component` and their draws."""
     from pvtrace_amd.material import Luminophore, Reactor, Scatterer, index_at
 
     root = scene.root
@@ -115,8 +115,20 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
         if hit is root:
             yield ray.propagate(distance, index), Event.EXIT, names
             return
-        cell = None
-        if medium.concentration_lattice is not None:
+        cell, along = None, None
+        if getattr(medium, "has_alignment", False):
+            from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+            if container is root:
+                raise UnsupportedSceneError(f"Root node {root.name!r}: the scene's root cannot carry an aligned component (Alignment).")
+            if medium.concentration_lattice is not None:
+                raise UnsupportedSceneError(
+                    f"Node {container.name!r}: alignment together with a concentration field in one material is out of scope "
+                    "(the march would need the factors).")
+            local = ray.representation(root, container)
+            along = local.direction
+            absorbed, depth = medium.is_absorbed_along(local, distance)
+        elif medium.concentration_lattice is not None:
             if container is root:
                 from pvtrace_amd.engine.compiler import UnsupportedSceneError
 
@@ -126,7 +138,10 @@ def _steps_on_host_objects(scene, ray, maxsteps, maxpathlength, emit_method):
             absorbed, depth = medium.is_absorbed(ray, distance)
         if absorbed:
             ray = ray.propagate(depth, index)
-            taker = medium.component(ray.wavelength) if cell is None else medium.component_at(ray.wavelength, cell)
+            if along is not None:
+                taker = medium.component_along(ray.wavelength, along)
+            else:
+                taker = medium.component(ray.wavelength) if cell is None else medium.component_at(ray.wavelength, cell)
             who = {"component": taker.name, "container": container.name}
             yield ray, Event.ABSORB, dict(who)
             if not taker.is_radiative(ray):

@@ -370,6 +370,10 @@ struct PackedScene {
     // behind pd -- a record's kPrMask counts bytes from the start of pd
     std::vector<double> pd;
     std::vector<unsigned char> pmask;
+    // aligned components (PvtAlignTables): records in `fd` (created when the scene has no lattice): fd[n] of a node that
+    // holds one names a record like a lattice's with shape 0, whose kFrComp + k word names the k-th component's record of
+    // kAl doubles in fd (-1: that component is not aligned)
+    bool aligned = false;
     double lazy_k = 0.0;
     bool exit_observed = false, fuse_exit = false, grid = false, hist_reads_position = false;
     bool hist_reads_counter = false;   // a histogram axis is a photon event counter (PVT_PROPX_EMISSIONS .. _REFLECTIONS)
@@ -403,13 +407,14 @@ struct SceneInputs {
     const PvtCoatingAbsorbTables* ab = nullptr;    // the coatings' absorptivities
     const PvtCoatingPatternTables* pt = nullptr;   // where the coatings cover
     Knows knows{};
+    const PvtAlignTables* al = nullptr;            // aligned components (behind `knows`: the older entries' records stay as written)
 };
 
 // The levels an entry can know, one row each.  A new entry that knows more gets a new row; nothing else names these limits.
 //                                 last selector      last property          last geometry        used by
 constexpr Knows kKnowsBeforeAbsorb{PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_MESH};     // pvt_scene_create .. pvt_scene_create_capture
 constexpr Knows kKnowsAbsorb      {PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH};     // pvt_scene_create_absorb
-constexpr Knows kKnowsOrigin      {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_FRUSTUM};  // pvt_scene_create_origin, _pattern, pvt_scene_lean_check
+constexpr Knows kKnowsOrigin      {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_FRUSTUM};  // pvt_scene_create_origin, _pattern, _aligned, pvt_scene_lean_check
 constexpr Knows kKnowsHostBuffer  {PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_FRUSTUM};  // pvt_trace_bundle*: pvt_scene_create, but a truncated cone is taken
 
 // ---- validation: every index into a table that the packer follows on the host or the kernel on the device, checked
@@ -1616,6 +1621,77 @@ int pack_patterns(const SceneInputs& in, PackedScene* p) {
     }
     p->pmask.assign(pt->mask, pt->mask + pt->n_mask);
     if (p->pmask.empty()) p->pmask.push_back(0);   // (flags alone: the buffer still ends in a byte)
+    return PVT_OK;
+}
+
+// Aligned components (PvtAlignTables, pvt_scene_create_aligned; called on a scene pack_scene has accepted, before anything
+// is uploaded): every value the kernel reads is checked, each failure with its own message, then PackedScene::ad is filled.
+// It stays empty -- the scene is then exactly the one without the struct -- when no component names a record.
+int pack_align(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    const PvtAlignTables* al = in.al;
+    p->aligned = false;
+    if (!al || al->n_components == 0) return PVT_OK;
+    const int C = t->n_components, N = t->n_nodes, R = al->n_records;
+    if (al->n_components != C || !al->comp_align) return fail(PVT_ERR_INVALID, "align tables: need one record index per component");
+    if (R < 0 || (R > 0 && (!al->axis || !al->abs_order || !al->emit_table))) return fail(PVT_ERR_INVALID, "align tables: missing arrays");
+    bool any = false;
+    for (int c = 0; c < C; c++) {
+        if (al->comp_align[c] < -1 || al->comp_align[c] >= R) return fail(PVT_ERR_INVALID, "align tables: component names a missing record");
+        any = any || al->comp_align[c] >= 0;
+    }
+    if (!any) return PVT_OK;
+    const PvtPhaseTables* ph = in.ph;
+    const int NP = ph ? ph->n_tables : 0;
+    for (int r = 0; r < R; r++) {
+        const double x = al->axis[r * 3], y = al->axis[r * 3 + 1], z = al->axis[r * 3 + 2];
+        const double len2 = (x * x + y * y) + z * z;
+        if (!(std::isfinite(len2) && std::fabs(len2 - 1.0) <= 1e-12)) return fail(PVT_ERR_INVALID, "align tables: every axis must be a unit vector within 1e-12");
+        const double s = al->abs_order[r];
+        if (!std::isfinite(s)) return fail(PVT_ERR_INVALID, "align tables: absorption orders must be finite");
+        if (!(s >= -0.5 && s <= 1.0)) return fail(PVT_ERR_INVALID, "align tables: absorption orders must lie in [-0.5, 1]");
+        const int j = al->emit_table[r];
+        if (j < -1 || j >= NP) return fail(PVT_ERR_INVALID, "align tables: emission table outside the phase tables");
+        if (j >= 0 && ph->table_nw[j] != 1) return fail(PVT_ERR_INVALID, "align tables: an emission table must have a single row");
+    }
+    for (int n = 0; n < N; n++)
+        for (int k = 0; k < t->comp_count[n]; k++) {
+            const int c = t->comp_start[n] + k;
+            if (c < 0 || c >= C) return fail(PVT_ERR_INVALID, "component run out of range");
+            const int r = al->comp_align[c];
+            if (r < 0) continue;
+            if (n == t->root_id) return fail(PVT_ERR_INVALID, "align tables: the root node cannot hold an aligned component");
+            if (in.fr && in.fr->n_nodes == N && in.fr->node_field[n] >= 0)
+                return fail(PVT_ERR_INVALID, "align tables: an aligned component in a node with a concentration field is out of scope");
+            const int j = al->emit_table[r];
+            if (j >= 0 && (t->comp_phase_type[c] != PVT_PHASE_TABLE || ph->comp_table[c] != j))
+                return fail(PVT_ERR_INVALID, "align tables: a component's emission table must be the phase table it names");
+        }
+    std::vector<double>& fd = p->fd;
+    if (fd.empty()) fd.assign((size_t)N, -1.0);
+    long long words = (long long)fd.size();
+    for (int n = 0; n < N; n++) words += kFrComp + (long long)t->comp_count[n] * (1 + kAl);
+    if (words > 0x7fffffffLL) return fail(PVT_ERR_INVALID, "align tables: more doubles than int32 offsets can index");
+    for (int n = 0; n < N; n++) {
+        bool holds = false;
+        for (int k = 0; k < t->comp_count[n]; k++) holds = holds || al->comp_align[t->comp_start[n] + k] >= 0;
+        if (!holds) continue;
+        const size_t at = fd.size();
+        fd[(size_t)n] = (double)at;
+        fd.resize(at + kFrComp + (size_t)t->comp_count[n], 0.0);   // (kFrShape stays 0: no lattice)
+        for (int k = 0; k < t->comp_count[n]; k++) {
+            const int r = al->comp_align[t->comp_start[n] + k];
+            if (r < 0) { fd[at + kFrComp + (size_t)k] = -1.0; continue; }
+            const size_t q = fd.size();
+            fd[at + kFrComp + (size_t)k] = (double)q;
+            fd.resize(q + kAl, 0.0);
+            fd[q + kAlOn] = 1.0;
+            for (int a = 0; a < 3; a++) fd[q + kAlAxis + a] = al->axis[r * 3 + a];
+            fd[q + kAlOrder] = al->abs_order[r];
+            fd[q + kAlEmit] = al->emit_table[r] >= 0 ? 1.0 : 0.0;
+        }
+    }
+    p->aligned = true;
     return PVT_OK;
 }
 

@@ -104,6 +104,7 @@ struct PvtScene {
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
     int pd_d = -1;                      // the coating patterns' flags, records and masks: where they start behind the double blob, in its allocation (KArgs::pd_d; -1 = no coating has a pattern or covers any normal)
+    int al_d = -1;                      // >= 0: the scene has aligned components, their records lie in d_fd and its launches run the family's kExtAligned kernels (-1 = no component is aligned)
     long long map_slots = 0;            // int64 slots the maps add behind the recorders' bins (pvt_scene_map_slots)
     long long* d_cd = nullptr;          // ray capture: capacity and first row per recorder (KArgs::cap_tab), null = none captured
     long long capture_rows = 0;         // rows of all captures of one tally set (pvt_scene_capture_rows)
@@ -360,7 +361,7 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
 
 // Which kernel a launch runs: decided once, here.  `family` is what pvt_scene_variant reports; the other members are
 // the template arguments of that family's entry points.
-struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even; };
+struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align; };
 Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit) {
     Variant v{};
     v.record = record; v.emit = emit; v.tab = lp.tab;
@@ -368,9 +369,11 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.mesh = s->d_bvh != nullptr;
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
     // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
-    // photon event counter or of the launch origin, or a truncated cone: the extension family, split as the plain ones
-    const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0;
+    // photon event counter or of the launch origin, a truncated cone or an aligned component: the extension family, split as
+    // the plain ones
+    const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0 || s->al_d >= 0;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
+    v.align = s->al_d >= 0;   // (the extension family's kernels that hold the aligned components' code)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
     return v;
@@ -401,6 +404,12 @@ Kernel kernel_of(const Variant& v) {
         switch (v.family) {
         case PVT_VARIANT_ROUGH:
             if constexpr (has_rough) {
+                if (v.align) {   // (the family's kernels compiled with the aligned components' code)
+                    if constexpr (T == 1) if (v.grid) return trace_kernel_rough_grid<R, W, E, kExtAligned>;
+                    if constexpr (T != 2) if (v.mesh) return trace_kernel_rough<R, T, W, E, true, kExtAligned>;
+                    if (!v.mesh) return trace_kernel_rough_w4<R, T, W, E, kExtAligned>;
+                    break;
+                }
                 if constexpr (T == 1) if (v.grid) return trace_kernel_rough_grid<R, W, E>;
                 if constexpr (T != 2) if (v.mesh) return trace_kernel_rough<R, T, W, E, true>;
                 if (!v.mesh) return trace_kernel_rough_w4<R, T, W, E>;
@@ -759,6 +768,13 @@ int pvt_scene_create_pattern(const PvtSceneTables* t, const PvtIndexTables* x, c
     return create_scene({t, x, ph, rs, fr, mp, cp, ab, pt, kKnowsOrigin}, device, out);
 }
 
+int pvt_scene_create_aligned(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                             const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
+                             const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt,
+                             const PvtAlignTables* al, int device, PvtScene** out) {
+    return create_scene({t, x, ph, rs, fr, mp, cp, ab, pt, kKnowsOrigin, al}, device, out);
+}
+
 }  // extern "C"
 
 namespace {
@@ -775,6 +791,8 @@ int create_scene(const SceneInputs& in, int device, PvtScene** out) {
     int rc = pack_scene(in, &packed);
     if (rc != PVT_OK) return rc;
     rc = pack_patterns(in, &packed);   // (validated before anything is uploaded)
+    if (rc != PVT_OK) return rc;
+    rc = pack_align(in, &packed);      // (likewise)
     if (rc != PVT_OK) return rc;
 
     // owned until every upload has succeeded: a failing HIP call must not leak the scene
@@ -872,6 +890,7 @@ int create_scene(const SceneInputs& in, int device, PvtScene** out) {
         HIP_TRY(hipMemcpy(reinterpret_cast<unsigned char*>(d_pd) + head, packed.pmask.data(), packed.pmask.size(), hipMemcpyHostToDevice));
         s->pd_d = (int)packed.gd.size();
     }
+    if (packed.aligned) s->al_d = 0;   // (their records were placed in packed.fd, uploaded above)
     if (!packed.cd.empty()) {
         HIP_TRY(hipMalloc(&s->d_cd, packed.cd.size() * sizeof(long long)));
         HIP_TRY(hipMemcpy(s->d_cd, packed.cd.data(), packed.cd.size() * sizeof(long long), hipMemcpyHostToDevice));

@@ -263,6 +263,14 @@ struct KArgs {
     int pd_d;
     double* origin_store;
 };
+// Aligned components (PvtAlignTables) live in KArgs::fd: fd[n] of a node that holds one names a record like a lattice's whose
+// kFrShape words are 0 (a lattice has >= 1 cell per axis) and whose kFrComp + k word names, for the node's k-th component,
+// where in fd its record of kAl doubles starts (-1: the component is not aligned): kAlOn != 0, the director in the root's
+// frame, the absorption order S_a, kAlEmit != 0 = the component's phase table is sampled about the director
+// What the extension family's kernels are compiled for (trace_body's ROUGH): kExtOff the other families, kExtRough the
+// family as it is for every scene without alignment, kExtAligned the same with the aligned components' code (UF_ALIGN)
+enum { kExtOff = 0, kExtRough = 1, kExtAligned = 2 };
+enum { kAlOn = 0, kAlAxis = 1, kAlOrder = 4, kAlEmit = 5, kAl = 6 };
 constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): index, position, direction, wavelength, path, clock,
                                // source | recorder << 32, the photon's event counters (kCountBits each)
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
@@ -765,6 +773,56 @@ __device__ __attribute__((noinline)) RoughEvent rough_event_call(double alpha, d
     return e;
 }
 
+// Aligned components (PvtAlignTables; include/pvtrace_hip.h states the rule, the Python Alignment follows the same): the
+// factor f = 1.0 - S (1.5 (mu mu) - 0.5) of the component whose record is `r`, mu = (dx nx + dy ny) + dz nz clamped to
+// [-1, 1] -- these operations in this order (the build has no FMA contraction).
+__device__ __forceinline__ double align_factor(const double* __restrict__ r, double dx, double dy, double dz) {
+    double mu = (dx * r[kAlAxis] + dy * r[kAlAxis + 1]) + dz * r[kAlAxis + 2];
+    mu = __builtin_fmin(__builtin_fmax(mu, -1.0), 1.0);
+    return 1.0 - r[kAlOrder] * (1.5 * (mu * mu) - 0.5);
+}
+// The scaled coefficients of a lane whose container holds an aligned component (`r`: the container's record in fd):
+// sum_k alpha_k(wl) f_k in component order and its first partial sum, for the depth and the component pick.  The
+// coefficients are looked up as the caller looks them up (ci0 / cd0: the records of the node's first component); a
+// component without alignment is not multiplied, and orders of 0 give f = 1.0 exactly, so such a container gets the
+// caller's sums bit for bit.  A FUNCTION, called only from field_march_call, which the trace_kernel_rough* variants call.
+struct AlignScale {
+    double alpha;   // sum_k alpha_k f_k
+    double pre0;    // alpha_0 f_0
+};
+template <int TAB_LDS>
+__device__ __attribute__((noinline)) AlignScale align_scale_call(Tables<TAB_LDS> T, const double* __restrict__ fd, const double* __restrict__ r,
+                                                                 int ci0, int cd0, int ccount, double wl, double dx, double dy, double dz) {
+    double sum = 0.0, p0 = 0.0;
+    for (int k = 0; k < ccount; k++) {
+        const int ci = ci0 + k * CI, cd = cd0 + k * CD;
+        double term = interp_clamped<TAB_LDS>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N), T.iv(ci + CI_ABS_G),
+                                              T.dv(cd + CD_ABS_SCALE), T.iv(ci + CI_ABS_HIST), T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
+        const int at = (int)r[kFrComp + k];
+        if (at >= 0) term = term * align_factor(fd + at, dx, dy, dz);
+        sum += term;
+        if (k == 0) p0 = sum;
+    }
+    return AlignScale{sum, p0};
+}
+// ... the pick's walk beyond two components, in a scene with aligned components (UF_ALIGN): `term` of the k-th component of
+// the container whose record starts at fd + frec times its factor along the photon's direction, or, in a container with
+// a lattice, times the cell's concentration as ever
+__device__ __forceinline__ double align_term(const double* __restrict__ fd, int frec, int k, int fcell, double term, double dx, double dy,
+                                             double dz) {
+    const int at = (int)fd[frec + kFrComp + k];
+    if (fd[frec + kFrShape] != 0.0) return term * fd[at + fcell];
+    return at >= 0 ? term * align_factor(fd + at, dx, dy, dz) : term;
+}
+// ... and the emission: the axis the phase table of the k-th component of that container is sampled about -- its director
+// when its record says so (kAlEmit), else what the caller holds (the incoming direction)
+__device__ __forceinline__ void align_axis(const double* __restrict__ fd, int frec, int k, double& ax, double& ay, double& az) {
+    if (frec < 0 || fd[frec + kFrShape] != 0.0) return;
+    const int at = (int)fd[frec + kFrComp + k];
+    if (at < 0 || fd[at + kAlEmit] == 0.0) return;
+    ax = fd[at + kAlAxis]; ay = fd[at + kAlAxis + 1]; az = fd[at + kAlAxis + 2];
+}
+
 // Concentration fields (PvtFieldTables; include/pvtrace_hip.h states the contract, the Python ConcentrationGrid marches
 // the same way): the free path of a lane whose container carries a lattice (UF_FIELD).  From the photon's position, cell
 // by cell along its direction up to the surface distance t0, the optical depth sum alpha_cell * segment grows until it
@@ -779,11 +837,20 @@ struct FieldMarch {
     double pre0;    // ... the first partial sum of that cell's coefficients ...
     int cell;       // ... and the cell's index into the value tables
 };
-template <int TAB_LDS>
+template <int TAB_LDS, bool ALIGNED>
 __device__ __attribute__((noinline)) FieldMarch field_march_call(Tables<TAB_LDS> T, const double* __restrict__ fd, int frec, int ci0,
                                                                  int cd0, int ccount, double wl, double px, double py, double pz,
                                                                  double dx, double dy, double dz, double tau, double t0) {
     const double* __restrict__ r = fd + frec;
+    if constexpr (ALIGNED) {   // (only the kExtAligned kernels' instantiation: the others call the function as it ever was)
+        if (r[kFrShape] == 0.0) {
+            // (PvtAlignTables) no lattice: a container with an aligned component.  The depth over the scaled sum, +inf when
+            // that is exactly 0 (the general division below 1e-250, as in the march: a factor near its zero makes tiny sums)
+            const AlignScale as = align_scale_call<TAB_LDS>(T, fd, r, ci0, cd0, ccount, wl, dx, dy, dz);
+            const double d = as.alpha == 0.0 ? INFINITY : (as.alpha > 1e-250 ? div_normal(tau, as.alpha) : tau / as.alpha);
+            return FieldMarch{d, as.alpha, as.pre0, 0};
+        }
+    }
     auto coef = [&](int k) -> double {
         const int ci = ci0 + k * CI, cd = cd0 + k * CD;
         return interp_clamped<TAB_LDS>(T, wl, T.iv(ci + CI_ABS_X), T.iv(ci + CI_ABS_Y), T.iv(ci + CI_ABS_N), T.iv(ci + CI_ABS_G),
@@ -1243,7 +1310,7 @@ struct Seen {
 // GRID: scenes of many nodes -- every lane finds the nodes its ray can cross through a uniform grid (see the node loop).
 // TAIL: the same loop as a FUNCTION for the last wave of a draining workgroup (`tail_run`, below): no rays to claim, no
 // rendezvous -- it takes the `tail_total` photons its caller left in the exchange buffer and steps them until none is left.
-template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH = false, int LEAN = 0>
+template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, int ROUGH = 0, int LEAN = 0>
 __device__ void tail_run(const KArgs* kernel_args, int total, unsigned int lds);
 
 // A wave leaves its workgroup: the LAST one to do so adds the workgroup's accumulators (LDS) to the launch's outputs -- one
@@ -1314,7 +1381,7 @@ __device__ __attribute__((noinline)) void leave_workgroup(const KArgs* kernel_ar
         }
 }
 
-template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, bool ROUGH = false,
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, int ROUGH = 0,
           int LEAN = 0>
 __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, unsigned int tail_lds = 0u) {
     // LEAN (the trace_kernel_lean family): the scene is of the plain kind the host proves at its creation (pvt_scene_pack.h:
@@ -1355,7 +1422,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT, UF_ALIGN };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1369,14 +1436,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.cabs_d >= 0 ? 1u << UF_CABS : 0u) |   // ... and cabs_d ...
         (ROUGH && A.count >= 1 ? 1u << UF_COUNT : 0u) | (ROUGH && A.count >= 2 ? 1u << UF_TQ_COUNT : 0u) |   // ... and count ...
         (ROUGH && A.origin != 0 ? 1u << UF_ORIGIN : 0u) |   // ... and origin ...
-        (ROUGH && A.pd_d >= 0 ? 1u << UF_CPAT : 0u);   // ... and pd_d)
+        (ROUGH && A.pd_d >= 0 ? 1u << UF_CPAT : 0u) |   // ... and pd_d ...
+        (ROUGH == kExtAligned ? 1u << UF_ALIGN : 0u);   // ... UF_ALIGN is the kernel's own: compiled in, not read)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT || bit == UF_ALIGN) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -2838,7 +2906,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const double tau = -pvt_log(1.0 - rng_uniform(rng));
                     if (uf(UF_FIELD)) frec = (int)A.fd[container];
                     if (frec >= 0) {
-                        const FieldMarch fm = field_march_call<TAB_LDS>(T, A.fd, frec, L.comp_i + crec * CI, L.comp_d + crec * CD, ccount,
+                        const FieldMarch fm = field_march_call<TAB_LDS, ROUGH == kExtAligned>(T, A.fd, frec, L.comp_i + crec * CI, L.comp_d + crec * CD, ccount,
                                                                         wl, pos.x, pos.y, pos.z, dir.x, dir.y, dir.z, tau, t0);
                         depth = fm.depth;
                         if (fm.depth < t0) { alpha = fm.alpha; pre0 = fm.pre0; fcell = fm.cell; }
@@ -2891,7 +2959,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                                                                   T.iv(ci + CI_ABS_G), T.dv(cd + CD_ABS_SCALE), T.iv(ci + CI_ABS_HIST),
                                                                   T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
                             if constexpr (ROUGH) {   // (a lattice: the cell's concentration of the component)
-                                if (frec >= 0) term = term * A.fd[(int)A.fd[frec + kFrComp + k] + fcell];
+                                if (frec >= 0) {   // (... or, PvtAlignTables, the component's factor along the photon's direction)
+                                    if constexpr (ROUGH == kExtAligned) term = align_term(A.fd, frec, k, fcell, term, dir.x, dir.y, dir.z);
+                                    else term = term * A.fd[(int)A.fd[frec + kFrComp + k] + fcell];
+                                }
                             }
                             running += term;
                             if (target <= running) { comp = cbase + k; break; }
@@ -3022,8 +3093,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         u3 = g2;
                     }
                     if (tabled) {   // about the incoming direction (PvtPhaseTables)
-                        if constexpr (MESH || SEENW == 1) dir = phase_table_turn_call(ptab, wl, u1, em_turn, u3, dir.x, dir.y, dir.z);
-                        else dir = phase_table_turn(ptab, wl, u1, em_turn, u3, dir.x, dir.y, dir.z);
+                        if constexpr (ROUGH == kExtAligned) {   // ... or about the director of an aligned emitter (PvtAlignTables)
+                            double ax = dir.x, ay = dir.y, az = dir.z;
+                            align_axis(A.fd, frec, cu - cbase, ax, ay, az);
+                            if constexpr (MESH || SEENW == 1) dir = phase_table_turn_call(ptab, wl, u1, em_turn, u3, ax, ay, az);
+                            else dir = phase_table_turn(ptab, wl, u1, em_turn, u3, ax, ay, az);
+                        } else {
+                            if constexpr (MESH || SEENW == 1) dir = phase_table_turn_call(ptab, wl, u1, em_turn, u3, dir.x, dir.y, dir.z);
+                            else dir = phase_table_turn(ptab, wl, u1, em_turn, u3, dir.x, dir.y, dir.z);
+                        }
                     } else {
                         double sp, cp;
                         pvt_sincos2pi(em_turn, &sp, &cp);
@@ -3609,7 +3687,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
 // The last wave of a draining workgroup finishes its photons here (see the drain in trace_body): the step loop alone, as a
 // function -- the kernels' own loop keeps its registers whatever this one needs, and what is specific to a wave that runs
 // alone on its SIMD (every step is latency, nothing overlaps) can be done here without a price on the bulk.
-template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, bool ROUGH, int LEAN>
+template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, int ROUGH, int LEAN>
 __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int total, unsigned int lds) {
     // The kernel's arguments, read where the kernel itself reads them.  The pointer arrives in vector registers: it is made
     // a scalar again (readfirstlane) and a pointer into the constant address space, so that the fields come through the
@@ -3646,17 +3724,17 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 // smooth variants keep their registers, spills and text bit for bit.  (A call of
 // the sampler from the smooth loop spilled 20-30 vector registers of every variant: the surface branch holds more values
 // than the callee-saved registers take.)
-template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH>
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, int EXT = kExtRough>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMeshWaves, kMeshWaves))) trace_kernel_rough(KArgs A) {
-    trace_body<RECORD, TAB_LDS, SEENW, EMIT, MESH, false, false, true>(A);
+    trace_body<RECORD, TAB_LDS, SEENW, EMIT, MESH, false, false, EXT>(A);
 }
-template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT>
+template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, int EXT = kExtRough>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_rough_w4(KArgs A) {
-    trace_body<RECORD, TAB_LDS, SEENW, EMIT, false, false, false, true>(A);
+    trace_body<RECORD, TAB_LDS, SEENW, EMIT, false, false, false, EXT>(A);
 }
-template <bool RECORD, int SEENW, bool EMIT>
+template <bool RECORD, int SEENW, bool EMIT, int EXT = kExtRough>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_rough_grid(KArgs A) {
-    trace_body<RECORD, 1, SEENW, EMIT, false, true, false, true>(A);
+    trace_body<RECORD, 1, SEENW, EMIT, false, true, false, EXT>(A);
 }
 // The lean family (trace_body's LEAN): scenes the host has proven plain -- see prove_lean.  Tables in LDS, at most 64
 // recorders, no mesh, no node grid, no rough / field / map extension.

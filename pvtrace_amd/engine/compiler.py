@@ -38,6 +38,7 @@ from pvtrace_amd.engine.recorder import (
 from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Sphere
 from pvtrace_amd.material import (
     Absorber,
+    Alignment,
     CoatedSurfaceDelegate,
     Coating,
     CoatingPattern,
@@ -167,6 +168,11 @@ class CompiledScene:
         }
         coat_rows = []
         self.component_names = []
+        # Aligned components (Alignment): comp_align names a component's alignment record (-1: none); a record holds the
+        # director in the ROOT's frame (align_axis, a unit vector), the absorption order and the single-row phase table of
+        # f(mu; S_e) the emission samples about that axis (align_emit_table: its id among the phase tables, -1 = S_e is 0).
+        # One record per (Alignment object, node).  Passed to the library as PvtAlignTables, only by scenes that use them.
+        align = {"index": {}, "comp": [], "axis": [], "abs_order": [], "emit_table": []}
 
         for i, node in enumerate(nodes):
             geometry = node.geometry
@@ -186,11 +192,19 @@ class CompiledScene:
             self.coat_count[i] = len(coat_rows) - self.coat_start[i]
 
             self.comp_start[i] = len(comp_cols["type"])
+            self._check_alignment(node, material, node is root)
             for component in material.components:
                 self._lower_component(node, component, comp_cols, pools)
                 self.component_names.append(component.name)
+                align["comp"].append(self._lower_alignment(i, node, component, comp_cols, align))
             self.comp_count[i] = len(material.components)
             self.node_field[i] = self._lower_fields(node, material, node is root, fields)
+
+        self.comp_align = np.array(align["comp"], dtype=_I32)
+        self.n_align = len(align["abs_order"])
+        self.align_axis = np.array(align["axis"], dtype=_F64).reshape(-1, 3)
+        self.align_abs_order = np.array(align["abs_order"], dtype=_F64)
+        self.align_emit_table = np.array(align["emit_table"], dtype=_I32)
 
         self.n_fields = len(fields["shape"])
         self.field_shape = np.array(fields["shape"], dtype=_I32).reshape(-1, 3)
@@ -539,9 +553,63 @@ class CompiledScene:
             ctab["value"].extend(table._grid.ravel().tolist())
         return ctab["index"][key][0]
 
-    def _pool_phase_table(self, table):
+    @staticmethod
+    def _check_alignment(node, material, is_root):
+        components = list(material.components)
+        aligned = [c for c in components if getattr(c, "alignment", None) is not None]
+        if not aligned:
+            return
+        if is_root:
+            raise UnsupportedSceneError(
+                f"Root node {node.name!r}: the scene's root cannot carry an aligned component (Alignment).")
+        if any(getattr(c, "concentration", None) is not None for c in components):
+            raise UnsupportedSceneError(
+                f"Node {node.name!r}: alignment together with a concentration field (ConcentrationGrid) on a component of "
+                "the same material is out of scope: the march would need the factors.")
+        for c in aligned:
+            a = c.alignment
+            if not isinstance(a, Alignment):
+                raise UnsupportedSceneError(f"Node {node.name!r}: alignment must be an Alignment, got {type(a).__name__}.")
+            if a.emission_order != 0.0 and not isinstance(c, Luminophore):
+                raise UnsupportedSceneError(
+                    f"Node {node.name!r}: component {c.name!r} has emission_order != 0, which applies to a Luminophore only.")
+            if a.emission_order != 0.0 and c.phase_function is not isotropic:
+                raise UnsupportedSceneError(
+                    f"Node {node.name!r}: component {c.name!r} has emission_order != 0 together with a phase function.")
+
+    def _lower_alignment(self, i, node, component, cols, align):
+        """Id of the component's alignment record (-1: none).  The director goes ONCE to the root's frame: with the rows
+        R0, R1, R2 of the node's rotation to the root, n_w,i = (Ri,0 nx + Ri,1 ny) + Ri,2 nz, then divided by
+        sqrt((x x + y y) + z z) of the result (rule 1 of the `Alignment` docstring).  An emission order != 0 turns the
+        component's phase function into the pooled single-row table of f(mu; S_e), one table per order."""
+        a = getattr(component, "alignment", None)
+        if a is None:
+            return -1
+        if a.emission_order != 0.0:   # (the column `_lower_component` has just written: isotropic)
+            cols["phase_type"][-1] = PHASE_TABLE
+            cols["phase_table"][-1] = self._pool_phase_table(a.emission_table, key=("aligned", float(a.emission_order)))
+        key = (id(a), i)
+        if key not in align["index"]:
+            rot = self.local_to_world[i][:3, :3]
+            nx, ny, nz = (float(v) for v in a.director)
+            w = [(float(rot[r, 0]) * nx + float(rot[r, 1]) * ny) + float(rot[r, 2]) * nz for r in range(3)]
+            norm = math.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+            if not (math.isfinite(norm) and norm > 0.0):
+                raise UnsupportedSceneError(f"Node {node.name!r}: the director of component {component.name!r} has no direction in the root's frame.")
+            align["index"][key] = (len(align["abs_order"]), a)   # (the object keeps its id from being reused)
+            align["axis"].append([v / norm for v in w])
+            align["abs_order"].append(float(a.absorption_order))
+            align["emit_table"].append(int(cols["phase_table"][-1]) if a.emission_order != 0.0 else -1)
+        return align["index"][key][0]
+
+    @property
+    def has_alignment(self):
+        """A component carries an `Alignment`: the scene needs pvt_scene_create_aligned's tables."""
+        return bool(np.any(self.comp_align >= 0))
+
+    def _pool_phase_table(self, table, key=None):
         ptab = self._ptab
-        key = id(table)
+        key = id(table) if key is None else key
         if key not in ptab["index"]:
             ptab["index"][key] = (len(ptab["nw"]), table)   # (the table itself keeps its id from being reused)
             nw, nmu = table.cdf.shape
@@ -851,12 +919,12 @@ class CompiledScene:
 
     # The tables of the later extensions are part of `tables()` only when the scene has the extension, so that a scene
     # without it lowers to the same tables, key for key, as before there was one: the volume maps', the captures', the
-    # absorbing coatings' (a coating has an absorptivity) and the coating patterns' (a coating has a pattern or
-    # facet=None).  Which attributes they are is what the binding reads for the extension's struct.
-    MAP_TABLE_FIELDS, CAPTURE_TABLE_FIELDS, ABSORB_TABLE_FIELDS, PATTERN_TABLE_FIELDS = (
+    # absorbing coatings' (a coating has an absorptivity), the coating patterns' (a coating has a pattern or
+    # facet=None) and the alignments' (a component has an Alignment).  Which attributes they are is what the binding reads for the extension's struct.
+    MAP_TABLE_FIELDS, CAPTURE_TABLE_FIELDS, ABSORB_TABLE_FIELDS, PATTERN_TABLE_FIELDS, ALIGN_TABLE_FIELDS = (
         tuple(attribute for attribute, _ in struct_type.POINTERS.values())
         for struct_type in (native.PvtMapTables, native.PvtCaptureTables, native.PvtCoatingAbsorbTables,
-                            native.PvtCoatingPatternTables))
+                            native.PvtCoatingPatternTables, native.PvtAlignTables))
 
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""
@@ -873,6 +941,8 @@ class CompiledScene:
             out.update({name: getattr(self, name) for name in self.ABSORB_TABLE_FIELDS})
         if self.has_coating_patterns:
             out.update({name: getattr(self, name) for name in self.PATTERN_TABLE_FIELDS})
+        if self.has_alignment:
+            out.update({name: getattr(self, name) for name in self.ALIGN_TABLE_FIELDS})
         return out
 
     @property

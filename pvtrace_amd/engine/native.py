@@ -222,13 +222,27 @@ class PvtCoatingPatternTables(C.Structure):
     ABSENT = staticmethod(lambda c: not getattr(c, "has_coating_patterns", False))
 
 
+class PvtAlignTables(C.Structure):
+    """Aligned components of a scene: directors in the root's frame, absorption orders and emission tables
+    (include/pvtrace_hip.h; pvt_scene_create_aligned); absent when no component has an `Alignment`."""
+    _fields_ = [
+        ("n_components", C.c_int32), ("n_records", C.c_int32),
+        ("comp_align", _p_i32), ("axis", _p_f64), ("abs_order", _p_f64), ("emit_table", _p_i32),
+    ]
+    POINTERS = {"comp_align": ("comp_align", np.int32), "axis": ("align_axis", np.float64),
+                "abs_order": ("align_abs_order", np.float64), "emit_table": ("align_emit_table", np.int32)}
+    COUNTS = {"n_components": lambda c: len(c.comp_align), "n_records": lambda c: c.n_align}
+    ABSENT = staticmethod(lambda c: not getattr(c, "has_alignment", False))
+
+
 # the extension structs, in the order the pvt_scene_create* entries take them behind the scene tables (each entry takes the
 # first so many of them: CREATION_ENTRIES)
 EXTENSION_TABLES = (PvtIndexTables, PvtPhaseTables, PvtSurfaceTables, PvtFieldTables, PvtMapTables, PvtCaptureTables,
-                    PvtCoatingAbsorbTables, PvtCoatingPatternTables)
+                    PvtCoatingAbsorbTables, PvtCoatingPatternTables, PvtAlignTables)
 CREATION_ENTRIES = {"pvt_scene_create": 0, "pvt_scene_create_ex": 1, "pvt_scene_create_phase": 2, "pvt_scene_create_rough": 3,
                     "pvt_scene_create_field": 4, "pvt_scene_create_maps": 5, "pvt_scene_create_capture": 6,
-                    "pvt_scene_create_absorb": 7, "pvt_scene_create_origin": 7, "pvt_scene_create_pattern": 8}
+                    "pvt_scene_create_absorb": 7, "pvt_scene_create_origin": 7, "pvt_scene_create_pattern": 8,
+                    "pvt_scene_create_aligned": 9}
 LEAN_CHECK_TABLES = 5   # pvt_scene_lean_check takes the first five
 
 
@@ -491,7 +505,7 @@ ABI_SYMBOLS = (
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
-    "pvt_scene_create_origin", "pvt_scene_create_pattern",
+    "pvt_scene_create_origin", "pvt_scene_create_pattern", "pvt_scene_create_aligned",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 
@@ -661,8 +675,8 @@ class DeviceScene:
         others, alive = extension_tables(compiled)
         handle = C.c_void_p()
         # (the newest entry, the only one Python ever calls: the older ones do the same with NULL for the structs they lack)
-        check(self.lib.pvt_scene_create_pattern(C.byref(st), *others, self.device, C.byref(handle)),
-              "pvt_scene_create_pattern")
+        check(self.lib.pvt_scene_create_aligned(C.byref(st), *others, self.device, C.byref(handle)),
+              "pvt_scene_create_aligned")
         del keep, alive
         self.handle = handle
         self.has_emitter = False

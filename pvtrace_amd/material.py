@@ -751,6 +751,134 @@ class PhaseFunctionTable(object):
         return self.turn(np.array([0.0, 0.0, 1.0]), mu, u[:, k - 1])
 
 
+ALIGN_TABLE_NODES = 513   # mu nodes of an aligned luminophore's emission table, uniformly spaced from exactly -1 to exactly 1
+
+
+class Alignment(object):
+    """Uniaxial alignment of a component's transition dipoles: dichroic absorption, dipole emission (extension; the
+    reference has no such component).
+
+    director : non-zero 3-vector n in the frame of the node that holds the material; normalised on construction.
+    absorption_order, emission_order : the order parameters S = <P2> of the absorption and of the emission dipoles about
+        the director, finite and in [-0.5, 1].  0 is the isotropic component, exactly as before; 1 the pure dipole along
+        n; -0.5 dipoles in the plane perpendicular to n.
+
+    No polarisation is tracked: both laws are the average over unpolarised light, so the polarisation memory between a
+    dipole emission and the next absorption is ignored.  With mu = d . n, the absorption of unpolarised light travelling
+    along d and the emission density along d have the same form,
+
+        f(mu; S) = 1 - S P2(mu),   P2(mu) = 1.5 mu^2 - 0.5,   f >= 0,   integral of f / 2 over mu = 1,
+
+    `Alignment.factor(mu, order)`.  The absorption rule, the same on the host and on the device (include/pvtrace_hip.h,
+    PvtAlignTables, states the same):
+
+    1. The flattener lowers each aligned component's director ONCE to the scene root's frame as a unit vector n_w: with
+       the rows R0, R1, R2 of the node's rotation to the root, n_w,i = (Ri,0 nx + Ri,1 ny) + Ri,2 nz, then divided by
+       sqrt((x x + y y) + z z) of the result, without FMA.
+    2. At the free-path site mu_k = (dx nx + dy ny) + dz nz, without FMA, clamped to [-1, 1].
+    3. f_k = 1.0 - S_k (1.5 (mu_k mu_k) - 0.5), exactly these operations in this order.
+    4. A component without alignment has f_k = 1 and is not multiplied.
+    5. The depth draw happens where and when an unaligned container draws, on the UNSCALED sum of alpha_k(lambda) (the
+       decision of the concentration fields): S = 1 along the director does not change who draws.
+    6. tau* = -ln(1 - u); the depth is tau* / sum_k alpha_k f_k.
+    7. The depth is +inf when the scaled sum is exactly 0.
+    8. The component is picked by the unaligned walk over alpha_k f_k, the two-component shortcut on the first partial
+       sum included.
+    9. Cached sums of coefficients (the device's tail function) are unscaled ones; the scaled sum is formed per step.
+
+    The emission rule: a `Luminophore` with emission_order S_e != 0 emits about n_w, not about +z and not about the ray.
+    f(mu; S_e) is tabulated on `ALIGN_TABLE_NODES` uniform mu nodes as ONE single-row `PhaseFunctionTable` and sampled
+    by its rule (steps 3 and 4 there) with the director as the axis: no u1, and the two isotropic draw sites serve as u2
+    and u3, so an aligned emission consumes exactly the draws an isotropic one does and the wavelength and delay draws
+    follow unchanged.  S_e = 0 is the isotropic phase function, with no table.
+
+    `absorption_order` applies to `Scatterer`, `Absorber`, `Reactor` and `Luminophore`; `emission_order != 0` to
+    `Luminophore` only, and not together with an explicit `phase_function`.  Alignment and a `ConcentrationGrid` in one
+    material, alignment on the scene's root, the host-buffer `trace_bundle` and the older `pvt_scene_create_*` entries
+    are refused.
+    """
+
+    def __init__(self, director, absorption_order=0.0, emission_order=0.0):
+        try:
+            n = np.array(director, dtype=np.float64)
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"Alignment: director must be a 3-vector ({exc})") from None
+        if n.shape != (3,) or not np.all(np.isfinite(n)):
+            raise ValueError("Alignment: director must be a finite 3-vector")
+        norm = math.sqrt(float((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]))
+        if not norm > 0.0:
+            raise ValueError("Alignment: director must not be the zero vector")
+        self.director = tuple(float(v) / norm for v in n)
+        self.absorption_order = self._order(absorption_order, "absorption_order")
+        self.emission_order = self._order(emission_order, "emission_order")
+        self._table = None
+
+    @staticmethod
+    def _order(value, what):
+        try:
+            s = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"Alignment: {what} must be a number, got {value!r}") from None
+        if not math.isfinite(s):
+            raise ValueError(f"Alignment: {what} must be finite, got {value!r}")
+        if not -0.5 <= s <= 1.0:
+            raise ValueError(f"Alignment: {what} must lie in [-0.5, 1], got {value!r}")
+        return s
+
+    @staticmethod
+    def factor(mu, order):
+        """f(mu; S) = 1.0 - S (1.5 (mu mu) - 0.5), in exactly this operation order (scalars or arrays)."""
+        return 1.0 - order * (1.5 * (mu * mu) - 0.5)
+
+    @staticmethod
+    def cosine(direction, axis):
+        """mu = (dx nx + dy ny) + dz nz clamped to [-1, 1]: step 2 of the absorption rule."""
+        mu = (float(direction[0]) * float(axis[0]) + float(direction[1]) * float(axis[1])) + float(direction[2]) * float(axis[2])
+        return min(max(mu, -1.0), 1.0)
+
+    @property
+    def emission_table(self):
+        """The single-row `PhaseFunctionTable` of f(mu; emission_order) on `ALIGN_TABLE_NODES` uniform mu nodes (None
+        when emission_order is 0); built once per object, so components that share an `Alignment` share the table."""
+        if self.emission_order == 0.0:
+            return None
+        if self._table is None:
+            k = np.arange(ALIGN_TABLE_NODES, dtype=np.float64)
+            mu = -1.0 + k * (2.0 / (ALIGN_TABLE_NODES - 1))
+            mu[0], mu[-1] = -1.0, 1.0
+            table = PhaseFunctionTable.__new__(PhaseFunctionTable)
+            values = np.maximum(self.factor(mu, self.emission_order), 0.0)
+            cdf = np.cumsum(0.5 * (values[:-1] + values[1:]) * np.diff(mu))
+            cdf = np.hstack([0.0, cdf / cdf[-1]])
+            cdf[-1] = 1.0
+            table.angle = np.degrees(np.arccos(mu))[::-1].copy()
+            table.values = values[::-1].copy()
+            table.wavelength = None
+            table.mu = mu
+            table.cdf = cdf[None, :]
+            self._table = table
+        return self._table
+
+    def emit_direction(self, u2, u3, axis=None):
+        """The emitted direction for the draws u2, u3 about `axis` (default: the director): the table's steps 3 and 4."""
+        table = self.emission_table
+        n = np.asarray(self.director if axis is None else axis, dtype=np.float64)
+        return table.turn(n, table.sample_mu(u2), u3)
+
+
+def _check_alignment(alignment, emitting, phase_function, what):
+    if alignment is None:
+        return None
+    if not isinstance(alignment, Alignment):
+        raise ValueError(f"alignment: expected None or an Alignment, got {type(alignment).__name__}")
+    if alignment.emission_order != 0.0:
+        if not emitting:
+            raise ValueError(f"{what}: emission_order != 0 applies to a Luminophore only")
+        if phase_function is not None:
+            raise ValueError(f"{what}: emission_order != 0 cannot be combined with an explicit phase_function")
+    return alignment
+
+
 def phase_direction(phase_function, ray):
     """A scattered or re-emitted direction: a `PhaseFunctionTable` draws about the ray's own direction at its
     wavelength, the built-ins (and user callables) are called with no arguments, about +z."""
@@ -1257,6 +1385,7 @@ class Component:
     def __init__(self, name="Component"):
         self.name = name
         self.concentration = None
+        self.alignment = None
 
     def concentration_at(self, cell):
         """Relative concentration in lattice cell `cell` (1 without a field)."""
@@ -1274,8 +1403,9 @@ class Scatterer(Component):
     """Scattering centre with attenuation coefficient (cm^-1), constant or spectral."""
 
     def __init__(self, coefficient, x=None, quantum_yield=1.0, tau_rad=None, tau_nr=None, phase_function=None,
-                 hist=False, name="Scatterer", concentration=None):
+                 hist=False, name="Scatterer", concentration=None, alignment=None):
         super().__init__(name=name)
+        self.alignment = _check_alignment(alignment, isinstance(self, Luminophore), phase_function, type(self).__name__)
         if concentration is not None and not isinstance(concentration, ConcentrationGrid):
             raise ValueError(f"concentration: expected None or a ConcentrationGrid, got {type(concentration).__name__}")
         self.concentration = concentration
@@ -1315,9 +1445,9 @@ class Scatterer(Component):
 class Absorber(Scatterer):
     """Non-radiative absorber (quantum yield 0)."""
 
-    def __init__(self, coefficient, x=None, tau_nr=None, name="Absorber", hist=False, concentration=None):
+    def __init__(self, coefficient, x=None, tau_nr=None, name="Absorber", hist=False, concentration=None, alignment=None):
         super().__init__(coefficient, x=x, quantum_yield=0.0, tau_rad=0.0, tau_nr=tau_nr, hist=hist, name=name,
-                         concentration=concentration)
+                         concentration=concentration, alignment=alignment)
 
     def is_radiative(self, ray):
         return False   # (and no draw, as in the reference, component.py:236-239)
@@ -1326,17 +1456,18 @@ class Absorber(Scatterer):
 class Reactor(Absorber):
     """Absorber whose absorptions are tallied as photochemical reactions."""
 
-    def __init__(self, coefficient, x=None, name="Reactor", hist=False, concentration=None):
-        super().__init__(coefficient, x=x, hist=hist, name=name, concentration=concentration)
+    def __init__(self, coefficient, x=None, name="Reactor", hist=False, concentration=None, alignment=None):
+        super().__init__(coefficient, x=x, hist=hist, name=name, concentration=concentration, alignment=alignment)
 
 
 class Luminophore(Scatterer):
     """Absorbs and re-emits with a new wavelength drawn from `emission`."""
 
     def __init__(self, coefficient, emission=None, x=None, hist=False, quantum_yield=1.0, tau_rad=None, tau_nr=None,
-                 phase_function=None, name="Luminophore", concentration=None):
+                 phase_function=None, name="Luminophore", concentration=None, alignment=None):
         super().__init__(coefficient, x=x, quantum_yield=quantum_yield, tau_rad=tau_rad, tau_nr=tau_nr,
-                         phase_function=phase_function, hist=hist, name=name, concentration=concentration)
+                         phase_function=phase_function, hist=hist, name=name, concentration=concentration,
+                         alignment=alignment)
         self._emission = emission
         if emission is None:   # the reference's default line: a Gaussian at 600 nm, 40 nm wide (component.py:330-335)
             emission = [lambda v: gaussian(v, 1.0, 600.0, 40.0)]
@@ -1348,9 +1479,19 @@ class Luminophore(Scatterer):
         """Re-emitted (reference component.py:381-440; draws in its order: phase function, wavelength, delay): a new
         direction, a wavelength from the emission spectrum above the point `method` allows -- "kT": from 3/2 kT (at `T` K)
         above the absorbed photon's energy, "redshift": from the absorbed wavelength, "full": the whole spectrum -- and,
-        with `tau_rad` set, an exponentially distributed emission delay.  Like the reference's it raises when "kT" lands
+        with `tau_rad` set, an exponentially distributed emission delay.  An aligned emitter (`Alignment` with an emission
+        order) emits about its director AS GIVEN, in the frame of the node that holds the material: `ray` must be in that
+        frame, as `photon_tracer` passes it (a caller holding a ray of another frame turns the director itself and calls
+        `alignment.emit_direction(u2, u3, axis=...)`).  Like the reference's it raises when "kT" lands
         outside the spectrum's range; the engine clamps there (differences between the two tracers)."""
-        direction = phase_direction(self.phase_function, ray)
+        alignment = getattr(self, "alignment", None)
+        if alignment is not None and alignment.emission_order != 0.0:
+            # (an aligned emitter: the table's u2, u3 about the director, which is given in the frame the ray is in)
+            u2 = np.random.uniform()
+            u3 = np.random.uniform()
+            direction = alignment.emit_direction(u2, u3)
+        else:
+            direction = phase_direction(self.phase_function, ray)
         nm = ray.wavelength
         if method == "kT":
             nm = 1240.0 / (1240.0 / nm + 3 / 2 * KB_EV * T)
@@ -1444,6 +1585,58 @@ class Material(object):
     def component_at(self, wavelength, cell):
         """Which component took the photon in lattice cell `cell`: `component`'s draw and rule over alpha_k c_k[cell]."""
         weights = np.array(self.cell_coefficients(wavelength, cell))
+        if np.any(weights < 0.0):
+            raise ValueError("Must be positive.")
+        steps = np.cumsum(weights)
+        ladder = np.hstack([0, steps / max(steps)])
+        at = np.interp(np.random.uniform(), ladder, list(range(len(self.components) + 1)))
+        return self.components[int(np.floor(at))]
+
+    # Aligned components (`Alignment`): the same decisions with every coefficient scaled by its component's factor
+    # f(mu_k; S_k), asked with the ray's direction in the frame of the node that holds this material (the frame the
+    # directors are in).  Only a container with an aligned component takes these.
+    @property
+    def has_alignment(self):
+        return any(getattr(c, "alignment", None) is not None for c in self.components)
+
+    def alignment_factors(self, direction):
+        """f_k of every component for a ray travelling along `direction` (1.0 for a component without alignment)."""
+        out = []
+        for c in self.components:
+            a = getattr(c, "alignment", None)
+            out.append(1.0 if a is None else float(Alignment.factor(Alignment.cosine(direction, a.director), a.absorption_order)))
+        return out
+
+    def aligned_coefficients(self, wavelength, direction):
+        """alpha_k(wavelength) f_k of every component, in component order."""
+        return [c.coefficient(wavelength) * f for c, f in zip(self.components, self.alignment_factors(direction))]
+
+    def total_attenutation_coefficient_along(self, wavelength, direction):
+        total = 0.0
+        for term in self.aligned_coefficients(wavelength, direction):
+            total = total + float(term)
+        return total
+
+    def penetration_depth_along(self, wavelength, direction):
+        """`penetration_depth` for a ray along `direction`: the draw is decided on the UNSCALED sum as there, the depth
+        is tau* over the scaled sum, inf when that is exactly 0."""
+        alpha = self.total_attenutation_coefficient(wavelength)
+        if np.isclose(alpha, 0.0):
+            return float("inf")
+        if not np.isfinite(alpha):
+            return 0.0
+        tau = -np.log(1 - np.random.uniform())
+        scaled = self.total_attenutation_coefficient_along(wavelength, direction)
+        return float("inf") if scaled == 0.0 else tau / scaled
+
+    def is_absorbed_along(self, local_ray, full_distance):
+        """(absorbed before `full_distance`?, the sampled depth), the ray given in this material's node frame."""
+        depth = self.penetration_depth_along(local_ray.wavelength, local_ray.direction)
+        return (depth < full_distance, depth)
+
+    def component_along(self, wavelength, direction):
+        """Which component took the photon: `component`'s draw and rule over alpha_k f_k."""
+        weights = np.array(self.aligned_coefficients(wavelength, direction))
         if np.any(weights < 0.0):
             raise ValueError("Must be positive.")
         steps = np.cumsum(weights)
