@@ -308,10 +308,21 @@ def pick_row(wavelengths, wl, u1):
     return (k + 1 if F(float(u1)) < t else k), t, ((k, k + 1) if t > 0 else None), (F(0) if exact else 3 * F(1, 2 ** 53) * t)
 
 
+_ROW_FRACTIONS = {}
+
+
+def _row_fractions(cdf_row):
+    """The exact values of a CDF row's doubles, converted once per row (keyed by the row's bytes)."""
+    key = np.ascontiguousarray(cdf_row, dtype=np.float64).tobytes()
+    if key not in _ROW_FRACTIONS:
+        _ROW_FRACTIONS[key] = [F(float(c)) for c in cdf_row]
+    return _ROW_FRACTIONS[key]
+
+
 def invert_cdf(mu_axis, cdf_row, u2):
     """Item 3 on exact rationals -> (segment j, mu): the first segment with C_j+1 > u2, by a linear scan."""
     u2 = F(float(u2))
-    cs = [F(float(c)) for c in cdf_row]
+    cs = _row_fractions(cdf_row)
     j = next(i for i in range(len(cs) - 1) if cs[i + 1] > u2)
     a, b = F(float(mu_axis[j])), F(float(mu_axis[j + 1]))
     mu = a + (u2 - cs[j]) / (cs[j + 1] - cs[j]) * (b - a)
@@ -352,6 +363,34 @@ def exact_phase_turn(table, wl, d, u1, u2, u3, trig=TRIG_KERNEL):
     out.segment, out.mu, out.direction, out.bound = out.rows[out.row]
     out.ambiguous = len(candidates) > 1
     return out
+
+
+def check_cdf_rows(table, who):
+    """Item 1 of the PvtPhaseTables contract on a compiled table, in exact rationals: each row is the trapezoid integral
+    of p in mu with a leading 0, divided by its last entry.  The host forms each term 0.5 (p_j + p_j+1)(mu_j+1 - mu_j)
+    with three roundings (the half is exact), sums j + 1 of them in order (numpy's cumsum along a row), and divides by
+    the total, itself a sum of n - 1 terms: entry j is within (3 + j + 3 + (n - 1) + 1) U = (n + j + 6) U of the exact
+    quotient, relatively (all terms are >= 0).  Returns the worst |C_j - exact| / (U exact)."""
+    mu = [F(float(m)) for m in table.mu]
+    assert mu[0] == -1 and mu[-1] == 1 and all(a < b for a, b in zip(mu, mu[1:]))
+    n = len(mu)
+    values = np.atleast_2d(table.values)
+    worst = 0.0
+    for row in range(len(table.cdf)):
+        p = [F(float(v)) for v in values[row][::-1]]
+        exact, running = [F(0)], F(0)
+        for j in range(n - 1):
+            running += (p[j] + p[j + 1]) / 2 * (mu[j + 1] - mu[j])
+            exact.append(running)
+        got = [F(float(c)) for c in table.cdf[row]]
+        assert got[0] == 0 and got[-1] == 1 and all(a <= b for a, b in zip(got, got[1:]))
+        for j in range(1, n):
+            want = exact[j] / exact[-1]
+            err = abs(got[j] - want)
+            assert err <= (n + j + 6) * F(1, 2 ** 53) * want, (who, row, j, float(err / want) * 2 ** 53)
+            if want:
+                worst = max(worst, float(err / want) * 2 ** 53)
+    return worst
 
 
 # ---- judging a case -------------------------------------------------------------------------------------------------------

@@ -104,25 +104,8 @@ def test_the_compiled_cdf_rows_are_the_trapezoid_integral_of_the_contract(key):
     order (numpy's cumsum along a row), and divides by the total, itself a sum of n - 1 terms: entry j is within
     (3 + j + 3 + (n - 1) + 1) U = (n + j + 6) U of the exact quotient, relatively (all terms are >= 0)."""
     table = X.TABLES[key]()
-    mu = [F(float(m)) for m in table.mu]
-    assert mu[0] == -1 and mu[-1] == 1 and all(a < b for a, b in zip(mu, mu[1:]))
-    n = len(mu)
-    values = np.atleast_2d(table.values)
-    worst = 0.0
-    for row in range(table.n_wavelength):
-        p = [F(float(v)) for v in values[row][::-1]]
-        exact, running = [F(0)], F(0)
-        for j in range(n - 1):
-            running += (p[j] + p[j + 1]) / 2 * (mu[j + 1] - mu[j])
-            exact.append(running)
-        got = [F(float(c)) for c in table.cdf[row]]
-        assert got[0] == 0 and got[-1] == 1 and all(a <= b for a, b in zip(got, got[1:]))
-        for j in range(1, n):
-            want = exact[j] / exact[-1]
-            err = abs(got[j] - want)
-            assert err <= (n + j + 6) * F(1, 2 ** 53) * want, (key, row, j, float(err / want) * 2 ** 53)
-            if want:
-                worst = max(worst, float(err / want) * 2 ** 53)
+    assert table.n_wavelength == len(table.cdf)
+    worst = X.check_cdf_rows(table, key)
     print(f"{key}: worst |C_j - exact| / (U exact) {worst:.2f}")
 
 
