@@ -902,6 +902,12 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */
 int pvt_scene_variant(PvtScene* scene);
+/* Which entry point of that family the last trace on this scene ran (diagnostics; additive under ABI 13).
+ * PVT_ENTRY_PARK: a tally launch of the lean family that parks its survivors for its successor on the stream
+ * (PVT_FLAG_CARRY_OUT, and not too wide to park) runs `trace_kernel_lean_park`, the family's kernel compiled without the
+ * drain rendezvous and the tail function, which such a launch cannot reach.  Every other launch: PVT_ENTRY_USUAL. */
+enum { PVT_ENTRY_USUAL = 0, PVT_ENTRY_PARK = 1 };
+int pvt_scene_entry(PvtScene* scene);
 /* Host-only (no GPU needed): *lean = 0 when the tables are not proven plain in the sense above, 2 when they are and every
  * spectrum is a constant or an even grid bit for bit (the family's kernels without table searches), 1 when some grid is
  * even only up to rounding (np.linspace: the family's kernels that search) -- the proof alone, on the packed tables;

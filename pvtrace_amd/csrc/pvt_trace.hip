@@ -165,6 +165,7 @@ struct PvtScene {
     bool lean_ok = false;           // see prove_lean: launches with the tables in LDS run the trace_kernel_lean family ...
     bool lean_even = false;         // ... its EVEN kernels (every spectrum a constant or on a proven even grid)
     int last_variant = -1;          // PVT_VARIANT_* of the last launch (-1: none yet)
+    bool last_park = false;         // ... and whether it ran the family's parking entry (Variant::park)
 };
 
 extern "C" {
@@ -361,8 +362,10 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
 
 // Which kernel a launch runs: decided once, here.  `family` is what pvt_scene_variant reports; the other members are
 // the template arguments of that family's entry points.
-struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align; };
-Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit) {
+// `carry_out`: the launch parks its survivors for its successor -- its FINAL value, after bind_carry has had its say (a
+// launch too wide to park finishes its own photons, and needs a kernel that can).
+struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align, park; };
+Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit, bool carry_out = false) {
     Variant v{};
     v.record = record; v.emit = emit; v.tab = lp.tab;
     v.seenw = s->n_rec <= 64 ? 1 : 4;
@@ -376,6 +379,7 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.align = s->al_d >= 0;   // (the extension family's kernels that hold the aligned components' code)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
+    v.park = v.family == PVT_VARIANT_LEAN && !record && carry_out;   // (the entries compiled without the drain and the tail)
     return v;
 }
 
@@ -422,6 +426,7 @@ Kernel kernel_of(const Variant& v) {
             if constexpr (has_grid) return trace_kernel_grid<R, W, E>;
             break;
         case PVT_VARIANT_LEAN:
+            if constexpr (has_lean && !R) if (v.park) { if (v.even) return trace_kernel_lean_park<E, true>; return trace_kernel_lean_park<E, false>; }
             if constexpr (has_lean) { if (v.even) return trace_kernel_lean_w4<R, E, true>; return trace_kernel_lean_w4<R, E, false>; }
             break;
         case PVT_VARIANT_W4:
@@ -648,8 +653,9 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     const bool emit = rays == nullptr && s->d_ed != nullptr;
     if (emit && (rc = grow_emit_pool(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
     if (s->origin_mask && (rc = grow_origin_store(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
-    const Variant v = choose_variant(s, lp, record, emit);
+    const Variant v = choose_variant(s, lp, record, emit, carry_out);
     s->last_variant = v.family;
+    s->last_park = v.park;
     hipError_t e = hipErrorNotSupported;
     if (const Kernel kernel = kernel_of(v)) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlock), lp.total, st, a);
@@ -1112,6 +1118,11 @@ int pvt_scene_variant(PvtScene* s) {
     if (!s) return fail(PVT_ERR_INVALID, "null scene");
     if (s->last_variant >= 0) return s->last_variant;
     return choose_variant(s, plan_lds(s, false), false, false).family;
+}
+
+int pvt_scene_entry(PvtScene* s) {
+    if (!s) return fail(PVT_ERR_INVALID, "null scene");
+    return s->last_park ? PVT_ENTRY_PARK : PVT_ENTRY_USUAL;
 }
 
 int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,

@@ -1097,6 +1097,16 @@ __device__ __attribute__((noinline)) void emit_chunk(const KArgs* A, unsigned lo
     pool[192] = ed.x; pool[256] = ed.y; pool[320] = ed.z;
     pool[384] = ew;
 }
+// The parking entries' own copy (trace_kernel_lean_park): a function is compiled for the most demanding occupancy among
+// its callers, and theirs -- five waves per SIMD -- would re-schedule the sampler under every other family as well.
+__device__ __attribute__((noinline)) void emit_chunk_park(const KArgs* A, unsigned long long gi, double* pool) {
+    V3 ep, ed;
+    double ew;
+    emit_one(*A, gi, ep, ed, ew);
+    pool[0] = ep.x; pool[64] = ep.y; pool[128] = ep.z;
+    pool[192] = ed.x; pool[256] = ed.y; pool[320] = ed.z;
+    pool[384] = ew;
+}
 
 __global__ void __launch_bounds__(kBlock) emit_kernel(KArgs A, double* opos, double* odir, double* owl) {
     unsigned int i = blockIdx.x * kBlock + threadIdx.x;
@@ -1382,7 +1392,7 @@ __device__ __attribute__((noinline)) void leave_workgroup(const KArgs* kernel_ar
 }
 
 template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, int ROUGH = 0,
-          int LEAN = 0>
+          int LEAN = 0, bool PARK = false>
 __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, unsigned int tail_lds = 0u) {
     // LEAN (the trace_kernel_lean family): the scene is of the plain kind the host proves at its creation (pvt_scene_pack.h:
     // prove_lean) -- unrotated boxes (in a world that is a box or a sphere) holding absorbers and isotropic luminophores, spectra on even grids, no coating, no
@@ -1390,6 +1400,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // asked of the tables in every trip: the code they make unreachable is left out, everything that remains is the
     // generic variant's, operation for operation.
     static_assert(!LEAN || (!MESH && !GRID && !ROUGH && TAB_LDS == 1 && SEENW == 1), "the lean variants: plain scenes only");
+    // PARK (the trace_kernel_lean_park entries): the launch parks its survivors for its successor on the stream --
+    // `carry_flags & 2`, which the host has decided before it chooses the kernel, is a constant true here.  A wave that finds
+    // the ray cursor dry parks and leaves, so the launch can reach neither the drain rendezvous nor the tail function: they
+    // are not compiled, and the registers and the call frame that only `tail_run` asks for are not the kernel's.  Draws,
+    // refill order and the resuming of carried photons are the other entries', operation for operation.
+    static_assert(!PARK || (LEAN && !RECORD && !TAIL), "the parking form: tally launches of the lean family only");
     extern __shared__ double smem_of_kernel[];
     // (In a called function the address of the kernel's dynamic LDS is looked up in a table in memory wherever it is used --
     // six scalar loads and waits per step of the tail function, measured in its ISA; the kernel hands it over instead.)
@@ -1731,7 +1747,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     int tail_n = 0;   // photons this wave hands to the tail function when it leaves the loop (0: none)
     // (mesh scenes never repack a draining workgroup -- KArgs::xslots is 0 there -- and the history variant of the grid walk
     // has no register to spare for the call: both keep their last wave in this loop)
-    constexpr bool kTailCall = !TAIL && !MESH && !(GRID && RECORD);
+    constexpr bool kTailCall = !TAIL && !MESH && !(GRID && RECORD) && !PARK;
 
     // Statistics of the parked first crossings, one lane per record: the recorder's distinct count, the
     // eight running sums (the angle is acos of the parked cosine; 1.0 -> exactly 0 for events without a
@@ -1918,7 +1934,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     if (b + lane_here < w_end) {
                         double* pool = ak->emit_pool + ((unsigned long long)blockIdx.x * kWaves + (unsigned long long)wave) * (7 * 64) + lane_here;
                         const unsigned long long gi_ = A.ray_offset + (unsigned long long)ray_lo + (unsigned long long)b + (unsigned long long)lane_here;
-                        emit_chunk((const KArgs*)ak, gi_, pool);
+                        if constexpr (PARK) emit_chunk_park((const KArgs*)ak, gi_, pool);
+                        else emit_chunk((const KArgs*)ak, gi_, pool);
                     }
                 }
                 if (seed_pool) {
@@ -2005,7 +2022,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         // emptied waves retire.  Which lane carries a photon never affects its history (RNG
         // stream, seen-mask and log rows travel with it), so results stay bit-identical.
         if constexpr (!RECORD) {
-            if ((ws & WS_EXHAUSTED) && (A.carry_flags & 2)) {
+            if ((ws & WS_EXHAUSTED) && (PARK || (A.carry_flags & 2))) {
                 // no rays left for this wave: its live photons are parked for the next launch on the stream
                 const unsigned long long live_mask = __ballot(alive);
                 if (live_mask != 0ull) {
@@ -2040,6 +2057,12 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 }
             }
         }
+        if constexpr (PARK) {
+            // (parked above, or nothing was alive: either way the wave is done -- the exit the other entries take through
+            // "nothing alive, no rays left", without the workgroup's count of dry waves that only the drain reads)
+            if (ws & WS_EXHAUSTED) break;
+            if (__ballot(alive) == 0ull) break;
+        } else {
         if ((ws & (WS_EXHAUSTED | WS_COUNTED)) == WS_EXHAUSTED) {
             ws |= WS_COUNTED;
             if (lane == 0) atomicAdd(&ctl[CTL_EXHAUSTED], 1);
@@ -2181,6 +2204,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if (keep == 1) ws = (ws & ~(unsigned int)WS_REGIME) | WS_SOLO;
             }
         }
+        }   // (!PARK)
         }   // (!TAIL)
 #if PVT_STATS
         {
@@ -3743,6 +3767,14 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 template <bool RECORD, bool EMIT, bool EVEN>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_lean_w4(KArgs A) {
     trace_body<RECORD, 1, 1, EMIT, false, false, false, false, EVEN ? kLeanEven : kLeanSearched>(A);
+}
+// The lean family's tally launches that park (trace_body's PARK): the step loop alone decides their registers.
+#ifndef PVT_PARK_WAVES
+#define PVT_PARK_WAVES 5
+#endif
+template <bool EMIT, bool EVEN>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PVT_PARK_WAVES, PVT_PARK_WAVES))) trace_kernel_lean_park(KArgs A) {
+    trace_body<false, 1, 1, EMIT, false, false, false, false, EVEN ? kLeanEven : kLeanSearched, true>(A);
 }
 
 }  // namespace

@@ -477,6 +477,7 @@ def declare_signatures(lib, names):
         "pvt_scene_launch_info": (
             [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_variant": ([vp], C.c_int),
+        "pvt_scene_entry": ([vp], C.c_int),
         "pvt_scene_lean_check": (scene_inputs(LEAN_CHECK_TABLES) + [C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_counters": ([vp, C.POINTER(C.c_uint64), C.c_int], C.c_int),
         "pvt_scene_clock": ([vp, C.POINTER(C.c_uint64)], C.c_int),
@@ -505,9 +506,11 @@ ABI_SYMBOLS = (
     "pvt_scene_create_ex", "pvt_scene_create_phase", "pvt_scene_create_rough", "pvt_scene_create_field",
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
-    "pvt_scene_create_origin", "pvt_scene_create_pattern", "pvt_scene_create_aligned",
+    "pvt_scene_create_origin", "pvt_scene_create_pattern", "pvt_scene_create_aligned", "pvt_scene_entry",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
+# the family's entry point a launch ran (PVT_ENTRY_*): its usual kernel, or the lean family's parking one
+ENTRY_NAMES = {"lean": ("trace_kernel_lean_w4", "trace_kernel_lean_park")}
 
 _lib = None
 ABI_VERSION = 13  # include/pvtrace_hip.h PVT_ABI_VERSION
@@ -747,7 +750,13 @@ class DeviceScene:
         variant = int(self.lib.pvt_scene_variant(self.handle))
         if variant < 0:
             check(variant, "pvt_scene_variant")
-        return {"grid": g.value, "block": b.value, "lds_bytes": l.value, "variant": VARIANT_NAMES[variant]}
+        info = {"grid": g.value, "block": b.value, "lds_bytes": l.value, "variant": VARIANT_NAMES[variant]}
+        entry = int(self.lib.pvt_scene_entry(self.handle))
+        if entry < 0:
+            check(entry, "pvt_scene_entry")
+        if VARIANT_NAMES[variant] in ENTRY_NAMES:   # (the families with more than one entry per kind of launch)
+            info["entry"] = ENTRY_NAMES[VARIANT_NAMES[variant]][entry]
+        return info
 
     # -- device buffers (torch tensors) ----------------------------------
     def new_tallies(self, sets=1, captures=True):
