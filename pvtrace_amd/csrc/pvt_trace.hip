@@ -342,7 +342,7 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
     if (lp.bins_in_lds) lds += bins_bytes;
     // (a scene that counts: the global ray index, which captures read, and the event counters)
     // (one that reads a launch origin: its kOriginWords words; a buffer that no longer fits is done without, as ever)
-    const size_t xw = 14 + (s->n_rec <= 64 ? 1 : 4) + (record ? 1 : 0) + (s->counting() ? 2 : 0) + (s->origin_mask ? kOriginWords : 0);
+    const size_t xw = xbuf_words(s->n_rec <= 64 ? 1 : 4, record, s->counting(), s->origin_mask != 0);
     const size_t xbytes = (size_t)kXSlots * xw * 8;
     // (mesh scenes do without: measured, repacking a draining workgroup buys their launches nothing, and the 9 KB hold
     // another level of the trees' top)
@@ -494,7 +494,7 @@ long long size_grid(const PvtScene* s, const PvtTraceParams* p, long long carrie
 int bind_carry(PvtScene* s, PvtScene::Carry& carry, unsigned int* blocks, long long grid, bool carry_in, bool* carry_out, KArgs& a) {
     if (!s->carry_cap) s->carry_cap = (unsigned int)((long long)s->num_cu * 4 * kBlock);
     if (grid * kBlock > (long long)s->carry_cap) *carry_out = false;   // an unusually wide launch finishes its own photons
-    const size_t bytes = (size_t)s->carry_cap * ((s->counting() ? kCarryStrideCount : kCarryStride) + (s->origin_mask ? kOriginWords : 0)) * 8;
+    const size_t bytes = (size_t)s->carry_cap * carry_words(s->counting(), s->origin_mask != 0) * 8;
     for (int q = 0; q < 2; q++)
         if (!carry.buf[q]) HIP_TRY(hipMalloc(&carry.buf[q], bytes));
     a.carry_cap = s->carry_cap;

@@ -276,12 +276,28 @@ constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): ind
 constexpr int kMeshQ = 8;    // leaves a lane notes before its triangles are tested
 constexpr int kCarryBase = 14;     // u64 words of a parked photon before its seen-mask
 constexpr int kCarryStride = 18;   // words per parked photon (room for the four-word mask of scenes with > 64 recorders)
-constexpr int kCarryStrideCount = 20;   // ... of a scene that counts (KArgs::count; a captured recorder makes it one): behind the
-                                        // mask the photon's global ray index (captures read it), then its event counters
+constexpr int kCountWords = 2;     // ... more of a scene that counts (KArgs::count; a captured recorder makes it one): the photon's
+                                   // global ray index (captures read it), then its event counters
 constexpr int kOriginWords = 4;    // the launch origin of a photon: wavelength, x, y, z of its GENERATE row.  A scene that reads one
                                    // (KArgs::origin) moves them with the photon: kOriginWords more words per exchange-buffer slot
-                                   // and per parked photon, BEHIND the ray index and the counters where the scene counts too --
-                                   // a parked photon takes kCarryStride (+ 2 counting) (+ kOriginWords origin) = 18, 20, 22 or 24 words
+                                   // and per parked photon, BEHIND the ray index and the counters where the scene counts too
+// How many u64 words a photon on the move takes: in a slot of the LDS exchange buffer and as a parked photon's record.  The
+// kernel lays both out by these and the host sizes both by them (plan_lds, bind_carry); trace_body's PVT_PHOTON_PUT /
+// PVT_PHOTON_GET say which word is what.
+constexpr int xbuf_words(int seenw, bool record, bool counting, bool origin) {
+    return kCarryBase + seenw + (record ? 1 : 0) + (counting ? kCountWords : 0) + (origin ? kOriginWords : 0);
+}
+constexpr int carry_words(bool counting, bool origin) { return (counting ? kCarryStride + kCountWords : kCarryStride) + (origin ? kOriginWords : 0); }
+static_assert(xbuf_words(1, false, false, false) == 15 && xbuf_words(4, false, false, false) == 18 && xbuf_words(1, true, false, false) == 16 &&
+              xbuf_words(4, true, true, true) == 25, "a buffer slot: 15 or 18 words, + 1 with a history, + 2 counting, + 4 with an origin");
+static_assert(carry_words(false, false) == 18 && carry_words(true, false) == 20 && carry_words(false, true) == 22 && carry_words(true, true) == 24,
+              "a parked photon: 18, 20, 22 or 24 words");
+static_assert(kCarryBase + 4 <= kCarryStride, "a parked photon's record has room for the four-word mask");
+// (trace_body works a record's length out flag by flag -- each flag read and turned into its words before the next is read:
+// handed to carry_words together, the two reads move the scalar spills of the extension family's tally kernels -- so the
+// terms it adds are held to the function here)
+static_assert(carry_words(true, false) == kCarryStride + kCountWords && carry_words(false, true) == kCarryStride + kOriginWords &&
+              carry_words(true, true) == kCarryStride + kCountWords + kOriginWords, "trace_body's record length is carry_words'");
 constexpr int kCountBits = 20;   // one event counter in the packed word: emissions | scatterings << 20 | reflections << 40.  A step
                                  // writes at most ONE row of a counted kind (kCountRowsPerStep), so no counter passes `maxsteps`;
                                  // the host refuses a launch whose maxsteps could overflow a field: the loop never saturates
@@ -1210,8 +1226,19 @@ __device__ __attribute__((noinline)) void capture_call(const long long* __restri
     }
 }
 
-// (VIA_A: inside a called function -- the tail function -- the kernel-argument segment pointer is not to be had from the
-// intrinsic (measured: garbage in a callee, ROCm 7.0); the caller's `A` already IS that segment, handed down explicitly)
+// The kernel-argument segment through a pointer the compiler cannot trace back to it (the empty `asm`): what is read through
+// it is a scalar load at the point of use.  A pointer or a launch invariant that only a rare path reads -- the ray arrays, the
+// emission pool, the log, the carry buffers, the origin store -- is re-read this way where it is used: kept as a loop
+// invariant it would sit in two scalar registers the loop is short of (spilled to VGPR lanes, each use a v_readlane), and
+// scalar loads cost the vector pipe nothing.  Of a KERNEL only: inside a called function the intrinsic returns garbage
+// (measured, ROCm 7.0) -- the tail function hands in the segment it was given (`A` there IS the segment, see tail_run).
+// (`PVT_KERNEL_ARGS_OPAQUE(ak);` declares the pointer.  A macro: as a __forceinline__ function returning the pointer the same
+// two statements move the scalar spills of two tally kernels of the extension family, docs/history.md)
+typedef const __attribute__((address_space(4))) KArgs* KArgsSegment;
+#define PVT_OPAQUE_POINTER(ak) asm volatile("" : "+s"(ak))
+#define PVT_KERNEL_ARGS_OPAQUE(ak) KArgsSegment ak = (KArgsSegment)__builtin_amdgcn_kernarg_segment_ptr(); PVT_OPAQUE_POINTER(ak)
+
+// (VIA_A: in the tail function, see above)
 template <bool RECORD, bool VIA_A = false>
 __device__ __forceinline__ void log_row(const KArgs& A, int rec_slot, int& nev, int kind, int hit,
                                         int container, int adjacent, int component, int source,
@@ -1220,12 +1247,9 @@ __device__ __forceinline__ void log_row(const KArgs& A, int rec_slot, int& nev, 
     if constexpr (RECORD) {
         if (rec_slot < 0 || nev >= A.max_events) return;   // rec_slot: index of the recorded ray, -1 = not recorded
         const long long row = (long long)rec_slot * A.max_events + nev;
-        // the log pointer is read from the kernel-argument segment at the point of use (scalar load) instead of
-        // living in two scalar registers across the whole loop
-        const __attribute__((address_space(4))) KArgs* ak =
-            VIA_A ? (const __attribute__((address_space(4))) KArgs*)(unsigned long long)&A
-                  : (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ak));
+        // (the log pointer: read where it is used, not held across the whole loop)
+        KArgsSegment ak = VIA_A ? (KArgsSegment)(unsigned long long)&A : (KArgsSegment)__builtin_amdgcn_kernarg_segment_ptr();
+        PVT_OPAQUE_POINTER(ak);
         u32x4* dst = reinterpret_cast<u32x4*>(ak->log_rows + row * kRecWords);
         const unsigned long long p0 = pvt_d2u(pos.x);
         const V3 n = has_normal ? nrm : V3{0.0, 0.0, 0.0};
@@ -1333,7 +1357,7 @@ __device__ __attribute__((noinline)) void leave_workgroup(const KArgs* kernel_ar
     extern __shared__ double smem[];
     const unsigned long long bits = (unsigned long long)kernel_args;
     const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)bits), hi = __builtin_amdgcn_readfirstlane((unsigned int)(bits >> 32));
-    const __attribute__((address_space(4))) KArgs* ak = (const __attribute__((address_space(4))) KArgs*)(((unsigned long long)hi << 32) | lo);
+    const KArgsSegment ak = (KArgsSegment)(((unsigned long long)hi << 32) | lo);
     const KArgs& A = *(const KArgs*)ak;
     const int lane = threadIdx.x & 63;
     // (the layout of trace_body: tables | sums | crossings | distinct | bins | control words)
@@ -1481,14 +1505,14 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     unsigned int* acc_distinct = reinterpret_cast<unsigned int*>(acc_cross + A.n_rec);
     unsigned int* acc_bins = acc_distinct + ((A.n_rec + 1) & ~1);   // (keeps what follows 8-byte aligned)
     int* ctl = reinterpret_cast<int*>(acc_bins + ((A.bins_in_lds ? A.total_bins : 0) + 1 & ~1));
-    unsigned long long* xbuf = reinterpret_cast<unsigned long long*>(ctl + CTL_WORDS);  // [14 + SEENW (+1 when RECORD)][xslots] u64 words
+    unsigned long long* xbuf = reinterpret_cast<unsigned long long*>(ctl + CTL_WORDS);  // [x_words][xslots] u64 words (see PVT_PHOTON_PUT)
     // per-wave queue of first crossings awaiting their statistics: [4 (+3 with positions)][kTallyQ] doubles
     // + [kTallyQ] recorder ids
-    constexpr int kXWords = 14 + SEENW + (RECORD ? 1 : 0);
+    constexpr int kXWords = xbuf_words(SEENW, RECORD, false, false);
     // (scenes that count, KArgs::count -- a captured recorder makes a scene one: two more words per slot, the photon's global ray
     // index, which captures read, and its event counters; the rough variants alone)
     // (scenes that read a launch origin, KArgs::origin: kOriginWords more behind those)
-    const int x_words = ROUGH ? kXWords + (A.count != 0 ? 2 : 0) + (A.origin != 0 ? kOriginWords : 0) : kXWords;
+    const int x_words = xbuf_words(SEENW, RECORD, ROUGH && A.count != 0, ROUGH && A.origin != 0);
     // (a histogram reads a counter: one more column, the packed word, behind the positions' or in their place; one reads a
     // launch origin: one more column behind that for each origin that IS read, in the order of their ids)
     const int tq_doubles = (A.tq_pos ? 7 : 4) + (ROUGH && A.count >= 2 ? 1 : 0) + (ROUGH ? __builtin_popcount((unsigned int)A.origin & 15u) : 0);
@@ -1651,9 +1675,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         if constexpr (TAIL) {
             store = A.origin_store;
         } else {
-            const __attribute__((address_space(4))) KArgs* ak =
-                (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(ak));
+            PVT_KERNEL_ARGS_OPAQUE(ak);
             store = ak->origin_store;
         }
         return store + ((unsigned long long)blockIdx.x * kBlock + (unsigned long long)threadIdx.x) * kOriginWords;
@@ -1667,15 +1689,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         if constexpr (TAIL) {
             return (unsigned int)A.origin;
         } else {
-            const __attribute__((address_space(4))) KArgs* ak =
-                (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(ak));
+            PVT_KERNEL_ARGS_OPAQUE(ak);
             return (unsigned int)ak->origin;
         }
     };
-    // where the origin words stand behind a slot's / a parked photon's other words (wave-uniform)
-    auto origin_xat = [&]() -> int { return kXWords + (uf(UF_COUNT) ? 2 : 0); };
-    auto origin_cat = [&]() -> int { return uf(UF_COUNT) ? kCarryStrideCount : kCarryStride; };
     unsigned int c_iters = 0u, c_steps = 0u, c_fused = 0u;   // this lane's share of the step counters (KArgs::counters)
     // (tail function) the absorption coefficients this lane's photon met last: container, wavelength bits, sum, first term
     // -- kept in LDS, in the exchange buffer the function was handed its photons through (free once they are read): four
@@ -1708,6 +1725,72 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     Seen<SEENW> seen;
 #pragma unroll
     for (int w = 0; w < SEENW; w++) seen.w[w] = 0ull;
+    // ---- a photon on the move: ONE put and ONE get -------------------------
+    // Everything that travels with a photon when it changes lanes -- through the LDS exchange buffer (the drain's repacking, the
+    // hand-over to the tail function) or through a carry record (parked for the next launch) -- is written by PVT_PHOTON_PUT
+    // and read by PVT_PHOTON_GET, and by nothing else: a word that is to travel is added HERE, to both, and to the word counts
+    // (xbuf_words / carry_words).  `word(k)` names word k of the place: PVT_SLOT_WORD for the buffer (column-major, stride
+    // kXSlots: constant offsets in the LDS instructions), PVT_SRC_WORD / PVT_DST_WORD for a carry record (photon-major: one
+    // base address, every word at an immediate offset).  The core -- words 0 to 13, then the seen-mask from word kCarryBase,
+    // then the history cursor of a RECORD launch (the buffer alone: a history launch carries nothing) -- stands at the same
+    // words in both.  What the rough variants add stands behind `base`, and that is the layouts' ONLY difference: kXWords in
+    // the buffer, kCarryStride in a record (whose mask always has room for four words).  Behind `base`: the global ray
+    // index and the event counters (kCountWords, UF_CAPTURE / UF_COUNT), then the launch origin (kOriginWords, UF_ORIGIN; it
+    // lives in the lane's side store, see origin_slot, not in a register).
+    // MACROS over the loop's own variables, and a bare block each, because every other form was measured to move the
+    // kernels' registers or code (docs/history.md): a helper that takes the variables by reference costs every kernel scalar
+    // spills, called or not; one that takes and returns them by value reorders the kernels it is inlined into and moves the
+    // extension family's spills; so does a lambda for `word`.  As they stand the six sites compile to the very code they
+    // compiled to spelled out.
+#define PVT_SLOT_WORD(k) xbuf[(k) * kXSlots + slot]
+#define PVT_SRC_WORD(k) src[k]
+#define PVT_DST_WORD(k) dst[k]
+#define PVT_PHOTON_PUT(word, base) { \
+        word(0) = pvt_d2u(pos.x); word(1) = pvt_d2u(pos.y); word(2) = pvt_d2u(pos.z); \
+        word(3) = pvt_d2u(dir.x); word(4) = pvt_d2u(dir.y); word(5) = pvt_d2u(dir.z); \
+        word(6) = pvt_d2u(wl); word(7) = pvt_d2u(travelled); word(8) = pvt_d2u(duration); \
+        word(9) = rng.s0; word(10) = rng.s1; word(11) = rng.s2; word(12) = rng.s3; \
+        word(13) = (unsigned long long)(unsigned int)count | ((unsigned long long)(unsigned int)source << 32); \
+        _Pragma("unroll") \
+        for (int w = 0; w < SEENW; w++) word(kCarryBase + w) = seen.w[w]; \
+        if constexpr (RECORD) { \
+            word(kCarryBase + SEENW) = (unsigned long long)(unsigned int)rec_slot | ((unsigned long long)(unsigned int)nev << 32); \
+        } \
+        if constexpr (ROUGH) { \
+            if (uf(UF_CAPTURE)) word(base) = gidx; \
+            if (uf(UF_COUNT)) word((base) + 1) = hcount; \
+            if (uf(UF_ORIGIN)) { \
+                const int at = uf(UF_COUNT) ? (base) + kCountWords : (base);   /* (wave-uniform) */ \
+                const double* o = origin_slot(); \
+                _Pragma("unroll") \
+                for (int k = 0; k < kOriginWords; k++) word(at + k) = pvt_d2u(o[k]); \
+            } \
+        } \
+    }
+#define PVT_PHOTON_GET(word, base) { \
+        pos = V3{pvt_u2d(word(0)), pvt_u2d(word(1)), pvt_u2d(word(2))}; \
+        dir = V3{pvt_u2d(word(3)), pvt_u2d(word(4)), pvt_u2d(word(5))}; \
+        wl = pvt_u2d(word(6)); travelled = pvt_u2d(word(7)); duration = pvt_u2d(word(8)); \
+        rng.s0 = word(9); rng.s1 = word(10); rng.s2 = word(11); rng.s3 = word(12); \
+        const unsigned long long cs_ = word(13); \
+        count = (int)(unsigned int)cs_; \
+        source = (int)(unsigned int)(cs_ >> 32); \
+        _Pragma("unroll") \
+        for (int w = 0; w < SEENW; w++) seen.w[w] = word(kCarryBase + w); \
+        if constexpr (RECORD) { \
+            const unsigned long long rn_ = word(kCarryBase + SEENW); \
+            rec_slot = (int)(unsigned int)rn_; \
+            nev = (int)(unsigned int)(rn_ >> 32); \
+        } \
+        if constexpr (ROUGH) { \
+            if (uf(UF_CAPTURE)) gidx = word(base); \
+            if (uf(UF_COUNT)) hcount = word((base) + 1); \
+            if (uf(UF_ORIGIN)) { \
+                const int at = uf(UF_COUNT) ? (base) + kCountWords : (base); \
+                origin_put(pvt_u2d(word(at)), pvt_u2d(word(at + 1)), pvt_u2d(word(at + 2)), pvt_u2d(word(at + 3))); \
+            } \
+        } \
+    }
 
 #if PVT_STATS
     unsigned long long st_iters = 0, st_lane_steps = 0, st_drain_iters = 0, st_drain_lane_steps = 0;
@@ -1803,34 +1886,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         tq_n = 0;
     };
     if constexpr (TAIL) {   // the photons the caller left in the exchange buffer, one per lane
-        constexpr int X = kXSlots;
         const int slot = lane;
         ws = WS_EXHAUSTED | WS_COUNTED | WS_SOLO;
         alive = slot < tail_total;
         if (alive) {
-            pos = V3{pvt_u2d(xbuf[0 * X + slot]), pvt_u2d(xbuf[1 * X + slot]), pvt_u2d(xbuf[2 * X + slot])};
-            dir = V3{pvt_u2d(xbuf[3 * X + slot]), pvt_u2d(xbuf[4 * X + slot]), pvt_u2d(xbuf[5 * X + slot])};
-            wl = pvt_u2d(xbuf[6 * X + slot]); travelled = pvt_u2d(xbuf[7 * X + slot]); duration = pvt_u2d(xbuf[8 * X + slot]);
-            rng.s0 = xbuf[9 * X + slot]; rng.s1 = xbuf[10 * X + slot]; rng.s2 = xbuf[11 * X + slot]; rng.s3 = xbuf[12 * X + slot];
-            const unsigned long long cs_ = xbuf[13 * X + slot];
-            count = (int)(unsigned int)cs_;
-            source = (int)(unsigned int)(cs_ >> 32);
-#pragma unroll
-            for (int w = 0; w < SEENW; w++) seen.w[w] = xbuf[(14 + w) * X + slot];
-            if constexpr (RECORD) {
-                const unsigned long long rn_ = xbuf[(14 + SEENW) * X + slot];
-                rec_slot = (int)(unsigned int)rn_;
-                nev = (int)(unsigned int)(rn_ >> 32);
-            }
-            if constexpr (ROUGH) {
-                if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
-                if (uf(UF_COUNT)) hcount = xbuf[(kXWords + 1) * X + slot];
-                if (uf(UF_ORIGIN)) {
-                    const int xo = origin_xat();
-                    origin_put(pvt_u2d(xbuf[xo * X + slot]), pvt_u2d(xbuf[(xo + 1) * X + slot]), pvt_u2d(xbuf[(xo + 2) * X + slot]),
-                               pvt_u2d(xbuf[(xo + 3) * X + slot]));
-                }
-            }
+            PVT_PHOTON_GET(PVT_SLOT_WORD, kXWords)
         }
     }
     if constexpr (TAIL) ac_lds[0] = ~0ull;   // (nothing known yet; after the reads above, same wave: in order)
@@ -1849,9 +1909,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             // that died in the last step, put a queue of ~10^5 same-address atomics in front of every step: measured
             // 21 us per iteration instead of 11.)
             if ((ws & WS_CARRY_IN) && need != 0ull) {
-                const __attribute__((address_space(4))) KArgs* ak =
-                    (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(ak));
+                PVT_KERNEL_ARGS_OPAQUE(ak);
                 const unsigned int have = *ak->carry_in_count;
                 if (c_next >= c_end) {
                     unsigned int b = ~0u;
@@ -1873,25 +1931,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const unsigned int want = __popcll(need), got = c_end - c_next < want ? c_end - c_next : want;
                     const unsigned int rank = rank_in(need);
                     if (!alive && rank < got) {
-                        // photon-major records: one base address, every word at an immediate offset
-                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * ((ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride) + (ROUGH && uf(UF_ORIGIN) ? kOriginWords : 0));
-                        pos = V3{pvt_u2d(src[0]), pvt_u2d(src[1]), pvt_u2d(src[2])};
-                        dir = V3{pvt_u2d(src[3]), pvt_u2d(src[4]), pvt_u2d(src[5])};
-                        wl = pvt_u2d(src[6]); travelled = pvt_u2d(src[7]); duration = pvt_u2d(src[8]);
-                        rng.s0 = src[9]; rng.s1 = src[10]; rng.s2 = src[11]; rng.s3 = src[12];
-                        const unsigned long long cs_ = src[13];
-                        count = (int)(unsigned int)cs_;
-                        source = (int)(unsigned int)(cs_ >> 32);
-#pragma unroll
-                        for (int w = 0; w < SEENW; w++) seen.w[w] = src[kCarryBase + w];
-                        if constexpr (ROUGH) {
-                            if (uf(UF_CAPTURE)) gidx = src[kCarryStride];
-                            if (uf(UF_COUNT)) hcount = src[kCarryStride + 1];
-                            if (uf(UF_ORIGIN)) {
-                                const int co = origin_cat();
-                                origin_put(pvt_u2d(src[co]), pvt_u2d(src[co + 1]), pvt_u2d(src[co + 2]), pvt_u2d(src[co + 3]));
-                            }
-                        }
+                        const unsigned long long* src = ak->carry_in + (unsigned long long)(c_next + rank) * ((ROUGH && uf(UF_COUNT) ? kCarryStride + kCountWords : kCarryStride) + (ROUGH && uf(UF_ORIGIN) ? kOriginWords : 0));
+                        PVT_PHOTON_GET(PVT_SRC_WORD, kCarryStride)
                         nev = 0;
                         alive = true;
                     }
@@ -1926,9 +1967,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 if constexpr (EMIT) {
                     // sample the whole chunk now (see KArgs::emit_pool); the stores are read back by lanes of this very
                     // wave, later in program order
-                    const __attribute__((address_space(4))) KArgs* ak =
-                        (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                    asm volatile("" : "+s"(ak));
+                    PVT_KERNEL_ARGS_OPAQUE(ak);
                     unsigned int lane_here = (unsigned int)lane;
                     asm volatile("" : "+v"(lane_here));
                     if (b + lane_here < w_end) {
@@ -1961,9 +2000,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 const unsigned int il = w_next + rank;   // index within the set
                 const unsigned int i = ray_lo + il;      // index within the launch
                 if constexpr (EMIT) {
-                    const __attribute__((address_space(4))) KArgs* ak =
-                        (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                    asm volatile("" : "+s"(ak));
+                    PVT_KERNEL_ARGS_OPAQUE(ak);
                     const double* pool = ak->emit_pool + ((unsigned long long)blockIdx.x * kWaves + (unsigned long long)wave) * (7 * 64) + (il - w_base);
                     pos = V3{pool[0], pool[64], pool[128]};
                     dir = V3{pool[192], pool[256], pool[320]};
@@ -1973,9 +2010,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     // the compiler cannot trace back to it: kept as loop invariants they would sit in six
                     // scalar registers the loop is short of (spilled to VGPR lanes, each use a VALU
                     // v_readlane); scalar loads cost the vector pipe nothing.
-                    const __attribute__((address_space(4))) KArgs* ak =
-                        (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                    asm volatile("" : "+s"(ak));
+                    PVT_KERNEL_ARGS_OPAQUE(ak);
                     const double* rp = ak->pos;
                     const double* rd = ak->dir;
                     const double* rw = ak->wl;
@@ -2026,32 +2061,14 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // no rays left for this wave: its live photons are parked for the next launch on the stream
                 const unsigned long long live_mask = __ballot(alive);
                 if (live_mask != 0ull) {
-                    const __attribute__((address_space(4))) KArgs* ak =
-                        (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                    asm volatile("" : "+s"(ak));
+                    PVT_KERNEL_ARGS_OPAQUE(ak);
                     unsigned int b = 0;
                     if (lane == 0) b = atomicAdd(cursor + 2, (unsigned int)__popcll(live_mask));
                     b = __builtin_amdgcn_readfirstlane(b);
                     const unsigned int at = b + rank_in(live_mask);
                     if (alive && at < ak->carry_cap) {
-                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * ((ROUGH && uf(UF_COUNT) ? kCarryStrideCount : kCarryStride) + (ROUGH && uf(UF_ORIGIN) ? kOriginWords : 0));
-                        dst[0] = pvt_d2u(pos.x); dst[1] = pvt_d2u(pos.y); dst[2] = pvt_d2u(pos.z);
-                        dst[3] = pvt_d2u(dir.x); dst[4] = pvt_d2u(dir.y); dst[5] = pvt_d2u(dir.z);
-                        dst[6] = pvt_d2u(wl); dst[7] = pvt_d2u(travelled); dst[8] = pvt_d2u(duration);
-                        dst[9] = rng.s0; dst[10] = rng.s1; dst[11] = rng.s2; dst[12] = rng.s3;
-                        dst[13] = (unsigned long long)(unsigned int)count | ((unsigned long long)(unsigned int)source << 32);
-#pragma unroll
-                        for (int w = 0; w < SEENW; w++) dst[kCarryBase + w] = seen.w[w];
-                        if constexpr (ROUGH) {
-                            if (uf(UF_CAPTURE)) dst[kCarryStride] = gidx;
-                            if (uf(UF_COUNT)) dst[kCarryStride + 1] = hcount;
-                            if (uf(UF_ORIGIN)) {
-                                const int co = origin_cat();
-                                const double* o = origin_slot();
-#pragma unroll
-                                for (int k = 0; k < kOriginWords; k++) dst[co + k] = pvt_d2u(o[k]);
-                            }
-                        }
+                        unsigned long long* dst = ak->carry_out + (unsigned long long)at * ((ROUGH && uf(UF_COUNT) ? kCarryStride + kCountWords : kCarryStride) + (ROUGH && uf(UF_ORIGIN) ? kOriginWords : 0));
+                        PVT_PHOTON_PUT(PVT_DST_WORD, kCarryStride)
                     }
                     alive = false;   // (the wave leaves through the "nothing alive, no rays left" exit below)
                 }
@@ -2105,58 +2122,18 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // the refill and the rendezvous, a function of its own: it cannot move this loop's registers); the
                 // photons go through the exchange buffer, as in a consolidation
                 if constexpr (kTailCall) {
-                    constexpr int X = kXSlots;
                     if (alive) {
                         const int slot = (int)rank_in(live_mask);
-                        xbuf[0 * X + slot] = pvt_d2u(pos.x); xbuf[1 * X + slot] = pvt_d2u(pos.y); xbuf[2 * X + slot] = pvt_d2u(pos.z);
-                        xbuf[3 * X + slot] = pvt_d2u(dir.x); xbuf[4 * X + slot] = pvt_d2u(dir.y); xbuf[5 * X + slot] = pvt_d2u(dir.z);
-                        xbuf[6 * X + slot] = pvt_d2u(wl); xbuf[7 * X + slot] = pvt_d2u(travelled); xbuf[8 * X + slot] = pvt_d2u(duration);
-                        xbuf[9 * X + slot] = rng.s0; xbuf[10 * X + slot] = rng.s1; xbuf[11 * X + slot] = rng.s2; xbuf[12 * X + slot] = rng.s3;
-                        xbuf[13 * X + slot] = (unsigned long long)(unsigned int)count | ((unsigned long long)(unsigned int)source << 32);
-#pragma unroll
-                        for (int w = 0; w < SEENW; w++) xbuf[(14 + w) * X + slot] = seen.w[w];
-                        if constexpr (RECORD) {
-                            xbuf[(14 + SEENW) * X + slot] = (unsigned long long)(unsigned int)rec_slot | ((unsigned long long)(unsigned int)nev << 32);
-                        }
-                        if constexpr (ROUGH) {
-                            if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
-                            if (uf(UF_COUNT)) xbuf[(kXWords + 1) * X + slot] = hcount;
-                            if (uf(UF_ORIGIN)) {
-                                const int xo = origin_xat();
-                                const double* o = origin_slot();
-#pragma unroll
-                                for (int k = 0; k < kOriginWords; k++) xbuf[(xo + k) * X + slot] = pvt_d2u(o[k]);
-                            }
-                        }
+                        PVT_PHOTON_PUT(PVT_SLOT_WORD, kXWords)
                     }
                     tail_n = live;   // (the call itself comes after the loop: nothing of the loop is live across it)
                     alive = false;
                     break;
                 }
             } else if (total <= 64 * (nw - 1) && total <= A.xslots) {
-                constexpr int X = kXSlots;   // (A.xslots is 0 or kXSlots: constant offsets in the LDS instructions)
                 if (alive) {
                     const int slot = before + (int)rank_in(live_mask);
-                    xbuf[0 * X + slot] = pvt_d2u(pos.x); xbuf[1 * X + slot] = pvt_d2u(pos.y); xbuf[2 * X + slot] = pvt_d2u(pos.z);
-                    xbuf[3 * X + slot] = pvt_d2u(dir.x); xbuf[4 * X + slot] = pvt_d2u(dir.y); xbuf[5 * X + slot] = pvt_d2u(dir.z);
-                    xbuf[6 * X + slot] = pvt_d2u(wl); xbuf[7 * X + slot] = pvt_d2u(travelled); xbuf[8 * X + slot] = pvt_d2u(duration);
-                    xbuf[9 * X + slot] = rng.s0; xbuf[10 * X + slot] = rng.s1; xbuf[11 * X + slot] = rng.s2; xbuf[12 * X + slot] = rng.s3;
-                    xbuf[13 * X + slot] = (unsigned long long)(unsigned int)count | ((unsigned long long)(unsigned int)source << 32);
-#pragma unroll
-                    for (int w = 0; w < SEENW; w++) xbuf[(14 + w) * X + slot] = seen.w[w];
-                    if constexpr (RECORD) {
-                        xbuf[(14 + SEENW) * X + slot] = (unsigned long long)(unsigned int)rec_slot | ((unsigned long long)(unsigned int)nev << 32);
-                    }
-                    if constexpr (ROUGH) {
-                        if (uf(UF_CAPTURE)) xbuf[kXWords * X + slot] = gidx;
-                        if (uf(UF_COUNT)) xbuf[(kXWords + 1) * X + slot] = hcount;
-                        if (uf(UF_ORIGIN)) {
-                            const int xo = origin_xat();
-                            const double* o = origin_slot();
-#pragma unroll
-                            for (int k = 0; k < kOriginWords; k++) xbuf[(xo + k) * X + slot] = pvt_d2u(o[k]);
-                        }
-                    }
+                    PVT_PHOTON_PUT(PVT_SLOT_WORD, kXWords)
                 }
                 __syncthreads();  // B
                 const int keep = (total + 63) >> 6;  // waves that stay, lowest ids of the set
@@ -2171,29 +2148,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 const int slot = pos_in_set * 64 + lane;
                 alive = slot < total;
                 if (alive) {
-                    pos = V3{pvt_u2d(xbuf[0 * X + slot]), pvt_u2d(xbuf[1 * X + slot]), pvt_u2d(xbuf[2 * X + slot])};
-                    dir = V3{pvt_u2d(xbuf[3 * X + slot]), pvt_u2d(xbuf[4 * X + slot]), pvt_u2d(xbuf[5 * X + slot])};
-                    wl = pvt_u2d(xbuf[6 * X + slot]); travelled = pvt_u2d(xbuf[7 * X + slot]); duration = pvt_u2d(xbuf[8 * X + slot]);
-                    rng.s0 = xbuf[9 * X + slot]; rng.s1 = xbuf[10 * X + slot]; rng.s2 = xbuf[11 * X + slot]; rng.s3 = xbuf[12 * X + slot];
-                    const unsigned long long cs_ = xbuf[13 * X + slot];
-                    count = (int)(unsigned int)cs_;
-                    source = (int)(unsigned int)(cs_ >> 32);
-#pragma unroll
-                    for (int w = 0; w < SEENW; w++) seen.w[w] = xbuf[(14 + w) * X + slot];
-                    if constexpr (RECORD) {
-                        const unsigned long long rn_ = xbuf[(14 + SEENW) * X + slot];
-                        rec_slot = (int)(unsigned int)rn_;
-                        nev = (int)(unsigned int)(rn_ >> 32);
-                    }
-                    if constexpr (ROUGH) {
-                        if (uf(UF_CAPTURE)) gidx = xbuf[kXWords * X + slot];
-                        if (uf(UF_COUNT)) hcount = xbuf[(kXWords + 1) * X + slot];
-                        if (uf(UF_ORIGIN)) {
-                            const int xo = origin_xat();
-                            origin_put(pvt_u2d(xbuf[xo * X + slot]), pvt_u2d(xbuf[(xo + 1) * X + slot]), pvt_u2d(xbuf[(xo + 2) * X + slot]),
-                                       pvt_u2d(xbuf[(xo + 3) * X + slot]));
-                        }
-                    }
+                    PVT_PHOTON_GET(PVT_SLOT_WORD, kXWords)
                 }
                 // the set shrinks to its `keep` lowest members
                 int kept = 0, m2 = 0;
@@ -3692,8 +3647,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // accumulators' places in LDS, the tally set, the output pointers -- is worked out inside it instead of being held
     // (or spilled) for the kernel's whole life.
     {
-        const __attribute__((address_space(4))) KArgs* ak =
-            (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        const KArgsSegment ak = (KArgsSegment)__builtin_amdgcn_kernarg_segment_ptr();
         if constexpr (kTailCall) {
             if (tail_n > 0) {
                 // (behind an opaque copy: every caller passes the same address expression, which interprocedural constant
@@ -3719,7 +3673,7 @@ __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int
     // inside a called function -- build/probe, ROCm 7.0 -- hence the explicit argument.)
     const unsigned long long bits = (unsigned long long)kernel_args;
     const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)bits), hi = __builtin_amdgcn_readfirstlane((unsigned int)(bits >> 32));
-    const __attribute__((address_space(4))) KArgs* ak = (const __attribute__((address_space(4))) KArgs*)(((unsigned long long)hi << 32) | lo);
+    const KArgsSegment ak = (KArgsSegment)(((unsigned long long)hi << 32) | lo);
     trace_body<RECORD, TAB_LDS, SEENW, false, MESH, GRID, true, ROUGH, LEAN>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
                                                                 __builtin_amdgcn_readfirstlane(lds));
 }
