@@ -388,15 +388,50 @@ typedef struct PvtFieldTables {
  * reductions move the maps with the bins.  The kernel adds one to a slot per event with a 64-bit integer atomic in
  * global memory (never staged in LDS, whatever the recorders' bins do), so the counts are exact and independent of
  * summation order, launch geometry, carrying and GPU count.  Map records live in global memory of their own, outside the
- * tables a launch stages in LDS.  A NULL struct, n_nodes 0 or n_maps 0 is exactly pvt_scene_create_field. */
+ * tables a launch stages in LDS.  A NULL struct, n_nodes 0 or n_maps 0 is exactly pvt_scene_create_field.
+ *
+ * PATH-LENGTH maps (map_kind PVT_MAP_PATHLENGTH, a value that is no PVT_EV_*; map_component must be -1): not events but the
+ * path photons travel in each voxel, the track-length estimator of the fluence, as fixed-point integers -- one count is
+ * PVT_FLUENCE_UNIT = 2^-30 of the scene's length unit, so these maps are as exact and as independent of summation order,
+ * launch geometry, carrying and GPU count as the others.  They own slots of the same block, laid out the same way.  The
+ * contract (the Python VolumeMap and engine.tally.map_histories walk the same way; the kernel and the host follow it
+ * operation for operation, without FMA):
+ *  1. A SEGMENT is one advance of a photon: from world position x along unit direction d for length L, while the photon's
+ *     container is the map's node.  A segment with non-finite L, or L <= 0, adds nothing.
+ *  2. Local start: p_a = ((R[a][0] x + R[a][1] y) + R[a][2] z) + t[a].
+ *  3. Local direction: u_a = (R[a][0] dx + R[a][1] dy) + R[a][2] dz.
+ *  4. R and t are the node's rows of PvtSceneTables.world_to_local.
+ *  5. Per axis the planes are lower_a + i h_a for i = 0 .. n_a, written `lower + (double)i * h`.  The cell index c_a runs
+ *     over -1 .. n_a; -1 and n_a are the two half-infinite slabs outside the lattice.
+ *  6. Start: c_a = clamp(floor((p_a - lower_a) / h_a), -1, n_a).  A NaN gives -1.
+ *  7. step_a is the sign of u_a; 0 means the axis never crosses.
+ *  8. The plane ahead is i = c_a + 1 for a positive step and i = c_a for a negative one; it exists when 0 <= i <= n_a, and
+ *     its parameter is (lower_a + i h_a - p_a) / u_a.  Otherwise the parameter is +inf.
+ *  9. The loop is that of the concentration fields' march.  Start with s = 0.  In each pass tmin is the least of the three
+ *     parameters; sout = max(min(tmin, L), s); the piece sout - s belongs to the current cell; stop when !(sout < L);
+ *     otherwise cross ONE axis whose parameter equals tmin -- ties in the order X, then Y, then Z, the others follow at
+ *     zero length -- and then s = sout.
+ * 10. A piece of length l adds k = (int64)(l * 2^30 + 0.5).  Nothing is added when k = 0.
+ * 11. The piece goes to slot ((cx ny + cy) nz + cz) nw' + iw when every c_a is in 0 .. n_a - 1 and the wavelength bin is in
+ *     range, otherwise to the map's single `outside` slot.
+ * 12. With a wavelength axis iw is a Histogram's bin (rule 5 above) of the wavelength the photon travels with; out of range
+ *     means the whole segment goes to `outside`.
+ * 13. No clamping: a map may be smaller than its node.
+ * 14. Hence (sum of all slots) * PVT_FLUENCE_UNIT is the path length travelled inside the node, to within half a unit per
+ *     piece.  A slot wraps at 2^63 units, about 8.6e9 length units; the `outside` slot of a small map in a large node is
+ *     the first to get there.
+ * The kernel adds k to a slot with one no-return 64-bit integer atomic in global memory per non-zero piece.  Event maps do
+ * not see these records (no event's kind equals PVT_MAP_PATHLENGTH), and a scene without one runs the kernels it ran. */
 #define PVT_MAX_MAP_SLOTS (1LL << 26)
+#define PVT_MAP_PATHLENGTH 100           /* map_kind of a path-length map: no PVT_EV_* has this value */
+#define PVT_FLUENCE_UNIT 9.31322574615478515625e-10   /* 2^-30: the length one count of a path-length map stands for */
 typedef struct PvtMapTables {
     int32_t n_nodes;                /* 0 = none (as a NULL struct), else the scene's n_nodes */
     int32_t n_maps;
     const int32_t* node_map_start;  /* (n_nodes) first map of each node */
     const int32_t* node_map_count;  /* (n_nodes) its maps; the runs tile [0, n_maps) in node order */
-    const int32_t* map_kind;        /* (n_maps) PVT_EV_ABSORB / EMIT / SCATTER / NONRADIATIVE / REACT */
-    const int32_t* map_component;   /* (n_maps) component id (one of the node's), -1 = any */
+    const int32_t* map_kind;        /* (n_maps) PVT_EV_ABSORB / EMIT / SCATTER / NONRADIATIVE / REACT, or PVT_MAP_PATHLENGTH */
+    const int32_t* map_component;   /* (n_maps) component id (one of the node's), -1 = any (PVT_MAP_PATHLENGTH: -1 only) */
     const int32_t* map_shape;       /* (n_maps, 3) nx, ny, nz, each >= 1 */
     const double* map_lower;        /* (n_maps, 3) finite */
     const double* map_h;            /* (n_maps, 3) cell widths (upper - lower) / n, finite and > 0 */

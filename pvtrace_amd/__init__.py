@@ -17,7 +17,7 @@ from pvtrace_amd.material import (
 )
 from pvtrace_amd.scene import Node, Scene
 from pvtrace_amd import engine
-from pvtrace_amd.engine.recorder import VolumeMap, VolumeMapResult
+from pvtrace_amd.engine.recorder import FLUENCE_UNIT, VolumeMap, VolumeMapResult
 from pvtrace_amd.device.lsc import LSC
 from pvtrace_amd import spec
 from pvtrace_amd.algorithm import photon_tracer

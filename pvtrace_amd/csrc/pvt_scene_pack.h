@@ -356,9 +356,11 @@ struct PackedScene {
     // volume maps (PvtMapTables): their own buffer of doubles, read from global memory alone (empty: none).
     // md[n] = where node n's block starts (-1: the node has no map), then the blocks: kMn* words (the node's map count and
     // its world->local rotation and translation) and one record of kMr words (kMr*) per map.  map_slots: the int64 slots
-    // the maps add behind the recorders' bins
+    // the maps add behind the recorders' bins.  path_maps: one of them is a path-length map (PVT_MAP_PATHLENGTH): the scene's
+    // launches run the extension family's kExtPath kernels
     std::vector<double> md;
     long long map_slots = 0;
+    bool path_maps = false;
     // ray capture (PvtCaptureTables): per recorder the rows it may keep (0: not captured) and its first row, read from
     // global memory alone (empty: no recorder is captured); capture_rows: the rows of all captures of one tally set
     std::vector<long long> cd;
@@ -689,9 +691,12 @@ int validate_map_tables(const PvtSceneTables* t, const PvtMapTables* mp) {
     for (int n = 0; n < N; n++)
         for (int m = mp->node_map_start[n]; m < mp->node_map_start[n] + mp->node_map_count[n]; m++) {
             const int kind = mp->map_kind[m];
-            if (kind != PVT_EV_ABSORB && kind != PVT_EV_EMIT && kind != PVT_EV_SCATTER && kind != PVT_EV_NONRADIATIVE && kind != PVT_EV_REACT)
-                return fail(PVT_ERR_INVALID, "map tables: map kind must be ABSORB, EMIT, SCATTER, NONRADIATIVE or REACT");
+            if (kind != PVT_EV_ABSORB && kind != PVT_EV_EMIT && kind != PVT_EV_SCATTER && kind != PVT_EV_NONRADIATIVE && kind != PVT_EV_REACT &&
+                kind != PVT_MAP_PATHLENGTH)
+                return fail(PVT_ERR_INVALID, "map tables: map kind must be ABSORB, EMIT, SCATTER, NONRADIATIVE, REACT or PVT_MAP_PATHLENGTH");
             const int c = mp->map_component[m];
+            if (kind == PVT_MAP_PATHLENGTH && c != -1)
+                return fail(PVT_ERR_INVALID, "map tables: a path-length map takes no component filter (map_component must be -1)");
             if (c < -1 || (c >= 0 && (bad_run(t->comp_start[n], t->comp_count[n], C) || c < t->comp_start[n] || c >= t->comp_start[n] + t->comp_count[n])))
                 return fail(PVT_ERR_INVALID, "map tables: map component must be -1 or a component of the map's node");
             long long cells = 1;
@@ -1469,12 +1474,14 @@ void pack_fields(const SceneInputs& in, PackedScene* p) {
 
 // The map buffer p->md (validated tables; left empty without maps): per node where its block starts, then per node with
 // maps its block -- the map count, the world->local rotation and translation of world_to_local (the doubles a field
-// record holds) -- and per map its record: kind, component, shape, lower, cell widths, wavelength bins and range, first slot.
+// record holds), how many of the maps are path-length maps (the marker the kernel asks before it walks) -- and per map
+// its record: kind, component, shape, lower, cell widths, wavelength bins and range, first slot.
 void pack_maps(const SceneInputs& in, PackedScene* p) {
     const PvtSceneTables* t = in.t;
     const PvtMapTables* mp = in.mp;
     p->md.clear();
     p->map_slots = 0;
+    p->path_maps = false;
     if (!mp || mp->n_nodes == 0 || mp->n_maps == 0) return;
     const int N = t->n_nodes;
     std::vector<double>& md = p->md;
@@ -1495,6 +1502,7 @@ void pack_maps(const SceneInputs& in, PackedScene* p) {
             const int m = mp->node_map_start[n] + k;
             double* q = r + kMnRec + k * kMr;
             q[kMrKind] = (double)mp->map_kind[m];
+            if (mp->map_kind[m] == PVT_MAP_PATHLENGTH) { r[kMnPath] += 1.0; p->path_maps = true; }
             q[kMrComp] = (double)mp->map_component[m];
             for (int a = 0; a < 3; a++) {
                 q[kMrShape + a] = (double)mp->map_shape[m * 3 + a];

@@ -106,6 +106,7 @@ struct PvtScene {
     int pd_d = -1;                      // the coating patterns' flags, records and masks: where they start behind the double blob, in its allocation (KArgs::pd_d; -1 = no coating has a pattern or covers any normal)
     int al_d = -1;                      // >= 0: the scene has aligned components, their records lie in d_fd and its launches run the family's kExtAligned kernels (-1 = no component is aligned)
     long long map_slots = 0;            // int64 slots the maps add behind the recorders' bins (pvt_scene_map_slots)
+    bool path_maps = false;             // one of the maps is a path-length map (PVT_MAP_PATHLENGTH): the scene's launches run the family's kExtPath kernels
     long long* d_cd = nullptr;          // ray capture: capacity and first row per recorder (KArgs::cap_tab), null = none captured
     long long capture_rows = 0;         // rows of all captures of one tally set (pvt_scene_capture_rows)
     double* d_gd = nullptr;
@@ -364,7 +365,7 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
 // the template arguments of that family's entry points.
 // `carry_out`: the launch parks its survivors for its successor -- its FINAL value, after bind_carry has had its say (a
 // launch too wide to park finishes its own photons, and needs a kernel that can).
-struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align, park; };
+struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align, path, park; };
 Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit, bool carry_out = false) {
     Variant v{};
     v.record = record; v.emit = emit; v.tab = lp.tab;
@@ -377,6 +378,7 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0 || s->al_d >= 0;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.align = s->al_d >= 0;   // (the extension family's kernels that hold the aligned components' code)
+    v.path = s->path_maps;    // (... and those that hold the path-length maps' walk on top of it)
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
     v.park = v.family == PVT_VARIANT_LEAN && !record && carry_out;   // (the entries compiled without the drain and the tail)
@@ -408,6 +410,12 @@ Kernel kernel_of(const Variant& v) {
         switch (v.family) {
         case PVT_VARIANT_ROUGH:
             if constexpr (has_rough) {
+                if (v.path) {   // (the family's kernels compiled with the path-length maps' walk, the aligned components' code included)
+                    if constexpr (T == 1) if (v.grid) return trace_kernel_rough_grid<R, W, E, kExtPath>;
+                    if constexpr (T != 2) if (v.mesh) return trace_kernel_rough<R, T, W, E, true, kExtPath>;
+                    if (!v.mesh) return trace_kernel_rough_w4<R, T, W, E, kExtPath>;
+                    break;
+                }
                 if (v.align) {   // (the family's kernels compiled with the aligned components' code)
                     if constexpr (T == 1) if (v.grid) return trace_kernel_rough_grid<R, W, E, kExtAligned>;
                     if constexpr (T != 2) if (v.mesh) return trace_kernel_rough<R, T, W, E, true, kExtAligned>;
@@ -888,6 +896,7 @@ int create_scene(const SceneInputs& in, int device, PvtScene** out) {
         HIP_TRY(hipMalloc(&s->d_md, packed.md.size() * sizeof(double)));
         HIP_TRY(hipMemcpy(s->d_md, packed.md.data(), packed.md.size() * sizeof(double), hipMemcpyHostToDevice));
         s->map_slots = packed.map_slots;
+        s->path_maps = packed.path_maps;
     }
     if (!packed.pd.empty()) {   // (global memory only: flags and records, the masks right behind them)
         const size_t head = packed.pd.size() * sizeof(double);

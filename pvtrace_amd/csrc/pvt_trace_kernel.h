@@ -67,10 +67,12 @@ enum { RT_W2L = 0, RT_L2W = 9, RT = 18 };                         // Lay::rot_d 
 enum { kFrShape = 0, kFrLower = 3, kFrH = 6, kFrRot = 9, kFrT = 18, kFrComp = 21 };   // a fielded node's record in KArgs::fd:
                                                                  // shape, lower, cell widths, world->local rotation (row-major)
                                                                  // and translation, then one value-table offset per component
-enum { kMnCount = 0, kMnRot = 1, kMnT = 10, kMnRec = 13 };         // a mapped node's block in KArgs::md: its map count, world->local
-                                                                 // rotation (row-major) and translation, then its map records
+enum { kMnCount = 0, kMnRot = 1, kMnT = 10, kMnPath = 13, kMnRec = 14 };   // a mapped node's block in KArgs::md: its map count, world->local
+                                                                 // rotation (row-major) and translation, how many of its maps are
+                                                                 // path-length maps (the marker path_map_call's caller asks), then
+                                                                 // its map records
 enum { kMrKind = 0, kMrComp, kMrShape, kMrLower = 5, kMrH = 8, kMrNw = 11, kMrWlo, kMrWhi, kMrOff, kMr = 16 };   // a map record: event
-                                                                 // kind, component (-1: any), shape, lower, cell widths,
+                                                                 // kind (a PVT_EV_* or PVT_MAP_PATHLENGTH), component (-1: any), shape, lower, cell widths,
                                                                  // wavelength bins (0: no axis) and range, first slot
 enum { CD_QY = 0, CD_TAU_RAD, CD_TAU_NR, CD_PHASE, CD_ABS_SCALE, CD_EMS_SCALE_X, CD_EMS_SCALE_C,
        CD_ABS_RCP, CD_EMS_RCP_X, CD_EMS_RCP_C, CD_ABS_W, CD_EMS_W, CD };   // component doubles (*_RCP: RN(1/spacing) of an evenly spaced table, else NaN;
@@ -268,8 +270,10 @@ struct KArgs {
 // where in fd its record of kAl doubles starts (-1: the component is not aligned): kAlOn != 0, the director in the root's
 // frame, the absorption order S_a, kAlEmit != 0 = the component's phase table is sampled about the director
 // What the extension family's kernels are compiled for (trace_body's ROUGH): kExtOff the other families, kExtRough the
-// family as it is for every scene without alignment, kExtAligned the same with the aligned components' code (UF_ALIGN)
-enum { kExtOff = 0, kExtRough = 1, kExtAligned = 2 };
+// family as it is for every scene without alignment, kExtAligned the same with the aligned components' code (UF_ALIGN),
+// kExtPath that again with the walk of the path-length maps at the advance site (UF_PMAP; path_map_call) -- the family's
+// fullest kernels: a scene with a path-length map runs them whether it has aligned components or not
+enum { kExtOff = 0, kExtRough = 1, kExtAligned = 2, kExtPath = 3 };
 enum { kAlOn = 0, kAlAxis = 1, kAlOrder = 4, kAlEmit = 5, kAl = 6 };
 constexpr int kCapWords = 12;  // u64 words of a captured row (PvtCaptures): index, position, direction, wavelength, path, clock,
                                // source | recorder << 32, the photon's event counters (kCountBits each)
@@ -974,6 +978,86 @@ __device__ __attribute__((noinline)) void volume_map_call(const double* __restri
     }
 }
 
+// Path-length maps (PvtMapTables, map kind PVT_MAP_PATHLENGTH; include/pvtrace_hip.h states the contract, the Python VolumeMap
+// and tally.map_histories walk the same way, operation for operation; the build has no FMA contraction): one SEGMENT of a
+// lane -- from the world position (px, py, pz) along the unit direction (dx, dy, dz) for `len` = the advance, while its
+// container is the node whose block is `r` (kMn*) -- laid into every path-length map of that node.  The local start and
+// direction are formed once, ((R0 x + R1 y) + R2 z) + t and (R0 dx + R1 dy) + R2 dz.  Per map the walk is field_march_call's,
+// on a lattice that has one half-infinite slab more on either side of each axis (cells -1 and n: nothing is clamped, the map
+// may be smaller than its node): a piece of length l adds k = (int64)(l 2^30 + 0.5) units with ONE no-return 64-bit integer
+// atomic in global memory, on the cell's slot when the cell lies in the lattice and the wavelength `wl` the photon travels
+// with in the map's range, else on the map's `outside` slot; k = 0 adds nothing.  `slots`: where the maps' block of the
+// lane's tally set starts.  A FUNCTION, called only from the kExtPath kernels' advance site.
+__device__ __attribute__((noinline)) void path_map_call(const double* __restrict__ r, unsigned long long* __restrict__ slots,
+                                                        double px, double py, double pz, double dx, double dy, double dz,
+                                                        double len, double wl) {
+    if (!(len > 0.0) || !(len < INFINITY)) return;   // (NaN, <= 0 or infinite: nothing)
+    const int count = (int)r[kMnCount];
+    const double lpx = ((r[kMnRot + 0] * px + r[kMnRot + 1] * py) + r[kMnRot + 2] * pz) + r[kMnT + 0];
+    const double lpy = ((r[kMnRot + 3] * px + r[kMnRot + 4] * py) + r[kMnRot + 5] * pz) + r[kMnT + 1];
+    const double lpz = ((r[kMnRot + 6] * px + r[kMnRot + 7] * py) + r[kMnRot + 8] * pz) + r[kMnT + 2];
+    const double lux = (r[kMnRot + 0] * dx + r[kMnRot + 1] * dy) + r[kMnRot + 2] * dz;
+    const double luy = (r[kMnRot + 3] * dx + r[kMnRot + 4] * dy) + r[kMnRot + 5] * dz;
+    const double luz = (r[kMnRot + 6] * dx + r[kMnRot + 7] * dy) + r[kMnRot + 8] * dz;
+    // one axis of the lattice in the node's frame: the cell the segment is in (-1 and n: the slabs outside) and the
+    // parameter of the plane ahead (INFINITY: none)
+    struct Axis {
+        double p, d, lo, h, t;
+        int n, c, step;
+        __device__ double next() const {
+            const int i = step > 0 ? c + 1 : c;   // the plane ahead: lower + i h, there when 0 <= i <= n
+            if (step == 0 || i < 0 || i > n) return INFINITY;
+            return (lo + (double)i * h - p) / d;
+        }
+    };
+    for (int m = 0; m < count; m++) {
+        const double* __restrict__ q = r + kMnRec + m * kMr;
+        if ((int)q[kMrKind] != PVT_MAP_PATHLENGTH) continue;
+        const int nw = (int)q[kMrNw];
+        const long long nwc = nw > 0 ? nw : 1;
+        bool wl_in = true;
+        long long iw = 0;
+        if (nw > 0) {   // a Histogram's rule, as in volume_map_call; out of range: the whole segment goes to `outside`
+            const double qw = (wl - q[kMrWlo]) / (q[kMrWhi] - q[kMrWlo]) * (double)nw;
+            wl_in = qw > -1.0 && qw < (double)nw;
+            if (wl_in) iw = (long long)qw;
+        }
+        auto axis = [&](int a, double p, double d) -> Axis {
+            Axis x;
+            x.p = p; x.d = d;
+            x.lo = q[kMrLower + a];
+            x.h = q[kMrH + a];
+            x.n = (int)q[kMrShape + a];
+            const double f = __builtin_floor((x.p - x.lo) / x.h);
+            x.c = (int)__builtin_fmin(__builtin_fmax(f, -1.0), (double)x.n);   // (NaN: cell -1)
+            x.step = x.d > 0.0 ? 1 : (x.d < 0.0 ? -1 : 0);
+            x.t = x.next();
+            return x;
+        };
+        Axis X = axis(0, lpx, lux), Y = axis(1, lpy, luy), Z = axis(2, lpz, luz);
+        unsigned long long* __restrict__ base = slots + (long long)q[kMrOff];
+        const long long outside = (long long)X.n * (long long)Y.n * (long long)Z.n * nwc;
+        double s = 0.0;
+        for (;;) {
+            // (a plane that rounding puts a hair behind the segment's start is crossed at zero length)
+            const double tmin = __builtin_fmin(__builtin_fmin(X.t, Y.t), Z.t);
+            const double sout = __builtin_fmax(__builtin_fmin(tmin, len), s);
+            const long long k = (long long)((sout - s) * 1073741824.0 + 0.5);
+            if (k != 0) {
+                const bool inside = wl_in && X.c >= 0 && X.c < X.n && Y.c >= 0 && Y.c < Y.n && Z.c >= 0 && Z.c < Z.n;
+                const long long slot = inside ? (((long long)X.c * Y.n + Y.c) * Z.n + Z.c) * nwc + iw : outside;
+                atomicAdd(base + slot, (unsigned long long)k);
+            }
+            if (!(sout < len)) break;
+            // the nearest plane is crossed (ties: one axis per pass, X then Y then Z, the others at zero length)
+            if (X.t == tmin) { X.c += X.step; X.t = X.next(); }
+            else if (Y.t == tmin) { Y.c += Y.step; Y.t = Y.next(); }
+            else { Z.c += Z.step; Z.t = Z.next(); }
+            s = sout;
+        }
+    }
+}
+
 // same, tables in global memory (emitter spectra)
 __device__ __forceinline__ double interp_global(const double* xs, const double* ys, int n, double x) {
     if (n == 1) return ys[0];
@@ -1462,7 +1546,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT, UF_ALIGN };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT, UF_ALIGN, UF_PMAP };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1477,14 +1561,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.count >= 1 ? 1u << UF_COUNT : 0u) | (ROUGH && A.count >= 2 ? 1u << UF_TQ_COUNT : 0u) |   // ... and count ...
         (ROUGH && A.origin != 0 ? 1u << UF_ORIGIN : 0u) |   // ... and origin ...
         (ROUGH && A.pd_d >= 0 ? 1u << UF_CPAT : 0u) |   // ... and pd_d ...
-        (ROUGH == kExtAligned ? 1u << UF_ALIGN : 0u);   // ... UF_ALIGN is the kernel's own: compiled in, not read)
+        (ROUGH >= kExtAligned ? 1u << UF_ALIGN : 0u) |   // ... UF_ALIGN is the kernel's own: compiled in, not read ...
+        (ROUGH == kExtPath && A.md != nullptr ? 1u << UF_PMAP : 0u);   // ... UF_PMAP too: the kExtPath kernels of a scene with maps)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT || bit == UF_ALIGN) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT || bit == UF_ALIGN || bit == UF_PMAP) return false;
             if (bit == UF_BY_NODE) return true;
         }
         unsigned int f = uflags;
@@ -2885,7 +2970,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     const double tau = -pvt_log(1.0 - rng_uniform(rng));
                     if (uf(UF_FIELD)) frec = (int)A.fd[container];
                     if (frec >= 0) {
-                        const FieldMarch fm = field_march_call<TAB_LDS, ROUGH == kExtAligned>(T, A.fd, frec, L.comp_i + crec * CI, L.comp_d + crec * CD, ccount,
+                        const FieldMarch fm = field_march_call<TAB_LDS, ROUGH >= kExtAligned>(T, A.fd, frec, L.comp_i + crec * CI, L.comp_d + crec * CD, ccount,
                                                                         wl, pos.x, pos.y, pos.z, dir.x, dir.y, dir.z, tau, t0);
                         depth = fm.depth;
                         if (fm.depth < t0) { alpha = fm.alpha; pre0 = fm.pre0; fcell = fm.cell; }
@@ -2896,6 +2981,17 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             }
             {
                 const double adv = __builtin_fmin(depth, t0);   // (depth == t0 is a surface event: same value)
+                if constexpr (ROUGH == kExtPath) {
+                    // ---- path-length maps (PvtMapTables, PVT_MAP_PATHLENGTH): the segment pos -> pos + adv dir, BEFORE the
+                    // advance, is laid cell by cell into the path-length maps of `container` -- only for the lanes whose
+                    // container's block says it has one (kMnPath), in the maps' block of the lane's tally set
+                    if (uf(UF_PMAP)) {
+                        const int mat = (int)A.md[container];
+                        if (mat >= 0 && A.md[mat + kMnPath] != 0.0)
+                            path_map_call(A.md + mat, reinterpret_cast<unsigned long long*>(A.rec_bins) + (long long)set * A.set_stride_i + A.total_bins,
+                                          pos.x, pos.y, pos.z, dir.x, dir.y, dir.z, adv, wl);
+                    }
+                }
                 pos.x = pos.x + dir.x * adv; pos.y = pos.y + dir.y * adv; pos.z = pos.z + dir.z * adv;
                 travelled += adv;
                 duration += div_known(adv * n_container, kCcm, kRcpCcm);
@@ -2939,7 +3035,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                                                                   T.dv(cd + CD_ABS_RCP), T.dv(cd + CD_ABS_W));
                             if constexpr (ROUGH) {   // (a lattice: the cell's concentration of the component)
                                 if (frec >= 0) {   // (... or, PvtAlignTables, the component's factor along the photon's direction)
-                                    if constexpr (ROUGH == kExtAligned) term = align_term(A.fd, frec, k, fcell, term, dir.x, dir.y, dir.z);
+                                    if constexpr (ROUGH >= kExtAligned) term = align_term(A.fd, frec, k, fcell, term, dir.x, dir.y, dir.z);
                                     else term = term * A.fd[(int)A.fd[frec + kFrComp + k] + fcell];
                                 }
                             }
@@ -3072,7 +3168,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         u3 = g2;
                     }
                     if (tabled) {   // about the incoming direction (PvtPhaseTables)
-                        if constexpr (ROUGH == kExtAligned) {   // ... or about the director of an aligned emitter (PvtAlignTables)
+                        if constexpr (ROUGH >= kExtAligned) {   // ... or about the director of an aligned emitter (PvtAlignTables)
                             double ax = dir.x, ay = dir.y, az = dir.z;
                             align_axis(A.fd, frec, cu - cbase, ax, ay, az);
                             if constexpr (MESH || SEENW == 1) dir = phase_table_turn_call(ptab, wl, u1, em_turn, u3, ax, ay, az);

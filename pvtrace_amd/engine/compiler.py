@@ -819,8 +819,8 @@ class CompiledScene:
     # -- volume maps -----------------------------------------------------
     def _lower_maps(self, root, nodes):
         """VolumeMap specs -> per-node runs (node_map_start / node_map_count) and one record per map, in node order:
-        the event kind, the component id (-1: any), shape, lower, cell widths h = (upper - lower) / n, wavelength bins
-        (0: no axis) and range, and the map's first slot in the maps' block, which follows the recorders' bins in the
+        the event kind (or the path-length kind), the component id (-1: any; always -1 for a path-length map), shape,
+        lower, cell widths h = (upper - lower) / n, wavelength bins (0: no axis) and range, and the map's first slot in the maps' block, which follows the recorders' bins in the
         int64 tally buffer (`map_slots` slots in all; `total_bins` keeps the reference's meaning)."""
         for node in root.preorder():
             if node.geometry is None and getattr(node, "volume_maps", None):
@@ -844,6 +844,10 @@ class CompiledScene:
                     raise UnsupportedSceneError(
                         f"VolumeMap {spec.name!r}: unknown event {spec.event!r}; use one of {sorted(MAP_EVENTS)}.")
                 component = -1
+                if spec.event == "pathlength" and spec.component is not None:
+                    raise UnsupportedSceneError(
+                        f"VolumeMap {spec.name!r}: a path-length map takes no component filter "
+                        f"(component={spec.component!r}).")
                 if spec.component is not None:
                     first, n = int(self.comp_start[i]), int(self.comp_count[i])
                     own = self.component_names[first:first + n]

@@ -280,7 +280,12 @@ class CapturedRays:
 
 
 # volume-map selector -> the event-log kind it counts (include/pvtrace_hip.h PVT_EV_*; light.Event has the same values)
-MAP_EVENTS = {"absorbed": 3, "emitted": 6, "scattered": 5, "lost": 4, "reacted": 8}
+# ... and "pathlength", which is no event: the kind of a path-length map (include/pvtrace_hip.h PVT_MAP_PATHLENGTH, a
+# value that is no PVT_EV_*)
+MAP_PATHLENGTH = 100
+MAP_EVENTS = {"absorbed": 3, "emitted": 6, "scattered": 5, "lost": 4, "reacted": 8, "pathlength": MAP_PATHLENGTH}
+# the length, in the scene's length unit, that one count of a path-length map stands for (PVT_FLUENCE_UNIT)
+FLUENCE_UNIT = 2.0 ** -30
 # slots (cells x wavelength bins, plus one `outside` slot per map) the maps of one scene may hold: 512 MiB of int64
 # counts per tally set (include/pvtrace_hip.h PVT_MAX_MAP_SLOTS)
 MAX_MAP_SLOTS = 1 << 26
@@ -295,8 +300,10 @@ class VolumeMap:
     lower,upper the lattice's box in the NODE's own frame, finite, lower < upper on each axis (both required, as for a
                 `ConcentrationGrid`; `VolumeMap.like(grid, name, ...)` copies a grid's lattice).  The root carries no map.
     event       "absorbed", "emitted", "scattered", "lost" or "reacted": the event-log kinds ABSORB, EMIT, SCATTER,
-                NONRADIATIVE, REACT, restricted to events whose `container` is this node
+                NONRADIATIVE, REACT, restricted to events whose `container` is this node; or "pathlength": no event but
+                the path photons travel in each voxel (below)
     component   None, or the name of one of the node's components: only events whose `component` column names it
+                (refused together with "pathlength": a path belongs to no component)
     wavelength  None, or (start, stop, bins): a fourth axis binned by `Histogram`'s rule on the wavelength column of the
                 event's row (the incoming wavelength for absorbed / lost / reacted / scattered, the new one for emitted)
 
@@ -316,6 +323,39 @@ class VolumeMap:
     8. No clamping: unlike a concentration field a map may be a region of interest smaller than its node, and clamping
        would pile the rest into its edge cells.
     9. Hence ``counts.sum() + outside`` is the number of matching events in the node.
+
+    A PATH-LENGTH map (``event="pathlength"``) holds the path photons travel in each voxel, the track-length estimator of
+    the fluence: multiplied by any absorption coefficient it is the local absorption rate of any species, present or not,
+    and where alpha h << 1 its variance is far below that of the `absorbed` counts.  Lengths are accumulated as fixed-point
+    integers, one count = `FLUENCE_UNIT` = 2^-30 of the scene's length unit, so the map is as exact and as independent of
+    summation order, launch geometry, carrying and GPU count as the others.  A slot wraps at 2^63 units, about 8.6e9 length
+    units; the `outside` slot of a small region of interest inside a large node is the first to get there.  The contract
+    (include/pvtrace_hip.h, PvtMapTables, states the same; the kernel and `engine.tally.map_histories` follow it operation
+    for operation, without FMA):
+
+    1. A *segment* is one advance of a photon: from world position x along unit direction d for length L, while the
+       photon's container is the map's node.  A segment with non-finite L, or L <= 0, adds nothing.
+    2. Local start: p_a = ((R[a][0] x + R[a][1] y) + R[a][2] z) + t[a].
+    3. Local direction: u_a = (R[a][0] dx + R[a][1] dy) + R[a][2] dz.
+    4. R and t are the node's `world_to_local` rows.
+    5. Per axis the planes are lower_a + i h_a for i = 0 ... n_a, written ``lower + float(i) * h``.  The cell index c_a
+       runs over -1 ... n_a; -1 and n_a are the two half-infinite slabs outside the lattice.
+    6. Start: c_a = clamp(floor((p_a - lower_a) / h_a), -1, n_a).  A NaN gives -1.
+    7. step_a is the sign of u_a; 0 means the axis never crosses.
+    8. The plane ahead is i = c_a + 1 for a positive step and i = c_a for a negative one; it exists when 0 <= i <= n_a, and
+       its parameter is (lower_a + i h_a - p_a) / u_a.  Otherwise the parameter is +inf.
+    9. The loop is that of a `ConcentrationGrid`'s march.  Start with s = 0.  In each pass tmin is the least of the three
+       parameters; sout = max(min(tmin, L), s); the piece sout - s belongs to the current cell; stop when not (sout < L);
+       otherwise cross ONE axis whose parameter equals tmin -- ties in the order X, then Y, then Z, the others follow at
+       zero length -- and then s = sout.
+    10. A piece of length l adds k = int(l * 2^30 + 0.5).  Nothing is added when k = 0.
+    11. The piece goes to slot ((cx ny + cy) nz + cz) nw' + iw when every c_a is in 0 ... n_a - 1 and the wavelength bin
+        is in range, otherwise to the map's single `outside` slot.
+    12. With a wavelength axis iw is a `Histogram`'s bin of the wavelength the photon travels with; out of range means
+        the whole segment goes to `outside`.
+    13. No clamping: a map may be smaller than its node.
+    14. Hence (sum of all slots) * `FLUENCE_UNIT` is the path length travelled inside the node, to within half a unit per
+        piece.
     """
 
     def __init__(self, name, shape, lower, upper, event="absorbed", component=None, wavelength=None):
@@ -338,6 +378,9 @@ class VolumeMap:
             wavelength = Histogram("wavelength", start, stop, bins)
             _require(math.isfinite(wavelength.start) and math.isfinite(wavelength.stop),
                      f"VolumeMap {name!r}: the wavelength range must be finite")
+        _require(event != "pathlength" or component is None,
+                 f"VolumeMap {name!r}: a path-length map takes no component filter (component={component!r}): the path "
+                 f"a photon travels belongs to no component")
         self.name, self.shape, self.lower, self.upper = name, dims, lo, hi
         self.event, self.component, self.wavelength = event, component, wavelength
 
@@ -368,7 +411,12 @@ class VolumeMap:
 class VolumeMapResult:
     """Counts of one `VolumeMap`: `counts` (int64, shape (nx, ny, nz) or (nx, ny, nz, nw)), `outside` (matching events
     of the node that fell outside the lattice or the wavelength range), `total` = counts.sum() + outside, and the
-    lattice: `shape`, `lower`, `upper`, `cell_volume`."""
+    lattice: `shape`, `lower`, `upper`, `cell_volume`.
+
+    `unit` is what one count stands for: 1 for an event map, `FLUENCE_UNIT` for a path-length map, whose `counts` and
+    `outside` are the raw, exact int64 units.  `pathlength` = counts * unit (float64, the path travelled in each cell in
+    the scene's length unit) and `fluence` = pathlength / cell_volume: path length per volume, summed over the launch's
+    photons -- dividing by the photon count is the caller's job."""
 
     def __init__(self, spec, slots):
         import numpy as np
@@ -384,6 +432,20 @@ class VolumeMapResult:
     @property
     def total(self):
         return int(self.counts.sum()) + self.outside
+
+    @property
+    def unit(self):
+        return FLUENCE_UNIT if self.spec.event == "pathlength" else 1
+
+    @property
+    def pathlength(self):
+        import numpy as np
+
+        return self.counts * np.float64(self.unit)
+
+    @property
+    def fluence(self):
+        return self.pathlength / self.cell_volume
 
     @property
     def shape(self):

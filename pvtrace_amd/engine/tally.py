@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from pvtrace_amd.engine.recorder import Heatmap
+from pvtrace_amd.engine.recorder import MAP_PATHLENGTH, Heatmap
 from pvtrace_amd.light import Event
 
 # recorder selector -> (history event, metadata keys that must all name the recorder's node)
@@ -208,19 +208,131 @@ def capture_histories(scene, histories, ray_offset=0, indices=None):
     return out
 
 
+def path_segment_pieces(p, u, length, lower, h, shape):
+    """The pieces of one segment in one lattice, by the path-length contract of the `VolumeMap` docstring (items 5-10), in
+    pure Python floats and in the contract's operation order: `p`, `u` the local start and direction, `length` = L.
+    Returns [((cx, cy, cz), units)] for every piece with units != 0, in walking order; a cell index of -1 or n is a slab
+    outside the lattice."""
+    inf = math.inf
+    if not (length > 0.0) or not (length < inf):
+        return []
+    c, step, t = [0, 0, 0], [0, 0, 0], [inf, inf, inf]
+
+    def ahead(a):
+        i = c[a] + 1 if step[a] > 0 else c[a]
+        if step[a] == 0 or i < 0 or i > shape[a]:
+            return inf
+        return (lower[a] + float(i) * h[a] - p[a]) / u[a]
+
+    for a in range(3):
+        f = (p[a] - lower[a]) / h[a]
+        # clamp(floor(f), -1, n); a NaN gives -1
+        c[a] = -1 if not (f >= -1.0) else (shape[a] if f >= float(shape[a]) else int(math.floor(f)))
+        step[a] = 1 if u[a] > 0.0 else (-1 if u[a] < 0.0 else 0)
+        t[a] = ahead(a)
+    pieces, s = [], 0.0
+    while True:
+        tmin = _fmin(_fmin(t[0], t[1]), t[2])
+        sout = _fmin(tmin, length)
+        sout = sout if sout > s else s          # max(min(tmin, L), s); min(NaN, L) = L as the kernel's fmin gives
+        k = int((sout - s) * 1073741824.0 + 0.5)
+        if k != 0:
+            pieces.append(((c[0], c[1], c[2]), k))
+        if not (sout < length):
+            break
+        a = 0 if t[0] == tmin else (1 if t[1] == tmin else 2)
+        c[a] += step[a]
+        t[a] = ahead(a)
+        s = sout
+    return pieces
+
+
+def _fmin(a, b):
+    """C's fmin: the other operand when one is a NaN."""
+    if a != a:
+        return b
+    if b != b:
+        return a
+    return a if a < b else b
+
+
+def path_map_slots(compiled, histories):
+    """(slots, pieces) of the compiled scene's path-length maps from one history per ray: two int64 arrays laid out as
+    the maps' block (`CompiledScene.map_offset`), the units every slot holds and how many pieces put them there (what a
+    comparison with another walk of the same histories may differ by, one unit each).  The event maps' slots stay 0."""
+    slots = np.zeros(compiled.map_slots, dtype=np.int64)
+    pieces = np.zeros(compiled.map_slots, dtype=np.int64)
+    mapped = {compiled.node_names[i]: i for i in range(len(compiled.node_names)) if compiled.node_map_count[i] > 0}
+    _path_maps(compiled, histories, mapped, slots, pieces)
+    return slots, pieces
+
+
+def _path_maps(compiled, histories, mapped, slots, pieces=None):
+    """The path-length maps' part of `map_histories`: every segment of every history, walked into `slots`."""
+    records = {}   # node index -> (world_to_local rows as Python floats, [(offset, shape, lower, h, nw, wl_start, wl_stop)])
+    for i in mapped.values():
+        first = int(compiled.node_map_start[i])
+        maps = []
+        for m in range(first, first + int(compiled.node_map_count[i])):
+            if int(compiled.map_kind[m]) != MAP_PATHLENGTH:
+                continue
+            maps.append((int(compiled.map_offset[m]), tuple(int(n) for n in compiled.map_shape[m]),
+                         tuple(float(v) for v in compiled.map_lower[m]), tuple(float(v) for v in compiled.map_h[m]),
+                         int(compiled.map_nw[m]), float(compiled.map_wl_start[m]), float(compiled.map_wl_stop[m])))
+        if maps:
+            records[i] = ([[float(v) for v in row] for row in compiled.world_to_local[i][:3]], maps)
+    if not records:
+        return
+    for history in histories:
+        history = list(history)
+        for (ray, _, _), (after, _, meta) in zip(history, history[1:]):
+            record = records.get(mapped.get((meta or {}).get("container")))
+            if record is None:
+                continue
+            length = float(after.travelled) - float(ray.travelled)
+            if not (length > 0.0) or not (length < math.inf):
+                continue
+            w2l, maps = record
+            x, y, z = (float(v) for v in ray.position)
+            dx, dy, dz = (float(v) for v in ray.direction)
+            p = [((w2l[a][0] * x + w2l[a][1] * y) + w2l[a][2] * z) + w2l[a][3] for a in range(3)]
+            u = [(w2l[a][0] * dx + w2l[a][1] * dy) + w2l[a][2] * dz for a in range(3)]
+            wl = float(ray.wavelength)
+            for at, shape, lower, h, nw, wl_start, wl_stop in maps:
+                nwc, iw, wl_in = max(nw, 1), 0, True
+                if nw > 0:   # a Histogram's rule; out of range: the whole segment goes to `outside`
+                    q = (wl - wl_start) / (wl_stop - wl_start) * float(nw)
+                    wl_in = q > -1.0 and q < float(nw)
+                    iw = int(q) if wl_in else 0
+                outside = shape[0] * shape[1] * shape[2] * nwc
+                for (cx, cy, cz), k in path_segment_pieces(p, u, length, lower, h, shape):
+                    inside = wl_in and 0 <= cx < shape[0] and 0 <= cy < shape[1] and 0 <= cz < shape[2]
+                    slot = at + (((cx * shape[1] + cy) * shape[2] + cz) * nwc + iw if inside else outside)
+                    slots[slot] += k
+                    if pieces is not None:
+                        pieces[slot] += 1
+
+
 def map_histories(scene, histories):
     """{map name: VolumeMapResult} from one history per ray: the scene's `VolumeMap`s binned on the host, in numpy, by
     the contract stated in the `VolumeMap` docstring -- every event of the map's kind whose container is the map's node,
     local point ((R0 x + R1 y) + R2 z) + t from the COMPILED scene's `world_to_local` rows (the tables the kernel reads,
     not a second composition of the node tree), i = floor((p - lower) / h), no clamping, one `outside` slot.  The host
-    path for `follow(backend="host")` users, and the referee of the kernel's maps."""
+    path for `follow(backend="host")` users, and the referee of the kernel's maps.
+
+    Path-length maps (``event="pathlength"``) are walked by `path_segment_pieces`, in pure Python floats: a ray's segments
+    are consecutive rows k, k + 1 of its history -- from row k's position along row k's direction, with row k's
+    wavelength, for L = `travelled` of row k + 1 minus that of row k, in the node row k + 1 names as its `container`."""
     from pvtrace_amd.engine.api import maps_from_slots
     from pvtrace_amd.engine.compiler import compile_scene
 
     compiled = scene if hasattr(scene, "map_specs") else compile_scene(scene)
     if not compiled.has_maps:
         return {}
-    kinds = sorted(set(int(k) for k in compiled.map_kind))
+    kinds = sorted(set(int(k) for k in compiled.map_kind) - {MAP_PATHLENGTH})
+    has_path = any(int(k) == MAP_PATHLENGTH for k in compiled.map_kind)
+    if has_path:
+        histories = list(histories)   # (walked a second time below)
     mapped = {compiled.node_names[i]: i for i in range(len(compiled.node_names)) if compiled.node_map_count[i] > 0}
     # the events a map can count, per node: kind, component name, world position, wavelength
     rows = {i: ([], [], [], []) for i in mapped.values()}
@@ -238,6 +350,8 @@ def map_histories(scene, histories):
             pos.append(tuple(float(v) for v in ray.position))
             wl.append(float(ray.wavelength))
     slots = np.zeros(compiled.map_slots, dtype=np.int64)
+    if has_path:
+        _path_maps(compiled, histories, mapped, slots)
     for i, (kind, comp, pos, wl) in rows.items():
         kind = np.array(kind, dtype=np.int64)
         x = np.array(pos, dtype=np.float64).reshape(len(pos), 3)
@@ -248,6 +362,8 @@ def map_histories(scene, histories):
         first = int(compiled.node_map_start[i])
         for m in range(first, first + int(compiled.node_map_count[i])):
             spec = compiled.map_specs[m]
+            if int(compiled.map_kind[m]) == MAP_PATHLENGTH:
+                continue
             match = kind == int(compiled.map_kind[m])
             if spec.component is not None:
                 match &= np.array([c == spec.component for c in comp], dtype=bool)
