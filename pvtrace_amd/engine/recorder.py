@@ -10,6 +10,9 @@ Numeric ids are part of the device ABI (include/pvtrace_hip.h) and equal the
 reference's (pvtrace/engine/recorder.py:33-53; kernel side _kernel.pyx:166-172,
 :482-498).
 """
+import math
+
+from pvtrace_amd.lattice import Lattice
 
 # property id -> what the histogram axis measures.  x/y/z are in the frame of
 # the node that owns the recorder.
@@ -359,20 +362,8 @@ class VolumeMap:
     """
 
     def __init__(self, name, shape, lower, upper, event="absorbed", component=None, wavelength=None):
-        import math
-
         _require(event in MAP_EVENTS, f"Unknown volume-map event {event!r}; use one of {sorted(MAP_EVENTS)}")
-        try:
-            dims = tuple(int(n) for n in shape)
-        except TypeError:
-            dims = ()
-        _require(len(dims) == 3 and all(float(n) == float(m) for n, m in zip(dims, shape)),
-                 f"VolumeMap {name!r}: shape must be three integers (nx, ny, nz), got {shape!r}")
-        _require(all(n >= 1 for n in dims), f"VolumeMap {name!r}: shape must be >= 1 on each axis, got {dims}")
-        lo, hi = tuple(float(v) for v in lower), tuple(float(v) for v in upper)
-        _require(len(lo) == 3 and len(hi) == 3, f"VolumeMap {name!r}: lower and upper must have three coordinates")
-        _require(all(math.isfinite(v) for v in lo + hi), f"VolumeMap {name!r}: lower and upper must be finite, got {lo} {hi}")
-        _require(all(a < b for a, b in zip(lo, hi)), f"VolumeMap {name!r}: needs lower < upper on each axis, got {lo} {hi}")
+        self.lattice = Lattice(shape, lower, upper, f"VolumeMap {name!r}")
         if wavelength is not None:
             start, stop, bins = wavelength
             wavelength = Histogram("wavelength", start, stop, bins)
@@ -381,18 +372,18 @@ class VolumeMap:
         _require(event != "pathlength" or component is None,
                  f"VolumeMap {name!r}: a path-length map takes no component filter (component={component!r}): the path "
                  f"a photon travels belongs to no component")
-        self.name, self.shape, self.lower, self.upper = name, dims, lo, hi
+        self.name, self.shape, self.lower, self.upper = name, self.lattice.shape, self.lattice.lower, self.lattice.upper
         self.event, self.component, self.wavelength = event, component, wavelength
 
     @classmethod
     def like(cls, grid, name, **kwargs):
-        """A map on the lattice (shape, lower, upper) of a `ConcentrationGrid`."""
-        return cls(name, tuple(grid.shape), tuple(float(v) for v in grid.lower), tuple(float(v) for v in grid.upper), **kwargs)
+        """A map on the lattice (shape, lower, upper) of a `ConcentrationGrid`, or of anything that exposes a `lattice`."""
+        return cls(name, grid.lattice.shape, grid.lattice.lower, grid.lattice.upper, **kwargs)
 
     @property
     def cell_widths(self):
         """h = (upper - lower) / n per axis, the widths the binning divides by."""
-        return tuple((b - a) / float(n) for a, b, n in zip(self.lower, self.upper, self.shape))
+        return self.lattice.h
 
     @property
     def wavelength_bins(self):

@@ -19,6 +19,7 @@ import math
 import numpy as np
 
 from pvtrace_amd.engine.recorder import MAP_PATHLENGTH, Heatmap
+from pvtrace_amd.lattice import cell_inside, slot as lattice_slot, walk
 from pvtrace_amd.light import Event
 
 # recorder selector -> (history event, metadata keys that must all name the recorder's node)
@@ -213,47 +214,10 @@ def path_segment_pieces(p, u, length, lower, h, shape):
     pure Python floats and in the contract's operation order: `p`, `u` the local start and direction, `length` = L.
     Returns [((cx, cy, cz), units)] for every piece with units != 0, in walking order; a cell index of -1 or n is a slab
     outside the lattice."""
-    inf = math.inf
-    if not (length > 0.0) or not (length < inf):
+    if not (length > 0.0) or not (length < math.inf):
         return []
-    c, step, t = [0, 0, 0], [0, 0, 0], [inf, inf, inf]
-
-    def ahead(a):
-        i = c[a] + 1 if step[a] > 0 else c[a]
-        if step[a] == 0 or i < 0 or i > shape[a]:
-            return inf
-        return (lower[a] + float(i) * h[a] - p[a]) / u[a]
-
-    for a in range(3):
-        f = (p[a] - lower[a]) / h[a]
-        # clamp(floor(f), -1, n); a NaN gives -1
-        c[a] = -1 if not (f >= -1.0) else (shape[a] if f >= float(shape[a]) else int(math.floor(f)))
-        step[a] = 1 if u[a] > 0.0 else (-1 if u[a] < 0.0 else 0)
-        t[a] = ahead(a)
-    pieces, s = [], 0.0
-    while True:
-        tmin = _fmin(_fmin(t[0], t[1]), t[2])
-        sout = _fmin(tmin, length)
-        sout = sout if sout > s else s          # max(min(tmin, L), s); min(NaN, L) = L as the kernel's fmin gives
-        k = int((sout - s) * 1073741824.0 + 0.5)
-        if k != 0:
-            pieces.append(((c[0], c[1], c[2]), k))
-        if not (sout < length):
-            break
-        a = 0 if t[0] == tmin else (1 if t[1] == tmin else 2)
-        c[a] += step[a]
-        t[a] = ahead(a)
-        s = sout
-    return pieces
-
-
-def _fmin(a, b):
-    """C's fmin: the other operand when one is a NaN."""
-    if a != a:
-        return b
-    if b != b:
-        return a
-    return a if a < b else b
+    units = ((cell, int((sout - s) * 1073741824.0 + 0.5)) for cell, s, sout in walk(p, u, length, lower, h, shape, slabs=True))
+    return [(cell, k) for cell, k in units if k != 0]
 
 
 def path_map_slots(compiled, histories):
@@ -307,7 +271,7 @@ def _path_maps(compiled, histories, mapped, slots, pieces=None):
                 outside = shape[0] * shape[1] * shape[2] * nwc
                 for (cx, cy, cz), k in path_segment_pieces(p, u, length, lower, h, shape):
                     inside = wl_in and 0 <= cx < shape[0] and 0 <= cy < shape[1] and 0 <= cz < shape[2]
-                    slot = at + (((cx * shape[1] + cy) * shape[2] + cz) * nwc + iw if inside else outside)
+                    slot = at + (lattice_slot(shape, (cx, cy, cz)) * nwc + iw if inside else outside)
                     slots[slot] += k
                     if pieces is not None:
                         pieces[slot] += 1
@@ -317,7 +281,7 @@ def map_histories(scene, histories):
     """{map name: VolumeMapResult} from one history per ray: the scene's `VolumeMap`s binned on the host, in numpy, by
     the contract stated in the `VolumeMap` docstring -- every event of the map's kind whose container is the map's node,
     local point ((R0 x + R1 y) + R2 z) + t from the COMPILED scene's `world_to_local` rows (the tables the kernel reads,
-    not a second composition of the node tree), i = floor((p - lower) / h), no clamping, one `outside` slot.  The host
+    not a second composition of the node tree), `lattice.cell_inside` per axis, no clamping, one `outside` slot.  The host
     path for `follow(backend="host")` users, and the referee of the kernel's maps.
 
     Path-length maps (``event="pathlength"``) are walked by `path_segment_pieces`, in pure Python floats: a ray's segments
@@ -372,8 +336,7 @@ def map_histories(scene, histories):
             with np.errstate(invalid="ignore"):
                 for a in range(3):
                     n = int(compiled.map_shape[m, a])
-                    f = np.floor((local[a] - compiled.map_lower[m, a]) / compiled.map_h[m, a])
-                    ok = (f >= 0.0) & (f <= n - 1.0)
+                    ok, f = cell_inside(local[a], compiled.map_lower[m, a], compiled.map_h[m, a], n)
                     inside &= ok
                     cell = cell * n + np.where(ok, f, 0.0).astype(np.int64)
                 nw = int(compiled.map_nw[m])

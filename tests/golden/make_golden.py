@@ -844,7 +844,134 @@ def make_recorder_ids():
     print("recorder_ids.json")
 
 
+def lattice_walk_cases(shape, seed):
+    """The seeded lattice and rays of one shape for lattice_walk.npz: (values, lower, upper, p, u, length, tau)."""
+    rng = np.random.default_rng(seed)
+    n = np.array(shape, dtype=np.float64)
+    # bounds that are not symmetric about 0; x and y share lower and h where the shape allows a true diagonal tie
+    lower = np.array([-0.75, -0.75, 0.125]) if shape[0] == shape[1] else np.array([-0.75, 0.375, -2.0])
+    upper = lower + (np.array([1.0, 1.0, 0.375]) * n if shape[0] == shape[1] else np.array([2.5, 1.0, 3.0]))
+    h = (upper - lower) / n
+    values = rng.uniform(0.0, 3.0, size=shape) * (rng.uniform(size=shape) > 0.2)
+    diag = float(np.linalg.norm(upper - lower))
+
+    def unit(v):
+        return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+    def inside(k):
+        return lower + rng.uniform(0.02, 0.98, size=(k, 3)) * (upper - lower)
+
+    ps, us, ls = [], [], []
+
+    def add(p, u, length):
+        ps.append(np.asarray(p, dtype=np.float64)); us.append(np.asarray(u, dtype=np.float64))
+        ls.append(np.broadcast_to(np.asarray(length, dtype=np.float64), (len(p),)).copy())
+
+    k = 120   # generic: starts in and around the box, any direction
+    add(lower + rng.uniform(-0.3, 1.3, size=(k, 3)) * (upper - lower), unit(rng.normal(size=(k, 3))),
+        rng.uniform(0.0, 2.0 * diag, size=k))
+    for zeros in (1, 2):   # one and two zero direction components
+        k = 50
+        u = rng.normal(size=(k, 3))
+        for row in u:
+            row[rng.choice(3, size=zeros, replace=False)] = 0.0
+        add(inside(k), unit(u), rng.uniform(0.0, 2.0 * diag, size=k))
+    k = 80   # a start exactly on a plane lower + float(i) * h, i = 0 .. n: interior planes and both outer faces
+    p = inside(k)
+    for row in p:
+        a = int(rng.integers(3))
+        row[a] = lower[a] + float(rng.integers(0, shape[a] + 1)) * h[a]
+    add(p, unit(rng.normal(size=(k, 3))), rng.uniform(0.0, 2.0 * diag, size=k))
+    for a in range(3):   # a start outside the box on each side, heading in, along and away
+        for side in (-1.0, 1.0):
+            k = 10
+            p = inside(k)
+            p[:, a] = (lower[a] if side < 0 else upper[a]) + side * rng.uniform(0.01, 1.5, size=k) * (upper[a] - lower[a])
+            add(p, unit(rng.normal(size=(k, 3))), rng.uniform(0.0, 3.0 * diag, size=k))
+    k = 30   # the diagonal tie: equal parameters on x and y from a point at the same fraction of its cell, and its twin
+    f = rng.uniform(0.05, 0.95, size=k)
+    p = inside(k)
+    p[:, 0], p[:, 1] = lower[0] + f * h[0], lower[1] + f * h[1]
+    u = unit(np.tile(np.array([h[0], h[1], 0.0]), (k, 1)))
+    twin = p.copy()
+    twin[:, 1] += 2.0 ** -40
+    length = rng.uniform(0.0, 2.0 * diag, size=k)
+    add(p, u, length); add(twin, u, length); add(p, -u, length); add(twin, -u, length)
+    k = 50   # a length that ends exactly on a plane: the walk's own expression for that plane's parameter
+    p, u = inside(k), unit(rng.normal(size=(k, 3)))
+    length = np.empty(k)
+    for j in range(k):
+        a = int(rng.integers(3))
+        i = int(rng.integers(0, shape[a] + 1))
+        length[j] = abs((lower[a] + float(i) * h[a] - p[j, a]) / u[j, a])
+    add(p, u, length)
+    k = 20   # zero and negative lengths
+    add(inside(k), unit(rng.normal(size=(k, 3))), np.where(np.arange(k) % 2 == 0, 0.0, -rng.uniform(0.0, 1.0, size=k)))
+    p, u, length = np.concatenate(ps), np.concatenate(us), np.concatenate(ls)
+    tau = -np.log(1.0 - rng.uniform(size=len(p)))
+    return values, lower, upper, p, u, length, tau
+
+
+def make_lattice_walk():
+    """lattice_walk.npz: what the host's lattice functions give on seeded rays -- the march of a `ConcentrationGrid`
+    (outcome and the cells it asks alpha of, in order, once with the drawn tau and once with tau = inf), the pieces of
+    `path_segment_pieces`, `ConcentrationGrid.cell_of` and `pattern_cell`.  Recorded from this project's own functions
+    (nothing of the reference is involved) before they were made to share pvtrace_amd/lattice.py; numbers only.  The
+    committed file is that recording: run again today, this writes what the shared code gives, a fixture of the code against
+    itself -- do not regenerate it unless the rays have to change, and then from a checkout of commit 79cb06a."""
+    from pvtrace_amd import material
+    from pvtrace_amd.engine.tally import path_segment_pieces
+
+    out = {}
+    for index, shape in enumerate(((1, 1, 1), (2, 2, 1), (3, 4, 5), (7, 1, 2))):
+        values, lower, upper, p, u, length, tau = lattice_walk_cases(shape, 20240 + index)
+        grid = material.ConcentrationGrid(values, lower, upper)
+        h = tuple(float(v) for v in grid.h)
+        lo = tuple(float(v) for v in lower)
+        bounded = material.CoatingPattern(values, lo, tuple(float(v) for v in upper))
+        free = material.CoatingPattern(values, tuple(None if n == 1 else v for n, v in zip(shape, lo)),
+                                       tuple(None if n == 1 else float(v) for n, v in zip(shape, upper)))
+        rows = {name: [] for name in ("absorbed", "depth", "cell", "visits", "visit_count", "free_visits",
+                                      "free_visit_count", "piece_cells", "piece_units", "piece_count", "cell_of",
+                                      "pattern_slot", "free_pattern_slot")}
+        for j in range(len(p)):
+            for name, t in (("visits", float(tau[j])), ("free_visits", np.inf)):
+                seen = []
+
+                def alpha(cell):
+                    seen.append(cell)
+                    return float(values[cell])
+
+                result = material._march(grid, p[j], u[j], t, float(length[j]), alpha)
+                rows[name].extend(seen)
+                rows[name[:-1] + "_count"].append(len(seen))
+                if name == "visits":
+                    rows["absorbed"].append(bool(result[0]))
+                    rows["depth"].append(float(result[1]))
+                    rows["cell"].append((-1, -1, -1) if result[2] is None else result[2])
+            pieces = path_segment_pieces([float(v) for v in p[j]], [float(v) for v in u[j]], float(length[j]), lo, h, shape)
+            rows["piece_cells"].extend(cell for cell, _ in pieces)
+            rows["piece_units"].extend(k for _, k in pieces)
+            rows["piece_count"].append(len(pieces))
+            rows["cell_of"].append(grid.cell_of(p[j]))
+            for name, pattern in (("pattern_slot", bounded), ("free_pattern_slot", free)):
+                slot = material.pattern_cell(pattern, p[j])
+                rows[name].append(-1 if slot is None else slot)
+        key = "x".join(str(n) for n in shape)
+        for name, value in (("values", values), ("lower", lower), ("upper", upper), ("p", p), ("u", u), ("length", length),
+                            ("tau", tau)):
+            out[f"{key}_{name}"] = value
+        for name, value in rows.items():
+            dtype = np.float64 if name == "depth" else (bool if name == "absorbed" else np.int64)
+            shape3 = (-1, 3) if name in ("cell", "visits", "free_visits", "piece_cells", "cell_of") else (-1,)
+            out[f"{key}_{name}"] = np.array(value, dtype=dtype).reshape(shape3)
+    save("lattice_walk.npz", **out)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--lattice":   # this project's own lattice functions: needs no reference tree
+        make_lattice_walk()
+        sys.exit(0)
     if not os.path.isdir(REF):
         sys.exit("reference tree not present; fixtures can only be regenerated in the build container")
     if len(sys.argv) > 1 and sys.argv[1] == "--units":   # only the small unit fixtures added in round 5
