@@ -41,7 +41,9 @@ enum {
 /* geometry / surface / component / phase / emit-method tags (compiler.py:25-48) */
 enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_MESH = 3,
        /* EXTENSION (the reference has no such shape): a truncated cone, see below */
-       PVT_GEOM_FRUSTUM = 4 };
+       PVT_GEOM_FRUSTUM = 4,
+       /* EXTENSION (the reference has no such shape): a convex polyhedron, a table of planes, see PvtPolyhedronTables */
+       PVT_GEOM_POLYHEDRON = 5 };
 /* PVT_GEOM_FRUSTUM: a truncated cone along the node's z axis, centred on its origin; geom_params = (length L,
  * radius_bottom r0 at z = -L/2, radius_top r1 at z = +L/2, 0).  L finite and > 0; r0, r1 finite and >= 0, not both 0
  * (else PVT_ERR_INVALID).  Convex, so the container rule of the analytic shapes applies unchanged.  The arithmetic is
@@ -599,6 +601,53 @@ typedef struct PvtAlignTables {
     const int32_t* emit_table;          /* (n_records) the single-row phase table of f(mu; S_e), -1 = S_e is 0 */
 } PvtAlignTables;
 
+/* ---- convex polyhedra (extension within v13, passed to pvt_scene_create_polyhedra) ---------------------------------
+ * PVT_GEOM_POLYHEDRON: the intersection of half-spaces; geom_params = (bounding radius, 0, 0, 0), the bounding radius being
+ * the largest vertex norm (finite and > 0, else PVT_ERR_INVALID).  Node n's planes are the rows
+ * planes[node_plane_start[n] .. + node_plane_count[n]) of (nx, ny, nz, h), 4 <= count <= PVT_MAX_POLYHEDRON_PLANES = 64,
+ * every row finite with | |n| - 1 | <= 1e-12.  The rule, in the words of pvtrace_amd.geometry.Polyhedron:
+ *
+ * The solid is { p : n_k.p < h_k for all k } in the node's own frame.  It need not contain the node's origin.
+ * The constructor normalises each row once: it divides the row by |n|.  From then on the stored doubles are the shape,
+ * bit for bit, on the host and on the GPU.
+ *
+ * Crossing distances of a ray (o, d) in the node's frame use IEEE double, no contraction and correctly rounded
+ * division.  Planes are taken in index order:
+ *
+ *     tin = -inf; tout = +inf; miss = false
+ *     for k:  den = (nx*d.x + ny*d.y) + nz*d.z
+ *             num = h - ((nx*o.x + ny*o.y) + nz*o.z)
+ *             if fabs(den) < 1e-300:  if num < 0: miss = true;  continue
+ *             t = num / den
+ *             if den < 0:  tin = fmax(tin, t)   else  tout = fmin(tout, t)
+ *     if !miss and !(tout < tin): candidates tin, then tout; each counts when finite and > EPS
+ *
+ * This is the box's rule, `!(tmax < tmin)` included.  A plane nearly parallel to the ray is harmless whichever sign its
+ * `den` rounds to.  An origin inside that plane gives a large t of the matching sense.  An origin outside gives a miss
+ * either way.
+ *
+ * The solid is convex, so the container rule of the analytic shapes (`nl == 1`) applies unchanged.
+ *
+ * Normal at a surface point p: the row k* that minimises fabs(((nx*p.x + ny*p.y) + nz*p.z) - h), the first minimum
+ * winning.  The normal is (nx, ny, nz) of k*, as stored.
+ *
+ * Additive under ABI 13.  The plane rows lie behind everything else in the scene's double blob and are read from global
+ * memory; a scene with such a node runs the PVT_VARIANT_ROUGH family (with or without meshes), is never lean, and gets
+ * no node grid.  The library checks the table, not the solid: that the planes bound a solid with no redundant plane is
+ * the caller's business (the Python class refuses anything else).  Which entry takes the type: pvt_scene_create_polyhedra
+ * alone; every older pvt_scene_create* entry, pvt_scene_lean_check and the host-buffer pvt_trace_bundle* entries (which
+ * have no way to receive the table) refuse it as "unknown geometry type".  Out of scope: non-convex solids, more than 64
+ * planes, the node grid and the lean family for such scenes, the host-buffer entries, a face index as a recorder
+ * property. */
+#define PVT_MAX_POLYHEDRON_PLANES 64
+typedef struct PvtPolyhedronTables {
+    int32_t n_nodes;                    /* 0 = none (as a NULL struct), else the scene's n_nodes */
+    const int32_t* node_plane_start;    /* (n_nodes) first row of the node's planes in `planes` */
+    const int32_t* node_plane_count;    /* (n_nodes) rows of the node, 4 .. 64; ignored for nodes of another type */
+    int32_t n_planes;                   /* rows in `planes` */
+    const double* planes;               /* (n_planes,4) rows (nx, ny, nz, h), unit normals within 1e-12 */
+} PvtPolyhedronTables;
+
 /* capture buffers of one launch (DEVICE pointers): `rows` holds sets x capture_rows x PVT_CAPTURE_ROW_WORDS uint64,
  * `cursors` sets x n_recorders int64, sets = the tally sets of the launch (1 without tally_bundle).  Word 11 of a row:
  * emissions | scatterings << 20 | reflections << 40, the photon's event counters (PVT_PROPX_*) */
@@ -804,6 +853,15 @@ int pvt_scene_create_aligned(const PvtSceneTables* tables, const PvtIndexTables*
                              const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables,
                              const PvtCoatingPatternTables* pattern_tables, const PvtAlignTables* align_tables, int device,
                              PvtScene** out);
+/* The same with convex polyhedra (PvtPolyhedronTables), and the one entry that knows geometry type PVT_GEOM_POLYHEDRON:
+ * NULL, n_nodes 0 or a scene with no such node = exactly pvt_scene_create_aligned.  Every entry before it refuses the type
+ * ("unknown geometry type"), as they did before it existed. */
+int pvt_scene_create_polyhedra(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
+                               const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
+                               const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
+                               const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables,
+                               const PvtCoatingPatternTables* pattern_tables, const PvtAlignTables* align_tables,
+                               const PvtPolyhedronTables* polyhedron_tables, int device, PvtScene** out);
 /* Attach / replace the device-side emitter of a scene (optional). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
 void pvt_scene_destroy(PvtScene* scene);
@@ -932,7 +990,7 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
  * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
  * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
  * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
- * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones, aligned components), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones, aligned components, convex polyhedra), MESH.  The environment variable PVT_NO_LEAN, read when the scene
  * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */

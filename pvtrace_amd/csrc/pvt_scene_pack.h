@@ -65,7 +65,7 @@ bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
     for (int n = 0; n < N; n++) {
         // (a truncated cone: the plain node loop serves its scene -- the `default` cases below, and the grid walk's
         // shape_hits in the kernel, mean "cylinder" and never see one)
-        if (t->geom_type[n] == PVT_GEOM_MESH || t->geom_type[n] == PVT_GEOM_FRUSTUM) return false;
+        if (t->geom_type[n] == PVT_GEOM_MESH || t->geom_type[n] == PVT_GEOM_FRUSTUM || t->geom_type[n] == PVT_GEOM_POLYHEDRON) return false;
         const double* w = t->world_to_local + n * 16;
         const double* l = t->local_to_world + n * 16;
         const double* gp = t->geom_params + n * 4;
@@ -342,6 +342,11 @@ struct PackedScene {
     int nd_small = 0, ni_small = 0, n_ctab = 0, n_rtab = 0, n_ptab = 0, lazy_root = 0;
     int rough_d = -1;   // where the nodes' GGX widths start in the double blob (-1: no node is rough)
     bool has_frustum = false;   // a node is a truncated cone (PVT_GEOM_FRUSTUM)
+    // convex polyhedra (PvtPolyhedronTables): a node is one (PVT_GEOM_POLYHEDRON).  Their plane rows (nx, ny, nz, h) lie
+    // BEHIND everything else in the double blob -- the absorbing coatings' block included -- so every other offset is what
+    // it would be without them; such a node's record names its rows in its second and third shape parameter (ND_PARAMS + 1:
+    // where they start in the double blob, ND_PARAMS + 2: how many, both as integers in the words' bits), which the host tables leave 0
+    bool has_polyhedron = false;
     // absorbing coatings (PvtCoatingAbsorbTables; -1: no coating absorbs).  Both blocks lie BEHIND everything the blobs of a
     // scene without them hold, so every other offset is what it would be without them, and are read from where the
     // spectra are read.  cabs_d: in the double blob, one record of kCa doubles (kCa*) per coating row, then the pooled
@@ -410,6 +415,7 @@ struct SceneInputs {
     const PvtCoatingPatternTables* pt = nullptr;   // where the coatings cover
     Knows knows{};
     const PvtAlignTables* al = nullptr;            // aligned components (behind `knows`: the older entries' records stay as written)
+    const PvtPolyhedronTables* pl = nullptr;       // convex polyhedra
 };
 
 // The levels an entry can know, one row each.  A new entry that knows more gets a new row; nothing else names these limits.
@@ -417,6 +423,7 @@ struct SceneInputs {
 constexpr Knows kKnowsBeforeAbsorb{PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_MESH};     // pvt_scene_create .. pvt_scene_create_capture
 constexpr Knows kKnowsAbsorb      {PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH};     // pvt_scene_create_absorb
 constexpr Knows kKnowsOrigin      {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_FRUSTUM};  // pvt_scene_create_origin, _pattern, _aligned, pvt_scene_lean_check
+constexpr Knows kKnowsPolyhedra   {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_POLYHEDRON};  // pvt_scene_create_polyhedra
 constexpr Knows kKnowsHostBuffer  {PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_FRUSTUM};  // pvt_trace_bundle*: pvt_scene_create, but a truncated cone is taken
 
 // ---- validation: every index into a table that the packer follows on the host or the kernel on the device, checked
@@ -1327,6 +1334,7 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
                     radius = std::sqrt(rmax * rmax + 0.25 * gp[0] * gp[0]);
                     break;
                 }
+                case PVT_GEOM_POLYHEDRON: radius = gp[0]; break;   // (its bounding radius: validate_polyhedra)
                 default: radius = INFINITY; break;   // (mesh scenes never take this path)
             }
             radius *= 1.0 + 1e-12;
@@ -1391,7 +1399,7 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     };
     // a searched table (CI_*_X, n points, its even_w in `w`): 2 = a constant or even bit for bit, 1 = even up to rounding, 0
     auto grid_kind = [&](int at, int n, double w) { return (n == 1 || w == w) ? 2 : (nearly_even(at, n) ? 1 : 0); };
-    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && !p->has_frustum && p->fd.empty() &&
+    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && !p->has_frustum && !p->has_polyhedron && p->fd.empty() &&
               p->md.empty() && p->cd.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
     for (int n = 0; n < N && ok; n++) {
         unsigned long long bits;
@@ -1703,6 +1711,50 @@ int pack_align(const SceneInputs& in, PackedScene* p) {
     return PVT_OK;
 }
 
+// Convex polyhedra (PvtPolyhedronTables, pvt_scene_create_polyhedra): every value the kernel reads, checked before anything
+// is packed, each failure with its own message.  A scene with no node of the type needs no struct and reads none.
+int validate_polyhedra(const SceneInputs& in) {
+    const PvtSceneTables* t = in.t;
+    const PvtPolyhedronTables* pl = in.pl;
+    const int N = t->n_nodes;
+    for (int n = 0; n < N; n++) {
+        if (t->geom_type[n] != PVT_GEOM_POLYHEDRON) continue;
+        if (!pl || pl->n_nodes == 0) return fail(PVT_ERR_INVALID, "polyhedron node without polyhedron tables");
+        if (pl->n_nodes != N || !pl->node_plane_start || !pl->node_plane_count || !pl->planes || pl->n_planes < 0)
+            return fail(PVT_ERR_INVALID, "polyhedron tables: need one run of planes per node");
+        const long long start = pl->node_plane_start[n], count = pl->node_plane_count[n];
+        if (count < 4 || count > PVT_MAX_POLYHEDRON_PLANES) return fail(PVT_ERR_INVALID, "polyhedron tables: a node needs 4 to 64 planes");
+        if (bad_run(start, count, pl->n_planes)) return fail(PVT_ERR_INVALID, "polyhedron tables: plane range outside the pool");
+        for (long long k = start; k < start + count; k++) {
+            const double* r = pl->planes + k * 4;
+            if (!(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3])))
+                return fail(PVT_ERR_INVALID, "polyhedron tables: plane rows must be finite");
+            const double len = std::sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+            if (!(std::fabs(len - 1.0) <= 1e-12)) return fail(PVT_ERR_INVALID, "polyhedron tables: every normal must be a unit vector within 1e-12");
+        }
+        const double radius = t->geom_params[n * 4];
+        if (!(std::isfinite(radius) && radius > 0.0)) return fail(PVT_ERR_INVALID, "polyhedron: bounding radius must be finite and > 0");
+    }
+    return PVT_OK;
+}
+
+// ... and placed (validated tables): the rows of every such node appended to the double blob, its record told where
+void pack_polyhedra(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    p->has_polyhedron = false;
+    for (int n = 0; n < t->n_nodes; n++) {
+        if (t->geom_type[n] != PVT_GEOM_POLYHEDRON) continue;
+        p->has_polyhedron = true;
+        const int start = in.pl->node_plane_start[n], count = in.pl->node_plane_count[n];
+        double* d = p->gd.data() + (size_t)n * ND;
+        const unsigned long long at = (unsigned long long)p->gd.size(), rows = (unsigned long long)count;
+        std::memcpy(&d[ND_PARAMS + 1], &at, 8);     // (integers in the words' bits, like ND_BITS: the kernel converts nothing)
+        std::memcpy(&d[ND_PARAMS + 2], &rows, 8);
+        p->gd.insert(p->gd.end(), in.pl->planes + (size_t)start * 4, in.pl->planes + (size_t)(start + count) * 4);
+    }
+    if (p->has_polyhedron) p->gd.push_back(0.0);   // (the blob's spare last element, as before)
+}
+
 // The scene's inputs (n_nodes and n_recorders already checked by the caller; the pattern tables are pack_patterns') -> *p.
 // No HIP call.
 int pack_scene(const SceneInputs& in, PackedScene* p) {
@@ -1711,6 +1763,8 @@ int pack_scene(const SceneInputs& in, PackedScene* p) {
     const PvtPhaseTables* ph = in.ph;
     const PvtSurfaceTables* rs = in.rs;
     int rc = validate_tables(in);
+    if (rc != PVT_OK) return rc;
+    rc = validate_polyhedra(in);
     if (rc != PVT_OK) return rc;
     const Classes classes = classify_nodes(in);
     Spectra spectra = pool_spectra(t);
@@ -1742,6 +1796,7 @@ int pack_scene(const SceneInputs& in, PackedScene* p) {
     pack_maps(in, p);
     pack_captures(in, p);
     pack_absorb(in, records, p);
+    pack_polyhedra(in, p);
     prove_shortcuts(t, p);
     prove_lean(t, p);
     return PVT_OK;

@@ -100,6 +100,7 @@ struct PvtScene {
     int n_nodes = 0, root = 0, n_rec = 0, total_bins = 0, n_coat = 0, n_ctab = 0, n_rtab = 0, n_lights = 0;
     int rough_d = -1;                   // where the nodes' GGX widths start in the double blob (-1: no rough node)
     bool has_frustum = false;           // a node is a truncated cone (PVT_GEOM_FRUSTUM): only the extension family traces one
+    bool has_polyhedron = false;        // a node is a convex polyhedron (PVT_GEOM_POLYHEDRON): likewise
     int cabs_d = -1, dcand_i = -1;      // absorbing coatings: their records in the double blob, the `detected` candidate tables in the int blob (-1: none)
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
@@ -375,7 +376,7 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
     // photon event counter or of the launch origin, a truncated cone or an aligned component: the extension family, split as
     // the plain ones
-    const bool extension = s->has_frustum || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0 || s->al_d >= 0;
+    const bool extension = s->has_frustum || s->has_polyhedron || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0 || s->al_d >= 0;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.align = s->al_d >= 0;   // (the extension family's kernels that hold the aligned components' code)
     v.path = s->path_maps;    // (... and those that hold the path-length maps' walk on top of it)
@@ -789,6 +790,13 @@ int pvt_scene_create_aligned(const PvtSceneTables* t, const PvtIndexTables* x, c
     return create_scene({t, x, ph, rs, fr, mp, cp, ab, pt, kKnowsOrigin, al}, device, out);
 }
 
+int pvt_scene_create_polyhedra(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph,
+                               const PvtSurfaceTables* rs, const PvtFieldTables* fr, const PvtMapTables* mp,
+                               const PvtCaptureTables* cp, const PvtCoatingAbsorbTables* ab, const PvtCoatingPatternTables* pt,
+                               const PvtAlignTables* al, const PvtPolyhedronTables* pl, int device, PvtScene** out) {
+    return create_scene({t, x, ph, rs, fr, mp, cp, ab, pt, kKnowsPolyhedra, al, pl}, device, out);
+}
+
 }  // extern "C"
 
 namespace {
@@ -826,6 +834,7 @@ int create_scene(const SceneInputs& in, int device, PvtScene** out) {
     s->total_bins = t->total_bins; s->n_coat = t->n_coatings; s->n_ctab = packed.n_ctab; s->n_rtab = packed.n_rtab;
     s->rough_d = packed.rough_d;
     s->has_frustum = packed.has_frustum;
+    s->has_polyhedron = packed.has_polyhedron;
     s->cabs_d = packed.cabs_d; s->dcand_i = packed.dcand_i;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;

@@ -714,6 +714,57 @@ __device__ __attribute__((noinline)) V3 frustum_normal_call(double length, doubl
     return V3{px / m, py / m, (-w) / m};
 }
 
+// Convex polyhedra (PVT_GEOM_POLYHEDRON; include/pvtrace_hip.h states the rule, geometry.Polyhedron performs the same
+// operations in the same order): the two candidate distances of the ray (o, d) in the node's frame -- entry, then exit -- a
+// candidate that is no crossing being 0 (never > kEps), as in FrustumHits.  `planes`: the node's `count` rows (nx, ny, nz, h)
+// in the double blob, global memory.  In the node loop the node is the wave's, so the rows sit at a wave-uniform address
+// and come through the scalar cache, 32 bytes a row; the loop's state is tin, tout and miss.  One IEEE division per plane
+// is the price of agreeing with the host bit for bit.  FUNCTIONS, called only from the trace_kernel_rough* variants: the
+// plain families carry none of it.
+struct PolyhedronHits { double t[2]; };
+__device__ __attribute__((noinline)) PolyhedronHits polyhedron_hits_call(CDoubles planes, int count, double ox, double oy, double oz,
+                                                                         double dx, double dy, double dz) {
+    // (a function's arguments arrive in vector registers; the node is the wave's, so the rows' address and their count are
+    // the same in every lane: said here, the rows come through the scalar cache and the loop is the wave's, not the lanes')
+    const unsigned long long addr = (unsigned long long)planes;
+    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)addr);
+    const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(addr >> 32));
+    const CDoubles rows = (CDoubles)(((unsigned long long)hi << 32) | (unsigned long long)lo);
+    const int n = __builtin_amdgcn_readfirstlane(count);
+    double tin = -INFINITY, tout = INFINITY;
+    bool miss = false;
+    for (int k = 0; k < n; k++) {
+        const double nx = rows[4 * k], ny = rows[4 * k + 1], nz = rows[4 * k + 2], h = rows[4 * k + 3];
+        const double den = (nx * dx + ny * dy) + nz * dz;
+        const double num = h - ((nx * ox + ny * oy) + nz * oz);
+        if (pvt_fabs(den) < 1e-300) {
+            if (num < 0.0) miss = true;
+            continue;
+        }
+        const double t = num / den;
+        if (den < 0.0) tin = __builtin_fmax(tin, t);
+        else tout = __builtin_fmin(tout, t);
+    }
+    PolyhedronHits hits{{0.0, 0.0}};
+    if (!miss && !(tout < tin)) {
+        if (pvt_fabs(tin) < INFINITY) hits.t[0] = tin;
+        if (pvt_fabs(tout) < INFINITY) hits.t[1] = tout;
+    }
+    return hits;
+}
+// ... and the outward normal at the point p of its surface: the row nearest to p, the first of equals; here the node is
+// the lane's own, so are the rows
+__device__ __attribute__((noinline)) V3 polyhedron_normal_call(const double* planes, int count, double px, double py, double pz) {
+    double best = INFINITY;
+    V3 n{0.0, 0.0, 0.0};
+    for (int k = 0; k < count; k++) {
+        const double nx = planes[4 * k], ny = planes[4 * k + 1], nz = planes[4 * k + 2], h = planes[4 * k + 3];
+        const double dist = pvt_fabs(((nx * px + ny * py) + nz * pz) - h);
+        if (dist < best) { best = dist; n = V3{nx, ny, nz}; }
+    }
+    return n;
+}
+
 // Rough interfaces (PvtSurfaceTables; include/pvtrace_hip.h states the contract, the Python FresnelSurfaceDelegate samples
 // the same way): one surface event of a lane whose hit node is rough where no coating covers it (UF_ROUGH) -- the draws
 // u_a, u_b, the microfacet normal m from the GGX distribution of visible normals of width `alpha` (Heitz 2018) about the
@@ -2829,6 +2880,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
 #pragma unroll
                     for (int j = 0; j < 4; j++)
                         if (fh.t[j] > kEps) fold(fh.t[j]);
+                } else if (ROUGH && gt == PVT_GEOM_POLYHEDRON) {   // EXTENSION: convex polyhedron (polyhedron_hits_call; no node grid holds one)
+                    // (the node's record names its rows: where they start in the double blob, how many, as integers in the words' bits -- pack_polyhedra)
+                    const PolyhedronHits ph = polyhedron_hits_call(T.gd + (int)pvt_d2u(gpar[1]), (int)pvt_d2u(gpar[2]), o.x, o.y, o.z, d.x, d.y, d.z);
+                    if (ph.t[0] > kEps) fold(ph.t[0]);
+                    if (ph.t[1] > kEps) fold(ph.t[1]);
                 } else {  // capped z cylinder (:301-345)
                     double half = 0.5 * gpar[0], radius = gpar[1];
                     double a = d.x * d.x + d.y * d.y;
@@ -3295,6 +3351,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             }
             if (ROUGH && !GRID && gt == PVT_GEOM_FRUSTUM)   // (no node grid holds a truncated cone: plan_node_grid)
                 return frustum_normal_call(param(0), param(1), param(2), lp.x, lp.y, lp.z);
+            if (ROUGH && !GRID && gt == PVT_GEOM_POLYHEDRON)   // (likewise; the rows from global memory, where the spectra of large scenes are read)
+                return polyhedron_normal_call(T.hd + (int)pvt_d2u(param(1)), (int)pvt_d2u(param(2)), lp.x, lp.y, lp.z);
             double half = 0.5 * param(0);
             double tol = 1e-8 + 1e-5 * pvt_fabs(half);
             if (pvt_fabs(lp.z + half) <= tol) return V3{0.0, 0.0, -1.0};

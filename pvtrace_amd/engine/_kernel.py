@@ -36,6 +36,13 @@ def _host_buffer_scene(compiled):
     """PvtSceneTables of `compiled` for the host-buffer entries, which keep the reference's interface: that has no
     place for refractive-index or phase-function tables, surface roughness or concentration fields, and tracing the scalar column instead
     would silently drop the dispersion (the library itself refuses a component tagged with a table phase function)."""
+    if getattr(compiled, "has_polyhedron", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has a convex polyhedron (Polyhedron), whose plane table the host-buffer trace_bundle entry (the "
+            "reference's interface) has no way to receive; trace it with engine.simulate."
+        )
     if getattr(compiled, "has_alignment", False):
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 

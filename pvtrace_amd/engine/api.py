@@ -437,7 +437,8 @@ def _scene_key(compiled, emitter, device):
                  + (compiled.CAPTURE_TABLE_FIELDS if compiled.has_captures else ())
                  + (compiled.ABSORB_TABLE_FIELDS if compiled.has_absorbing_coatings else ())
                  + (compiled.PATTERN_TABLE_FIELDS if compiled.has_coating_patterns else ())
-                 + (compiled.ALIGN_TABLE_FIELDS if getattr(compiled, "has_alignment", False) else ())):
+                 + (compiled.ALIGN_TABLE_FIELDS if getattr(compiled, "has_alignment", False) else ())
+                 + (compiled.POLYHEDRON_TABLE_FIELDS if getattr(compiled, "has_polyhedron", False) else ())):
         a = np.ascontiguousarray(getattr(compiled, name))
         h.update(a.dtype.str.encode()); h.update(repr(a.shape).encode()); h.update(a.data if a.size else b"")
     h.update(repr((int(compiled.root_id), int(compiled.total_bins))).encode())

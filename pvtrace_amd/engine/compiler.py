@@ -35,7 +35,7 @@ from pvtrace_amd.engine.recorder import (
     Recorder,
     VolumeMap,
 )
-from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Sphere
+from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Polyhedron, Sphere, _polyhedron_analysis
 from pvtrace_amd.material import (
     Absorber,
     Alignment,
@@ -62,6 +62,7 @@ MAX_PATTERN_CELLS = 1 << 26   # cells of all coating patterns of a scene: 64 MiB
 
 GEOM_BOX, GEOM_SPHERE, GEOM_CYLINDER, GEOM_MESH = 0, 1, 2, 3
 GEOM_FRUSTUM = 4   # EXTENSION: truncated cone (include/pvtrace_hip.h: PVT_GEOM_FRUSTUM)
+GEOM_POLYHEDRON = 5   # EXTENSION: convex polyhedron, a table of planes (include/pvtrace_hip.h: PVT_GEOM_POLYHEDRON)
 SURF_FRESNEL, SURF_NULL = 0, 1
 COMP_ABSORBER, COMP_SCATTERER, COMP_LUMINOPHORE, COMP_REACTOR = 0, 1, 2, 3
 PHASE_ISOTROPIC, PHASE_HENYEY_GREENSTEIN, PHASE_CONE = 0, 1, 2
@@ -157,6 +158,11 @@ class CompiledScene:
         self.mesh_face_start = np.zeros(count, dtype=_I32)
         self.mesh_face_count = np.zeros(count, dtype=_I32)
         self._mesh_pool = {"vertices": [], "faces": [], "normals": [], "nv": 0, "nf": 0}
+        # Convex polyhedra (Polyhedron): per node where its plane rows (nx, ny, nz, h) start in the pool and how many they
+        # are (0: the node is no polyhedron).  Passed to the library as PvtPolyhedronTables, only by scenes that hold one.
+        self.poly_start = np.zeros(count, dtype=_I32)
+        self.poly_count = np.zeros(count, dtype=_I32)
+        self._poly_pool = []
 
         pools = {"abs_x": [], "abs_y": [], "ems_x": [], "ems_cdf": []}
         comp_cols = {
@@ -334,6 +340,9 @@ class CompiledScene:
         self.mesh_faces = (np.concatenate(pool["faces"]).astype(_I32) if pool["nf"] else np.zeros((0, 3), dtype=_I32))
         self.mesh_normals = (np.concatenate(pool["normals"]) if pool["nf"] else np.zeros((0, 3), dtype=_F64))
         del self._mesh_pool
+        self.poly_planes = (np.ascontiguousarray(np.concatenate(self._poly_pool), dtype=_F64) if self._poly_pool
+                            else np.zeros((0, 4), dtype=_F64))
+        del self._poly_pool
 
         self._lower_recorders(nodes)
         self._lower_maps(root, nodes)
@@ -360,6 +369,19 @@ class CompiledScene:
             self.geom_params[i, 0] = float(geometry.length)
             self.geom_params[i, 1] = float(geometry.radius_bottom)
             self.geom_params[i, 2] = float(geometry.radius_top)
+        elif isinstance(geometry, Polyhedron):
+            # EXTENSION: the reference has no convex polyhedron; the stored rows are the shape, checked again here because
+            # the attributes may have been changed since construction
+            problem, rows, vertices, _, _ = _polyhedron_analysis(geometry.planes)
+            if problem is None and np.any(np.abs(np.sqrt(np.sum(rows[:, :3] ** 2, axis=1)) - 1.0) > 1e-12):
+                problem = "Polyhedron plane normals must be unit vectors."
+            if problem:
+                raise UnsupportedSceneError(problem)
+            self.geom_type[i] = GEOM_POLYHEDRON
+            self.geom_params[i, 0] = float(np.max(np.sqrt(np.sum(vertices * vertices, axis=1))))   # bounding radius
+            self.poly_start[i] = sum(len(rows) for rows in self._poly_pool)
+            self.poly_count[i] = len(rows)
+            self._poly_pool.append(rows)
         elif isinstance(geometry, Mesh):
             # EXTENSION: the reference engine rejects meshes (compiler.py:220-223)
             pool = self._mesh_pool
@@ -469,6 +491,10 @@ class CompiledScene:
     @property
     def has_frustum(self):
         return bool(np.any(self.geom_type == GEOM_FRUSTUM))
+
+    @property
+    def has_polyhedron(self):
+        return bool(np.any(self.geom_type == GEOM_POLYHEDRON))
 
     @property
     def has_roughness(self):
@@ -924,11 +950,11 @@ class CompiledScene:
     # The tables of the later extensions are part of `tables()` only when the scene has the extension, so that a scene
     # without it lowers to the same tables, key for key, as before there was one: the volume maps', the captures', the
     # absorbing coatings' (a coating has an absorptivity), the coating patterns' (a coating has a pattern or
-    # facet=None) and the alignments' (a component has an Alignment).  Which attributes they are is what the binding reads for the extension's struct.
-    MAP_TABLE_FIELDS, CAPTURE_TABLE_FIELDS, ABSORB_TABLE_FIELDS, PATTERN_TABLE_FIELDS, ALIGN_TABLE_FIELDS = (
+    # facet=None), the alignments' (a component has an Alignment) and the polyhedra's (a node is a Polyhedron).  Which attributes they are is what the binding reads for the extension's struct.
+    MAP_TABLE_FIELDS, CAPTURE_TABLE_FIELDS, ABSORB_TABLE_FIELDS, PATTERN_TABLE_FIELDS, ALIGN_TABLE_FIELDS, POLYHEDRON_TABLE_FIELDS = (
         tuple(attribute for attribute, _ in struct_type.POINTERS.values())
         for struct_type in (native.PvtMapTables, native.PvtCaptureTables, native.PvtCoatingAbsorbTables,
-                            native.PvtCoatingPatternTables, native.PvtAlignTables))
+                            native.PvtCoatingPatternTables, native.PvtAlignTables, native.PvtPolyhedronTables))
 
     def tables(self):
         """dict of every numeric table (for fixtures / debugging)."""
@@ -947,6 +973,8 @@ class CompiledScene:
             out.update({name: getattr(self, name) for name in self.PATTERN_TABLE_FIELDS})
         if self.has_alignment:
             out.update({name: getattr(self, name) for name in self.ALIGN_TABLE_FIELDS})
+        if self.has_polyhedron:
+            out.update({name: getattr(self, name) for name in self.POLYHEDRON_TABLE_FIELDS})
         return out
 
     @property

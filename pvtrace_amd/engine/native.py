@@ -235,14 +235,31 @@ class PvtAlignTables(C.Structure):
     ABSENT = staticmethod(lambda c: not getattr(c, "has_alignment", False))
 
 
+class PvtPolyhedronTables(C.Structure):
+    """Convex polyhedra of a scene: per node its run of plane rows (nx, ny, nz, h) in the pool (include/pvtrace_hip.h;
+    pvt_scene_create_polyhedra); absent when no node is a `Polyhedron`."""
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("node_plane_start", _p_i32), ("node_plane_count", _p_i32),
+        ("n_planes", C.c_int32), ("planes", _p_f64),
+    ]
+    POINTERS = {"node_plane_start": ("poly_start", np.int32), "node_plane_count": ("poly_count", np.int32),
+                "planes": ("poly_planes", np.float64)}
+    COUNTS = {"n_nodes": lambda c: len(c.poly_start), "n_planes": lambda c: len(c.poly_planes)}
+    ABSENT = staticmethod(lambda c: not getattr(c, "has_polyhedron", False))
+
+
 # the extension structs, in the order the pvt_scene_create* entries take them behind the scene tables (each entry takes the
 # first so many of them: CREATION_ENTRIES)
 EXTENSION_TABLES = (PvtIndexTables, PvtPhaseTables, PvtSurfaceTables, PvtFieldTables, PvtMapTables, PvtCaptureTables,
-                    PvtCoatingAbsorbTables, PvtCoatingPatternTables, PvtAlignTables)
+                    PvtCoatingAbsorbTables, PvtCoatingPatternTables, PvtAlignTables, PvtPolyhedronTables)
 CREATION_ENTRIES = {"pvt_scene_create": 0, "pvt_scene_create_ex": 1, "pvt_scene_create_phase": 2, "pvt_scene_create_rough": 3,
                     "pvt_scene_create_field": 4, "pvt_scene_create_maps": 5, "pvt_scene_create_capture": 6,
                     "pvt_scene_create_absorb": 7, "pvt_scene_create_origin": 7, "pvt_scene_create_pattern": 8,
                     "pvt_scene_create_aligned": 9}
+# The newest entry, the one Python calls: pvt_scene_create_aligned and the tenth struct, PvtPolyhedronTables.  It stands
+# beside CREATION_ENTRIES, not in it: that table lists the entries from before the convex polyhedron, which all refuse
+# geometry type 5, and of which pvt_scene_create_aligned is the only one that can be handed alignment tables.
+NEWEST_ENTRY = ("pvt_scene_create_polyhedra", 10)
 LEAN_CHECK_TABLES = 5   # pvt_scene_lean_check takes the first five
 
 
@@ -486,7 +503,7 @@ def declare_signatures(lib, names):
             [C.POINTER(PvtSceneTables), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
              C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64], C.c_int),
     }
-    for name, count in CREATION_ENTRIES.items():
+    for name, count in list(CREATION_ENTRIES.items()) + [NEWEST_ENTRY]:
         sigs[name] = (scene_inputs(count) + [C.c_int, C.POINTER(vp)], C.c_int)
     for name in names:
         argtypes, restype = sigs[name]
@@ -507,6 +524,7 @@ ABI_SYMBOLS = (
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
     "pvt_scene_create_origin", "pvt_scene_create_pattern", "pvt_scene_create_aligned", "pvt_scene_entry",
+    "pvt_scene_create_polyhedra",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 # the family's entry point a launch ran (PVT_ENTRY_*): its usual kernel, or the lean family's parking one
@@ -675,11 +693,10 @@ class DeviceScene:
         self.compiled = compiled
         self.device = int(device)
         st, keep = scene_tables_struct(compiled)
-        others, alive = extension_tables(compiled)
+        others, alive = extension_tables(compiled, NEWEST_ENTRY[1])
         handle = C.c_void_p()
         # (the newest entry, the only one Python ever calls: the older ones do the same with NULL for the structs they lack)
-        check(self.lib.pvt_scene_create_aligned(C.byref(st), *others, self.device, C.byref(handle)),
-              "pvt_scene_create_aligned")
+        check(getattr(self.lib, NEWEST_ENTRY[0])(C.byref(st), *others, self.device, C.byref(handle)), NEWEST_ENTRY[0])
         del keep, alive
         self.handle = handle
         self.has_emitter = False

@@ -497,6 +497,373 @@ class Frustum(Geometry):
         return (px / m, py / m, (-w) / m)
 
 
+MAX_POLYHEDRON_PLANES = 64   # (include/pvtrace_hip.h: PVT_MAX_POLYHEDRON_PLANES)
+
+
+def _plane_triple_vertices(rows):
+    """Every point where three of the planes `rows` (P, 4) meet and no plane is violated, near-equal points merged ->
+    (V, 3) array and the tolerance used (brute force over the triples; P <= 64 makes at most 41 664 of them)."""
+    P = len(rows)
+    n, h = rows[:, :3], rows[:, 3]
+    idx = np.array([(i, j, k) for i in range(P) for j in range(i + 1, P) for k in range(j + 1, P)], dtype=np.int64)
+    A = n[idx]
+    det = np.linalg.det(A)
+    ok = np.abs(det) > 1e-6   # (unit normals: a triple of nearly dependent planes would place its point badly)
+    if not np.any(ok):
+        return np.zeros((0, 3)), 0.0
+    pts = np.linalg.solve(A[ok], h[idx[ok]][..., None])[..., 0]
+    pts = pts[np.all(np.isfinite(pts), axis=1)]
+    slack = pts @ n.T - h
+    scale = max(float(np.max(np.abs(h))), 1e-300)
+    near = pts[np.all(slack <= 1e-7 * scale, axis=1)]
+    if len(near):
+        scale = max(scale, float(np.max(np.abs(near))))
+    tol = 1e-9 * scale
+    pts = pts[np.all(slack <= tol, axis=1)]
+    merged = []
+    for p in pts:
+        if not any(float(np.max(np.abs(p - q))) <= 100.0 * tol for q in merged):
+            merged.append(p)
+    return np.array(merged, dtype=np.float64).reshape(-1, 3), 100.0 * tol
+
+
+def _face_loop(vertices, on, normal):
+    """The indices `on` of the vertices of one face, ordered counter-clockwise seen from outside (along -normal), and the
+    face's area."""
+    pts = vertices[on]
+    centre = pts.mean(axis=0)
+    a = int(np.argmin(np.abs(normal)))
+    u = np.cross(normal, np.eye(3)[a])
+    u = u / math.sqrt(float(np.dot(u, u)))
+    v = np.cross(normal, u)
+    rel = pts - centre
+    order = np.argsort(np.arctan2(rel @ v, rel @ u), kind="stable")
+    loop = [on[int(i)] for i in order]
+    q = vertices[loop]
+    area = 0.5 * float(np.dot(normal, np.sum(np.cross(q, np.roll(q, -1, axis=0)), axis=0)))
+    return loop, area
+
+
+_ANALYSES = {}   # bytes of a table's rows -> its analysis: a scene is lowered on every `simulate`, a table analysed once
+
+
+def _polyhedron_analysis(planes):
+    """(problem, rows, vertices, faces, areas) of a plane table: `problem` is what is wrong with it (else None), `rows` the
+    rows as float64 (NOT normalised), and for a sound table the vertices, per plane its vertex loop and its area.  The
+    answer depends on the rows' doubles alone and is kept by their bytes (the last 64 tables)."""
+    try:
+        key = np.ascontiguousarray(planes, dtype=np.float64).tobytes() if np.ndim(planes) == 2 else None
+    except (TypeError, ValueError):
+        key = None
+    if key is not None and key in _ANALYSES:
+        return _ANALYSES[key]
+    found = _polyhedron_analysis_of(planes)
+    if key is not None:
+        if len(_ANALYSES) >= 64:
+            _ANALYSES.pop(next(iter(_ANALYSES)))
+        _ANALYSES[key] = found
+    return found
+
+
+def _polyhedron_rows(planes):
+    """(problem, rows) by the checks that need no geometry: the table's form, finite entries, the count, no zero normal."""
+    try:
+        rows = np.array(planes, dtype=np.float64)
+    except (TypeError, ValueError):
+        return "Polyhedron planes must be an array of rows (nx, ny, nz, h).", None
+    if rows.ndim != 2 or rows.shape[1] != 4:
+        return "Polyhedron planes must be an array of rows (nx, ny, nz, h).", None
+    if not np.all(np.isfinite(rows)):
+        return "Polyhedron plane entries must be finite.", None
+    P = rows.shape[0]
+    if not 4 <= P <= MAX_POLYHEDRON_PLANES:
+        return f"Polyhedron needs between 4 and {MAX_POLYHEDRON_PLANES} planes, got {P}.", None
+    length = np.sqrt((rows[:, 0] * rows[:, 0] + rows[:, 1] * rows[:, 1]) + rows[:, 2] * rows[:, 2])
+    if np.any(length == 0.0) or not np.all(np.isfinite(length)):
+        return "Polyhedron plane normals must not be zero.", None
+    return None, rows
+
+
+def _polyhedron_analysis_of(planes):
+    try:
+        rows = np.array(planes, dtype=np.float64)
+    except (TypeError, ValueError):
+        return "Polyhedron planes must be an array of rows (nx, ny, nz, h).", None, None, None, None
+    if rows.ndim != 2 or rows.shape[1] != 4:
+        return "Polyhedron planes must be an array of rows (nx, ny, nz, h).", None, None, None, None
+    if not np.all(np.isfinite(rows)):
+        return "Polyhedron plane entries must be finite.", None, None, None, None
+    P = rows.shape[0]
+    if not 4 <= P <= MAX_POLYHEDRON_PLANES:
+        return (f"Polyhedron needs between 4 and {MAX_POLYHEDRON_PLANES} planes, got {P}.", None, None, None, None)
+    length = np.sqrt((rows[:, 0] * rows[:, 0] + rows[:, 1] * rows[:, 1]) + rows[:, 2] * rows[:, 2])
+    if np.any(length == 0.0) or not np.all(np.isfinite(length)):
+        return "Polyhedron plane normals must not be zero.", None, None, None, None
+    unit = rows / length[:, None]
+    n = unit[:, :3]
+    # bounded: no direction u != 0 with n_k . u <= 0 for every k.  Normals of rank < 3 leave a line free; otherwise the cone
+    # of such directions is pointed and its extreme rays lie along +-(n_i x n_j)
+    unbounded = np.linalg.matrix_rank(n, tol=1e-9) < 3
+    if not unbounded:
+        pairs = np.array([(i, j) for i in range(P) for j in range(i + 1, P)], dtype=np.int64)
+        rays = np.cross(n[pairs[:, 0]], n[pairs[:, 1]])
+        norms = np.sqrt(np.sum(rays * rays, axis=1))
+        rays = rays[norms > 1e-9] / norms[norms > 1e-9][:, None]
+        rays = np.concatenate([rays, -rays])
+        unbounded = bool(np.any(np.all(rays @ n.T <= 1e-9, axis=1)))
+    if unbounded:
+        return "Polyhedron is unbounded: its plane normals leave a direction open.", None, None, None, None
+    vertices, tol = _plane_triple_vertices(unit)
+    if len(vertices) < 4:
+        return "Polyhedron is empty or has no interior.", None, None, None, None
+    centre = vertices.mean(axis=0)
+    scale = float(np.max(np.abs(vertices - centre)))
+    if not float(np.max(n @ centre - unit[:, 3])) < -1e-9 * scale:
+        return "Polyhedron is empty or has no interior.", None, None, None, None
+    faces, areas = [], []
+    for k in range(P):
+        for j in range(k):
+            if float(np.max(np.abs(n[k] - n[j]))) <= 1e-9 and abs(unit[k, 3] - unit[j, 3]) <= tol:
+                return (f"Polyhedron plane {k} is redundant: it repeats plane {j}.", None, None, None, None)
+        on = [int(i) for i in np.nonzero(np.abs(vertices @ n[k] - unit[k, 3]) <= tol)[0]]
+        loop, area = _face_loop(vertices, on, n[k]) if len(on) >= 3 else (on, 0.0)
+        if len(on) < 3 or not area > 1e-9 * scale * scale:
+            return (f"Polyhedron plane {k} is redundant: it owns no face of positive area.", None, None, None, None)
+        faces.append(loop)
+        areas.append(area)
+    return None, rows, vertices, faces, areas
+
+
+class Polyhedron(Geometry):
+    """Convex polyhedron: the intersection of half-spaces.  EXTENSION (the reference has no such shape).
+
+    `Polyhedron(planes, material=None)` takes `planes` as an array (P, 4) of rows (nx, ny, nz, h), with
+    4 <= P <= `MAX_POLYHEDRON_PLANES` = 64.
+
+    The solid is { p : n_k.p < h_k for all k } in the node's own frame.  It need not contain the node's origin.
+    The constructor normalises each row once: it divides the row by |n|.  From then on the stored doubles are the shape,
+    bit for bit, on the host and on the GPU.  (Once per construction: the computed |n| of a stored row may differ from 1 in
+    its last bit, so `Polyhedron(p.planes)` may differ from `p` in a last bit too.  `p.copy()` is the same shape exactly.)
+
+    Crossing distances of a ray (o, d) in the node's frame use IEEE double, no contraction and correctly rounded
+    division.  Planes are taken in index order:
+
+        tin = -inf; tout = +inf; miss = false
+        for k:  den = (nx*d.x + ny*d.y) + nz*d.z
+                num = h - ((nx*o.x + ny*o.y) + nz*o.z)
+                if fabs(den) < 1e-300:  if num < 0: miss = true;  continue
+                t = num / den
+                if den < 0:  tin = fmax(tin, t)   else  tout = fmin(tout, t)
+        if !miss and !(tout < tin): candidates tin, then tout; each counts when finite and > EPS
+
+    This is the box's rule, `!(tmax < tmin)` included.  A plane nearly parallel to the ray is harmless whichever sign its
+    `den` rounds to.  An origin inside that plane gives a large t of the matching sense.  An origin outside gives a miss
+    either way.
+
+    The solid is convex, so the container rule of the analytic shapes (`nl == 1`) applies unchanged.
+
+    Normal at a surface point p: the row k* that minimises fabs(((nx*p.x + ny*p.y) + nz*p.z) - h), the first minimum
+    winning.  The normal is (nx, ny, nz) of k*, as stored.
+
+    `contains` and `is_on_surface` follow the tolerances of `Box`.
+
+    The device kernel (csrc/pvt_trace_kernel.h: polyhedron_hits_call, polyhedron_normal_call) repeats these operations in
+    this order.  Out of scope: non-convex solids, more than 64 planes.
+    """
+
+    def __init__(self, planes, material=None):
+        super(Polyhedron, self).__init__(material=material)
+        problem, rows = _polyhedron_rows(planes)     # (the solid itself is analysed once, on the normalised rows)
+        if problem:
+            raise ValueError(problem)
+        length = np.sqrt((rows[:, 0] * rows[:, 0] + rows[:, 1] * rows[:, 1]) + rows[:, 2] * rows[:, 2])
+        self._set_rows(rows / length[:, None])
+
+    def _set_rows(self, rows):
+        """Take `rows` as the shape, as they are (no normalisation)."""
+        problem, rows, vertices, faces, areas = _polyhedron_analysis(rows)
+        if problem:
+            raise ValueError(problem)
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        rows.setflags(write=False)
+        self._planes = rows
+        self._rows = [tuple(float(x) for x in row) for row in rows]
+        self._vertices, self._faces, self._areas = vertices, faces, areas
+
+    def copy(self, material=None):
+        """The same shape, row for row and bit for bit (nothing is normalised again), with `material`."""
+        twin = Polyhedron.__new__(Polyhedron)
+        Geometry.__init__(twin, material=material)
+        twin._set_rows(self._planes)
+        return twin
+
+    @staticmethod
+    def parameter_problem(planes):
+        """What is wrong with the plane table, or None."""
+        return _polyhedron_analysis(planes)[0]
+
+    # -- constructors ------------------------------------------------------
+    @classmethod
+    def prism(cls, polygon, length, material=None):
+        """A convex counter-clockwise polygon in xy, extruded +-length/2 along z.  The sides come first, in polygon order
+        (side i runs from point i to point i + 1), then the -z cap, then the +z cap."""
+        try:
+            pts = np.array(polygon, dtype=np.float64)
+            L = float(length)
+        except (TypeError, ValueError):
+            raise ValueError("Polyhedron.prism needs a polygon of (x, y) points and a length.") from None
+        if pts.ndim != 2 or pts.shape[1] != 2 or len(pts) < 3 or not np.all(np.isfinite(pts)):
+            raise ValueError("Polyhedron.prism needs a polygon of at least three finite (x, y) points.")
+        if not (math.isfinite(L) and L > 0.0):
+            raise ValueError("Polyhedron.prism length must be finite and > 0.")
+        edges = np.roll(pts, -1, axis=0) - pts
+        turn = edges[:, 0] * np.roll(edges, -1, axis=0)[:, 1] - edges[:, 1] * np.roll(edges, -1, axis=0)[:, 0]
+        if not np.all(turn > 0.0):
+            raise ValueError("Polyhedron.prism polygon must be convex and counter-clockwise, without straight corners.")
+        rows = [(e[1], -e[0], 0.0, e[1] * p[0] - e[0] * p[1]) for p, e in zip(pts, edges)]
+        rows += [(0.0, 0.0, -1.0, 0.5 * L), (0.0, 0.0, 1.0, 0.5 * L)]
+        return cls(rows, material=material)
+
+    @classmethod
+    def regular_prism(cls, sides, circumradius, length, material=None, phase=0.0):
+        """A prism over the regular polygon of `sides` corners on the circle of `circumradius`, the first at angle `phase`."""
+        sides = int(sides)
+        if sides < 3:
+            raise ValueError("Polyhedron.regular_prism needs at least 3 sides.")
+        if not (math.isfinite(float(circumradius)) and float(circumradius) > 0.0):
+            raise ValueError("Polyhedron.regular_prism circumradius must be finite and > 0.")
+        angles = float(phase) + 2.0 * math.pi * np.arange(sides) / sides
+        polygon = float(circumradius) * np.stack([np.cos(angles), np.sin(angles)], axis=1)
+        return cls.prism(polygon, length, material=material)
+
+    @classmethod
+    def box(cls, size, material=None):
+        """`Box(size)` as six planes: -x, +x, -y, +y, -z, +z."""
+        size = np.array(size, dtype=np.float64)
+        if size.shape != (3,):
+            raise ValueError("Box size must be (length, width, height).")
+        rows = []
+        for a in range(3):
+            for sign in (-1.0, 1.0):
+                row = [0.0, 0.0, 0.0, 0.5 * size[a]]
+                row[a] = sign
+                rows.append(row)
+        return cls(rows, material=material)
+
+    @classmethod
+    def from_vertices(cls, points, material=None):
+        """The convex hull of `points` by brute force over point triples, coplanar triples merged.  Refused when it would
+        need more than 64 planes."""
+        try:
+            pts = np.array(points, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("Polyhedron.from_vertices needs an array of (x, y, z) points.") from None
+        if pts.ndim != 2 or pts.shape[1] != 3 or len(pts) < 4 or not np.all(np.isfinite(pts)):
+            raise ValueError("Polyhedron.from_vertices needs at least four finite (x, y, z) points.")
+        scale = float(np.max(np.abs(pts - pts.mean(axis=0))))
+        tol = 1e-9 * scale
+        rows = []
+        N = len(pts)
+        for i in range(N):
+            for j in range(i + 1, N):
+                e = pts[j] - pts[i]
+                normals = np.cross(e, pts[j + 1:] - pts[i])
+                for n in normals:
+                    size = math.sqrt(float(np.dot(n, n)))
+                    if not size > 1e-9 * scale * scale:
+                        continue
+                    n = n / size
+                    side = (pts - pts[i]) @ n
+                    if np.all(side <= tol):
+                        pass
+                    elif np.all(side >= -tol):
+                        n = -n
+                    else:
+                        continue
+                    h = float(np.dot(n, pts[i]))
+                    if not any(float(np.max(np.abs(n - r[:3]))) <= 1e-9 and abs(h - r[3]) <= tol for r in rows):
+                        rows.append(np.array([n[0], n[1], n[2], h]))
+                        if len(rows) > MAX_POLYHEDRON_PLANES:
+                            raise ValueError(f"Polyhedron.from_vertices: the hull needs more than {MAX_POLYHEDRON_PLANES} planes.")
+        if len(rows) < 4:
+            raise ValueError("Polyhedron.from_vertices: the points span no solid.")
+        rows = np.array(rows) + 0.0    # (-0.0 -> 0.0)
+        return cls(rows, material=material)
+
+    # -- properties ----------------------------------------------------------
+    @property
+    def planes(self):
+        """(P, 4) the stored rows (nx, ny, nz, h), unit normals; read-only."""
+        return self._planes
+
+    @property
+    def vertices(self):
+        return self._vertices.copy()
+
+    @property
+    def faces(self):
+        """Per plane, the loop of its vertices (indices into `vertices`), counter-clockwise seen from outside."""
+        return [list(loop) for loop in self._faces]
+
+    def facet_normal(self, k):
+        """The outward normal of face k as stored: what to hand to `Coating(facet=...)` or `Recorder(facet=...)` for an
+        unrotated node."""
+        return tuple(self._rows[int(k)][:3])
+
+    @property
+    def volume(self):
+        centre = self._vertices.mean(axis=0)
+        return float(sum(area * (row[3] - float(np.dot(row[:3], centre))) for area, row in zip(self._areas, self._planes)) / 3.0)
+
+    @property
+    def surface_area(self):
+        return float(sum(self._areas))
+
+    @property
+    def bounding_radius(self):
+        """Largest vertex norm: a sphere of this radius about the node's origin holds the solid."""
+        return float(np.max(np.sqrt(np.sum(self._vertices * self._vertices, axis=1))))
+
+    # -- queries -------------------------------------------------------------
+    def _ray_distances(self, o, d):
+        ox, oy, oz = float(o[0]), float(o[1]), float(o[2])
+        dx, dy, dz = float(d[0]), float(d[1]), float(d[2])
+        tin, tout, miss = -math.inf, math.inf, False
+        for nx, ny, nz, h in self._rows:
+            den = (nx * dx + ny * dy) + nz * dz
+            num = h - ((nx * ox + ny * oy) + nz * oz)
+            if abs(den) < 1e-300:
+                if num < 0.0:
+                    miss = True
+                continue
+            t = num / den
+            if den < 0.0:
+                tin = max(tin, t)
+            else:
+                tout = min(tout, t)
+        if miss or tout < tin:
+            return []
+        return [t for t in (tin, tout) if math.isfinite(t) and t > EPS_ZERO]
+
+    def _plane_values(self, point):
+        px, py, pz = (float(x) for x in np.asarray(point, dtype=np.float64)[:3])
+        return [((nx * px + ny * py) + nz * pz) - h for nx, ny, nz, h in self._rows]
+
+    def contains(self, point):
+        return bool(all(-(s + EPS_ZERO) > 0.0 for s in self._plane_values(point)))
+
+    def is_on_surface(self, point):
+        values = self._plane_values(point)
+        return bool(all(s <= EPS_ZERO for s in values) and any(abs(s) < EPS_ZERO for s in values))
+
+    def normal(self, surface_point):
+        best, out = math.inf, None
+        for s, row in zip(self._plane_values(surface_point), self._rows):
+            if abs(s) < best:
+                best, out = abs(s), row[:3]
+        return tuple(out)
+
+
 class Mesh(Geometry):
     """Closed triangle mesh (reference pvtrace/geometry/mesh.py:11-24: `Mesh(trimesh, material)`).
 

@@ -19,7 +19,7 @@ import numpy as np
 from pvtrace_amd.data import fluro_red, lumogen_f_red_305
 from pvtrace_amd.engine.compiler import UnsupportedSceneError
 from pvtrace_amd.engine.instrument import auto_recorders, recorders_from_spec
-from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Sphere
+from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Polyhedron, Sphere
 from pvtrace_amd.light import (
     CircularMask, ConstantWavelengthMask, CubeMask, Light, RectangularMask, SpectrumWavelengthMask,
 )
@@ -213,6 +213,17 @@ class _Builder:
             except ValueError as exc:
                 raise SpecError(f"node {name!r}: {exc}") from None
             return Node(name=name, geometry=shape)
+        if "polyhedron" in entry or "prism" in entry:   # EXTENSION: a convex polyhedron (geometry.Polyhedron)
+            try:
+                if "polyhedron" in entry:
+                    g = entry["polyhedron"]
+                    shape = Polyhedron(g["planes"], material=self.material(g["material"]))
+                else:
+                    g = entry["prism"]
+                    shape = Polyhedron.prism(g["polygon"], g["length"], material=self.material(g["material"]))
+            except ValueError as exc:
+                raise SpecError(f"node {name!r}: {exc}") from None
+            return Node(name=name, geometry=shape)
         if "mesh" in entry:   # reference: trimesh.exchange.load (cli/parse.py:130-138); here STL only
             g = entry["mesh"]
             path = g["file"] if os.path.isabs(g["file"]) else os.path.join(self.base, g["file"])
@@ -232,7 +243,7 @@ class _Builder:
                 direction = self.direction(mask["direction"])
             return Node(name=name, light=Light(wavelength=wavelength, position=position,
                                                direction=direction, name=name))
-        raise SpecError(f"node {name!r}: needs a geometry (box / sphere / cylinder / frustum / mesh) or a light")
+        raise SpecError(f"node {name!r}: needs a geometry (box / sphere / cylinder / frustum / polyhedron / prism / mesh) or a light")
 
     def scene(self):
         entries = self.spec["nodes"]
