@@ -19,6 +19,8 @@ from pvtrace_amd.engine import native as N
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libpvt_oracle.so")
 
+WALK_LIB = os.path.join(HERE, "libpvt_bvh_walk.so")
+
 MATH_LIBM = 0       # bit-identical to the reference kernel
 MATH_PORTABLE = 1   # bit-identical to the HIP kernel
 
@@ -35,6 +37,9 @@ def build(force=False):
     if stale:
         subprocess.check_call(["make", "-C", HERE, "-B", "libpvt_oracle.so"],
                               stdout=subprocess.DEVNULL)
+    walk_deps = [os.path.join(HERE, "bvh_walk.cpp"), os.path.join(HERE, "..", "pvtrace_amd", "csrc", "pvt_bvh.h"), LIB]
+    if force or not os.path.exists(WALK_LIB) or any(os.path.getmtime(d) > os.path.getmtime(WALK_LIB) for d in walk_deps):
+        subprocess.check_call(["make", "-C", HERE, "libpvt_bvh_walk.so"], stdout=subprocess.DEVNULL)   # (no -B: it would rebuild the library above under a process that may have loaded it)
     return LIB
 
 
@@ -278,6 +283,54 @@ def mesh_hits(vertices, faces, origin, direction):
     n = lib().pvt_oracle_mesh_hits(v.ctypes.data, f.ctypes.data, len(f), o.ctypes.data, d.ctypes.data,
                                    ts.ctypes.data, tris.ctypes.data, cap)
     return ts[:n].copy(), tris[:n].copy()
+
+
+_walk_lib = None
+
+
+def bvh_walk_check(vertices, faces, origins, directions, crossings=None, want_reached=False):
+    """The host restatement of the kernel's f32 BVH cull (oracle/bvh_walk.cpp) on the tree `BvhBuilder` builds for the mesh.
+    `crossings`: (ray, face, t) arrays sorted by ray -- the crossings to look for; None: the brute-force loop of `mesh_hits`
+    finds them.  -> dict: `lost` (crossings in a leaf the walk does not reach), `first_lost` (ray, face), `min_slack`
+    (least slack / pad) and `at` (its ray, face, axis), `checked`, `pad`, `leaves`, `most_leaves`, `records`, `depth`, and with
+    `want_reached` the faces reached per ray as a list of arrays."""
+    global _walk_lib
+    if _walk_lib is None:
+        build()
+        lib()                                   # (libpvt_oracle.so first: the walk library links it)
+        L = C.CDLL(WALK_LIB)
+        L.pvt_bvh_walk_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64]
+        L.pvt_bvh_walk_check.restype = C.c_int
+        _walk_lib = L
+    v = np.ascontiguousarray(vertices, dtype=np.float64); f = np.ascontiguousarray(faces, dtype=np.int32)
+    o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+    n = len(o)
+    if crossings is None:
+        cr = cf = ct = None
+        nc = -1
+    else:
+        cr = np.ascontiguousarray(crossings[0], dtype=np.int32); cf = np.ascontiguousarray(crossings[1], dtype=np.int32)
+        ct = np.ascontiguousarray(crossings[2], dtype=np.float64)
+        nc = len(cr)
+        assert np.all(np.diff(cr) >= 0), "crossings must be sorted by ray"
+    out = np.zeros(13)
+    ptr = np.zeros(n + 1, dtype=np.int64) if want_reached else None
+    reached = np.zeros(max(n * len(f), 1), dtype=np.int32) if want_reached else None
+    data = lambda a: None if a is None else a.ctypes.data
+    code = _walk_lib.pvt_bvh_walk_check(v.ctypes.data, len(v), f.ctypes.data, len(f), o.ctypes.data, d.ctypes.data, n,
+                                        data(cr), data(cf), data(ct), nc, out.ctypes.data, data(ptr), data(reached),
+                                        0 if reached is None else reached.size)
+    if code != 0:
+        raise RuntimeError(f"pvt_bvh_walk_check failed: {code}")
+    result = {"lost": int(out[0]), "first_lost": (int(out[1]), int(out[2])), "min_slack": float(out[3]),
+              "at": (int(out[4]), int(out[5]), int(out[6])), "checked": int(out[7]), "pad": float(out[8]),
+              "leaves": int(out[9]), "most_leaves": int(out[10]), "records": int(out[11]), "depth": int(out[12])}
+    if want_reached:
+        result["reached"] = [reached[ptr[j]:ptr[j + 1]].copy() for j in range(n)]
+    return result
 
 
 # ---------------------------------------------------------------------------

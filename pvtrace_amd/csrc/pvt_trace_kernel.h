@@ -3371,6 +3371,25 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 nrm.y = T.dv(q + 3) * nloc.x + T.dv(q + 4) * nloc.y + T.dv(q + 5) * nloc.z;
                 nrm.z = T.dv(q + 6) * nloc.x + T.dv(q + 7) * nloc.y + T.dv(q + 8) * nloc.z;
             }
+            if constexpr (MESH) {
+                // EXTENSION (meshes): a flight of thousands of length units ends short of the face, or beyond it, by the
+                // rounding of its length -- ulp(t) / 2, 4.5e-13 at t = 3 755 -- which is more than kEps: from there the next
+                // intersection would find the SAME face ahead and cross it a second time.  The landing point is put back on
+                // the face's plane along the ray when it is off it by more than kEps / 4 (never in a scene of ordinary size:
+                // there the distance is a few 1e-16, and nothing changes).  oracle/pvt_oracle.c does the same, bit for bit.
+                if (ev_kind != PVT_EV_EXIT && node_geom(tb) == PVT_GEOM_MESH) {
+                    const V3 lp = local_point();
+                    const pvt::MeshTri* tr = A.tris + tri1;
+                    const double off = ((lp.x - tr->v[0]) * nloc.x + (lp.y - tr->v[1]) * nloc.y) + (lp.z - tr->v[2]) * nloc.z;
+                    const double back = -off / dot3(nrm, dir);
+                    // (only what the flight's own rounding explains, a few ulp of its length: a larger distance -- a grazing ray
+                    // on a sliver, whose stored normal is itself only so good -- stays as it is; flights of ordinary length never get here)
+                    if (pvt_fabs(back) > 0.25 * kEps && pvt_fabs(back) < 2e-15 * t0) {
+                        pos.x = pos.x + dir.x * back; pos.y = pos.y + dir.y * back; pos.z = pos.z + dir.z * back;
+                        travelled += back;
+                    }
+                }
+            }
         }
 
         PVT_MARK(3);  // frame + normal
