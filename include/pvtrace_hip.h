@@ -1004,7 +1004,10 @@ int pvt_scene_entry(PvtScene* scene);
 /* Host-only (no GPU needed): *lean = 0 when the tables are not proven plain in the sense above, 2 when they are and every
  * spectrum is a constant or an even grid bit for bit (the family's kernels without table searches), 1 when some grid is
  * even only up to rounding (np.linspace: the family's kernels that search) -- the proof alone, on the packed tables;
- * whether a launch then runs PVT_VARIANT_LEAN also needs the tables to fit in LDS. */
+ * whether a launch then runs PVT_VARIANT_LEAN also needs the tables to fit in LDS.  When *lean is 0 the call still
+ * returns PVT_OK, and pvt_last_error() reads "not lean: " followed by the first fact the proof asks for that the tables
+ * do not meet -- among them "an index pair without a proven critical-angle threshold": the lean kernels decide total
+ * reflection by a proven cosine threshold alone. */
 int pvt_scene_lean_check(const PvtSceneTables* tables, const PvtIndexTables* index_tables, const PvtPhaseTables* phase_tables,
                          const PvtSurfaceTables* surface_tables, const PvtFieldTables* field_tables,
                          const PvtMapTables* map_tables, int32_t* lean);

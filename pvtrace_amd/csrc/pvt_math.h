@@ -48,6 +48,49 @@ PVT_HD_STATIC double pvt_clear_lo(double x) {
 PVT_HD_STATIC double pvt_sqrt(double x) { return __builtin_sqrt(x); }
 PVT_HD_STATIC double pvt_fabs(double x) { return __builtin_fabs(x); }
 
+#if defined(__HIPCC__)
+// RN(x/y) for finite normal y with a normal reciprocal and x zero or normal with |x| > 1e-280, the quotient
+// neither overflowing nor subnormal (wavelengths, Fresnel amplitudes, free paths: many orders of magnitude
+// inside): the compiler's IEEE division sequence (reciprocal estimate, two Newton steps, quotient, residual,
+// final fused correction) without the operand scaling and the special-case fix-up that only matter outside
+// that range -- same intermediate values, same result, three instructions fewer.
+__device__ __forceinline__ double div_normal(double x, double y) {
+    double r = __builtin_amdgcn_rcp(y);
+    double e = __builtin_fma(-y, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-y, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    const double q = x * r;
+    e = __builtin_fma(-y, q, x);
+    return __builtin_fma(e, r, q);
+}
+// RN(sqrt(x)) for x zero, or normal and not below 2^-767 (NaN for negative x, like the library): the compiler's
+// IEEE square-root sequence (reciprocal-root estimate, one coupled Newton step, two fused residual corrections,
+// zeros and +inf passed through) without the scaling of tiny operands.  The operands in the kernel are 1 - c^2
+// and (1 - c)(1 + c) for cosines and sines: zero, or 2^-53 and above.
+__device__ __forceinline__ double sqrt_normal(double x) {
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    double d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    return __builtin_amdgcn_class(x, 0x260) ? x : g;   // -0, +0, +inf
+}
+#endif
+// The quotient and the root of the range-proven functions below (pvt_log_unit, pvt_acos_unit): on the device the short
+// sequences above, whose operand ranges each call site states; on the host the plain IEEE operations they equal.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PVT_DIV_IN_RANGE(x, y) div_normal((x), (y))
+#define PVT_SQRT_IN_RANGE(x) sqrt_normal(x)
+#else
+#define PVT_DIV_IN_RANGE(x, y) ((x) / (y))
+#define PVT_SQRT_IN_RANGE(x) __builtin_sqrt(x)
+#endif
+
 // ---------------------------------------------------------------- log
 PVT_HD_STATIC double pvt_log(double x) {
     const double ln2_hi = 6.93147180369123816490e-01;
@@ -79,6 +122,38 @@ PVT_HD_STATIC double pvt_log(double x) {
     double f = x - 1.0;
     double hfsq = 0.5 * f * f;
     double s = f / (2.0 + f);
+    double z = s * s;
+    double w = z * z;
+    double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+    double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+    double R = t2 + t1;
+    double dk = (double)k;
+    return s * (hfsq + R) + dk * ln2_lo - hfsq + f + dk * ln2_hi;
+}
+
+// pvt_log on the arguments the photon loop draws: x = 1 - rng_uniform() = k 2^-53 with 1 <= k <= 2^53.  Such an x is
+// never zero, negative, subnormal or infinite, so none of pvt_log's special cases can be met, and x == 1 needs none:
+// the reduction gives k = 0 and f = 0, hence s = 0, R = 0 and the sum +0.0, pvt_log's own answer.  What is left is
+// pvt_log's reduction and polynomial, operation for operation -- the same bits on the whole domain
+// (tests/test_log_acos_unit.py).  The quotient f / (2 + f): f is zero or 2^-53 <= |f| < 0.42, the divisor lies in
+// [1.70, 2.42] -- div_normal's preconditions.
+PVT_HD_STATIC double pvt_log_unit(double x) {
+    const double ln2_hi = 6.93147180369123816490e-01;
+    const double ln2_lo = 1.90821492927058770002e-10;
+    const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,
+                 Lg3 = 2.857142874366239149e-01, Lg4 = 2.222219843214978396e-01,
+                 Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+                 Lg7 = 1.479819860511658591e-01;
+    const uint64_t u = pvt_d2u(x);
+    uint32_t hx = (uint32_t)(u >> 32);
+    // reduce to [sqrt(2)/2, sqrt(2))
+    hx += 0x3ff00000u - 0x3fe6a09eu;
+    const int k = (int)(hx >> 20) - 0x3ff;
+    hx = (hx & 0x000fffffu) + 0x3fe6a09eu;
+    x = pvt_u2d(((uint64_t)hx << 32) | (u & 0xffffffffull));
+    double f = x - 1.0;
+    double hfsq = 0.5 * f * f;
+    double s = PVT_DIV_IN_RANGE(f, 2.0 + f);
     double z = s * s;
     double w = z * z;
     double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
@@ -249,6 +324,38 @@ PVT_HD_STATIC double pvt_acos(double x) {
     double df = pvt_clear_lo(s);  // x > 0.5
     double c = (z - df * df) / (s + df);
     double w = r * s + c;
+    return 2.0 * (df + w);
+}
+
+// pvt_acos on [0, 1], the clamped cosines the tallies park (-0.0 counts as 0): 1.0 gives exactly 0.0, anything up to
+// 2^-57 gives pio2_hi, as pvt_acos does; the branch for x < -0.5 and the one for |x| > 1 or NaN are left out.  The
+// rest is pvt_acos operation for operation -- the same bits on the whole domain (tests/test_log_acos_unit.py).
+// Operand ranges of the short sequences (div_normal, sqrt_normal):
+//   * z is x^2 with 2^-57 < x < 0.5, or (1 - x) / 2 with 0.5 <= x < 1: 2^-114 < z <= 0.25;
+//   * p / q of the rational R(z): 2^-117 < p < 0.05 and 0.51 < q <= 1;
+//   * the root of z = (1 - x) / 2: 2^-54 <= z <= 0.25, so 2^-27 <= s <= 0.5;
+//   * (z - df^2) / (s + df), df = s without its low word: the numerator is zero or at least an ulp of z
+//     (>= 2^-106) and below 2^-19 s^2, the divisor lies in [2^-27, 1].
+PVT_HD_STATIC double pvt_acos_unit(double x) {
+    const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
+    const double pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01,
+                 pS2 = 2.01212532134862925881e-01, pS3 = -4.00555345006794114027e-02,
+                 pS4 = 7.91534994289814532176e-04, pS5 = 3.47933107596021167570e-05;
+    const double qS1 = -2.40339491173441421878e+00, qS2 = 2.02094576023350569471e+00,
+                 qS3 = -6.88283971605453293030e-01, qS4 = 7.70381505559019352791e-02;
+    const uint32_t ix = pvt_hi(x) & 0x7fffffffu;
+    if (ix >= 0x3ff00000u) return 0.0;  // x == 1, the only such value of the domain
+    const int small = ix < 0x3fe00000u;  // x < 0.5
+    if (small && ix <= 0x3c600000u) return pio2_hi;
+    const double z = small ? x * x : (1.0 - x) * 0.5;
+    const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const double r = PVT_DIV_IN_RANGE(p, q);
+    if (small) return pio2_hi - (x - (pio2_lo - x * r));
+    const double s = PVT_SQRT_IN_RANGE(z);
+    const double df = pvt_clear_lo(s);
+    const double c = PVT_DIV_IN_RANGE(z - df * df, s + df);
+    const double w = r * s + c;
     return 2.0 * (df + w);
 }
 

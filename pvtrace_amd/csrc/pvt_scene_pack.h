@@ -387,6 +387,7 @@ struct PackedScene {
     int origin_mask = 0;   // bit k: a histogram axis is launch-origin property PVT_PROPX_ORIGIN_WAVELENGTH + k
     bool lean_ok = false;   // see prove_lean: the scene may run the trace_kernel_lean family ...
     bool lean_even = false; // ... and every spectrum its loop reads is a constant or on a proven even grid (its EVEN kernels)
+    const char* lean_why = nullptr;   // the first clause of prove_lean that failed (a literal; null when lean_ok)
     int grid_dims[3] = {0, 0, 0};
     std::vector<pvt::BvhNode> bvh_nodes;
     std::vector<pvt::MeshTri> bvh_tris;
@@ -1142,6 +1143,9 @@ int fill(const SceneInputs& in, const Classes& k, const Spectra& sp, const Recor
     }
     // index table of each class (-1: scalar)
     auto class_table = [&](int m) { return p->n_rtab > 0 ? x->node_table[k.idx_first[m]] : -1; };
+    // (PVT_NO_COS_THRESHOLD: no finite threshold counts as proven, so every such pair takes the kernel's computed arm --
+    // the reference's own expression, same results -- and the scene is not lean: prove_lean's last clause)
+    const bool no_threshold = getenv("PVT_NO_COS_THRESHOLD") != nullptr;
     if (lay.crit_d >= 0)
         for (int c = 0; c < M; c++)
             for (int a = 0; a < M; a++) {
@@ -1150,7 +1154,7 @@ int fill(const SceneInputs& in, const Classes& k, const Spectra& sp, const Recor
                 // a pair with a dispersive side has no angle of its own: NaN sends its lanes to the computed branch
                 if (class_table(c) >= 0 || class_table(a) >= 0) crit = NAN;
                 gd[lay.crit_d + c * M + a] = crit;
-                gd[lay.ccrit_d + c * M + a] = crit == crit ? cosine_threshold(crit) : NAN;
+                gd[lay.ccrit_d + c * M + a] = crit != crit || (no_threshold && crit < INFINITY) ? NAN : cosine_threshold(crit);
             }
     for (int q = 0; q < Q; q++) {
         double* d = gd.data() + lay.rot_d + q * RT;
@@ -1382,7 +1386,12 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
 //     (abscissae off x0 + i (xl - x0) / (n - 1) by more than 1e-9 of the spacing) is not the plain kind: generic family.
 //     That last clause is the definition of the class, not something the kernel relies on;
 //   * at most 64 recorders, and every entry of the candidate tables carries kRecPlain (no source filter, nothing to
-//     compare with the normal).
+//     compare with the normal);
+//   * every entry of the cosine-threshold table (Lay::ccrit_d) is a number: whichever (container, adjacent) pair of index
+//     classes a crossing brings up, total reflection is decided by comparing the cosine with a proven threshold, and the
+//     lean kernels do not hold the arm that evaluates acos and asin instead.  (An entry is NaN only where
+//     cosine_threshold could prove none; PVT_NO_COS_THRESHOLD makes every finite one NaN, for tests.)
+constexpr const char* kLeanNoThreshold = "an index pair without a proven critical-angle threshold";
 void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     const Lay& lay = p->lay;
     const std::vector<double>& gd = p->gd;
@@ -1401,6 +1410,9 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     auto grid_kind = [&](int at, int n, double w) { return (n == 1 || w == w) ? 2 : (nearly_even(at, n) ? 1 : 0); };
     bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && !p->has_frustum && !p->has_polyhedron && p->fd.empty() &&
               p->md.empty() && p->cd.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
+    // (the first clause that fails is named for pvt_scene_lean_check)
+    const char* why = ok ? nullptr : "an extension, a mesh, a node grid, or too many nodes or recorders";
+    auto refuse = [&](const char* clause) { if (ok) why = clause; ok = false; };
     for (int n = 0; n < N && ok; n++) {
         unsigned long long bits;
         std::memcpy(&bits, &gd[(size_t)n * ND + ND_BITS], 8);
@@ -1408,26 +1420,31 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
         const int geom = (int)(((unsigned int)bits >> 8) & 0xffu), rot_class = (int)(unsigned int)(bits >> 32);
         const int* q = gi.data() + n * NI;
         const bool shape_ok = geom == PVT_GEOM_BOX || (geom == PVT_GEOM_SPHERE && n == t->root_id);
-        if (!ident || !shape_ok || rot_class != 0 || q[NI_KCOUNT] != 0 || q[NI_CCOUNT] > 2) ok = false;
+        if (!ident || !shape_ok || rot_class != 0 || q[NI_KCOUNT] != 0 || q[NI_CCOUNT] > 2) refuse("a node that is no unrotated box, or holds more than two components");
         for (int k = 0; k < q[NI_CCOUNT] && ok; k++) {
             const int* ci = gi.data() + lay.comp_i + (q[NI_CREC] + k) * CI;
             const double* cd = gd.data() + lay.comp_d + (q[NI_CREC] + k) * CD;
             const bool luminophore = ci[CI_TYPE] == PVT_COMP_LUMINOPHORE;
-            if (!luminophore && ci[CI_TYPE] != PVT_COMP_ABSORBER) ok = false;
-            if (ci[CI_PHASE] != PVT_PHASE_ISOTROPIC) ok = false;
+            if (!luminophore && ci[CI_TYPE] != PVT_COMP_ABSORBER) refuse("a component that is neither an absorber nor a luminophore");
+            if (ci[CI_PHASE] != PVT_PHASE_ISOTROPIC) refuse("a phase function that is not isotropic");
             const int ka = ci[CI_ABS_HIST] != 0 ? 0 : grid_kind(ci[CI_ABS_X], ci[CI_ABS_N], cd[CD_ABS_W]);
             const int ke = !luminophore ? 2 : (ci[CI_EMS_HIST] != 0 ? 0 : grid_kind(ci[CI_EMS_X], ci[CI_EMS_N], cd[CD_EMS_W]));
-            if (ka == 0 || ke == 0) ok = false;
+            if (ka == 0 || ke == 0) refuse("a spectrum that is a histogram or off the even grid");
             if (ka != 2 || ke != 2) all_even = false;
         }
     }
     for (int block = 0; block < N * 7 && ok; block++) {   // (by_node: one candidate block per node and selector)
         const int* rec = gi.data() + lay.cand_i + block * 8;
         for (int b = 0; b < 6; b++)
-            if (rec[2 + b] >= 0 && !(rec[2 + b] & kRecPlain)) ok = false;
+            if (rec[2 + b] >= 0 && !(rec[2 + b] & kRecPlain)) refuse("a recorder entry that is not plain");
         for (int j = 0; j < rec[1]; j++)
-            if (!(gi[(size_t)lay.cand_list + rec[0] + j] & kRecPlain)) ok = false;
+            if (!(gi[(size_t)lay.cand_list + rec[0] + j] & kRecPlain)) refuse("a recorder entry that is not plain");
     }
+    // (with by_node the classes are few enough for the tables: crit_d >= 0; a NaN means cosine_threshold could not prove one)
+    if (ok && lay.ccrit_d < 0) refuse(kLeanNoThreshold);
+    for (int e = 0; e < lay.n_cls * lay.n_cls && ok; e++)
+        if (gd[(size_t)lay.ccrit_d + e] != gd[(size_t)lay.ccrit_d + e]) refuse(kLeanNoThreshold);
+    p->lean_why = why;
     p->lean_ok = ok;
     p->lean_even = ok && all_even;
 }

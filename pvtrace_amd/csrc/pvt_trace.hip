@@ -1151,6 +1151,8 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     const int rc = pack_scene({t, x, ph, rs, fr, mp, nullptr, nullptr, nullptr, kKnowsOrigin}, &packed);
     if (rc != PVT_OK) return rc;
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
+    // (no failure: the call is answered; pvt_last_error() names the first clause of prove_lean the scene does not meet)
+    if (!packed.lean_ok) g_error = std::string("not lean: ") + (packed.lean_why ? packed.lean_why : "unknown");
     return PVT_OK;
 }
 

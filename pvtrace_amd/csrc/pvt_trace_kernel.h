@@ -344,35 +344,8 @@ __device__ __forceinline__ double rng_uniform(Rng& r) {
 // (reciprocal estimate, two Newton steps, quotient, residual, final fused correction) without the operand
 // scaling and the special-case fix-up that only matter outside that range -- same intermediate values, same
 // result, four instructions fewer.  Zero, infinities and NaN come out as garbage (callers never use them).
-// RN(x/y) likewise, for finite normal y with a normal reciprocal and x zero or normal with |x| > 1e-280, the
-// quotient neither overflowing nor subnormal (wavelengths, Fresnel amplitudes, free paths: many orders of
-// magnitude inside): three instructions fewer than the general sequence.
-__device__ __forceinline__ double div_normal(double x, double y) {
-    double r = __builtin_amdgcn_rcp(y);
-    double e = __builtin_fma(-y, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-y, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    const double q = x * r;
-    e = __builtin_fma(-y, q, x);
-    return __builtin_fma(e, r, q);
-}
-// RN(sqrt(x)) for x zero, or normal and not below 2^-767 (NaN for negative x, like the library): the compiler's
-// IEEE square-root sequence (reciprocal-root estimate, one coupled Newton step, two fused residual corrections,
-// zeros and +inf passed through) without the scaling of tiny operands.  The operands here are 1 - c^2 and
-// (1 - c)(1 + c) for cosines and sines: zero, or 2^-53 and above.
-__device__ __forceinline__ double sqrt_normal(double x) {
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = y * 0.5;
-    const double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    return __builtin_amdgcn_class(x, 0x260) ? x : g;   // -0, +0, +inf
-}
+// (div_normal and sqrt_normal, the same idea for quotients and square roots, stand in pvt_math.h: the range-proven
+// functions there are built on them.)
 __device__ __forceinline__ double sqrt1m2_normal(double c) { return sqrt_normal((1.0 - c) * (1.0 + c)); }   // pvt_sqrt1m2
 __device__ __forceinline__ double rcp_normal(double x) {
     double r = __builtin_amdgcn_rcp(x);
@@ -1297,6 +1270,8 @@ __global__ void __launch_bounds__(kBlock) math_kernel(int fn, const double* x, d
         case 17: r = rcp_normal(v); break;
         case 18: r = div_normal(v, v * 0.7310585786300049 + 0.25); break;
         case 19: r = sqrt_normal(v); break;
+        case 20: r = pvt_log_unit(v); break;    // (v = k 2^-53, 1 <= k <= 2^53)
+        case 21: r = pvt_acos_unit(v); break;   // (v in [0, 1])
         default: { double d = v * 0.7310585786300049 + 0.25; r = div_known(v, d, 1.0 / d); break; }
     }
     y[i] = r;
@@ -1621,11 +1596,17 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
             if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT || bit == UF_ALIGN || bit == UF_PMAP) return false;
-            if (bit == UF_BY_NODE) return true;
+            if (bit == UF_BY_NODE || bit == UF_CRIT) return true;   // (UF_CRIT: the threshold table is there and holds no NaN)
         }
         unsigned int f = uflags;
         asm volatile("" : "+s"(f));
         return ((f >> bit) & 1u) != 0u;
+    };
+    // The logarithm of a draw, log(1 - rng_uniform()): the lean bodies take pvt_log_unit, which is pvt_log on exactly
+    // those arguments without the special cases none of them can reach -- the same bits, half the instructions.
+    auto log_draw = [](double x) __attribute__((always_inline)) -> double {
+        if constexpr (LEAN != kLeanOff) return pvt_log_unit(x);
+        else return pvt_log(x);
     };
 
     // ---- stage tables + zero accumulators --------------------------------
@@ -1975,7 +1956,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     auto tally_flush = [&]() {
         if (lane < tq_n) {
             const int r = tq_r[lane];
-            const double q_wl = tq_d[lane], q_angle = pvt_acos(tq_d[kTallyQ + lane]);
+            // (the parked cosine is t_cos, clamped to [0, 1] where the step forms it: pvt_acos_unit's domain)
+            const double q_wl = tq_d[lane], q_angle = pvt_acos_unit(tq_d[kTallyQ + lane]);
             const double q_duration = tq_d[2 * kTallyQ + lane], q_travelled = tq_d[3 * kTallyQ + lane];
             const int ri = L.rec_i + r * RI;
             atomicAdd(&acc_distinct[r], 1u);
@@ -2113,6 +2095,10 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         else emit_chunk((const KArgs*)ak, gi_, pool);
                     }
                 }
+                // (GIVEN rays are not staged like this.  Copying a chunk's 64 rays into the pool here, coalesced, and
+                // refilling from L2 was built and measured for the lean kernels: 2.4 % slower than reading the arrays in
+                // the refill, in 10 of 10 alternated runs -- the other waves of the SIMD already cover the refill's
+                // misses, and the copy is seven more loads and stores per chunk.  profiles/staged_refill.md)
                 if (seed_pool) {
                     // Seed the whole chunk NOW, with every lane busy, instead of inside each later
                     // refill with only the dead lanes active (8 64-bit multiplies per seed): lane l
@@ -3017,13 +3003,13 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
             // ONE advance for all three outcomes: to the absorption point if that comes first, else to the surface
             double depth = INFINITY;
             if constexpr (!ROUGH) {
-                if (hit != k_root && alpha > kAlphaZero) depth = div_normal(-pvt_log(1.0 - rng_uniform(rng)), alpha);
+                if (hit != k_root && alpha > kAlphaZero) depth = div_normal(-log_draw(1.0 - rng_uniform(rng)), alpha);
             } else {
                 // (the variants of scenes with a rough node or a lattice) the same draw on the unscaled sum; a container
                 // with a lattice marches its cells to tau* (PvtFieldTables), and the pick below divides that cell's
                 // coefficients.  (The tail's alpha cache holds the unscaled sums, which stay right for the draw.)
                 if (hit != k_root && alpha > kAlphaZero) {
-                    const double tau = -pvt_log(1.0 - rng_uniform(rng));
+                    const double tau = -log_draw(1.0 - rng_uniform(rng));
                     if (uf(UF_FIELD)) frec = (int)A.fd[container];
                     if (frec >= 0) {
                         const FieldMarch fm = field_march_call<TAB_LDS, ROUGH >= kExtAligned>(T, A.fd, frec, L.comp_i + crec * CI, L.comp_d + crec * CD, ccount,
@@ -3174,7 +3160,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                                                                 T.dv(cd + CD_EMS_RCP_C), __builtin_nan(""), eh ? __builtin_nan("") : ew);
                 }
                 // radiative / non-radiative lifetime: the last draw of either end
-                if (tau > 0.0) duration += -pvt_log(1.0 - rng_uniform(rng)) * tau;
+                if (tau > 0.0) duration += -log_draw(1.0 - rng_uniform(rng)) * tau;
             }
         } else {
             const int cu = comp;                       // the component's id (what the event and `source` name) ...
@@ -3273,7 +3259,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     terminal = true;
                 }
                 // radiative / non-radiative lifetime: the last draw of either branch
-                if (tau > 0.0) duration += -pvt_log(1.0 - rng_uniform(rng)) * tau;
+                if (tau > 0.0) duration += -log_draw(1.0 - rng_uniform(rng)) * tau;
             }
         }
 
@@ -3445,7 +3431,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // comparison of c1 itself wherever it could prove the two agree for every double)
                 const bool crit_tab = uf(UF_CRIT);
                 const double cc = kHoist ? hr_cc : (crit_tab ? T.dv(L.ccrit_d + kc * n_cls + ka) : __builtin_nan(""));
-                if (cc == cc) tir = c1 < cc;
+                // (lean: every pair the scene can produce has a proven threshold -- prove_lean's last clause -- so the
+                // arm that evaluates the reference's expression is not compiled)
+                if (LEAN != kLeanOff || cc == cc) tir = c1 < cc;
                 else {   // (rare: the threshold could not be proven, or the scene has too many indices for the tables)
                     if (kHoist && !uf(UF_BY_NODE)) { kc = T.iv(container * NI + NI_NCLS); ka = T.iv(adjacent * NI + NI_NCLS); }
                     // (a pair with a dispersive side has a NaN angle in the table: its quotient is formed here, with n at

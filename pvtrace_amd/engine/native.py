@@ -661,6 +661,14 @@ def lean_kind(compiled):
     return int(lean.value)
 
 
+def lean_refusal(compiled):
+    """Why the library does not prove the scene plain: the first clause of the proof that its packed tables fail
+    (pvt_scene_lean_check's message), or None for a lean scene.  Host only."""
+    if lean_kind(compiled) != 0:
+        return None
+    return load_library().pvt_last_error().decode().removeprefix("not lean: ")
+
+
 def node_grid_plan(compiled):
     """The node grid the library files the nodes of a many-node scene under (host only, no GPU needed;
     include/pvtrace_hip.h: pvt_node_grid_plan) -> dict(dims, lo, cell, guard, odd, masks[cells, 2] uint64),
