@@ -43,7 +43,9 @@ enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_ME
        /* EXTENSION (the reference has no such shape): a truncated cone, see below */
        PVT_GEOM_FRUSTUM = 4,
        /* EXTENSION (the reference has no such shape): a convex polyhedron, a table of planes, see PvtPolyhedronTables */
-       PVT_GEOM_POLYHEDRON = 5 };
+       PVT_GEOM_POLYHEDRON = 5,
+       /* EXTENSION (the reference has no such shape): a solid of revolution of a conic, see below */
+       PVT_GEOM_CONICOID = 6 };
 /* PVT_GEOM_FRUSTUM: a truncated cone along the node's z axis, centred on its origin; geom_params = (length L,
  * radius_bottom r0 at z = -L/2, radius_top r1 at z = +L/2, 0).  L finite and > 0; r0, r1 finite and >= 0, not both 0
  * (else PVT_ERR_INVALID).  Convex, so the container rule of the analytic shapes applies unchanged.  The arithmetic is
@@ -64,6 +66,39 @@ enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_ME
  * lean, and gets no node grid.  Which entry takes the type: pvt_scene_create_origin, pvt_scene_lean_check and the
  * host-buffer entries; every older pvt_scene_create* entry refuses it as before ("unknown geometry type"), as they refuse
  * the extension selectors and properties -- no entry was added. */
+/* PVT_GEOM_CONICOID: the solid of revolution { x*x + y*y < q(z), -L/2 < z < L/2 } of the conic q(z) = p0 + p1*z + p2*z*z,
+ * along the node's z axis, centred on its origin; geom_params = (L, p0, p1, p2).  Ellipsoids and spheroids, spherical caps
+ * (dome and plano-convex lenses), paraboloids, convex hyperboloid sheets; the cylinder and the cone as degenerate cases.
+ * The parameters must be finite, L > 0, q > 0 on the open interval, q(+-L/2) >= -2^-40*S with
+ * S = |p0| + |p1|*half + |p2|*half*half, and the solid convex: sqrt(q) is concave exactly when p1*p1 - 4*p0*p2 >= 0, and
+ * a profile with p1*p1 - 4*p0*p2 < -2^-40*(p1*p1 + 4|p0*p2|) is refused (a cone written as (rm + k*z)^2 is not, for one
+ * rounding).  Each problem is PVT_ERR_INVALID with its own message.  Convex, so the container rule of the analytic
+ * shapes applies unchanged.  An end with q(+-half) <= 2^-40*S is a POLE: it has no cap, no
+ * cap candidate and no cap normal.
+ * The arithmetic.  Host and device perform the same operations in the same order, in IEEE double, with no contraction and
+ * correctly rounded `/` and square root:
+ *     half = 0.5*L;  g = 0.5*p1 + p2*o.z;  s = d.x*d.x + d.y*d.y
+ *     a = s - (p2*d.z)*d.z
+ *     b = 2.0*((o.x*d.x + o.y*d.y) - g*d.z)
+ *     c = (o.x*o.x + o.y*o.y) - (p0 + (p1 + p2*o.z)*o.z)
+ *     disc = b*b - 4.0*a*c
+ *     if disc >= 0:
+ *         sq = sqrt(disc);  qq = -0.5*(b + copysign(sq, b))
+ *         if qq != 0:            t = c/qq
+ *         if fabs(a) > 1e-300:   t = qq/a
+ * ONE branch: always the cancellation-free roots.  A root is a crossing when z = o.z + t*d.z has -half < z < half
+ * strictly and t > EPS_ZERO, in the order written.
+ * Caps follow, -z then +z.  Each is tried when fabs(d.z) > 1e-300 and that end is no pole: t = (-+half - o.z)/d.z;
+ * x = o.x + t*d.x, y likewise; the cap is a candidate when x*x + y*y <= q_end, q_end being the Horner value
+ * p0 + (p1 + p2*z_end)*z_end, and t > EPS_ZERO.
+ * Normal, with tol = 1e-8 + 1e-5*fabs(half): at an end that is no pole, fabs(p.z -+ half) <= tol gives (0, 0, -+1), -z
+ * first; otherwise w = 0.5*p1 + p2*p.z, m = sqrt((p.x*p.x + p.y*p.y) + w*w), n = (p.x/m, p.y/m, (-w)/m).
+ * Additive under ABI 13.  A node record holds three shape parameters, so the four of such a node lie behind everything
+ * else in the scene's double blob and the record names where (as the plane rows of a polyhedron).  A scene with such a
+ * node runs the PVT_VARIANT_ROUGH family (with or without meshes), is never lean, and gets no node grid.  Which entry
+ * takes the type: pvt_scene_create_polyhedra alone, with or without polyhedron tables; every older pvt_scene_create*
+ * entry, pvt_scene_lean_check and the host-buffer pvt_trace_bundle* entries refuse it as "unknown geometry type" -- no
+ * entry was added. */
 enum { PVT_SURF_FRESNEL = 0, PVT_SURF_NULL = 1 };
 enum { PVT_COMP_ABSORBER = 0, PVT_COMP_SCATTERER = 1, PVT_COMP_LUMINOPHORE = 2, PVT_COMP_REACTOR = 3 };
 enum { PVT_PHASE_ISOTROPIC = 0, PVT_PHASE_HG = 1, PVT_PHASE_CONE = 2,
@@ -855,7 +890,8 @@ int pvt_scene_create_aligned(const PvtSceneTables* tables, const PvtIndexTables*
                              PvtScene** out);
 /* The same with convex polyhedra (PvtPolyhedronTables), and the one entry that knows geometry type PVT_GEOM_POLYHEDRON:
  * NULL, n_nodes 0 or a scene with no such node = exactly pvt_scene_create_aligned.  Every entry before it refuses the type
- * ("unknown geometry type"), as they did before it existed. */
+ * ("unknown geometry type"), as they did before it existed.  It is also the one entry that knows PVT_GEOM_CONICOID, which
+ * needs no table: the same refusals hold for that type. */
 int pvt_scene_create_polyhedra(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                                const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
                                const PvtFieldTables* field_tables, const PvtMapTables* map_tables,
@@ -990,7 +1026,7 @@ int pvt_scene_launch_info(PvtScene* scene, int32_t* grid, int32_t* block, int32_
  * table, no rough node, field or map, at most 64 recorders none of which filters by source, no mesh, no node grid --
  * and its tables fit in LDS: its launches run a variant of the trace kernel compiled for exactly that (same arithmetic,
  * same draws, bit-identical histories).  Everything else runs the generic families: W4 (analytic shapes, node loop),
- * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones, aligned components, convex polyhedra), MESH.  The environment variable PVT_NO_LEAN, read when the scene
+ * GRID (many nodes), ROUGH (rough nodes, fields, maps, captures, absorbing and patterned coatings, truncated cones, aligned components, convex polyhedra, conicoids), MESH.  The environment variable PVT_NO_LEAN, read when the scene
  * is created, sends a plain scene to the generic family too (parity tests, A/B runs). */
 enum { PVT_VARIANT_LEAN = 0, PVT_VARIANT_W4 = 1, PVT_VARIANT_GRID = 2, PVT_VARIANT_ROUGH = 3, PVT_VARIANT_MESH = 4 };
 /* ... of the last trace on this scene; before the first one, of a tally launch.  Returns PVT_VARIANT_*, < 0 on error. */

@@ -26,7 +26,7 @@ LAYOUT = {
     "engine": "engine", "engine.api": "engine.api", "engine.compiler": "engine.compiler", "engine.emit": "engine.emit",
     "engine.recorder": "engine.recorder", "engine.tally": "engine.tally", "engine.build": "engine.build",
     "geometry": "geometry", "geometry.geometry": "geometry", "geometry.box": "geometry", "geometry.sphere": "geometry",
-    "geometry.cylinder": "geometry", "geometry.frustum": "geometry", "geometry.polyhedron": "geometry", "geometry.mesh": "geometry", "geometry.utils": "geometry",
+    "geometry.cylinder": "geometry", "geometry.frustum": "geometry", "geometry.conicoid": "geometry", "geometry.polyhedron": "geometry", "geometry.mesh": "geometry", "geometry.utils": "geometry",
     "geometry.transformable": "geometry", "geometry.transformations": "geometry", "geometry.intersection": "scene",
     "light": "light", "light.light": "light", "light.ray": "light", "light.event": "light",
     "material": "material", "material.material": "material", "material.component": "material",

@@ -65,7 +65,8 @@ bool plan_node_grid(const PvtSceneTables* t, NodeGrid* g) {
     for (int n = 0; n < N; n++) {
         // (a truncated cone: the plain node loop serves its scene -- the `default` cases below, and the grid walk's
         // shape_hits in the kernel, mean "cylinder" and never see one)
-        if (t->geom_type[n] == PVT_GEOM_MESH || t->geom_type[n] == PVT_GEOM_FRUSTUM || t->geom_type[n] == PVT_GEOM_POLYHEDRON) return false;
+        if (t->geom_type[n] == PVT_GEOM_MESH || t->geom_type[n] == PVT_GEOM_FRUSTUM || t->geom_type[n] == PVT_GEOM_POLYHEDRON ||
+            t->geom_type[n] == PVT_GEOM_CONICOID) return false;
         const double* w = t->world_to_local + n * 16;
         const double* l = t->local_to_world + n * 16;
         const double* gp = t->geom_params + n * 4;
@@ -347,6 +348,11 @@ struct PackedScene {
     // it would be without them; such a node's record names its rows in its second and third shape parameter (ND_PARAMS + 1:
     // where they start in the double blob, ND_PARAMS + 2: how many, both as integers in the words' bits), which the host tables leave 0
     bool has_polyhedron = false;
+    // solids of revolution of a conic (PVT_GEOM_CONICOID): a node is one.  A node record holds three shape parameters and
+    // such a node has four, so (L, p0, p1, p2) lie BEHIND everything else in the double blob, the polyhedra's rows
+    // included; the node's record keeps L and names the place in its second shape parameter (ND_PARAMS + 1, an integer in
+    // the word's bits)
+    bool has_conicoid = false;
     // absorbing coatings (PvtCoatingAbsorbTables; -1: no coating absorbs).  Both blocks lie BEHIND everything the blobs of a
     // scene without them hold, so every other offset is what it would be without them, and are read from where the
     // spectra are read.  cabs_d: in the double blob, one record of kCa doubles (kCa*) per coating row, then the pooled
@@ -424,7 +430,7 @@ struct SceneInputs {
 constexpr Knows kKnowsBeforeAbsorb{PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_MESH};     // pvt_scene_create .. pvt_scene_create_capture
 constexpr Knows kKnowsAbsorb      {PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH};     // pvt_scene_create_absorb
 constexpr Knows kKnowsOrigin      {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_FRUSTUM};  // pvt_scene_create_origin, _pattern, _aligned, pvt_scene_lean_check
-constexpr Knows kKnowsPolyhedra   {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_POLYHEDRON};  // pvt_scene_create_polyhedra
+constexpr Knows kKnowsPolyhedra   {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_CONICOID};  // pvt_scene_create_polyhedra (the polyhedron, and the conicoid after it)
 constexpr Knows kKnowsHostBuffer  {PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_FRUSTUM};  // pvt_trace_bundle*: pvt_scene_create, but a truncated cone is taken
 
 // ---- validation: every index into a table that the packer follows on the host or the kernel on the device, checked
@@ -495,6 +501,34 @@ void put_grid_table(const GridTables& g, int j, double* d) {
     for (int i = 0; i < na * nw; i++) d[nw + na + i] = g.value[g.value_start[j] + i];
 }
 
+// A conicoid's ends (include/pvtrace_hip.h): the Horner values of q at -half and +half and the slack 2^-40 * S, with the
+// operations of geometry.Conicoid._ends
+struct ConicoidEnds { double half, q_lo, q_hi, slack; };
+ConicoidEnds conicoid_ends(const double* gp) {
+    const double L = gp[0], p0 = gp[1], p1 = gp[2], p2 = gp[3];
+    const double half = 0.5 * L;
+    const double S = (std::fabs(p0) + std::fabs(p1) * half) + (std::fabs(p2) * half) * half;
+    return {half, p0 + (p1 + p2 * (-half)) * (-half), p0 + (p1 + p2 * half) * half, 0x1p-40 * S};
+}
+// What is wrong with (L, p0, p1, p2), or null: geometry.Conicoid.parameter_problem, test for test and word for word
+const char* conicoid_problem(const double* gp) {
+    const double L = gp[0], p0 = gp[1], p1 = gp[2], p2 = gp[3];
+    if (!(std::isfinite(L) && std::isfinite(p0) && std::isfinite(p1) && std::isfinite(p2)))
+        return "conicoid: length and profile (p0, p1, p2) must be finite numbers";
+    if (!(L > 0.0)) return "conicoid: length must be > 0";
+    const ConicoidEnds e = conicoid_ends(gp);
+    bool inside = p0 > 0.0;
+    if (p2 > 0.0) {
+        const double zv = -0.5 * p1 / p2;
+        if (-e.half < zv && zv < e.half && !(p0 + (p1 + p2 * zv) * zv > e.slack)) inside = false;
+    }
+    if (!inside) return "conicoid: q(z) must be > 0 inside (-L/2, L/2): the solid has no interior or is pinched";
+    if (e.q_lo < -e.slack || e.q_hi < -e.slack) return "conicoid: q(z) is negative at an end";
+    if (p1 * p1 - 4.0 * p0 * p2 < -0x1p-40 * (p1 * p1 + 4.0 * std::fabs(p0 * p2)))
+        return "conicoid: the solid is not convex (p1*p1 - 4*p0*p2 < 0: sqrt(q) is not concave)";
+    return nullptr;
+}
+
 // the core tables, first part: the root, the geometry of every node and the meshes
 int validate_nodes(const PvtSceneTables* t, const Knows& knows) {
     const int N = t->n_nodes;
@@ -508,6 +542,10 @@ int validate_nodes(const PvtSceneTables* t, const Knows& knows) {
             if (!(std::isfinite(gp[1]) && std::isfinite(gp[2]) && gp[1] >= 0.0 && gp[2] >= 0.0))
                 return fail(PVT_ERR_INVALID, "frustum: radii must be finite and >= 0");
             if (gp[1] == 0.0 && gp[2] == 0.0) return fail(PVT_ERR_INVALID, "frustum: radii must not both be 0");
+        }
+        if (g == PVT_GEOM_CONICOID) {   // (L, p0, p1, p2): the rules and the messages of geometry.Conicoid.parameter_problem
+            const char* problem = conicoid_problem(t->geom_params + n * 4);
+            if (problem) return fail(PVT_ERR_INVALID, problem);
         }
         if (g != PVT_GEOM_MESH) continue;
         if (!t->mesh_face_start || !t->mesh_face_count || !t->mesh_vertices || !t->mesh_faces || !t->mesh_normals)
@@ -1339,6 +1377,14 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
                     break;
                 }
                 case PVT_GEOM_POLYHEDRON: radius = gp[0]; break;   // (its bounding radius: validate_polyhedra)
+                case PVT_GEOM_CONICOID: {   // sqrt(max of q on [-half, half] + half^2): the ends, and the vertex of a q that opens downwards
+                    const ConicoidEnds e = conicoid_ends(gp);
+                    double qmax = std::fmax(e.q_lo, e.q_hi);
+                    const double zv = gp[3] < 0.0 ? -0.5 * gp[2] / gp[3] : INFINITY;
+                    if (-e.half < zv && zv < e.half) qmax = std::fmax(qmax, gp[1] + (gp[2] + gp[3] * zv) * zv);
+                    radius = std::sqrt(qmax + e.half * e.half);
+                    break;
+                }
                 default: radius = INFINITY; break;   // (mesh scenes never take this path)
             }
             radius *= 1.0 + 1e-12;
@@ -1408,7 +1454,7 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     };
     // a searched table (CI_*_X, n points, its even_w in `w`): 2 = a constant or even bit for bit, 1 = even up to rounding, 0
     auto grid_kind = [&](int at, int n, double w) { return (n == 1 || w == w) ? 2 : (nearly_even(at, n) ? 1 : 0); };
-    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && !p->has_frustum && !p->has_polyhedron && p->fd.empty() &&
+    bool ok = t->n_coatings == 0 && p->n_ctab == 0 && p->n_rtab == 0 && p->n_ptab == 0 && p->rough_d < 0 && !p->has_frustum && !p->has_polyhedron && !p->has_conicoid && p->fd.empty() &&
               p->md.empty() && p->cd.empty() && p->bvh_nodes.empty() && !p->grid && lay.by_node == 1 && R <= 64;
     // (the first clause that fails is named for pvt_scene_lean_check)
     const char* why = ok ? nullptr : "an extension, a mesh, a node grid, or too many nodes or recorders";
@@ -1772,6 +1818,22 @@ void pack_polyhedra(const SceneInputs& in, PackedScene* p) {
     if (p->has_polyhedron) p->gd.push_back(0.0);   // (the blob's spare last element, as before)
 }
 
+// Conicoids (validated parameters): the four of every such node appended to the double blob, its record told where
+void pack_conicoids(const SceneInputs& in, PackedScene* p) {
+    const PvtSceneTables* t = in.t;
+    p->has_conicoid = false;
+    for (int n = 0; n < t->n_nodes; n++) {
+        if (t->geom_type[n] != PVT_GEOM_CONICOID) continue;
+        p->has_conicoid = true;
+        double* d = p->gd.data() + (size_t)n * ND;
+        const unsigned long long at = (unsigned long long)p->gd.size();
+        std::memcpy(&d[ND_PARAMS + 1], &at, 8);     // (an integer in the word's bits, as a polyhedron's)
+        d[ND_PARAMS + 2] = 0.0;
+        p->gd.insert(p->gd.end(), t->geom_params + (size_t)n * 4, t->geom_params + (size_t)n * 4 + 4);
+    }
+    if (p->has_conicoid) p->gd.push_back(0.0);   // (the blob's spare last element, as before)
+}
+
 // The scene's inputs (n_nodes and n_recorders already checked by the caller; the pattern tables are pack_patterns') -> *p.
 // No HIP call.
 int pack_scene(const SceneInputs& in, PackedScene* p) {
@@ -1814,6 +1876,7 @@ int pack_scene(const SceneInputs& in, PackedScene* p) {
     pack_captures(in, p);
     pack_absorb(in, records, p);
     pack_polyhedra(in, p);
+    pack_conicoids(in, p);
     prove_shortcuts(t, p);
     prove_lean(t, p);
     return PVT_OK;

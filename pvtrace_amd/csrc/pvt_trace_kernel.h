@@ -54,7 +54,7 @@ constexpr unsigned long long kEmitSalt = 0xA5A5A5A55A5A5A5Aull;
 // Rotations, refractive-index reciprocals and critical angles live in small side tables indexed by CLASS (nodes with
 // bit-identical rotations / refractive indices share an entry), so a scene of 120 tiles costs 12 KB of LDS, not 56.
 enum { ND_T = 0, ND_PARAMS = 3, ND_BITS = 6, ND_N = 7, ND = 8 };  // node doubles: translation of world->local, three shape
-                                                                 // parameters (no shape has four), one word of {bit 0: the
+                                                                 // parameters (a shape with four keeps them behind the blob), one word of {bit 0: the
                                                                  // rotation is the identity, bit for bit; bits 8-15: geometry
                                                                  // type; high half: rotation class}, refractive index
 enum { NI_SURF = 0, NI_CSTART, NI_CCOUNT, NI_CREC, NI_KSTART, NI_KCOUNT, NI_MESH, NI_CAND, NI_NCLS, NI };  // node ints (NI_CSTART: id of the
@@ -634,8 +634,8 @@ __device__ __attribute__((noinline)) V3 phase_table_turn_call(const double* tab,
 // intermediate of the general branch is the capped cylinder's.  A FUNCTION, called only from the trace_kernel_rough*
 // variants: the plain families carry none of it.
 struct FrustumHits { double t[4]; };
-__device__ __attribute__((noinline)) FrustumHits frustum_hits_call(double length, double r0, double r1, double ox, double oy, double oz,
-                                                                   double dx, double dy, double dz) {
+__device__ __forceinline__ FrustumHits frustum_hits(double length, double r0, double r1, double ox, double oy, double oz,
+                                                    double dx, double dy, double dz) {
     FrustumHits h{{0.0, 0.0, 0.0, 0.0}};
     const double half = 0.5 * length, rm = 0.5 * (r0 + r1), k = (r1 - r0) / length;
     const double e = rm + k * oz, f = k * dz, s = dx * dx + dy * dy;
@@ -675,7 +675,7 @@ __device__ __attribute__((noinline)) FrustumHits frustum_hits_call(double length
     return h;
 }
 // ... and the outward normal at the point p of its surface: the cylinder's cap rule, then the gradient of the side
-__device__ __attribute__((noinline)) V3 frustum_normal_call(double length, double r0, double r1, double px, double py, double pz) {
+__device__ __forceinline__ V3 frustum_normal(double length, double r0, double r1, double px, double py, double pz) {
     const double half = 0.5 * length;
     const double tol = 1e-8 + 1e-5 * pvt_fabs(half);
     if (pvt_fabs(pz + half) <= tol) return V3{0.0, 0.0, -1.0};
@@ -736,6 +736,78 @@ __device__ __attribute__((noinline)) V3 polyhedron_normal_call(const double* pla
         if (dist < best) { best = dist; n = V3{nx, ny, nz}; }
     }
     return n;
+}
+
+// Solids of revolution of a conic (PVT_GEOM_CONICOID; include/pvtrace_hip.h states the arithmetic, geometry.Conicoid
+// performs the same operations in the same order): the four candidate distances of the ray (o, d) in the node's frame, in
+// fold order -- root, root, -z cap, +z cap -- a candidate that is no crossing being 0 (never > kEps), as FrustumHits.  ONE
+// branch, always the roots without the cancellation: a near-paraxial ray onto a paraboloid has a -> 0.  An end where q is
+// within 2^-40 S of zero is a pole and has no cap.  FUNCTIONS, called only from the trace_kernel_rough* variants: the plain
+// families carry none of it.
+__device__ __forceinline__ FrustumHits conicoid_hits(double length, double p0, double p1, double p2, double ox, double oy,
+                                                     double oz, double dx, double dy, double dz) {
+    FrustumHits h{{0.0, 0.0, 0.0, 0.0}};
+    const double half = 0.5 * length, g = 0.5 * p1 + p2 * oz, s = dx * dx + dy * dy;
+    const double a = s - (p2 * dz) * dz;
+    const double b = 2.0 * ((ox * dx + oy * dy) - g * dz);
+    const double c = (ox * ox + oy * oy) - (p0 + (p1 + p2 * oz) * oz);
+    const double disc = b * b - 4.0 * a * c;
+    if (disc >= 0.0) {
+        const double sq = pvt_sqrt(disc);
+        const double qq = -0.5 * (b + __builtin_copysign(sq, b));
+        const bool has_a = qq != 0.0, has_b = pvt_fabs(a) > 1e-300;
+        double ta = 0.0, tb = 0.0;
+        if (has_a) ta = c / qq;
+        if (has_b) tb = qq / a;
+        double z = oz + ta * dz;
+        if (has_a && z > -half && z < half) h.t[0] = ta;
+        z = oz + tb * dz;
+        if (has_b && z > -half && z < half) h.t[1] = tb;
+    }
+    if (pvt_fabs(dz) > 1e-300) {
+        const double slack = 0x1p-40 * ((pvt_fabs(p0) + pvt_fabs(p1) * half) + (pvt_fabs(p2) * half) * half);
+        const double q_lo = p0 + (p1 + p2 * (-half)) * (-half), q_hi = p0 + (p1 + p2 * half) * half;
+        if (!(q_lo <= slack)) {
+            const double t = (-half - oz) / dz;
+            const double x = ox + t * dx, y = oy + t * dy;
+            if (x * x + y * y <= q_lo) h.t[2] = t;
+        }
+        if (!(q_hi <= slack)) {
+            const double t = (half - oz) / dz;
+            const double x = ox + t * dx, y = oy + t * dy;
+            if (x * x + y * y <= q_hi) h.t[3] = t;
+        }
+    }
+    return h;
+}
+// ... and the outward normal at the point p of its surface: the cap rule at an end that is no pole, then the gradient
+__device__ __forceinline__ V3 conicoid_normal(double length, double p0, double p1, double p2, double px, double py, double pz) {
+    const double half = 0.5 * length;
+    const double tol = 1e-8 + 1e-5 * pvt_fabs(half);
+    const double slack = 0x1p-40 * ((pvt_fabs(p0) + pvt_fabs(p1) * half) + (pvt_fabs(p2) * half) * half);
+    const double q_lo = p0 + (p1 + p2 * (-half)) * (-half), q_hi = p0 + (p1 + p2 * half) * half;
+    if (!(q_lo <= slack) && pvt_fabs(pz + half) <= tol) return V3{0.0, 0.0, -1.0};
+    if (!(q_hi <= slack) && pvt_fabs(pz - half) <= tol) return V3{0.0, 0.0, 1.0};
+    const double w = 0.5 * p1 + p2 * pz;
+    const double m = pvt_sqrt((px * px + py * py) + w * w);
+    return V3{px / m, py / m, (-w) / m};
+}
+
+// The ONE pair of out-of-line entries of the two quadrics of revolution, so that the step loop of the trace_kernel_rough*
+// variants holds one call in the node loop and one at the normal site for both shapes, as it did for the truncated cone
+// alone: (g0, g1, g2, g3) = (L, r0, r1, NaN) of a truncated cone, (L, p0, p1, p2) of a conicoid -- no conicoid has a NaN, the
+// packer refuses it.  In the node loop the node is the wave's, so is the shape: the function says so (a function's
+// arguments arrive in vector registers) and branches on the first active lane's word, a scalar branch.
+__device__ __attribute__((noinline)) FrustumHits quadric_hits_call(double g0, double g1, double g2, double g3, double ox, double oy,
+                                                                   double oz, double dx, double dy, double dz) {
+    const unsigned int top = __builtin_amdgcn_readfirstlane((unsigned int)(pvt_d2u(g3) >> 32));
+    if ((top & 0x7ff00000u) == 0x7ff00000u) return frustum_hits(g0, g1, g2, ox, oy, oz, dx, dy, dz);
+    return conicoid_hits(g0, g1, g2, g3, ox, oy, oz, dx, dy, dz);
+}
+// ... and the normal: here the hit node is the lane's own, so is the branch
+__device__ __attribute__((noinline)) V3 quadric_normal_call(double g0, double g1, double g2, double g3, double px, double py, double pz) {
+    if (g3 != g3) return frustum_normal(g0, g1, g2, px, py, pz);
+    return conicoid_normal(g0, g1, g2, g3, px, py, pz);
 }
 
 // Rough interfaces (PvtSurfaceTables; include/pvtrace_hip.h states the contract, the Python FresnelSurfaceDelegate samples
@@ -2861,8 +2933,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         t = (-b + sq) / (2.0 * a);
                         if (t > kEps) fold(t);
                     }
-                } else if (ROUGH && gt == PVT_GEOM_FRUSTUM) {   // EXTENSION: truncated cone (frustum_hits_call; no node grid holds one)
-                    const FrustumHits fh = frustum_hits_call(gpar[0], gpar[1], gpar[2], o.x, o.y, o.z, d.x, d.y, d.z);
+                } else if (ROUGH && (gt == PVT_GEOM_FRUSTUM || gt == PVT_GEOM_CONICOID)) {   // EXTENSION: truncated cone, conicoid (quadric_hits_call; no node grid holds one)
+                    // (a conicoid's record names where its four parameters lie in the double blob -- pack_conicoids; the node is
+                    // the wave's, so they come through the scalar cache; a truncated cone has three and a NaN for the fourth)
+                    double q0 = gpar[0], q1 = gpar[1], q2 = gpar[2], q3 = __builtin_nan("");
+                    if (gt == PVT_GEOM_CONICOID) {
+                        const CDoubles cq = T.gd + (int)pvt_d2u(gpar[1]);
+                        q0 = cq[0]; q1 = cq[1]; q2 = cq[2]; q3 = cq[3];
+                    }
+                    const FrustumHits fh = quadric_hits_call(q0, q1, q2, q3, o.x, o.y, o.z, d.x, d.y, d.z);
 #pragma unroll
                     for (int j = 0; j < 4; j++)
                         if (fh.t[j] > kEps) fold(fh.t[j]);
@@ -3335,8 +3414,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 double mag = pvt_sqrt(dot3(lp, lp));
                 return V3{lp.x / mag, lp.y / mag, lp.z / mag};
             }
-            if (ROUGH && !GRID && gt == PVT_GEOM_FRUSTUM)   // (no node grid holds a truncated cone: plan_node_grid)
-                return frustum_normal_call(param(0), param(1), param(2), lp.x, lp.y, lp.z);
+            if (ROUGH && !GRID && (gt == PVT_GEOM_FRUSTUM || gt == PVT_GEOM_CONICOID)) {   // (no node grid holds either: plan_node_grid)
+                // (a conicoid's four parameters from global memory, the node being the lane's own)
+                double q0 = param(0), q1 = param(1), q2 = param(2), q3 = __builtin_nan("");
+                if (gt == PVT_GEOM_CONICOID) {
+                    const double* cq = T.hd + (int)pvt_d2u(q1);
+                    q0 = cq[0]; q1 = cq[1]; q2 = cq[2]; q3 = cq[3];
+                }
+                return quadric_normal_call(q0, q1, q2, q3, lp.x, lp.y, lp.z);
+            }
             if (ROUGH && !GRID && gt == PVT_GEOM_POLYHEDRON)   // (likewise; the rows from global memory, where the spectra of large scenes are read)
                 return polyhedron_normal_call(T.hd + (int)pvt_d2u(param(1)), (int)pvt_d2u(param(2)), lp.x, lp.y, lp.z);
             double half = 0.5 * param(0);

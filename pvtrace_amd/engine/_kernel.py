@@ -43,6 +43,13 @@ def _host_buffer_scene(compiled):
             "The scene has a convex polyhedron (Polyhedron), whose plane table the host-buffer trace_bundle entry (the "
             "reference's interface) has no way to receive; trace it with engine.simulate."
         )
+    if getattr(compiled, "has_conicoid", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has a solid of revolution of a conic (Conicoid), which the host-buffer trace_bundle entry (the "
+            "reference's interface) does not take; trace it with engine.simulate."
+        )
     if getattr(compiled, "has_alignment", False):
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 
@@ -134,8 +141,8 @@ def trace_bundle(compiled, positions, directions, wavelengths, seed, maxsteps, m
     sampled on the device (`wavelengths` must then be the ray count).  `devices` (a list of GPU
     ids, repeats allowed) splits the bundle over several GPUs inside this one call
     (`pvt_trace_bundle_multi`); the result is independent of the list."""
+    st, keep = _host_buffer_scene(compiled)   # (refuses what the entries cannot take before anything else is touched)
     lib = N.load_library()
-    st, keep = _host_buffer_scene(compiled)
     if positions is None:
         n = int(wavelengths)
         rays_ref = None
@@ -191,8 +198,8 @@ def trace_bundle_sets(compiled, positions, directions, wavelengths, seed, maxste
                       *, device=0, ray_offset=0):
     """Tally-mode trace of consecutive bundles of `bundle` rays in ONE launch (host buffers; the C entry
     `pvt_trace_bundle` with `PvtTraceParams.tally_bundle`) -> one dict of rec_* arrays per bundle."""
+    st, keep = _host_buffer_scene(compiled)   # (refuses what the entries cannot take before anything else is touched)
     lib = N.load_library()
-    st, keep = _host_buffer_scene(compiled)
     pos = np.ascontiguousarray(positions, dtype=np.float64)
     dirs = np.ascontiguousarray(directions, dtype=np.float64)
     wl = np.ascontiguousarray(wavelengths, dtype=np.float64)

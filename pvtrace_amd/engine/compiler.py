@@ -35,7 +35,7 @@ from pvtrace_amd.engine.recorder import (
     Recorder,
     VolumeMap,
 )
-from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Polyhedron, Sphere, _polyhedron_analysis
+from pvtrace_amd.geometry import Box, Conicoid, Cylinder, Frustum, Mesh, Polyhedron, Sphere, _polyhedron_analysis
 from pvtrace_amd.material import (
     Absorber,
     Alignment,
@@ -63,6 +63,7 @@ MAX_PATTERN_CELLS = 1 << 26   # cells of all coating patterns of a scene: 64 MiB
 GEOM_BOX, GEOM_SPHERE, GEOM_CYLINDER, GEOM_MESH = 0, 1, 2, 3
 GEOM_FRUSTUM = 4   # EXTENSION: truncated cone (include/pvtrace_hip.h: PVT_GEOM_FRUSTUM)
 GEOM_POLYHEDRON = 5   # EXTENSION: convex polyhedron, a table of planes (include/pvtrace_hip.h: PVT_GEOM_POLYHEDRON)
+GEOM_CONICOID = 6   # EXTENSION: solid of revolution of a conic (include/pvtrace_hip.h: PVT_GEOM_CONICOID)
 SURF_FRESNEL, SURF_NULL = 0, 1
 COMP_ABSORBER, COMP_SCATTERER, COMP_LUMINOPHORE, COMP_REACTOR = 0, 1, 2, 3
 PHASE_ISOTROPIC, PHASE_HENYEY_GREENSTEIN, PHASE_CONE = 0, 1, 2
@@ -369,6 +370,15 @@ class CompiledScene:
             self.geom_params[i, 0] = float(geometry.length)
             self.geom_params[i, 1] = float(geometry.radius_bottom)
             self.geom_params[i, 2] = float(geometry.radius_top)
+        elif isinstance(geometry, Conicoid):
+            # EXTENSION: the reference has no such solid; (length, p0, p1, p2), checked again here because the attributes
+            # may have been changed since construction
+            problem = Conicoid.parameter_problem(geometry.length, geometry.profile)
+            if problem:
+                raise UnsupportedSceneError(problem)
+            self.geom_type[i] = GEOM_CONICOID
+            self.geom_params[i, 0] = float(geometry.length)
+            self.geom_params[i, 1:4] = [float(v) for v in geometry.profile]
         elif isinstance(geometry, Polyhedron):
             # EXTENSION: the reference has no convex polyhedron; the stored rows are the shape, checked again here because
             # the attributes may have been changed since construction
@@ -491,6 +501,10 @@ class CompiledScene:
     @property
     def has_frustum(self):
         return bool(np.any(self.geom_type == GEOM_FRUSTUM))
+
+    @property
+    def has_conicoid(self):
+        return bool(np.any(self.geom_type == GEOM_CONICOID))
 
     @property
     def has_polyhedron(self):

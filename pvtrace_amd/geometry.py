@@ -371,7 +371,7 @@ class Frustum(Geometry):
 
     `length > 0`; both radii finite and >= 0, at most one of them 0 (a full cone whose apex lies on a cap plane).
 
-    The arithmetic, which the device kernel (csrc/pvt_trace_kernel.h: frustum_hits_call, frustum_normal_call) repeats operation
+    The arithmetic, which the device kernel (csrc/pvt_trace_kernel.h: frustum_hits, frustum_normal) repeats operation
     for operation in IEEE double, no contraction, correctly rounded `/` and square root:
 
         half = 0.5*L;  rm = 0.5*(r0 + r1);  k = (r1 - r0)/L
@@ -494,6 +494,247 @@ class Frustum(Geometry):
         m = math.sqrt((px * px + py * py) + w * w)
         if m == 0.0:
             raise GeometryError("Point on the frustum's apex has no normal.")
+        return (px / m, py / m, (-w) / m)
+
+
+_TWO_M40 = 2.0 ** -40   # (Conicoid: the share of S below which an end value of q is a pole, and the slack of its checks)
+
+
+class Conicoid(Geometry):
+    """Solid of revolution of a conic about z, centred on the origin: { x*x + y*y < q(z), -L/2 < z < L/2 } with
+    q(z) = p0 + p1*z + p2*z*z.  EXTENSION (the reference has no such shape).  `Conicoid(length, profile, material=None)`
+    with `profile = (p0, p1, p2)`: ellipsoids and spheroids, spherical caps (dome and plano-convex lenses), paraboloids,
+    convex hyperboloid sheets; the cylinder and the cone as degenerate cases.  The classmethods `ellipsoid`,
+    `spherical_cap`, `plano_convex`, `paraboloid` and `frustum` only compute (length, profile).
+
+    The parameters must be finite, L > 0, q > 0 on the open interval, q(+-L/2) >= -2^-40*S with
+    S = |p0| + |p1|*half + |p2|*half*half, and the solid convex: sqrt(q) is concave exactly when p1*p1 - 4*p0*p2 >= 0, and
+    a profile with p1*p1 - 4*p0*p2 < -2^-40*(p1*p1 + 4|p0*p2|) is refused (a cone written as (rm + k*z)^2 is not, for one
+    rounding).  `parameter_problem` names each problem with its own message.  Convex, so the container rule of the analytic
+    shapes applies unchanged.  An end with q(+-half) <= 2^-40*S is a POLE: it has no cap, no cap candidate and no cap normal.
+
+    The arithmetic (include/pvtrace_hip.h states it in the same words; csrc/pvt_trace_kernel.h: conicoid_hits,
+    conicoid_normal).  Host and device perform the same operations in the same order, in IEEE double, with no
+    contraction and correctly rounded `/` and square root:
+
+        half = 0.5*L;  g = 0.5*p1 + p2*o.z;  s = d.x*d.x + d.y*d.y
+        a = s - (p2*d.z)*d.z
+        b = 2.0*((o.x*d.x + o.y*d.y) - g*d.z)
+        c = (o.x*o.x + o.y*o.y) - (p0 + (p1 + p2*o.z)*o.z)
+        disc = b*b - 4.0*a*c
+        if disc >= 0:
+            sq = sqrt(disc);  qq = -0.5*(b + copysign(sq, b))
+            if qq != 0:            t = c/qq
+            if fabs(a) > 1e-300:   t = qq/a
+
+    ONE branch: always the cancellation-free roots.  A root is a crossing when z = o.z + t*d.z has -half < z < half
+    strictly and t > EPS_ZERO, in the order written.
+    Caps follow, -z then +z.  Each is tried when fabs(d.z) > 1e-300 and that end is no pole: t = (-+half - o.z)/d.z;
+    x = o.x + t*d.x, y likewise; the cap is a candidate when x*x + y*y <= q_end, q_end being the Horner value
+    p0 + (p1 + p2*z_end)*z_end, and t > EPS_ZERO.
+    Normal, with tol = 1e-8 + 1e-5*fabs(half): at an end that is no pole, fabs(p.z -+ half) <= tol gives (0, 0, -+1), -z
+    first; otherwise w = 0.5*p1 + p2*p.z, m = sqrt((p.x*p.x + p.y*p.y) + w*w), n = (p.x/m, p.y/m, (-w)/m).
+    `GeometryError` when m == 0 (a cone's apex).
+    """
+
+    def __init__(self, length, profile, material=None):
+        super(Conicoid, self).__init__(material=material)
+        self.length = length
+        self.profile = tuple(profile) if isinstance(profile, (tuple, list, np.ndarray)) else profile
+        problem = self.parameter_problem(length, profile)
+        if problem:
+            raise ValueError(problem)
+
+    @staticmethod
+    def _ends(L, p0, p1, p2):
+        """(half, q(-half), q(+half), 2^-40 * S) of checked parameters: the Horner values the caps are cut at."""
+        half = 0.5 * L
+        S = (abs(p0) + abs(p1) * half) + (abs(p2) * half) * half
+        return half, p0 + (p1 + p2 * (-half)) * (-half), p0 + (p1 + p2 * half) * half, _TWO_M40 * S
+
+    @staticmethod
+    def parameter_problem(length, profile):
+        """What is wrong with (length, (p0, p1, p2)), or None.  The messages are the library's (csrc/pvt_scene_pack.h)."""
+        try:
+            p0, p1, p2 = (float(v) for v in profile)
+            L = float(length)
+        except (TypeError, ValueError):
+            return "conicoid: length and profile (p0, p1, p2) must be finite numbers"
+        if not all(math.isfinite(v) for v in (L, p0, p1, p2)):
+            return "conicoid: length and profile (p0, p1, p2) must be finite numbers"
+        if not L > 0.0:
+            return "conicoid: length must be > 0"
+        half, q_lo, q_hi, slack = Conicoid._ends(L, p0, p1, p2)
+        # q inside the open interval: its value at the centre, and at its minimum where that lies inside (below the ends'
+        # slack there, a waist has closed: two solids that touch)
+        inside = p0 > 0.0
+        if p2 > 0.0:
+            zv = -0.5 * p1 / p2
+            if -half < zv < half and not p0 + (p1 + p2 * zv) * zv > slack:
+                inside = False
+        if not inside:
+            return "conicoid: q(z) must be > 0 inside (-L/2, L/2): the solid has no interior or is pinched"
+        if q_lo < -slack or q_hi < -slack:
+            return "conicoid: q(z) is negative at an end"
+        if p1 * p1 - 4.0 * p0 * p2 < -_TWO_M40 * (p1 * p1 + 4.0 * abs(p0 * p2)):
+            return "conicoid: the solid is not convex (p1*p1 - 4*p0*p2 < 0: sqrt(q) is not concave)"
+        return None
+
+    # -- builders: (length, profile) only -------------------------------------------------------------------------------
+    @classmethod
+    def ellipsoid(cls, equatorial_radius, polar_radius, material=None):
+        """x*x + y*y over a*a plus z*z over c*c below 1: a = equatorial_radius, c = polar_radius; both ends are poles."""
+        a, c = float(equatorial_radius), float(polar_radius)
+        if not (math.isfinite(a) and math.isfinite(c) and a > 0.0 and c > 0.0):
+            raise ValueError("Conicoid.ellipsoid radii must be finite and > 0.")
+        return cls(2.0 * c, (a * a, 0.0, -(a * a) / (c * c)), material=material)
+
+    @classmethod
+    def spherical_cap(cls, radius, height, material=None):
+        """The cap of height h of a sphere of radius R: flat base at -h/2, pole at +h/2, 0 < h <= 2R."""
+        R, h = float(radius), float(height)
+        if not (math.isfinite(R) and math.isfinite(h) and 0.0 < h <= 2.0 * R):
+            raise ValueError("Conicoid.spherical_cap needs a finite radius and 0 < height <= 2 * radius.")
+        zc = 0.5 * h - R   # the sphere's centre
+        return cls(h, (R * R - zc * zc, 2.0 * zc, -1.0), material=material)
+
+    @classmethod
+    def plano_convex(cls, diameter, radius_of_curvature, material=None):
+        """A plano-convex lens: the spherical cap of radius `radius_of_curvature` whose flat base has `diameter`."""
+        D, R = float(diameter), float(radius_of_curvature)
+        if not (math.isfinite(D) and math.isfinite(R) and 0.0 < D <= 2.0 * R):
+            raise ValueError("Conicoid.plano_convex needs 0 < diameter <= 2 * radius_of_curvature, both finite.")
+        return cls.spherical_cap(R, R - math.sqrt(R * R - 0.25 * D * D), material=material)
+
+    @classmethod
+    def paraboloid(cls, focal_length, height, material=None):
+        """r*r = 4 f (z + h/2): vertex (a pole) at -h/2, open end capped at +h/2, focus at -h/2 + f."""
+        f, h = float(focal_length), float(height)
+        if not (math.isfinite(f) and math.isfinite(h) and f > 0.0 and h > 0.0):
+            raise ValueError("Conicoid.paraboloid focal length and height must be finite and > 0.")
+        return cls(h, (2.0 * f * h, 4.0 * f, 0.0), material=material)
+
+    @classmethod
+    def frustum(cls, length, r0, r1, material=None):
+        """The truncated cone of `Frustum(length, r0, r1)`: q = (rm + k*z)^2 written out."""
+        problem = Frustum.parameter_problem(length, r0, r1)
+        if problem:
+            raise ValueError(problem)
+        L, r0, r1 = float(length), float(r0), float(r1)
+        rm, k = 0.5 * (r0 + r1), (r1 - r0) / L
+        return cls(L, (rm * rm, 2.0 * rm * k, k * k), material=material)
+
+    # -- descriptors ------------------------------------------------------------------------------------------------------
+    def _constants(self):
+        p0, p1, p2 = (float(v) for v in self.profile)
+        return float(self.length), p0, p1, p2
+
+    def poles(self):
+        """(the -z end is a pole, the +z end is a pole)"""
+        _, q_lo, q_hi, slack = self._ends(*self._constants())
+        return q_lo <= slack, q_hi <= slack
+
+    def radius_at(self, z):
+        """sqrt(q(z)) (0 where q < 0); a number or an array."""
+        _, p0, p1, p2 = self._constants()
+        q = p0 + (p1 + p2 * np.asarray(z, dtype=np.float64)) * np.asarray(z, dtype=np.float64)
+        r = np.sqrt(np.maximum(q, 0.0))
+        return float(r) if np.ndim(r) == 0 else r
+
+    @property
+    def volume(self):
+        L, p0, _, p2 = self._constants()
+        return math.pi * (p0 * L + p2 * L ** 3 / 12.0)
+
+    @property
+    def bounding_radius(self):
+        """Of a sphere about the origin that holds the solid: sqrt(max of q on [-half, half] + half*half)."""
+        L, p0, p1, p2 = self._constants()
+        half, q_lo, q_hi, _ = self._ends(L, p0, p1, p2)
+        qmax = max(q_lo, q_hi)
+        if p2 < 0.0 and -half < -0.5 * p1 / p2 < half:
+            zv = -0.5 * p1 / p2
+            qmax = max(qmax, p0 + (p1 + p2 * zv) * zv)
+        return math.sqrt(qmax + half * half)
+
+    @property
+    def focus(self):
+        """None, or the focal z values: (z,) of a paraboloid, (z-, z+) of a prolate ellipsoid."""
+        _, p0, p1, p2 = self._constants()
+        if p2 == 0.0:
+            return (-p0 / p1 + 0.25 * p1,) if p1 != 0.0 else None
+        if -1.0 < p2 < 0.0:
+            zc = -0.5 * p1 / p2
+            a2 = p0 + (p1 + p2 * zc) * zc     # equatorial radius squared; the polar one is a2 / -p2
+            e = math.sqrt(a2 / -p2 - a2)
+            return (zc - e, zc + e)
+        return None
+
+    # -- the geometry protocol --------------------------------------------------------------------------------------------
+    def _candidates(self, o, d):
+        """The four candidate distances in fold order -- root, root, -z cap, +z cap -- None where there is none."""
+        L, p0, p1, p2 = self._constants()
+        half, q_lo, q_hi, slack = self._ends(L, p0, p1, p2)
+        ox, oy, oz = float(o[0]), float(o[1]), float(o[2])
+        dx, dy, dz = float(d[0]), float(d[1]), float(d[2])
+        out = [None, None, None, None]
+        g = 0.5 * p1 + p2 * oz
+        s = dx * dx + dy * dy
+        a = s - (p2 * dz) * dz
+        b = 2.0 * ((ox * dx + oy * dy) - g * dz)
+        c = (ox * ox + oy * oy) - (p0 + (p1 + p2 * oz) * oz)
+        disc = b * b - 4.0 * a * c
+        if disc >= 0.0:
+            sq = math.sqrt(disc)
+            qq = -0.5 * (b + math.copysign(sq, b))
+            roots = [c / qq if qq != 0.0 else None, qq / a if abs(a) > 1e-300 else None]
+            for j, t in enumerate(roots):
+                if t is not None and -half < oz + t * dz < half:
+                    out[j] = t
+        if abs(dz) > 1e-300:
+            for j, (cap, q_end) in enumerate(((-half, q_lo), (half, q_hi))):
+                if q_end <= slack:   # a pole: no cap
+                    continue
+                t = (cap - oz) / dz
+                x, y = ox + t * dx, oy + t * dy
+                if x * x + y * y <= q_end:
+                    out[2 + j] = t
+        return out
+
+    def _ray_distances(self, o, d):
+        return [t for t in self._candidates(o, d) if t is not None and t > EPS_ZERO]
+
+    def contains(self, point):
+        p = np.asarray(point, dtype=np.float64)
+        r = math.hypot(p[0], p[1])
+        half = 0.5 * float(self.length)
+        return bool(
+            self.radius_at(float(p[2])) - (r + EPS_ZERO) > 0.0
+            and half - (abs(p[2]) + EPS_ZERO) > 0.0
+        )
+
+    def is_on_surface(self, point):
+        p = np.asarray(point, dtype=np.float64)
+        r, half = math.hypot(p[0], p[1]), 0.5 * float(self.length)
+        rz = self.radius_at(float(p[2]))
+        on_cap = abs(abs(p[2]) - half) < EPS_ZERO and r <= rz + EPS_ZERO
+        on_side = abs(r - rz) < EPS_ZERO and abs(p[2]) <= half + EPS_ZERO
+        return bool(on_cap or on_side)
+
+    def normal(self, surface_point):
+        p = np.asarray(surface_point, dtype=np.float64)
+        L, p0, p1, p2 = self._constants()
+        half, q_lo, q_hi, slack = self._ends(L, p0, p1, p2)
+        tol = 1e-8 + 1e-5 * abs(half)
+        if not q_lo <= slack and abs(p[2] + half) <= tol:
+            return (0.0, 0.0, -1.0)
+        if not q_hi <= slack and abs(p[2] - half) <= tol:
+            return (0.0, 0.0, 1.0)
+        px, py = float(p[0]), float(p[1])
+        w = 0.5 * p1 + p2 * float(p[2])
+        m = math.sqrt((px * px + py * py) + w * w)
+        if m == 0.0:
+            raise GeometryError("Point on the conicoid's apex has no normal.")
         return (px / m, py / m, (-w) / m)
 
 

@@ -19,7 +19,7 @@ import numpy as np
 from pvtrace_amd.data import fluro_red, lumogen_f_red_305
 from pvtrace_amd.engine.compiler import UnsupportedSceneError
 from pvtrace_amd.engine.instrument import auto_recorders, recorders_from_spec
-from pvtrace_amd.geometry import Box, Cylinder, Frustum, Mesh, Polyhedron, Sphere
+from pvtrace_amd.geometry import Box, Conicoid, Cylinder, Frustum, Mesh, Polyhedron, Sphere
 from pvtrace_amd.light import (
     CircularMask, ConstantWavelengthMask, CubeMask, Light, RectangularMask, SpectrumWavelengthMask,
 )
@@ -213,6 +213,23 @@ class _Builder:
             except ValueError as exc:
                 raise SpecError(f"node {name!r}: {exc}") from None
             return Node(name=name, geometry=shape)
+        for key in ("conicoid", "ellipsoid", "spherical-cap", "paraboloid"):   # EXTENSION: a solid of revolution of a conic (geometry.Conicoid)
+            if key not in entry:
+                continue
+            g = entry[key]
+            try:
+                material = self.material(g["material"])
+                if key == "conicoid":
+                    shape = Conicoid(g["length"], g["profile"], material=material)
+                elif key == "ellipsoid":
+                    shape = Conicoid.ellipsoid(g["equatorial-radius"], g["polar-radius"], material=material)
+                elif key == "spherical-cap":
+                    shape = Conicoid.spherical_cap(g["radius"], g["height"], material=material)
+                else:
+                    shape = Conicoid.paraboloid(g["focal-length"], g["height"], material=material)
+            except (TypeError, ValueError) as exc:
+                raise SpecError(f"node {name!r}: {exc}") from None
+            return Node(name=name, geometry=shape)
         if "polyhedron" in entry or "prism" in entry:   # EXTENSION: a convex polyhedron (geometry.Polyhedron)
             try:
                 if "polyhedron" in entry:
@@ -243,7 +260,7 @@ class _Builder:
                 direction = self.direction(mask["direction"])
             return Node(name=name, light=Light(wavelength=wavelength, position=position,
                                                direction=direction, name=name))
-        raise SpecError(f"node {name!r}: needs a geometry (box / sphere / cylinder / frustum / polyhedron / prism / mesh) or a light")
+        raise SpecError(f"node {name!r}: needs a geometry (box / sphere / cylinder / frustum / conicoid / ellipsoid / spherical-cap / paraboloid / polyhedron / prism / mesh) or a light")
 
     def scene(self):
         entries = self.spec["nodes"]
