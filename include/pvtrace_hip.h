@@ -101,6 +101,16 @@ enum { PVT_GEOM_BOX = 0, PVT_GEOM_SPHERE = 1, PVT_GEOM_CYLINDER = 2, PVT_GEOM_ME
  * entry was added. */
 enum { PVT_SURF_FRESNEL = 0, PVT_SURF_NULL = 1 };
 enum { PVT_COMP_ABSORBER = 0, PVT_COMP_SCATTERER = 1, PVT_COMP_LUMINOPHORE = 2, PVT_COMP_REACTOR = 3 };
+/* The built-in phase functions, about +z of the WORLD frame (a component) or of the light's frame (PVT_DIR_*), on two
+ * draws in stream order (_kernel.pyx:455-476).  PVT_PHASE_HG with |g| >= 2.220446049250313e-13: s = 2 u0 - 1,
+ * q = (1 - g g) / (1 + g s), cos = (1 / (2 g)) ((1 + g g) - q q), azimuth 2 pi u1.  PVT_PHASE_CONE: sin = sqrt(u0)
+ * sin(theta_max), azimuth 2 pi u1.  Otherwise (isotropic, and HG below that |g|): azimuth 2 pi u0, cos = 2 u1 - 1.  The
+ * partner of the sine / cosine is sqrt((1 - c)(1 + c)); the direction is (sin cos(az), sin sin(az), cos).
+ * DEPARTURE from the reference: the HG cosine cancels for small |g| and at the ends of the draw grid and can leave
+ * [-1, 1] by a few ulp (g = 0.3 at u0 = 0 gives a cosine below -1; about one draw in 10^5 at |g| <= 1e-10), where the
+ * reference's acos is NaN.  It is clamped to [-1, 1] before its sine is formed, as the table turn's cosine is.  An
+ * in-range value keeps its bits, so the engine departs from the reference only where the reference returns NaN -- the
+ * precedent of the critical-angle rule.  tests/exact_emission.py restates all of this and holds every implementation. */
 enum { PVT_PHASE_ISOTROPIC = 0, PVT_PHASE_HG = 1, PVT_PHASE_CONE = 2,
        /* EXTENSION (the reference engine rejects it, compiler.py:300-310; its Python path and its scene-spec parser have it,
         * material/utils.py:176-186, cli/parse.py:166-167): cosine-weighted about +z, theta = asin(sqrt(p1)), phi = 2 pi p2 */
@@ -694,7 +704,13 @@ typedef struct PvtCaptures {
 /* ---- optional device-side emission (replaces the Python/numpy emitter,
  * reference pvtrace/engine/emit.py:22-134).  Ray i is emitted by light
  * i % n_lights (scene.emit round-robin, scene/scene.py:141-151) from its own
- * RNG stream keyed by (emit_seed, global ray index).                        */
+ * RNG stream keyed by (emit_seed, global ray index): ((emit_seed + gi) mod 2^64) xor 0xA5A5A5A55A5A5A5A.
+ * Draw order: the wavelength (a spectrum light only: PVT_WL_SPECTRUM interpolates (cdf, x) at u, the knot at or
+ * below u found with <=, x[0] for u <= cdf[0], the last x for u >= the last cdf; PVT_WL_SPECTRUM_HIST below), then the
+ * position (-p + 2 p u per axis; the disc: angle RN(2 pi) u first, then radius sqrt(u) r), then the direction (the
+ * built-in phase functions above; PVT_DIR_LAMBERTIAN: sin = sqrt(u0), azimuth 2 pi u1).  Local -> world:
+ * ((m0 x + m1 y) + m2 z) + m3 per row, no fused multiply-add.  tests/exact_emission.py holds the referee, the host
+ * sampler and the three compiled copies of the kernel's emitter to this rule ray by ray. */
 enum { PVT_WL_CONSTANT = 0, PVT_WL_SPECTRUM = 1,
        PVT_WL_SPECTRUM_HIST = 2 /* histogram-sampled Distribution (material/distribution.py:171-176): x[#{cdf_i < u}], no interpolation */ };
 enum { PVT_POS_POINT = 0, PVT_POS_RECT = 1, PVT_POS_CIRCLE = 2, PVT_POS_CUBE = 3 };

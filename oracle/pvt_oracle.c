@@ -406,6 +406,9 @@ static void sample_phase(const MathSel* M, int type, double param, Rng* rng, dou
         double s = 2.0 * g1 - 1.0;
         double q = (1.0 - g * g) / (1.0 + g * s);
         cos_t = 1.0 / (2.0 * g) * (1.0 + g * g - q * q);
+        /* DEPARTURE: the quotient cancels for small |g| and at the ends of the draw grid and may leave [-1, 1] by a
+         * few ulp, where the reference's acos(cos_t) is NaN; clamped in both modes (an in-range value keeps its bits) */
+        cos_t = fmin(fmax(cos_t, -1.0), 1.0);
         turn = rng_uniform(rng);
         by_cosine = 1;
     } else if (type == PVT_PHASE_CONE) {

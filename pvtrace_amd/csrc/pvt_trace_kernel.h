@@ -1197,6 +1197,9 @@ __device__ __forceinline__ V3 sample_phase(int type, double param, Rng& rng) {
         double s = 2.0 * g1 - 1.0;
         double q = (1.0 - g * g) / (1.0 + g * s);
         cos_t = 1.0 / (2.0 * g) * (1.0 + g * g - q * q);
+        // the quotient cancels for small |g| and at the ends of the draw grid and may leave [-1, 1] by a few ulp, where
+        // the reference's acos is NaN: clamped, as the table turn's cosine is (an in-range value keeps its bits)
+        cos_t = __builtin_fmin(__builtin_fmax(cos_t, -1.0), 1.0);
         turn = rng_uniform(rng);
         sin_t = pvt_sqrt1m2(cos_t);
     } else if (type == PVT_PHASE_CONE) {
@@ -3271,6 +3274,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                         double sg = 2.0 * g1 - 1.0;
                         double q = (1.0 - pp * pp) / (1.0 + pp * sg);
                         em_c = 1.0 / (2.0 * pp) * (1.0 + pp * pp - q * q);
+                        em_c = __builtin_fmin(__builtin_fmax(em_c, -1.0), 1.0);   // (sample_phase: NaN in the reference)
                         em_turn = rng_uniform(rng);
                         em_s = sqrt1m2_normal(em_c);
                     } else if (pt == PVT_PHASE_CONE) {

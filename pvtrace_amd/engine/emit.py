@@ -304,7 +304,8 @@ def _sample_light(tab, i, n, uniform):
     elif kind == DIR_HG:
         s = 2 * uniform(n) - 1
         mu = (1 + prm * prm - ((1 - prm * prm) / (1 + prm * s)) ** 2) / (2 * prm)
-        direc = _sphere(np.arccos(mu), 2 * np.pi * uniform(n))
+        # (the quotient may leave [-1, 1] by a few ulp for small |g| and at the ends of the draw grid, where arccos is NaN)
+        direc = _sphere(np.arccos(np.clip(mu, -1.0, 1.0)), 2 * np.pi * uniform(n))
     else:
         direc = np.tile((0.0, 0.0, 1.0), (n, 1))
     return pos, direc, wl

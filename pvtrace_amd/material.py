@@ -106,6 +106,7 @@ def henyey_greenstein(g=0.0):
         return isotropic()
     s = 2 * p - 1
     mu = 1 / (2 * g) * (1 + g ** 2 - ((1 - g ** 2) / (1 + g * s)) ** 2)
+    mu = min(max(mu, -1.0), 1.0)   # the quotient may leave [-1, 1] by a few ulp (small |g|, p = 0): arccos would be NaN
     phi = 2 * np.pi * np.random.uniform()
     return spherical_to_cart(np.arccos(mu), phi)
 
