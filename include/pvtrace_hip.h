@@ -1053,6 +1053,20 @@ int pvt_scene_variant(PvtScene* scene);
  * drain rendezvous and the tail function, which such a launch cannot reach.  Every other launch: PVT_ENTRY_USUAL. */
 enum { PVT_ENTRY_USUAL = 0, PVT_ENTRY_PARK = 1 };
 int pvt_scene_entry(PvtScene* scene);
+/* Whether the last trace on this scene ran a solo entry (diagnostics; additive under ABI 13): 1 or 0, < 0 on error.
+ * A lean scene that is ONE unrotated box inside a root that is a box or a sphere strictly holding it, with no component in
+ * the root and no recorder on it, is "solo".  Its tally launches -- not its history launches (record_every > 0), and no
+ * launch of a scene where somebody observes exits -- run `trace_kernel_solo_park` / `trace_kernel_solo_fin`: the lean
+ * kernels with the node stage of a step in closed form (same arithmetic, same draws, bit-identical histories).
+ * pvt_scene_variant and pvt_scene_entry report such a launch as PVT_VARIANT_LEAN and PVT_ENTRY_PARK / PVT_ENTRY_USUAL as
+ * before.  The environment variable PVT_NO_SOLO, read when the scene is created, switches the solo entries off. */
+int pvt_scene_solo(PvtScene* scene);
+/* Host-only (no GPU needed): *solo = 1 when the tables are proven solo in the sense above (PVT_NO_SOLO unset), else 0;
+ * the call still returns PVT_OK then, and pvt_last_error() reads "not solo: " followed by the first clause the tables do
+ * not meet. */
+int pvt_scene_solo_check(const PvtSceneTables* tables, const PvtIndexTables* index_tables, const PvtPhaseTables* phase_tables,
+                         const PvtSurfaceTables* surface_tables, const PvtFieldTables* field_tables,
+                         const PvtMapTables* map_tables, int32_t* solo);
 /* Host-only (no GPU needed): *lean = 0 when the tables are not proven plain in the sense above, 2 when they are and every
  * spectrum is a constant or an even grid bit for bit (the family's kernels without table searches), 1 when some grid is
  * even only up to rounding (np.linspace: the family's kernels that search) -- the proof alone, on the packed tables;

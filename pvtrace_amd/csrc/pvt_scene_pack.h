@@ -394,6 +394,9 @@ struct PackedScene {
     bool lean_ok = false;   // see prove_lean: the scene may run the trace_kernel_lean family ...
     bool lean_even = false; // ... and every spectrum its loop reads is a constant or on a proven even grid (its EVEN kernels)
     const char* lean_why = nullptr;   // the first clause of prove_lean that failed (a literal; null when lean_ok)
+    bool solo = false;                // see prove_solo: tally launches with a lazy root may run the trace_kernel_solo entries
+    const char* solo_why = nullptr;   // the first clause of prove_solo that failed (a literal; null when solo)
+    const char* fuse_why = nullptr;   // the first clause of the fused exit's proof that failed (prove_shortcuts; null when fuse_exit)
     int grid_dims[3] = {0, 0, 0};
     std::vector<pvt::BvhNode> bvh_nodes;
     std::vector<pvt::MeshTri> bvh_tris;
@@ -1405,13 +1408,21 @@ void prove_shortcuts(const PvtSceneTables* t, PackedScene* p) {
     }
     // Fused exit (kernel surface branch): the scene is ONE unrotated box inside a lazy root whose medium neither
     // absorbs nor is listened to -- a photon that leaves the box's surface outwards can only leave the scene.
-    if (p->lazy_root && N == 2 && !getenv("PVT_NO_FUSED_EXIT")) {
+    // (the first clause that fails is named for pvt_scene_solo_check: fuse_why, null when fuse_exit holds)
+    const char* why = nullptr;
+    auto refuse = [&](const char* clause) { if (!why) why = clause; };
+    if (N != 2) refuse("not exactly one node inside the root");
+    else if (!p->lazy_root) refuse("the root is no box or sphere that strictly holds the child (or PVT_NO_LAZY_ROOT is set)");
+    else if (getenv("PVT_NO_FUSED_EXIT")) refuse("the fused exit is switched off (PVT_NO_FUSED_EXIT)");
+    else {
         const int child = 1 - root;
-        bool ok = t->geom_type[child] == PVT_GEOM_BOX && unrotated(t, child) && t->comp_count[root] == 0;
+        if (t->geom_type[child] != PVT_GEOM_BOX || !unrotated(t, child)) refuse("the child is no unrotated box");
+        if (t->comp_count[root] != 0) refuse("a component in the root");
         for (int r = 0; r < R; r++)
-            if (t->rec_node[r] == root) ok = false;
-        p->fuse_exit = ok;
+            if (t->rec_node[r] == root) refuse("a recorder on the root");
     }
+    p->fuse_why = why;
+    p->fuse_exit = why == nullptr;
 }
 
 // Lean scenes (kernel: trace_body's LEAN, the trace_kernel_lean family): every fact that variant holds as a constant,
@@ -1493,6 +1504,24 @@ void prove_lean(const PvtSceneTables* t, PackedScene* p) {
     p->lean_why = why;
     p->lean_ok = ok;
     p->lean_even = ok && all_even;
+}
+
+// Solo scenes (kernel: trace_body's SOLO, the trace_kernel_solo entries): a lean scene that moreover has the fused exit --
+// ONE unrotated box inside a lazy root (a box or a sphere) that holds no component and carries no recorder -- with its few
+// nodes numbered as they are (Lay::by_node).  The node stage of such a scene has three outcomes (inside the box, outside
+// and hitting it, outside and missing it), which the SOLO form selects instead of folding crossings.  Both facts are the
+// ones prove_shortcuts and prove_lean have established; the clauses below only name which of them a scene fails, in the
+// order a reader would ask (pvt_scene_solo_check); the fused exit's own clauses are named where they are decided, in
+// prove_shortcuts (PackedScene::fuse_why).  Whether a LAUNCH is solo is the host's decision on top of this: it
+// also needs `lazy_root` and `fuse_exit` in the launch's arguments -- a tally launch, nobody observing exits.
+void prove_solo(const PvtSceneTables*, PackedScene* p) {
+    const char* why = nullptr;
+    auto refuse = [&](const char* clause) { if (!why) why = clause; };
+    if (!p->lean_ok) refuse("the scene is not lean");
+    if (!p->fuse_exit) refuse(p->fuse_why ? p->fuse_why : "the fused exit is not proven");
+    if (p->lay.by_node != 1) refuse("the nodes are not numbered as they are (Lay::by_node)");
+    p->solo_why = why;
+    p->solo = why == nullptr;
 }
 
 // The field buffer p->fd (validated tables; left empty when no node carries a lattice): per node where its record starts,
@@ -1879,6 +1908,7 @@ int pack_scene(const SceneInputs& in, PackedScene* p) {
     pack_conicoids(in, p);
     prove_shortcuts(t, p);
     prove_lean(t, p);
+    prove_solo(t, p);
     return PVT_OK;
 }
 

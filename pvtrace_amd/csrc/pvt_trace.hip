@@ -168,6 +168,8 @@ struct PvtScene {
     bool lean_ok = false;           // see prove_lean: launches with the tables in LDS run the trace_kernel_lean family ...
     bool lean_even = false;         // ... its EVEN kernels (every spectrum a constant or on a proven even grid)
     int last_variant = -1;          // PVT_VARIANT_* of the last launch (-1: none yet)
+    bool solo = false;              // see prove_solo: tally launches with `lazy_root` and `fuse_exit` run the trace_kernel_solo entries
+    bool last_solo = false;         // ... whether the last launch did (Variant::solo)
     bool last_park = false;         // ... and whether it ran the family's parking entry (Variant::park)
 };
 
@@ -367,8 +369,9 @@ LdsPlan plan_lds(const PvtScene* s, bool record) {
 // the template arguments of that family's entry points.
 // `carry_out`: the launch parks its survivors for its successor -- its FINAL value, after bind_carry has had its say (a
 // launch too wide to park finishes its own photons, and needs a kernel that can).
-struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align, path, park; };
-Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit, bool carry_out = false) {
+// `shortcuts`: the launch's arguments carry both `lazy_root` and `fuse_exit` (a tally launch, nobody observing exits).
+struct Variant { int family; bool record; Tab tab; int seenw; bool emit, mesh, grid, even, align, path, park, solo; };
+Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool emit, bool carry_out = false, bool shortcuts = false) {
     Variant v{};
     v.record = record; v.emit = emit; v.tab = lp.tab;
     v.seenw = s->n_rec <= 64 ? 1 : 4;
@@ -384,6 +387,7 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.family = extension ? PVT_VARIANT_ROUGH : v.mesh ? PVT_VARIANT_MESH : v.grid ? PVT_VARIANT_GRID : lean ? PVT_VARIANT_LEAN : PVT_VARIANT_W4;
     v.even = v.family == PVT_VARIANT_LEAN && s->lean_even;
     v.park = v.family == PVT_VARIANT_LEAN && !record && carry_out;   // (the entries compiled without the drain and the tail)
+    v.solo = v.family == PVT_VARIANT_LEAN && !record && s->solo && shortcuts;   // (one box in a lazy root: the closed-form node stage)
     return v;
 }
 
@@ -436,6 +440,11 @@ Kernel kernel_of(const Variant& v) {
             if constexpr (has_grid) return trace_kernel_grid<R, W, E>;
             break;
         case PVT_VARIANT_LEAN:
+            if constexpr (has_lean && !R) if (v.solo) {
+                if (v.park) { if (v.even) return trace_kernel_solo_park<E, true>; return trace_kernel_solo_park<E, false>; }
+                if (v.even) return trace_kernel_solo_fin<E, true>;
+                return trace_kernel_solo_fin<E, false>;
+            }
             if constexpr (has_lean && !R) if (v.park) { if (v.even) return trace_kernel_lean_park<E, true>; return trace_kernel_lean_park<E, false>; }
             if constexpr (has_lean) { if (v.even) return trace_kernel_lean_w4<R, E, true>; return trace_kernel_lean_w4<R, E, false>; }
             break;
@@ -663,8 +672,9 @@ int trace_launch(PvtScene* s, const PvtRays* rays, const PvtTraceParams* p, cons
     const bool emit = rays == nullptr && s->d_ed != nullptr;
     if (emit && (rc = grow_emit_pool(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
     if (s->origin_mask && (rc = grow_origin_store(s, (size_t)slot, grid, st, a)) != PVT_OK) return rc;
-    const Variant v = choose_variant(s, lp, record, emit, carry_out);
+    const Variant v = choose_variant(s, lp, record, emit, carry_out, a.lazy_root != 0 && a.fuse_exit != 0);
     s->last_variant = v.family;
+    s->last_solo = v.solo;
     s->last_park = v.park;
     hipError_t e = hipErrorNotSupported;
     if (const Kernel kernel = kernel_of(v)) {
@@ -845,6 +855,7 @@ int create_scene(const SceneInputs& in, int device, PvtScene** out) {
     s->grid = packed.grid;
     s->lean_ok = packed.lean_ok && !getenv("PVT_NO_LEAN");   // (PVT_NO_LEAN: the generic family, for parity tests and A/B runs)
     s->lean_even = s->lean_ok && packed.lean_even;
+    s->solo = s->lean_ok && packed.solo && !getenv("PVT_NO_SOLO");   // (PVT_NO_SOLO: the lean family's own entries, for parity tests and A/B runs)
     for (int a = 0; a < 3; a++) s->grid_dims[a] = packed.grid_dims[a];
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -1145,6 +1156,11 @@ int pvt_scene_entry(PvtScene* s) {
     return s->last_park ? PVT_ENTRY_PARK : PVT_ENTRY_USUAL;
 }
 
+int pvt_scene_solo(PvtScene* s) {
+    if (!s) return fail(PVT_ERR_INVALID, "null scene");
+    return s->last_solo ? 1 : 0;
+}
+
 int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
                          const PvtFieldTables* fr, const PvtMapTables* mp, int32_t* lean) {
     if (!t || !lean) return fail(PVT_ERR_INVALID, "null argument");
@@ -1155,6 +1171,20 @@ int pvt_scene_lean_check(const PvtSceneTables* t, const PvtIndexTables* x, const
     *lean = packed.lean_ok ? (packed.lean_even ? 2 : 1) : 0;
     // (no failure: the call is answered; pvt_last_error() names the first clause of prove_lean the scene does not meet)
     if (!packed.lean_ok) g_error = std::string("not lean: ") + (packed.lean_why ? packed.lean_why : "unknown");
+    return PVT_OK;
+}
+
+int pvt_scene_solo_check(const PvtSceneTables* t, const PvtIndexTables* x, const PvtPhaseTables* ph, const PvtSurfaceTables* rs,
+                         const PvtFieldTables* fr, const PvtMapTables* mp, int32_t* solo) {
+    if (!t || !solo) return fail(PVT_ERR_INVALID, "null argument");
+    if (t->n_nodes <= 0 || t->n_nodes > PVT_MAX_NODES || t->n_recorders > PVT_MAX_RECORDERS) return fail(PVT_ERR_INVALID, "bad argument");
+    PackedScene packed;
+    const int rc = pack_scene({t, x, ph, rs, fr, mp, nullptr, nullptr, nullptr, kKnowsOrigin}, &packed);
+    if (rc != PVT_OK) return rc;
+    const bool off = getenv("PVT_NO_SOLO") != nullptr;   // (as at scene creation)
+    *solo = packed.solo && !off ? 1 : 0;
+    // (no failure: the call is answered; pvt_last_error() names the first clause of prove_solo the scene does not meet)
+    if (!*solo) g_error = std::string("not solo: ") + (off ? "PVT_NO_SOLO is set" : packed.solo_why ? packed.solo_why : "unknown");
     return PVT_OK;
 }
 

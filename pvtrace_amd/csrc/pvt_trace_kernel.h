@@ -1531,6 +1531,13 @@ struct Seen {
 // rendezvous -- it takes the `tail_total` photons its caller left in the exchange buffer and steps them until none is left.
 template <bool RECORD, int TAB_LDS, int SEENW, bool MESH, bool GRID, int ROUGH = 0, int LEAN = 0>
 __device__ void tail_run(const KArgs* kernel_args, int total, unsigned int lds);
+// (the SOLO instantiation of the same loop, for the trace_kernel_solo_fin entries: a function of its own, so that
+// tail_run's instantiations keep their names)
+#ifndef PVT_SOLO_TAIL
+#define PVT_SOLO_TAIL 1   // the tail function takes the closed-form node stage too (0: the node loop alone, the A/B of profiles/solo_step.md)
+#endif
+template <int LEAN>
+__device__ void tail_run_solo(const KArgs* kernel_args, int total, unsigned int lds);
 
 // A wave leaves its workgroup: the LAST one to do so adds the workgroup's accumulators (LDS) to the launch's outputs -- one
 // global atomic per non-zero slot -- and its step counters to the scene's.  (No closing barrier: retiring waves must never
@@ -1601,7 +1608,7 @@ __device__ __attribute__((noinline)) void leave_workgroup(const KArgs* kernel_ar
 }
 
 template <bool RECORD, int TAB_LDS, int SEENW, bool EMIT, bool MESH, bool GRID = false, bool TAIL = false, int ROUGH = 0,
-          int LEAN = 0, bool PARK = false>
+          int LEAN = 0, bool PARK = false, bool SOLO = false>
 __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, unsigned int tail_lds = 0u) {
     // LEAN (the trace_kernel_lean family): the scene is of the plain kind the host proves at its creation (pvt_scene_pack.h:
     // prove_lean) -- unrotated boxes (in a world that is a box or a sphere) holding absorbers and isotropic luminophores, spectra on even grids, no coating, no
@@ -1615,6 +1622,11 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // are not compiled, and the registers and the call frame that only `tail_run` asks for are not the kernel's.  Draws,
     // refill order and the resuming of carried photons are the other entries', operation for operation.
     static_assert(!PARK || (LEAN && !RECORD && !TAIL), "the parking form: tally launches of the lean family only");
+    // SOLO (the trace_kernel_solo entries): moreover the scene is ONE unrotated box inside a lazy root that holds nothing and
+    // that nobody listens to (pvt_scene_pack.h: prove_solo), and the launch has `lazy_root` and `fuse_exit`.  The node stage of
+    // a trip is then one of three outcomes that two comparisons on the slab test decide: see "SOLO" there.  The node loop
+    // stays in the text: a wave with a lane the closed form does not cover runs it for that trip.
+    static_assert(!SOLO || (LEAN && !RECORD), "the solo form: tally launches of the lean family only");
     extern __shared__ double smem_of_kernel[];
     // (In a called function the address of the kernel's dynamic LDS is looked up in a table in memory wherever it is used --
     // six scalar loads and waits per step of the tail function, measured in its ISA; the kernel hands it over instead.)
@@ -2622,7 +2634,82 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                     }
                 }
                 // (grid scenes have visited every node they need by now)
-                for (int k = 0; k < (GRID ? 0 : k_nodes); k++) {
+                // ---- SOLO: the two-node stage in closed form ------------------------------------------------------------
+                // The scene is one unrotated box (`child`) in a lazy root, and this launch has `lazy_root` (prove_solo, and
+                // the host's choice of the entry).  What the loop below does for such a scene, pass by pass -- it visits the
+                // child first (k = 0: the only node that is not the root), the root last:
+                //   child, nhits == 0 on entry.  The slab test gives tmin <= tmax (a miss, tmax < tmin, folds nothing: such a
+                //   lane sends its wave to the loop itself, below).  With e = tmin > kEps and x = tmax > kEps, e implies x.
+                //     e && x : fold(tmin) finds nhits == 0: t1 = tmin, n1 = child, tfirst = tmin, nl = 1.  fold(tmax):
+                //              `tmax < t1` is false (tmax >= tmin, a tie included), n2 < 0: t2 = tmax, n2 = child, nl = 2.
+                //              nl != 1: the child does not hold the ray; cnode stays -1.  nhits = 2.
+                //     !e && x: fold(tmax) alone: t1 = tmax, n1 = child, nl = 1, tfirst = tmax < cbest = inf: cnode = child,
+                //              cbest = tmax.  nhits = 1.  (tmax == inf would leave cnode at -1 -- and fails `t1 < bound`
+                //              below: undecided, the loop itself.)
+                //     neither: nothing folded: nhits = 0, cnode = -1.
+                //   root, lazy.  undecided = !(bound > 0) || (nhits > 0 && !(t1 < bound)) || (nhits >= 2 && !(t2 < bound)) ||
+                //   (cnode >= 0 && !(cbest < bound)) -- `lazy_exact` is false: this launch has its own lazy root -- which is,
+                //   in the three cases, !(bound > 0) || (e && !(tmin < bound)) || (x && !(tmax < bound)): t1 is tmin when e,
+                //   else tmax when x; t2 is tmax when e; cbest is tmax when !e && x.  Decided, the root adds one crossing
+                //   behind all the others and is intersected with nothing (nl = 0: it cannot become the container by `holds`):
+                //     e && x : nhits = 3, n1 = n2 = child, cnode = root (it was -1).
+                //     !e && x: nhits = 2, n2 = root (t2 = inf), cnode stays child.
+                //     neither: nhits = 1, t1 = bound, n1 = root, cnode = root.
+                //   the selection after the loop: hit = n1, t0 = t1; nhits == 1: container = hit, adjacent = -1; else
+                //   container = cnode (>= 0 in both cases), adjacent = (container == hit) ? n2 : hit:
+                //     e && x : hit = child, t0 = tmin, container = root,  adjacent = child
+                //     !e && x: hit = child, t0 = tmax, container = child, adjacent = root
+                //     neither: hit = root,  t0 = bound, container = root, adjacent = -1      (nhits is never 0: not terminal)
+                // Same operations on the same operands in the same order as the loop's (translation, three rcp_normal, the slab
+                // arm for rays parallel to no face, the bound): the same bits.  A wave any of whose lanes is undecided, holds a
+                // direction component below 1e-300 or misses the slab (tmax < tmin) runs the loop itself for that trip.
+                // The three outcomes are handed to the selection after the loop as the values the folds would have left in
+                // n1, t1, n2, cnode -- and nhits as 2 or 1, all that selection asks of a count that is not 0 -- and the loop
+                // runs no pass: nothing of the closed form is live across the loop or the selection.
+                // (The root's number behind an opaque copy: the two records' addresses are worked out in the trip, as the
+                // loop works out its node's -- left to the compiler they are launch invariants held in scalar registers for the
+                // whole kernel, which the parking entries do not have to spare.)
+                int loop_nodes = k_nodes;   // passes of the node loop in this trip (wave-uniform)
+                if constexpr (SOLO && (!TAIL || PVT_SOLO_TAIL)) {
+                    int kr = k_root;
+                    asm volatile("" : "+s"(kr));
+                    const int child = 1 - kr;
+                    const int hc = child * ND, hr = kr * ND;
+                    const double cx = T.du(hc + ND_T), cy = T.du(hc + ND_T + 1), cz = T.du(hc + ND_T + 2);
+                    const double cg[3] = {T.du(hc + ND_PARAMS), T.du(hc + ND_PARAMS + 1), T.du(hc + ND_PARAMS + 2)};
+                    const double oo[3] = {pos.x + cx, pos.y + cy, pos.z + cz}, dd[3] = {dir.x, dir.y, dir.z};
+                    double tmin = -INFINITY, tmax = INFINITY;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        const double ia = rcp_normal(dd[a]);   // (garbage below 1e-300: the wave takes the loop)
+                        const double sz = cg[a];
+                        const double ta = (-0.5 * sz - oo[a]) * ia, tb = (0.5 * sz - oo[a]) * ia;
+                        tmin = __builtin_fmax(tmin, __builtin_fmin(ta, tb));
+                        tmax = __builtin_fmin(tmax, __builtin_fmax(ta, tb));
+                    }
+                    V3 ro;
+                    ro.x = pos.x + T.du(hr + ND_T); ro.y = pos.y + T.du(hr + ND_T + 1); ro.z = pos.z + T.du(hr + ND_T + 2);
+                    const double rg0 = T.du(hr + ND_PARAMS), rg1 = T.du(hr + ND_PARAMS + 1), rg2 = T.du(hr + ND_PARAMS + 2);
+                    double bound;
+                    if (uf(UF_LAZY1)) {
+                        const double mx = 0.5 * rg0 - pvt_fabs(ro.x), my = 0.5 * rg1 - pvt_fabs(ro.y), mz = 0.5 * rg2 - pvt_fabs(ro.z);
+                        bound = __builtin_fmin(__builtin_fmin(mx, my), mz);
+                    } else {
+                        bound = (rg0 * rg0 - dot3(ro, ro)) * A.lazy_k;
+                    }
+                    const bool e = tmin > kEps, x = tmax > kEps;
+                    const bool undecided = !(bound > 0.0) || (e && !(tmin < bound)) || (x && !(tmax < bound));
+                    const bool parallel = pvt_fabs(dd[0]) < 1e-300 || pvt_fabs(dd[1]) < 1e-300 || pvt_fabs(dd[2]) < 1e-300;
+                    if (__ballot(undecided || parallel || tmax < tmin) == 0ull) {
+                        n1 = x ? child : kr;
+                        t1 = e ? tmin : (x ? tmax : bound);
+                        n2 = kr;                             // (read only where the child holds the ray: !e && x)
+                        cnode = (x && !e) ? child : kr;
+                        nhits = x ? 2 : 1;
+                        loop_nodes = 0;
+                    }
+                }
+                for (int k = 0; k < (GRID ? 0 : (SOLO ? loop_nodes : k_nodes)); k++) {
                     const int node = !lazy_root ? k : (k == k_nodes - 1 ? k_root : (k < k_root ? k : k + 1));
                     // An unrotated node (identity rotation, bit for bit -- the usual case) only translates:
                     // 1*x + 0*y + 0*z + t equals x + t up to the sign of a zero, which no comparison,
@@ -3905,7 +3992,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 // propagation would otherwise put back into the callee -- table lookups and all)
                 unsigned int lds_at = (unsigned int)(unsigned long long)(__attribute__((address_space(3))) double*)smem_of_kernel;
                 asm volatile("" : "+s"(lds_at));
-                tail_run<RECORD, TAB_LDS, SEENW, MESH, GRID, ROUGH, LEAN>((const KArgs*)ak, tail_n, lds_at);
+                if constexpr (SOLO) tail_run_solo<LEAN>((const KArgs*)ak, tail_n, lds_at);
+                else tail_run<RECORD, TAB_LDS, SEENW, MESH, GRID, ROUGH, LEAN>((const KArgs*)ak, tail_n, lds_at);
             }
         }
         leave_workgroup<TAB_LDS>((const KArgs*)ak);
@@ -3927,6 +4015,15 @@ __device__ __attribute__((noinline)) void tail_run(const KArgs* kernel_args, int
     const KArgsSegment ak = (KArgsSegment)(((unsigned long long)hi << 32) | lo);
     trace_body<RECORD, TAB_LDS, SEENW, false, MESH, GRID, true, ROUGH, LEAN>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
                                                                 __builtin_amdgcn_readfirstlane(lds));
+}
+
+template <int LEAN>
+__device__ __attribute__((noinline)) void tail_run_solo(const KArgs* kernel_args, int total, unsigned int lds) {
+    const unsigned long long bits = (unsigned long long)kernel_args;   // (see tail_run)
+    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)bits), hi = __builtin_amdgcn_readfirstlane((unsigned int)(bits >> 32));
+    const KArgsSegment ak = (KArgsSegment)(((unsigned long long)hi << 32) | lo);
+    trace_body<false, 1, 1, false, false, false, true, 0, LEAN, false, true>(*(const KArgs*)ak, __builtin_amdgcn_readfirstlane(total),
+                                                                         __builtin_amdgcn_readfirstlane(lds));
 }
 
 // Entry points.  Every variant runs four waves per SIMD.  Scenes of analytic shapes, tally launches and
@@ -3980,6 +4077,16 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 template <bool EMIT, bool EVEN>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PVT_PARK_WAVES, PVT_PARK_WAVES))) trace_kernel_lean_park(KArgs A) {
     trace_body<false, 1, 1, EMIT, false, false, false, false, EVEN ? kLeanEven : kLeanSearched, true>(A);
+}
+// The solo entries (trace_body's SOLO): tally launches of a lean scene that is one box in a lazy root, see prove_solo.
+// `park` as trace_kernel_lean_park (five waves, no drain, no tail), `fin` as trace_kernel_lean_w4 (the drain and the tail).
+template <bool EMIT, bool EVEN>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PVT_PARK_WAVES, PVT_PARK_WAVES))) trace_kernel_solo_park(KArgs A) {
+    trace_body<false, 1, 1, EMIT, false, false, false, false, EVEN ? kLeanEven : kLeanSearched, true, true>(A);
+}
+template <bool EMIT, bool EVEN>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) trace_kernel_solo_fin(KArgs A) {
+    trace_body<false, 1, 1, EMIT, false, false, false, false, EVEN ? kLeanEven : kLeanSearched, false, true>(A);
 }
 
 }  // namespace

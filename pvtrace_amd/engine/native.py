@@ -496,6 +496,8 @@ def declare_signatures(lib, names):
         "pvt_scene_variant": ([vp], C.c_int),
         "pvt_scene_entry": ([vp], C.c_int),
         "pvt_scene_lean_check": (scene_inputs(LEAN_CHECK_TABLES) + [C.POINTER(C.c_int32)], C.c_int),
+        "pvt_scene_solo": ([vp], C.c_int),
+        "pvt_scene_solo_check": (scene_inputs(LEAN_CHECK_TABLES) + [C.POINTER(C.c_int32)], C.c_int),
         "pvt_scene_counters": ([vp, C.POINTER(C.c_uint64), C.c_int], C.c_int),
         "pvt_scene_clock": ([vp, C.POINTER(C.c_uint64)], C.c_int),
         "pvt_scene_launch_span": ([vp, vp, C.POINTER(C.c_uint64)], C.c_int),
@@ -524,7 +526,7 @@ ABI_SYMBOLS = (
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
     "pvt_scene_create_origin", "pvt_scene_create_pattern", "pvt_scene_create_aligned", "pvt_scene_entry",
-    "pvt_scene_create_polyhedra",
+    "pvt_scene_create_polyhedra", "pvt_scene_solo", "pvt_scene_solo_check",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 # the family's entry point a launch ran (PVT_ENTRY_*): its usual kernel, or the lean family's parking one
@@ -669,6 +671,27 @@ def lean_refusal(compiled):
     return load_library().pvt_last_error().decode().removeprefix("not lean: ")
 
 
+def solo_check(compiled):
+    """True when the library proves the scene solo from its packed tables -- lean, and one unrotated box in a lazy root
+    that holds nothing and carries no recorder (host only; include/pvtrace_hip.h: pvt_scene_solo_check): its tally
+    launches may run the trace_kernel_solo entries.  False under PVT_NO_SOLO."""
+    lib = load_library()
+    st, keep = scene_tables_struct(compiled)
+    others, alive = extension_tables(compiled, LEAN_CHECK_TABLES)
+    solo = C.c_int32(0)
+    check(lib.pvt_scene_solo_check(C.byref(st), *others, C.byref(solo)), "pvt_scene_solo_check")
+    del keep, alive
+    return bool(solo.value)
+
+
+def solo_refusal(compiled):
+    """The first clause of the solo proof that the scene's packed tables fail (pvt_scene_solo_check's message), or None
+    for a solo scene.  Host only."""
+    if solo_check(compiled):
+        return None
+    return load_library().pvt_last_error().decode().removeprefix("not solo: ")
+
+
 def node_grid_plan(compiled):
     """The node grid the library files the nodes of a many-node scene under (host only, no GPU needed;
     include/pvtrace_hip.h: pvt_node_grid_plan) -> dict(dims, lo, cell, guard, odd, masks[cells, 2] uint64),
@@ -782,6 +805,14 @@ class DeviceScene:
         if VARIANT_NAMES[variant] in ENTRY_NAMES:   # (the families with more than one entry per kind of launch)
             info["entry"] = ENTRY_NAMES[VARIANT_NAMES[variant]][entry]
         return info
+
+    def solo(self):
+        """Whether the last launch on this scene ran a solo entry (pvt_scene_solo): a tally launch of a scene that is one
+        box in a lazy root; `launch_info` goes on reporting the lean family and its park / usual entry for it."""
+        solo = int(self.lib.pvt_scene_solo(self.handle))
+        if solo < 0:
+            check(solo, "pvt_scene_solo")
+        return bool(solo)
 
     # -- device buffers (torch tensors) ----------------------------------
     def new_tallies(self, sets=1, captures=True):

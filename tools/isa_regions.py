@@ -100,7 +100,8 @@ def main():
 
     # functions of the assembly: `name:  ; @name` ... `.Lfunc_end`; the kernel, and tally_flush_call where it exists
     funcs = [(m.group(1), s[m.end():s.index(".Lfunc_end", m.end())]) for m in re.finditer(r"^(\w+):\s+; @\1\s*$", s, re.M)]
-    kernels = [(n, b) for n, b in funcs if variant in n and ("trace_kernel" in n or "tail_kernel" in n)]
+    # (the tail functions too: `tail_runILb0ELi1ELi1ELb0ELb0ELi0ELi2E`, `tail_run_soloILi2E`)
+    kernels = [(n, b) for n, b in funcs if variant in n and ("trace_kernel" in n or "tail_kernel" in n or "tail_run" in n)]
     called = [b for n, b in funcs if "tally_flush_call" in n]
     for name, body in kernels:
         body = "\n".join([body] + called)
