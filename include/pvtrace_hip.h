@@ -247,8 +247,8 @@ typedef struct PvtSceneTables {
     const double* coat_lo;          /* (n_coatings,3) open local AABB, -inf/inf = unbounded */
     const double* coat_hi;
     const double* coat_reflectivity;/* <0: keep Fresnel */
-    const int32_t* coat_reflect_mode;   /* 0 specular, 1 lambertian */
-    const int32_t* coat_transmit_mode;  /* 0 Fresnel refraction, 1 index matched */
+    const int32_t* coat_reflect_mode;   /* 0 specular, 1 lambertian; >= PVT_COAT_LOBE: a lobe ("Scattering coatings" below) */
+    const int32_t* coat_transmit_mode;  /* 0 Fresnel refraction, 1 index matched; >= PVT_COAT_LOBE: a lobe */
     /* recorder source filter (extension; NULL = no filter): 0 any, 1 photons emitted by a
      * light (source id < 0), 2 by any component, 3 by component rec_source_id */
     const int32_t* rec_source_mode;
@@ -646,6 +646,36 @@ typedef struct PvtAlignTables {
     const int32_t* emit_table;          /* (n_records) the single-row phase table of f(mu; S_e), -1 = S_e is 0 */
 } PvtAlignTables;
 
+/* ---- Scattering coatings (extension within v13, taken by pvt_scene_create_polyhedra; no struct of their own) ---------
+ * A coat_reflect_mode / coat_transmit_mode word of PVT_COAT_LOBE + 4 table + axis sends the reflected / transmitted light
+ * into a tabulated lobe: `table` names a table of PvtPhaseTables, `axis` is one of PVT_LOBE_*.  A reflection takes
+ * PVT_LOBE_NORMAL or PVT_LOBE_SPECULAR, a transmission PVT_LOBE_NORMAL, PVT_LOBE_REFRACTED or PVT_LOBE_STRAIGHT.  The rule
+ * of a scattering coating (the Python ScatterLobe docstring states the same; the kernel and the host delegate both follow
+ * it):
+ *  1. Coverage, R, A and the one outcome draw u are untouched: rules 1-5 of the absorbing coating and the rules of
+ *     where a coating covers.  Beyond the critical angle a transmission lobe about "refracted" behaves as "fresnel": R
+ *     stays 1.  Beyond the critical angle a lobe about "normal" or "straight" behaves as "matched": the coating's R
+ *     applies.
+ *  2. The outgoing normal.  With N the logged geometric normal and d the incoming direction, s = +1 if N . d < 0, else
+ *     -1.  N_out = s N for a reflection and -s N for a transmission.
+ *  3. The axis a.  "normal": N_out.  "specular": d - 2 (d . N) N, as the specular body forms it.  "refracted": the
+ *     Snell direction, as the Fresnel body forms it, at the indices of the photon's wavelength.  "straight": d.
+ *  4. The draws come after u: u1 (only when the table has more than one wavelength row), u2 and u3.  Steps 2-4 of the
+ *     `PhaseFunctionTable` contract are applied about a at the photon's current wavelength, in the world frame, with
+ *     no FMA, and give d'.
+ *  5. The fold: if d' . N_out < 0, then d' <- d' - 2 (d' . N_out) N_out.  The fold takes no draw.  Exactly 0 stays.
+ *  6. Event kind, recorder selector, the logged normal, the `reflections` counter, `Event.DETECT` and the rule that
+ *     roughness applies only where no coating covers stay as for the built-in modes.
+ * (The dot product of the fold is (x x' + y y') + z z' and each component of the fold d' - (2 t) N_out, without FMA.)
+ * The packer checks, before anything is uploaded: the phase tables are there ("coating lobe without phase tables"), the
+ * table lies in them ("coating lobe names a missing phase table"), the axis is one its slot takes ("coating lobe axis not
+ * legal for a reflection" / "... for a transmission").  Every entry before pvt_scene_create_polyhedra, pvt_scene_lean_check
+ * and the host-buffer entries refuse a mode word above 1 ("coating mode out of range"); every entry refuses a negative one
+ * and one in 2 .. PVT_COAT_LOBE - 1 with the same message.  Launches of a scene with a lobe run the PVT_VARIANT_ROUGH
+ * family.  A scene whose words are all 0 or 1 packs and traces exactly as before. */
+#define PVT_COAT_LOBE 16
+enum { PVT_LOBE_NORMAL = 0, PVT_LOBE_SPECULAR = 1, PVT_LOBE_REFRACTED = 2, PVT_LOBE_STRAIGHT = 3 };
+
 /* ---- convex polyhedra (extension within v13, passed to pvt_scene_create_polyhedra) ---------------------------------
  * PVT_GEOM_POLYHEDRON: the intersection of half-spaces; geom_params = (bounding radius, 0, 0, 0), the bounding radius being
  * the largest vertex norm (finite and > 0, else PVT_ERR_INVALID).  Node n's planes are the rows
@@ -907,7 +937,8 @@ int pvt_scene_create_aligned(const PvtSceneTables* tables, const PvtIndexTables*
 /* The same with convex polyhedra (PvtPolyhedronTables), and the one entry that knows geometry type PVT_GEOM_POLYHEDRON:
  * NULL, n_nodes 0 or a scene with no such node = exactly pvt_scene_create_aligned.  Every entry before it refuses the type
  * ("unknown geometry type"), as they did before it existed.  It is also the one entry that knows PVT_GEOM_CONICOID, which
- * needs no table: the same refusals hold for that type. */
+ * needs no table: the same refusals hold for that type.  And the one entry that takes scattering coatings (a coating mode
+ * word >= PVT_COAT_LOBE): every other entry refuses them ("coating mode out of range"). */
 int pvt_scene_create_polyhedra(const PvtSceneTables* tables, const PvtIndexTables* index_tables,
                                const PvtPhaseTables* phase_tables, const PvtSurfaceTables* surface_tables,
                                const PvtFieldTables* field_tables, const PvtMapTables* map_tables,

@@ -12,7 +12,7 @@ from pvtrace_amd.light import (
 from pvtrace_amd.material import (
     Absorber, AbsorptivityTable, Alignment, CoatedSurfaceDelegate, Coating, CoatingPattern, ConcentrationGrid, Distribution, FresnelSurfaceDelegate,
     Luminophore, Material, NullSurfaceDelegate, PhaseFunctionTable, Reactor, ReflectivityTable,
-    RefractiveIndexTable, Scatterer, Surface,
+    RefractiveIndexTable, ScatterLobe, Scatterer, Surface,
     SurfaceDelegate, cone, henyey_greenstein, isotropic, lambertian, pattern_cell,
 )
 from pvtrace_amd.scene import Node, Scene

@@ -360,6 +360,10 @@ struct PackedScene {
     // recorder selector, PVT_RECX_DETECTED -- one block {start, count, bin[6]} per candidate node (NI_CAND; the blocks of
     // Lay::cand_i keep their seven selectors), then the walked lists; `start` is absolute in the int blob
     int cabs_d = -1, dcand_i = -1;
+    // scattering coatings (a coating mode word >= PVT_COAT_LOBE; -1: no coating has a lobe): in the int blob, BEHIND everything
+    // else it holds -- the `detected` candidate tables included -- one record of kCl ints (kCl*) per coating row: where the
+    // reflection lobe's phase table starts in the double blob (-1: a built-in mode) and its axis, the same of the transmission
+    int clobe_i = -1;
     // concentration fields (PvtFieldTables): their own buffer of doubles, read from global memory alone (empty: none).
     // fd[n] = where node n's lattice record starts (-1: none), then the records (kFr* words and one value-table offset
     // per component), then the pooled value tables
@@ -408,9 +412,12 @@ struct PackedScene {
 // what the calling entry KNOWS.  An entry from before an extension keeps refusing what that extension added, with the
 // message it always had: a recorder selector beyond Knows::max_selector ("recorder selector out of range"), a histogram
 // property beyond max_prop ("histogram property out of range": the kernel reads column `prop` of its tally queue, so an id
-// beyond the ones it parks would read past the queue), a geometry type beyond max_geom ("unknown geometry type").
+// beyond the ones it parks would read past the queue), a geometry type beyond max_geom ("unknown geometry type"), a coating
+// mode word beyond max_coat_mode ("coating mode out of range": 1 = the built-in modes alone, the entries from before the
+// scattering coatings).
 struct Knows {
     int max_selector, max_prop, max_geom;   // the last recorder selector, histogram property and geometry type known
+    int max_coat_mode = 1;                  // the largest coat_reflect_mode / coat_transmit_mode word taken
 };
 
 struct SceneInputs {
@@ -433,7 +440,7 @@ struct SceneInputs {
 constexpr Knows kKnowsBeforeAbsorb{PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_MESH};     // pvt_scene_create .. pvt_scene_create_capture
 constexpr Knows kKnowsAbsorb      {PVT_RECX_DETECTED, PVT_PROPX_REFLECTIONS, PVT_GEOM_MESH};     // pvt_scene_create_absorb
 constexpr Knows kKnowsOrigin      {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_FRUSTUM};  // pvt_scene_create_origin, _pattern, _aligned, pvt_scene_lean_check
-constexpr Knows kKnowsPolyhedra   {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_CONICOID};  // pvt_scene_create_polyhedra (the polyhedron, and the conicoid after it)
+constexpr Knows kKnowsPolyhedra   {PVT_RECX_DETECTED, PVT_PROPX_ORIGIN_Z,    PVT_GEOM_CONICOID, 0x7fffffff};  // pvt_scene_create_polyhedra (the polyhedron, the conicoid after it, then the scattering coatings)
 constexpr Knows kKnowsHostBuffer  {PVT_REC_EXIT,      PVT_PROP_Z,            PVT_GEOM_FRUSTUM};  // pvt_trace_bundle*: pvt_scene_create, but a truncated cone is taken
 
 // ---- validation: every index into a table that the packer follows on the host or the kernel on the device, checked
@@ -848,6 +855,27 @@ int validate_ranges(const PvtSceneTables* t, const Knows& knows) {
 
 // The order is behaviour: the first check that fails names the refusal.  The core tables are checked in two parts, around
 // the extension structs.  (Pattern tables are checked by pack_patterns, on a scene pack_scene has accepted.)
+// the coatings' mode words: a built-in mode, or -- for an entry that takes them -- a lobe (PVT_COAT_LOBE + 4 table + axis)
+// whose table lies in the phase tables (validated before this) and whose axis is one its slot takes
+int validate_coating_modes(const SceneInputs& in) {
+    const PvtSceneTables* t = in.t;
+    const int NP = in.ph ? in.ph->n_tables : 0;
+    for (int k = 0; k < t->n_coatings; k++)
+        for (int slot = 0; slot < 2; slot++) {
+            const int m = slot == 0 ? t->coat_reflect_mode[k] : t->coat_transmit_mode[k];
+            if (m == 0 || m == 1) continue;
+            if (m < PVT_COAT_LOBE || m > in.knows.max_coat_mode) return fail(PVT_ERR_INVALID, "coating mode out of range");
+            const int table = (m - PVT_COAT_LOBE) >> 2, axis = (m - PVT_COAT_LOBE) & 3;
+            if (NP <= 0) return fail(PVT_ERR_INVALID, "coating lobe without phase tables");
+            if (table >= NP) return fail(PVT_ERR_INVALID, "coating lobe names a missing phase table");
+            if (slot == 0 && axis != PVT_LOBE_NORMAL && axis != PVT_LOBE_SPECULAR)
+                return fail(PVT_ERR_INVALID, "coating lobe axis not legal for a reflection");
+            if (slot == 1 && axis != PVT_LOBE_NORMAL && axis != PVT_LOBE_REFRACTED && axis != PVT_LOBE_STRAIGHT)
+                return fail(PVT_ERR_INVALID, "coating lobe axis not legal for a transmission");
+        }
+    return PVT_OK;
+}
+
 int validate_tables(const SceneInputs& in) {
     const PvtSceneTables* t = in.t;
     int rc = validate_nodes(t, in.knows);
@@ -861,6 +889,7 @@ int validate_tables(const SceneInputs& in) {
     if (rc == PVT_OK) rc = validate_capture_tables(t, in.cp);
     if (rc == PVT_OK) rc = validate_absorb_tables(t, in.ab);
     if (rc == PVT_OK) rc = validate_ranges(t, in.knows);
+    if (rc == PVT_OK) rc = validate_coating_modes(in);
     return rc;
 }
 
@@ -1338,8 +1367,12 @@ int fill(const SceneInputs& in, const Classes& k, const Spectra& sp, const Recor
         }
         d[KD_REFL] = t->coat_reflectivity[c];
         int* q = gi.data() + lay.coat_i + c * KI;
-        q[KI_RMODE] = t->coat_reflect_mode[c];
-        q[KI_TMODE] = t->coat_transmit_mode[c];
+        // (a lobe's word is replaced by its stand-in among the built-in modes, whose body leaves the lobe's axis in the
+        // photon's direction and decides what holds beyond the critical angle: specular for a reflection; Fresnel for a
+        // transmission about "refracted", matched for one about "normal" or "straight" -- pack_lobes keeps table and axis)
+        const int rm = t->coat_reflect_mode[c], tm = t->coat_transmit_mode[c];
+        q[KI_RMODE] = rm >= PVT_COAT_LOBE ? 0 : rm;
+        q[KI_TMODE] = tm >= PVT_COAT_LOBE ? (((tm - PVT_COAT_LOBE) & 3) == PVT_LOBE_REFRACTED ? 0 : 1) : tm;
         const int j = p->n_ctab > 0 ? t->coat_table[c] : -1;
         q[KI_TNW] = j >= 0 ? t->ctab_nw[j] : 0;   // 0: no table
         q[KI_TNA] = j >= 0 ? t->ctab_na[j] : 0;
@@ -1885,10 +1918,14 @@ int pack_scene(const SceneInputs& in, PackedScene* p) {
     if (x)
         for (int n = 0; n < t->n_nodes; n++)
             if (x->n_tables > 0 && x->node_table[n] >= 0) p->n_rtab = x->n_tables;
-    p->n_ptab = 0;   // (likewise: a table no component uses is validated, never placed)
+    p->n_ptab = 0;   // (likewise: a table no component and no coating lobe uses is validated, never placed)
     if (ph)
         for (int c = 0; c < t->n_components; c++)
             if (ph->n_tables > 0 && ph->comp_table[c] >= 0) p->n_ptab = ph->n_tables;
+    bool lobes = false;
+    for (int k = 0; k < t->n_coatings; k++)
+        lobes = lobes || t->coat_reflect_mode[k] >= PVT_COAT_LOBE || t->coat_transmit_mode[k] >= PVT_COAT_LOBE;
+    if (lobes) p->n_ptab = ph->n_tables;   // (validated: the phase tables are there)
     p->rough_d = -1;   // (a struct of zeros places nothing: the scene lays out as a smooth one)
     if (rs && rs->n_nodes > 0)
         for (int n = 0; n < t->n_nodes; n++)
@@ -1904,6 +1941,20 @@ int pack_scene(const SceneInputs& in, PackedScene* p) {
     pack_maps(in, p);
     pack_captures(in, p);
     pack_absorb(in, records, p);
+    p->clobe_i = -1;
+    if (lobes) {   // (validated words) the rows' lobe records, behind everything else in the int blob
+        std::vector<int>& gi = p->gi;
+        p->clobe_i = (int)gi.size();
+        gi.resize(gi.size() + (size_t)t->n_coatings * kCl + 1, 0);   // (and the blob's spare last element, as before)
+        for (int k = 0; k < t->n_coatings; k++) {
+            int* q = gi.data() + p->clobe_i + (size_t)k * kCl;
+            const int rm = t->coat_reflect_mode[k] - PVT_COAT_LOBE, tm = t->coat_transmit_mode[k] - PVT_COAT_LOBE;
+            q[kClRTab] = rm >= 0 ? ptab_at[(size_t)(rm >> 2)] : -1;
+            q[kClRAxis] = rm >= 0 ? (rm & 3) : 0;
+            q[kClTTab] = tm >= 0 ? ptab_at[(size_t)(tm >> 2)] : -1;
+            q[kClTAxis] = tm >= 0 ? (tm & 3) : 0;
+        }
+    }
     pack_polyhedra(in, p);
     pack_conicoids(in, p);
     prove_shortcuts(t, p);

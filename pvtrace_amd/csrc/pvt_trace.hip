@@ -102,6 +102,7 @@ struct PvtScene {
     bool has_frustum = false;           // a node is a truncated cone (PVT_GEOM_FRUSTUM): only the extension family traces one
     bool has_polyhedron = false;        // a node is a convex polyhedron (PVT_GEOM_POLYHEDRON): likewise
     bool has_conicoid = false;          // a node is a solid of revolution of a conic (PVT_GEOM_CONICOID): likewise
+    int clobe_i = -1;                   // scattering coatings: the coating rows' lobe records in the int blob (KArgs::clobe_i; -1 = no coating has a lobe)
     int cabs_d = -1, dcand_i = -1;      // absorbing coatings: their records in the double blob, the `detected` candidate tables in the int blob (-1: none)
     double* d_fd = nullptr;             // the concentration fields (KArgs::fd), null = no node carries a lattice
     double* d_md = nullptr;             // the volume maps' records (KArgs::md), null = the scene has no map
@@ -257,6 +258,7 @@ KArgs base_args(const PvtScene* s, const PvtTraceParams* p) {
     a.n_coat = s->n_coat; a.n_ctab = s->n_ctab; a.n_rtab = s->n_rtab; a.n_lights = s->n_lights;
     a.rough_d = s->rough_d;
     a.cabs_d = s->cabs_d; a.dcand_i = s->dcand_i;
+    a.clobe_i = s->clobe_i;
     a.fd = s->d_fd;
     a.md = s->d_md;
     a.pd_d = s->pd_d;
@@ -378,9 +380,9 @@ Variant choose_variant(const PvtScene* s, const LdsPlan& lp, bool record, bool e
     v.mesh = s->d_bvh != nullptr;
     v.grid = lp.tab == Tab::Lds && s->lay.grid_d >= 0 && !v.mesh;   // many nodes: per-lane walk of the node grid
     // a rough node, a concentration field, a volume map, a captured recorder, an absorbing coating or a histogram of a
-    // photon event counter or of the launch origin, a truncated cone, a polyhedron, a conicoid or an aligned component: the extension family, split as
+    // photon event counter or of the launch origin, a truncated cone, a polyhedron, a conicoid, an aligned component or a scattering coating: the extension family, split as
     // the plain ones
-    const bool extension = s->has_frustum || s->has_polyhedron || s->has_conicoid || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0 || s->al_d >= 0;
+    const bool extension = s->has_frustum || s->has_polyhedron || s->has_conicoid || s->rough_d >= 0 || s->d_fd || s->d_md || s->d_cd || s->cabs_d >= 0 || s->counting() || s->origin_mask || s->pd_d >= 0 || s->al_d >= 0 || s->clobe_i >= 0;
     const bool lean = lp.tab == Tab::Lds && s->lean_ok && v.seenw == 1;   // plain scenes (prove_lean)
     v.align = s->al_d >= 0;   // (the extension family's kernels that hold the aligned components' code)
     v.path = s->path_maps;    // (... and those that hold the path-length maps' walk on top of it)
@@ -848,6 +850,7 @@ int create_scene(const SceneInputs& in, int device, PvtScene** out) {
     s->has_polyhedron = packed.has_polyhedron;
     s->has_conicoid = packed.has_conicoid;
     s->cabs_d = packed.cabs_d; s->dcand_i = packed.dcand_i;
+    s->clobe_i = packed.clobe_i;
     s->lazy_root = packed.lazy_root; s->lazy_k = packed.lazy_k;
     s->exit_observed = packed.exit_observed; s->fuse_exit = packed.fuse_exit; s->hist_reads_position = packed.hist_reads_position;
     s->hist_reads_counter = packed.hist_reads_counter;

@@ -92,6 +92,10 @@ enum { kCaA = 0, kCaNw, kCaNa, kCaTab, kCa };   // an absorbing scene's record p
                                                                  // absorptivity, its table's axis lengths (kCaNw = 0: none) and
                                                                  // where the table starts in the double blob (wavelengths, angles
                                                                  // in radians, values row-major by angle)
+enum { kClRTab = 0, kClRAxis, kClTTab, kClTAxis, kCl };   // a scattering coating's record per coating row at KArgs::clobe_i:
+                                                                 // where the reflection lobe's table starts in the double blob
+                                                                 // (-1: the row reflects by a built-in mode) and its axis
+                                                                 // (PVT_LOBE_*), the same of the transmission lobe
 enum { kPrShape = 0, kPrBounded = 3, kPrLower = 6, kPrH = 9, kPrMask = 12, kPr = 13 };   // a coating pattern's record at KArgs::pd_d:
                                                                  // shape, per axis 1 = bounded (else index 0), lower, cell
                                                                  // widths, and where its mask starts, in BYTES from pd
@@ -143,6 +147,11 @@ struct KArgs {
     const double* dir;
     const double* wl;
     unsigned int n_rays;
+    // Scattering coatings (include/pvtrace_hip.h, "Scattering coatings"): where the coating rows' lobe records start in the
+    // int blob -- kCl words per row, behind everything else the blob holds and read from where the guide tables are read;
+    // -1 = no coating has a lobe (UF_CLOBE off).  (It stands where the struct had four bytes of padding: no other member
+    // moves and the argument block keeps its size.)
+    int clobe_i;
     unsigned int* cursor;   // [0] ray cursor, [1] claim cursor of resumed photons, [2] photons parked; (PVT_STATS builds) [2..] u64 counters
     unsigned int* cursor_next;   // the block the NEXT launch on this stream will use: cleared by this launch (no memset
                                  // kernel between launches: a one-workgroup fill cannot start while persistent workgroups
@@ -265,6 +274,7 @@ struct KArgs {
     int pd_d;
     double* origin_store;
 };
+static_assert(offsetof(KArgs, clobe_i) % 8 == 4 && offsetof(KArgs, cursor) == offsetof(KArgs, clobe_i) + 4, "KArgs::clobe_i fills padding");
 // Aligned components (PvtAlignTables) live in KArgs::fd: fd[n] of a node that holds one names a record like a lattice's whose
 // kFrShape words are 0 (a lattice has >= 1 cell per axis) and whose kFrComp + k word names, for the node's k-th component,
 // where in fd its record of kAl doubles starts (-1: the component is not aligned): kAlOn != 0, the director in the root's
@@ -626,6 +636,25 @@ __device__ __forceinline__ V3 phase_table_turn(const double* tab, double wl, dou
 __device__ __attribute__((noinline)) V3 phase_table_turn_call(const double* tab, double wl, double u1, double u2, double u3,
                                                               double dx, double dy, double dz) {
     return phase_table_turn(tab, wl, u1, u2, u3, dx, dy, dz);
+}
+
+// Scattering coatings (include/pvtrace_hip.h, "Scattering coatings"; the Python ScatterLobe states the same rule): the
+// direction of a photon that a lobe coating has just reflected or transmitted.  `tab` is the lobe's phase table in the
+// blob the spectra are read from; (ax, ay, az) is what the built-in body of the row's stand-in mode has left in `dir` --
+// the specular direction, the Snell direction, or d itself -- and the axis unless `normal_axis`, when N_out = (nx, ny, nz)
+// is (rule 3); u1 (drawn by the caller only when the table has several rows), u2, u3 are rule 4's draws; the fold of
+// rule 5 is applied here.  A FUNCTION, called only from the trace_kernel_rough* variants, and there only by the lanes of
+// a scene with a lobe (UF_CLOBE) that stand on a lobe row.
+__device__ __attribute__((noinline)) V3 coat_lobe_call(const double* tab, int normal_axis, double wl, double u1, double u2, double u3,
+                                                        double ax, double ay, double az, double nx, double ny, double nz) {
+    if (normal_axis) { ax = nx; ay = ny; az = nz; }
+    V3 o = phase_table_turn(tab, wl, u1, u2, u3, ax, ay, az);
+    const double t = (o.x * nx + o.y * ny) + o.z * nz;
+    if (t < 0.0) {
+        const double t2 = 2.0 * t;
+        o = V3{o.x - t2 * nx, o.y - t2 * ny, o.z - t2 * nz};
+    }
+    return o;
 }
 
 // Truncated cones (PVT_GEOM_FRUSTUM; include/pvtrace_hip.h states the arithmetic, geometry.Frustum performs the same
@@ -1659,7 +1688,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
     // conditions each becomes a 64-bit lane mask that the allocator holds (spills) for the whole loop; `uf(bit)`
     // re-derives the answer from the word where it is asked (the empty asm keeps the compiler from hoisting it).
     enum { UF_COATED = 0, UF_FUSE_EXIT, UF_CRIT, UF_HAS_REC, UF_TQ_POS, UF_BINS_LDS, UF_EMIT_FULL, UF_EMIT_KT, UF_LAZY1, UF_LAZY2, UF_BY_NODE,
-           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT, UF_ALIGN, UF_PMAP };
+           UF_TAIL_LAZY1, UF_TAIL_LAZY2, UF_CTAB, UF_DISP, UF_ROUGH, UF_FIELD, UF_VMAP, UF_CAPTURE, UF_CABS, UF_COUNT, UF_TQ_COUNT, UF_ORIGIN, UF_CPAT, UF_ALIGN, UF_PMAP, UF_CLOBE };
     unsigned int uflags_ =
         (A.n_coat > 0 ? 1u << UF_COATED : 0u) | (A.fuse_exit != 0 ? 1u << UF_FUSE_EXIT : 0u) | (L.crit_d >= 0 ? 1u << UF_CRIT : 0u) |
         (A.n_rec > 0 ? 1u << UF_HAS_REC : 0u) | (A.tq_pos ? 1u << UF_TQ_POS : 0u) | (A.bins_in_lds ? 1u << UF_BINS_LDS : 0u) |
@@ -1675,14 +1704,15 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
         (ROUGH && A.origin != 0 ? 1u << UF_ORIGIN : 0u) |   // ... and origin ...
         (ROUGH && A.pd_d >= 0 ? 1u << UF_CPAT : 0u) |   // ... and pd_d ...
         (ROUGH >= kExtAligned ? 1u << UF_ALIGN : 0u) |   // ... UF_ALIGN is the kernel's own: compiled in, not read ...
-        (ROUGH == kExtPath && A.md != nullptr ? 1u << UF_PMAP : 0u);   // ... UF_PMAP too: the kExtPath kernels of a scene with maps)
+        (ROUGH == kExtPath && A.md != nullptr ? 1u << UF_PMAP : 0u) |   // ... UF_PMAP too: the kExtPath kernels of a scene with maps ...
+        (ROUGH && A.clobe_i >= 0 ? 1u << UF_CLOBE : 0u);   // ... and clobe_i)
     if constexpr (TAIL) {   // (only where the launch itself has no lazy root: see KArgs::lazy_tail)
         if (A.lazy_root == 0) uflags_ |= (A.lazy_tail == 1 ? 1u << UF_TAIL_LAZY1 : 0u) | (A.lazy_tail == 2 ? 1u << UF_TAIL_LAZY2 : 0u);
     }
     const unsigned int uflags = uflags_;
     auto uf = [&](int bit) -> bool {
         if constexpr (LEAN != kLeanOff) {   // (proven: no coating, no table of an extension; few nodes, numbered as they are)
-            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT || bit == UF_ALIGN || bit == UF_PMAP) return false;
+            if (bit == UF_COATED || bit == UF_CTAB || bit == UF_DISP || bit == UF_ROUGH || bit == UF_FIELD || bit == UF_VMAP || bit == UF_CAPTURE || bit == UF_CABS || bit == UF_COUNT || bit == UF_TQ_COUNT || bit == UF_ORIGIN || bit == UF_CPAT || bit == UF_ALIGN || bit == UF_PMAP || bit == UF_CLOBE) return false;
             if (bit == UF_BY_NODE || bit == UF_CRIT) return true;   // (UF_CRIT: the threshold table is there and holds no NaN)
         }
         unsigned int f = uflags;
@@ -3762,6 +3792,26 @@ __device__ __forceinline__ void trace_body(const KArgs& A, int tail_total = 0, u
                 }
                 ev_kind = PVT_EV_TRANSMIT;
                 t_sel = (container == hit) ? PVT_REC_ESCAPING : PVT_REC_ENTERING;
+            }
+            // (scenes with a scattering coating) a row whose mode is a lobe: the body above has run the row's stand-in
+            // mode -- specular; Fresnel for a lobe about "refracted", matched for one about "normal" or "straight" -- and
+            // left the axis in `dir`; the lobe's draws follow u (include/pvtrace_hip.h, "Scattering coatings")
+            if constexpr (ROUGH) {
+                if (uf(UF_CLOBE) && coat >= 0 && ev_kind != PVT_EV_DETECT) {
+                    const bool tr = ev_kind == PVT_EV_TRANSMIT;
+                    const int q = A.clobe_i + coat * kCl + (tr ? kClTTab : kClRTab);
+                    const int at = T.si(q);
+                    if (at >= 0) {
+                        const double* tab = (TAB_LDS == 1 ? T.ld : T.hd) + at;
+                        const bool out = flip != tr;   // N_out = s N for a reflection, -s N for a transmission; s = +1 where N . d < 0 (`flip`)
+                        const double so = out ? 1.0 : -1.0;
+                        double u1 = 0.0;
+                        if (tab[0] > 1.0) u1 = rng_uniform(rng);
+                        const double u2 = rng_uniform(rng), u3 = rng_uniform(rng);
+                        dir = coat_lobe_call(tab, T.si(q + 1) == PVT_LOBE_NORMAL ? 1 : 0, wl, u1, u2, u3, dir.x, dir.y, dir.z,
+                                             so * nrm.x, so * nrm.y, so * nrm.z);
+                    }
+                }
             }
             // Fused exit (tally launches of a scene that is ONE unrotated box in an empty, unobserved world; the
             // host sets the flag).  A photon that has just been sent away from the box's surface on the OUTSIDE

@@ -57,6 +57,13 @@ def _host_buffer_scene(compiled):
             "The scene has aligned components (Alignment), which the host-buffer trace_bundle entry (the reference's "
             "interface) cannot take; trace it with engine.simulate."
         )
+    if getattr(compiled, "has_coating_lobes", False):
+        from pvtrace_amd.engine.compiler import UnsupportedSceneError
+
+        raise UnsupportedSceneError(
+            "The scene has scattering coatings (Coating(reflection=ScatterLobe(...)) or transmission=), which the "
+            "host-buffer trace_bundle entry (the reference's interface) cannot take; trace it with engine.simulate."
+        )
     if int(getattr(compiled, "n_phase_tables", 0)) > 0:
         from pvtrace_amd.engine.compiler import UnsupportedSceneError
 

@@ -52,6 +52,7 @@ from pvtrace_amd.material import (
     Reactor,
     ReflectivityTable,
     RefractiveIndexTable,
+    ScatterLobe,
     Scatterer,
     isotropic,
 )
@@ -69,6 +70,8 @@ COMP_ABSORBER, COMP_SCATTERER, COMP_LUMINOPHORE, COMP_REACTOR = 0, 1, 2, 3
 PHASE_ISOTROPIC, PHASE_HENYEY_GREENSTEIN, PHASE_CONE = 0, 1, 2
 PHASE_LAMBERTIAN = 3   # extension: the reference compiler rejects it (compiler.py:300-310); cli/parse.py:166-167 builds it
 PHASE_TABLE = 4        # extension: a PhaseFunctionTable, sampled about the incoming direction (comp_phase_table)
+COAT_LOBE = 16         # extension: a coat_reflect_mode / coat_transmit_mode word >= 16 is a ScatterLobe, COAT_LOBE + 4 table + axis
+                       # (include/pvtrace_hip.h: PVT_COAT_LOBE); axis 0 normal, 1 specular, 2 refracted, 3 straight
 EMIT_KT, EMIT_REDSHIFT, EMIT_FULL = 0, 1, 2
 EMIT_METHODS = {"kT": EMIT_KT, "redshift": EMIT_REDSHIFT, "full": EMIT_FULL}
 
@@ -236,6 +239,12 @@ class CompiledScene:
         self.comp_phase_type = np.array(comp_cols["phase_type"], dtype=_I32)
         self.comp_phase_param = np.array(comp_cols["phase_param"], dtype=_F64)
         self.comp_phase_table = np.array(comp_cols["phase_table"], dtype=_I32)
+        # Scattering coatings (Coating(reflection=ScatterLobe(...)) / transmission=): their tables join the phase pool
+        # behind the components', one entry per table object however many lobes or coatings share it, and the row's mode
+        # word names table and axis (COAT_LOBE).  A scene without a lobe pools nothing and keeps the words 0 / 1.
+        coat_modes = [(self._lower_coat_mode(r, coating.reflection, Coating.REFLECTION_MODES, ScatterLobe.REFLECTION_ABOUT, "reflection"),
+                       self._lower_coat_mode(r, coating.transmission, Coating.TRANSMISSION_MODES, ScatterLobe.TRANSMISSION_ABOUT, "transmission"))
+                      for r, coating in enumerate(coat_rows)]
         ptab = self._ptab
         self.n_phase_tables = len(ptab["nw"])
         self.ptab_nw = np.array(ptab["nw"], dtype=_I32)
@@ -312,8 +321,7 @@ class CompiledScene:
                 self.coat_table[r] = self._pool_coating_table(coating.reflectivity, ctab)
             elif coating.reflectivity is not None:
                 self.coat_reflectivity[r] = coating.reflectivity
-            self.coat_reflect_mode[r] = Coating.REFLECTION_MODES[coating.reflection]
-            self.coat_transmit_mode[r] = Coating.TRANSMISSION_MODES[coating.transmission]
+            self.coat_reflect_mode[r], self.coat_transmit_mode[r] = coat_modes[r]
         self.n_coatings = ncoat
         self.n_coat_tables = len(ctab["nw"])
         for key in ("nw", "na", "wl_start", "angle_start", "value_start"):
@@ -646,6 +654,24 @@ class CompiledScene:
     def has_alignment(self):
         """A component carries an `Alignment`: the scene needs pvt_scene_create_aligned's tables."""
         return bool(np.any(self.comp_align >= 0))
+
+    def _lower_coat_mode(self, r, mode, names, about, slot):
+        """The mode word of coating row `r`: a built-in's number, or COAT_LOBE + 4 table + axis of a ScatterLobe."""
+        if isinstance(mode, ScatterLobe):
+            if mode.about not in about or not isinstance(mode.table, PhaseFunctionTable):   # (assigned after construction, perhaps)
+                raise UnsupportedSceneError(f"Coating {r}: a {slot} lobe must be a PhaseFunctionTable about one of {sorted(about)}.")
+            word = COAT_LOBE + 4 * self._pool_phase_table(mode.table) + about[mode.about]
+            if word > np.iinfo(_I32).max:
+                raise UnsupportedSceneError(f"Coating {r}: too many phase tables for a {slot} lobe.")
+            return word
+        if mode not in names:
+            raise UnsupportedSceneError(f"Coating {r}: {slot} must be one of {sorted(names)} or a ScatterLobe.")
+        return names[mode]
+
+    @property
+    def has_coating_lobes(self):
+        """A coating reflects or transmits into a `ScatterLobe`: the scene needs pvt_scene_create_polyhedra."""
+        return bool(np.any(self.coat_reflect_mode >= COAT_LOBE) or np.any(self.coat_transmit_mode >= COAT_LOBE))
 
     def _pool_phase_table(self, table, key=None):
         ptab = self._ptab

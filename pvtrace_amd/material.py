@@ -754,6 +754,99 @@ class PhaseFunctionTable(object):
         return self.turn(np.array([0.0, 0.0, 1.0]), mu, u[:, k - 1])
 
 
+class ScatterLobe(object):
+    """Where a coating sends the light it reflects or transmits: a `PhaseFunctionTable` whose angle is measured from an
+    axis of the surface event (extension; the reference writes such surfaces as Python delegates).
+
+    table : a `PhaseFunctionTable` p(theta); theta is the angle between the outgoing direction and the axis.
+    about : the axis.  As `Coating(reflection=...)`: "normal" or "specular".  As `Coating(transmission=...)`: "normal",
+        "refracted" or "straight".
+
+    The rule of a scattering coating, the same on the host and on the device (include/pvtrace_hip.h, "Scattering
+    coatings", states the same):
+
+    1. Coverage, R, A and the one outcome draw u are untouched: rules 1-5 of the absorbing coating and the rules of
+       where a coating covers.  Beyond the critical angle a transmission lobe about "refracted" behaves as "fresnel": R
+       stays 1.  Beyond the critical angle a lobe about "normal" or "straight" behaves as "matched": the coating's R
+       applies.
+    2. The outgoing normal.  With N the logged geometric normal and d the incoming direction, s = +1 if N . d < 0, else
+       -1.  N_out = s N for a reflection and -s N for a transmission.
+    3. The axis a.  "normal": N_out.  "specular": d - 2 (d . N) N, as the specular body forms it.  "refracted": the
+       Snell direction, as the Fresnel body forms it, at the indices of the photon's wavelength.  "straight": d.
+    4. The draws come after u: u1 (only when the table has more than one wavelength row), u2 and u3.  Steps 2-4 of the
+       `PhaseFunctionTable` contract are applied about a at the photon's current wavelength, in the world frame, with
+       no FMA, and give d'.
+    5. The fold: if d' . N_out < 0, then d' <- d' - 2 (d' . N_out) N_out.  The fold takes no draw.  Exactly 0 stays.
+    6. Event kind, recorder selector, the logged normal, the `reflections` counter, `Event.DETECT` and the rule that
+       roughness applies only where no coating covers stay as for the built-in modes.
+    """
+
+    ABOUT = ("normal", "specular", "refracted", "straight")
+    REFLECTION_ABOUT = {"normal": 0, "specular": 1}
+    TRANSMISSION_ABOUT = {"normal": 0, "refracted": 2, "straight": 3}
+
+    def __init__(self, table, about="normal"):
+        if not isinstance(table, PhaseFunctionTable):
+            raise ValueError("table must be a PhaseFunctionTable")
+        if about not in self.ABOUT:
+            raise ValueError(f"about must be one of {list(self.ABOUT)}")
+        self.table = table
+        self.about = about
+
+    @classmethod
+    def lambertian(cls, nodes=257, about="normal"):
+        """The cosine lobe: p = cos(theta) up to 90 degrees and 0 beyond, a knot exactly at 90 degrees (`nodes` odd)."""
+        nodes = int(nodes)
+        if nodes < 3 or nodes % 2 == 0:
+            raise ValueError("nodes must be odd and at least 3: 90 degrees is a knot")
+        half = nodes // 2
+        angle = np.concatenate([np.linspace(0.0, 90.0, half + 1), np.linspace(90.0, 180.0, half + 1)[1:]])
+        values = np.where(angle < 90.0, np.cos(np.radians(angle)), 0.0)
+        return cls(PhaseFunctionTable(angle, values), about=about)
+
+    @classmethod
+    def gaussian(cls, sigma_degrees, about, nodes=1025):
+        """A Gaussian gloss lobe p = exp(-theta^2 / (2 sigma^2)) on `nodes` evenly spaced angles."""
+        sigma = float(sigma_degrees)
+        if not (math.isfinite(sigma) and sigma > 0.0):
+            raise ValueError("sigma_degrees must be finite and > 0")
+        nodes = int(nodes)
+        if nodes < 3:
+            raise ValueError("nodes must be at least 3")
+        angle = np.linspace(0.0, 180.0, nodes)
+        angle[-1] = 180.0
+        if not sigma > angle[1] / 8.0:
+            raise ValueError("sigma_degrees is too small for the angle grid: raise nodes")
+        values = np.exp(-0.5 * (angle / sigma) ** 2)
+        return cls(PhaseFunctionTable(angle, values), about=about)
+
+    def turn(self, direction, normal, transmit, wavelength=None, n1=None, n2=None):
+        """Rules 2-5 for one photon travelling along `direction` at a point of geometric `normal`: the new direction,
+        its draws u1 (if the table has several rows), u2, u3 taken from numpy's global generator in that order."""
+        d = np.asarray(direction, dtype=np.float64)
+        nrm = np.asarray(normal, dtype=np.float64)
+        s = 1.0 if float(np.dot(nrm, d)) < 0.0 else -1.0
+        n_out = (-s if transmit else s) * nrm
+        if self.about == "normal":
+            axis = n_out
+        elif self.about == "specular":
+            axis = np.asarray(specular_reflection(d, nrm), dtype=np.float64)
+        elif self.about == "refracted":
+            axis = np.asarray(fresnel_refraction(d, -s * nrm, n1, n2), dtype=np.float64)
+        else:
+            axis = d
+        table = self.table
+        u1 = np.random.uniform() if table.n_wavelength > 1 else 0.0
+        u2 = np.random.uniform()
+        u3 = np.random.uniform()
+        mu = table.sample_mu(u2, table.rows(wavelength, u1))
+        out = np.asarray(table.turn(axis, mu, u3), dtype=np.float64)
+        across = float(np.dot(out, n_out))
+        if across < 0.0:
+            out = out - 2.0 * across * n_out
+        return out
+
+
 ALIGN_TABLE_NODES = 513   # mu nodes of an aligned luminophore's emission table, uniformly spaced from exactly -1 to exactly 1
 
 
@@ -1001,9 +1094,13 @@ class Coating(object):
         ARRIVING at a covered point is absorbed there (extension; the reference has no such coating).  It is per
         incident photon, like the EQE of a solar cell, not a share of the light that was not reflected.
     reflection : "specular" or "lambertian" (cosine-weighted about the outward
-        facet normal, in the local frame).
+        facet normal, in the local frame), or a `ScatterLobe` about "normal" or "specular" (extension): a tabulated
+        reflection lobe, under the rule of a scattering coating in the `ScatterLobe` docstring.
     transmission : "fresnel" (Snell refraction) or "matched" (index-matched:
-        direction unchanged, e.g. a perfectly coupled solar cell).
+        direction unchanged, e.g. a perfectly coupled solar cell), or a `ScatterLobe` about "normal", "refracted" or
+        "straight" (extension): a tabulated transmission lobe, under the same rule.  Beyond the critical angle a lobe
+        about "refracted" behaves as "fresnel" (R stays 1), one about "normal" or "straight" as "matched" (the
+        coating's R applies): that is what lets a diffusing dot extract guided light.
 
     The rule of an absorbing coating, the same on the host and on the device (include/pvtrace_hip.h,
     PvtCoatingAbsorbTables, states the same):
@@ -1078,9 +1175,17 @@ class Coating(object):
                 wl, angle, r, a = over
                 where = "" if wl is None else f" at {wl:g} nm, {angle:g} degrees"
                 raise ValueError(f"reflectivity + absorptivity must not exceed 1: R = {r:g}, A = {a:g}{where}")
-        if reflection not in self.REFLECTION_MODES:
+        if isinstance(reflection, ScatterLobe):
+            if reflection.about not in ScatterLobe.REFLECTION_ABOUT:
+                raise ValueError(
+                    f"a reflection lobe must be about one of {sorted(ScatterLobe.REFLECTION_ABOUT)}, got {reflection.about!r}")
+        elif reflection not in self.REFLECTION_MODES:
             raise ValueError(f"reflection must be one of {sorted(self.REFLECTION_MODES)}")
-        if transmission not in self.TRANSMISSION_MODES:
+        if isinstance(transmission, ScatterLobe):
+            if transmission.about not in ScatterLobe.TRANSMISSION_ABOUT:
+                raise ValueError(
+                    f"a transmission lobe must be about one of {sorted(ScatterLobe.TRANSMISSION_ABOUT)}, got {transmission.about!r}")
+        elif transmission not in self.TRANSMISSION_MODES:
             raise ValueError(
                 f"transmission must be one of {sorted(self.TRANSMISSION_MODES)}"
             )
@@ -1094,6 +1199,12 @@ class Coating(object):
                 (-math.inf if lo is None else float(lo), math.inf if hi is None else float(hi))
             )
         self.region = tuple(bounds)
+
+    @property
+    def transmits_matched(self):
+        """Beyond the critical angle the coating's R applies: "matched", or a lobe about "normal" or "straight"."""
+        t = self.transmission
+        return t.about != "refracted" if isinstance(t, ScatterLobe) else t == "matched"
 
     def covers(self, normal, position):
         """Rule 1 of "where a coating covers" in the class docstring; `position` in the node's frame."""
@@ -1141,7 +1252,7 @@ class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
         fresnel = self._smooth_reflectivity(surface, ray, geometry, container, adjacent)
         if coating.reflectivity is None:
             return fresnel
-        if fresnel == 1.0 and coating.transmission != "matched":
+        if fresnel == 1.0 and not coating.transmits_matched:
             return 1.0   # beyond the critical angle no refracted ray exists: stays totally reflected
         if isinstance(coating.reflectivity, ReflectivityTable):
             normal = _flipped_normal(geometry, ray)
@@ -1162,8 +1273,19 @@ class CoatedSurfaceDelegate(FresnelSurfaceDelegate):
             return a.at(ray.wavelength, math.degrees(math.acos(cosang)))
         return a
 
+    def reflected_direction(self, surface, ray, geometry, container, adjacent):
+        coating = self._match(ray, geometry)
+        if coating is not None and isinstance(coating.reflection, ScatterLobe):   # (rules 2-5 of a scattering coating)
+            out = coating.reflection.turn(ray.direction, geometry.normal(ray.position), False, getattr(ray, "wavelength", None))
+            return tuple(out.tolist())
+        return super(CoatedSurfaceDelegate, self).reflected_direction(surface, ray, geometry, container, adjacent)
+
     def transmitted_direction(self, surface, ray, geometry, container, adjacent):
         coating = self._match(ray, geometry)
+        if coating is not None and isinstance(coating.transmission, ScatterLobe):   # (rules 2-5 of a scattering coating)
+            n1, n2 = self._indices(ray, container, adjacent)
+            out = coating.transmission.turn(ray.direction, geometry.normal(ray.position), True, getattr(ray, "wavelength", None), n1, n2)
+            return tuple(out.tolist())
         if coating is not None and coating.transmission == "matched":
             return tuple(ray.direction)
         return super(CoatedSurfaceDelegate, self).transmitted_direction(
