@@ -743,8 +743,10 @@ typedef struct PvtCaptures {
  * sampler and the three compiled copies of the kernel's emitter to this rule ray by ray. */
 enum { PVT_WL_CONSTANT = 0, PVT_WL_SPECTRUM = 1,
        PVT_WL_SPECTRUM_HIST = 2 /* histogram-sampled Distribution (material/distribution.py:171-176): x[#{cdf_i < u}], no interpolation */ };
-enum { PVT_POS_POINT = 0, PVT_POS_RECT = 1, PVT_POS_CIRCLE = 2, PVT_POS_CUBE = 3 };
-enum { PVT_DIR_Z = 0, PVT_DIR_CONE = 1, PVT_DIR_ISOTROPIC = 2, PVT_DIR_LAMBERTIAN = 3, PVT_DIR_HG = 4 };
+enum { PVT_POS_POINT = 0, PVT_POS_RECT = 1, PVT_POS_CIRCLE = 2, PVT_POS_CUBE = 3,
+       PVT_POS_GRID = 4 /* EXTENSION within v13: a weight lattice (PvtSourceTables), pvt_scene_set_sources only */ };
+enum { PVT_DIR_Z = 0, PVT_DIR_CONE = 1, PVT_DIR_ISOTROPIC = 2, PVT_DIR_LAMBERTIAN = 3, PVT_DIR_HG = 4,
+       PVT_DIR_TABLE = 5 /* EXTENSION within v13: a tabulated direction (PvtSourceTables), pvt_scene_set_sources only */ };
 typedef struct PvtEmitterTables {
     int32_t n_lights, n_spec;
     const int32_t* wl_type;
@@ -759,6 +761,51 @@ typedef struct PvtEmitterTables {
     const double* spec_x;           /* pooled inverse-CDF tables */
     const double* spec_cdf;
 } PvtEmitterTables;
+
+/* ---- tabulated sources (extension within v13, passed to pvt_scene_set_sources beside the emitter) -----------------
+ * A light whose pos_type is PVT_POS_GRID names a position grid, light_grid[i] >= 0; a light whose dir_type is
+ * PVT_DIR_TABLE names a direction table, light_table[i] >= 0; every other light has -1 there.  The emitter's pos_param
+ * and dir_param of such a light are not read: the packer writes where the light's records lie into them.
+ *
+ * The position grid (the Python PositionGrid states the same): a non-negative weight per cell of a lattice in the
+ * light's own frame, shape (nx, ny, nz), each >= 1, at most 2^22 cells.  An axis with grid_bounded = 0 has one cell,
+ * the coordinate on it is exactly 0.0 and no draw is taken for it.
+ *  1. The CDF has C_0 = 0.  C_{k+1} is the running sum of the weights in slot order (ix ny + iy) nz + iz, divided by
+ *     the total.  The last entry is set to exactly 1.  (grid_cdf holds the cells + 1 entries of each grid.)
+ *  2. Draw u_c.  The cell is the slot k with C_k <= u_c < C_{k+1}.  It is found by the bisection the phase tables use
+ *     (cdf[m] <= u ? a = m : b = m), so a cell of zero weight is never chosen.
+ *  3. For each bounded axis, in the order x, y, z, draw u_a.  h_a = (upper_a - lower_a) / n_a is one division (grid_h
+ *     holds it).  The coordinate is lower_a + ((double)i_a + u_a) * h_a: an add, a multiply and an add, with no fused
+ *     multiply-add.
+ *  4. In the light's draw order, these draws stand where the built-in masks' position draws stand.  That is after the
+ *     wavelength draw of a spectrum light and before the direction draws.
+ *
+ * The direction table: a table in the layout of PvtPhaseTables, sampled by steps 3 and 4 of its contract about the
+ * light's +z.  The first row is used; u1 is drawn whenever the table has several rows; u2 gives the polar cosine, u3
+ * the azimuth.  These draws stand where the built-in directions' draws stand.  Equal tables may be stored once.
+ * A separate struct so that PvtEmitterTables keeps the length old callers pass. */
+typedef struct PvtSourceTables {
+    int32_t n_lights;               /* the emitter's n_lights */
+    int32_t n_grids, n_tables;      /* position grids, direction tables */
+    int32_t n_grid_cdf;             /* length of the grid CDF pool */
+    int32_t n_table_wavelength, n_table_mu, n_table_cdf;   /* lengths of the tables' wavelength, mu and CDF pools */
+    const int32_t* light_grid;      /* (n_lights) grid of each light, -1 = none */
+    const int32_t* light_table;     /* (n_lights) direction table of each light, -1 = none */
+    const int32_t* grid_shape;      /* (n_grids,3) cells per axis */
+    const int32_t* grid_bounded;    /* (n_grids,3) 1 = bounded, 0 = a one-cell axis without bounds */
+    const double* grid_lower;       /* (n_grids,3) lower bound, 0 on an axis without bounds */
+    const double* grid_h;           /* (n_grids,3) cell width (upper - lower) / n, 1 on an axis without bounds */
+    const int32_t* grid_cdf_start;  /* (n_grids) first CDF entry of each grid in `grid_cdf` (cells + 1 entries) */
+    const double* grid_cdf;         /* pooled CDFs */
+    const int32_t* table_nw;        /* (n_tables) rows (wavelengths) of each table, >= 1 */
+    const int32_t* table_nmu;       /* (n_tables) mu points of each table, >= 2 */
+    const int32_t* table_wl_start;  /* (n_tables) first wavelength of each table in `table_wavelength` */
+    const int32_t* table_mu_start;  /* (n_tables) first point of each table in `table_mu` */
+    const int32_t* table_cdf_start; /* (n_tables) first CDF entry of each table in `table_cdf` (nw x nmu, row-major) */
+    const double* table_wavelength; /* pooled row wavelengths, nm, finite and strictly increasing per table */
+    const double* table_mu;         /* pooled mu axes, each from exactly -1 to exactly 1 */
+    const double* table_cdf;        /* pooled CDF rows, each from exactly 0 to exactly 1 */
+} PvtSourceTables;
 
 typedef struct PvtTraceParams {
     int64_t n_rays;         /* rays in this bundle                                   */
@@ -945,8 +992,16 @@ int pvt_scene_create_polyhedra(const PvtSceneTables* tables, const PvtIndexTable
                                const PvtCaptureTables* capture_tables, const PvtCoatingAbsorbTables* absorb_tables,
                                const PvtCoatingPatternTables* pattern_tables, const PvtAlignTables* align_tables,
                                const PvtPolyhedronTables* polyhedron_tables, int device, PvtScene** out);
-/* Attach / replace the device-side emitter of a scene (optional). */
+/* Attach / replace the device-side emitter of a scene (optional).  It takes no source tables: a type word outside the
+ * built-ins, PVT_POS_GRID and PVT_DIR_TABLE among them, is refused with PVT_ERR_INVALID ("emitter type out of range"),
+ * and so the host-buffer entries refuse it (pvt_trace_bundle, pvt_trace_bundle_multi). */
 int pvt_scene_set_emitter(PvtScene* scene, const PvtEmitterTables* emitter);
+/* The same with tabulated sources (PvtSourceTables), and the one entry that knows PVT_POS_GRID and PVT_DIR_TABLE:
+ * `sources` NULL = exactly pvt_scene_set_emitter.  The tables are validated first (pvt_sources_check). */
+int pvt_scene_set_sources(PvtScene* scene, const PvtEmitterTables* emitter, const PvtSourceTables* sources);
+/* The validation pvt_scene_set_sources runs, without a scene or a GPU: PVT_OK, or PVT_ERR_INVALID with the refusal in
+ * pvt_last_error(). */
+int pvt_sources_check(const PvtEmitterTables* emitter, const PvtSourceTables* sources);
 void pvt_scene_destroy(PvtScene* scene);
 
 /* Device-resident entry: every pointer in rays / tallies / log is a DEVICE

@@ -663,6 +663,88 @@ int validate_phase_tables(const PvtSceneTables* t, const PvtPhaseTables* ph) {
     return PVT_OK;
 }
 
+// the emitter and its tabulated sources (PvtSourceTables, pvt_scene_set_sources; `src` null: pvt_scene_set_emitter, which
+// knows the built-in type words only).  A light names a grid exactly when it is tagged PVT_POS_GRID, a table exactly when
+// it is tagged PVT_DIR_TABLE; the grids' messages are the Python PositionGrid's
+constexpr long long kSourceGridCells = 1ll << 22;
+int validate_sources(const PvtEmitterTables* e, const PvtSourceTables* src) {
+    if (!e || e->n_lights <= 0) return fail(PVT_ERR_INVALID, "bad emitter");
+    const int Lt = e->n_lights;
+    if (!e->wl_type || !e->pos_type || !e->dir_type) return fail(PVT_ERR_INVALID, "emitter: missing arrays");
+    const int pos_top = src ? PVT_POS_GRID : PVT_POS_CUBE, dir_top = src ? PVT_DIR_TABLE : PVT_DIR_HG;
+    for (int i = 0; i < Lt; i++)
+        if (e->wl_type[i] < 0 || e->wl_type[i] > PVT_WL_SPECTRUM_HIST || e->pos_type[i] < 0 || e->pos_type[i] > pos_top ||
+            e->dir_type[i] < 0 || e->dir_type[i] > dir_top)
+            return fail(PVT_ERR_INVALID, "emitter type out of range");
+    if (!src) return PVT_OK;
+    if (!e->wl_value || !e->pos_param || !e->dir_param || !e->light_to_world) return fail(PVT_ERR_INVALID, "emitter: missing arrays");
+    const int G = src->n_grids, T = src->n_tables;
+    if (src->n_lights != Lt || !src->light_grid || !src->light_table)
+        return fail(PVT_ERR_INVALID, "source tables: need one grid and one table index per light");
+    if (G < 0 || T < 0 || (G > 0 && (!src->grid_shape || !src->grid_bounded || !src->grid_lower || !src->grid_h ||
+                                     !src->grid_cdf_start || !src->grid_cdf)) ||
+        (T > 0 && (!src->table_nw || !src->table_nmu || !src->table_wl_start || !src->table_mu_start || !src->table_cdf_start ||
+                   !src->table_wavelength || !src->table_mu || !src->table_cdf)))
+        return fail(PVT_ERR_INVALID, "source tables: missing arrays");
+    for (int i = 0; i < Lt; i++) {
+        const int g = src->light_grid[i], t = src->light_table[i];
+        if (g < -1 || g >= G) return fail(PVT_ERR_INVALID, "source tables: light names a missing grid");
+        if (t < -1 || t >= T) return fail(PVT_ERR_INVALID, "source tables: light names a missing table");
+        if ((e->pos_type[i] == PVT_POS_GRID) != (g >= 0))
+            return fail(PVT_ERR_INVALID, "source tables: a light names a grid exactly when it is tagged PVT_POS_GRID");
+        if ((e->dir_type[i] == PVT_DIR_TABLE) != (t >= 0))
+            return fail(PVT_ERR_INVALID, "source tables: a light names a table exactly when it is tagged PVT_DIR_TABLE");
+    }
+    long long total = 0;
+    for (int g = 0; g < G; g++) {
+        long long cells = 1;
+        for (int a = 0; a < 3; a++) {
+            const long long n = src->grid_shape[g * 3 + a];
+            if (n < 1) return fail(PVT_ERR_INVALID, "position grid: shape must be >= 1 on each axis");
+            cells *= n;
+            if (cells > kSourceGridCells) return fail(PVT_ERR_INVALID, "position grid: more than 2^22 cells");
+            const double lo = src->grid_lower[g * 3 + a], h = src->grid_h[g * 3 + a];
+            if (src->grid_bounded[g * 3 + a] == 0) {
+                if (n != 1) return fail(PVT_ERR_INVALID, "position grid: only an axis with one cell may be unbounded");
+                continue;
+            }
+            if (!(std::isfinite(lo) && std::isfinite(h))) return fail(PVT_ERR_INVALID, "position grid: lower and upper must be finite");
+            if (!(h > 0.0)) return fail(PVT_ERR_INVALID, "position grid: needs lower < upper on each axis");
+        }
+        const long long c0 = src->grid_cdf_start[g];
+        if (c0 < 0 || c0 + cells + 1 > src->n_grid_cdf) return fail(PVT_ERR_INVALID, "position grid: CDF range out of bounds");
+        const double* cdf = src->grid_cdf + c0;
+        for (long long k = 0; k <= cells; k++)
+            if (!std::isfinite(cdf[k]) || (k > 0 && !(cdf[k] >= cdf[k - 1])))
+                return fail(PVT_ERR_INVALID, "position grid: weights must be finite and >= 0");
+        if (cdf[0] != 0.0 || cdf[cells] != 1.0)
+            return fail(PVT_ERR_INVALID, "position grid: the CDF must run from exactly 0 to exactly 1");
+        total += kSgCdf + cells + 1;
+    }
+    for (int j = 0; j < T; j++) {
+        const long long nw = src->table_nw[j], nm = src->table_nmu[j];
+        const long long w0 = src->table_wl_start[j], m0 = src->table_mu_start[j], c0 = src->table_cdf_start[j];
+        if (nw < 1 || nm < 2 || w0 < 0 || m0 < 0 || c0 < 0 || w0 + nw > src->n_table_wavelength || m0 + nm > src->n_table_mu ||
+            c0 + nw * nm > src->n_table_cdf)
+            return fail(PVT_ERR_INVALID, "direction table: wavelength, mu or CDF range out of bounds");
+        if (!increasing_finite(src->table_wavelength + w0, nw))
+            return fail(PVT_ERR_INVALID, "direction table: wavelengths must be finite and strictly increasing");
+        const double* mu = src->table_mu + m0;
+        if (mu[0] != -1.0 || mu[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "direction table: the mu axis must run from exactly -1 to exactly 1");
+        for (long long i = 1; i < nm; i++)
+            if (!(mu[i] > mu[i - 1])) return fail(PVT_ERR_INVALID, "direction table: the mu axis must be strictly increasing");
+        for (long long r = 0; r < nw; r++) {
+            const double* cdf = src->table_cdf + c0 + r * nm;
+            if (cdf[0] != 0.0 || cdf[nm - 1] != 1.0) return fail(PVT_ERR_INVALID, "direction table: every CDF row must run from exactly 0 to exactly 1");
+            for (long long i = 1; i < nm; i++)
+                if (!(cdf[i] >= cdf[i - 1])) return fail(PVT_ERR_INVALID, "direction table: every CDF row must be non-decreasing");
+        }
+        total += 2 + nw + nm + nw * nm;
+    }
+    if (total > (1ll << 27)) return fail(PVT_ERR_INVALID, "source tables: more than 2^27 doubles");
+    return PVT_OK;
+}
+
 // rough interfaces (PvtSurfaceTables, pvt_scene_create_rough): one finite GGX width 0 <= alpha <= 1 per node
 int validate_surface_tables(const PvtSceneTables* t, const PvtSurfaceTables* rs) {
     if (!rs || rs->n_nodes == 0) return PVT_OK;

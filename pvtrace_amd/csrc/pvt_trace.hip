@@ -185,8 +185,10 @@ int pvt_device_count(void) {
     return n;
 }
 
-int pvt_scene_set_emitter(PvtScene* s, const PvtEmitterTables* e) {
-    if (!s || !e || e->n_lights <= 0) return fail(PVT_ERR_INVALID, "bad emitter");
+// The emitter's blobs, and behind them the records of its tabulated sources (`src` null: none; validated by the caller):
+// a PVT_POS_GRID light's pos_param[0] and a PVT_DIR_TABLE light's dir_param are overwritten with where its grid's (kSg*)
+// and its table's record ({n_wavelength, n_mu}, wavelengths, mu, CDF rows: what phase_table_turn reads) start in `ed`.
+static int pack_emitter(PvtScene* s, const PvtEmitterTables* e, const PvtSourceTables* src) {
     HIP_TRY(hipSetDevice(s->device));
     std::vector<double> ed;
     std::vector<int> ei;
@@ -203,6 +205,31 @@ int pvt_scene_set_emitter(PvtScene* s, const PvtEmitterTables* e) {
     o.wl_spec_n = push(ei, e->wl_spec_n, Lt);
     o.pos_type = push(ei, e->pos_type, Lt);
     o.dir_type = push(ei, e->dir_type, Lt);
+    if (src) {
+        std::vector<int> grid_at(src->n_grids > 0 ? src->n_grids : 0), table_at(src->n_tables > 0 ? src->n_tables : 0);
+        for (int g = 0; g < src->n_grids; g++) {
+            grid_at[g] = (int)ed.size();
+            size_t cells = 1;
+            for (int a = 0; a < 3; a++) { ed.push_back((double)src->grid_shape[g * 3 + a]); cells *= (size_t)src->grid_shape[g * 3 + a]; }
+            for (int a = 0; a < 3; a++) ed.push_back(src->grid_bounded[g * 3 + a] != 0 ? 1.0 : 0.0);
+            push(ed, src->grid_lower + g * 3, 3);
+            push(ed, src->grid_h + g * 3, 3);
+            push(ed, src->grid_cdf + src->grid_cdf_start[g], cells + 1);
+        }
+        for (int j = 0; j < src->n_tables; j++) {
+            table_at[j] = (int)ed.size();
+            const size_t nw = (size_t)src->table_nw[j], nm = (size_t)src->table_nmu[j];
+            ed.push_back((double)nw);
+            ed.push_back((double)nm);
+            push(ed, src->table_wavelength + src->table_wl_start[j], nw);
+            push(ed, src->table_mu + src->table_mu_start[j], nm);
+            push(ed, src->table_cdf + src->table_cdf_start[j], nw * nm);
+        }
+        for (int i = 0; i < Lt; i++) {
+            if (src->light_grid[i] >= 0) ed[o.pos_param + (size_t)i * 3] = (double)grid_at[src->light_grid[i]];
+            if (src->light_table[i] >= 0) ed[o.dir_param + i] = (double)table_at[src->light_table[i]];
+        }
+    }
     ed.push_back(0.0);
     ei.push_back(0);
     if (s->d_ed) { (void)hipFree(s->d_ed); s->d_ed = nullptr; }
@@ -214,6 +241,20 @@ int pvt_scene_set_emitter(PvtScene* s, const PvtEmitterTables* e) {
     s->eoff = o;
     s->n_lights = Lt;
     return PVT_OK;
+}
+
+int pvt_sources_check(const PvtEmitterTables* e, const PvtSourceTables* src) { return validate_sources(e, src); }
+
+int pvt_scene_set_emitter(PvtScene* s, const PvtEmitterTables* e) {
+    if (!s || !e || e->n_lights <= 0) return fail(PVT_ERR_INVALID, "bad emitter");
+    const int rc = validate_sources(e, nullptr);
+    return rc != PVT_OK ? rc : pack_emitter(s, e, nullptr);
+}
+
+int pvt_scene_set_sources(PvtScene* s, const PvtEmitterTables* e, const PvtSourceTables* src) {
+    if (!s || !e || e->n_lights <= 0) return fail(PVT_ERR_INVALID, "bad emitter");
+    const int rc = validate_sources(e, src);
+    return rc != PVT_OK ? rc : pack_emitter(s, e, src);
 }
 
 void pvt_scene_destroy(PvtScene* s) {

@@ -99,6 +99,11 @@ enum { kClRTab = 0, kClRAxis, kClTTab, kClTAxis, kCl };   // a scattering coatin
 enum { kPrShape = 0, kPrBounded = 3, kPrLower = 6, kPrH = 9, kPrMask = 12, kPr = 13 };   // a coating pattern's record at KArgs::pd_d:
                                                                  // shape, per axis 1 = bounded (else index 0), lower, cell
                                                                  // widths, and where its mask starts, in BYTES from pd
+enum { kSgShape = 0, kSgBounded = 3, kSgLower = 6, kSgH = 9, kSgCdf = 12 };   // a position grid's record in the emitter's double
+                                                                 // blob (a PVT_POS_GRID light's pos_param[0] names where it
+                                                                 // starts): shape, per axis 1 = bounded (else the coordinate
+                                                                 // is 0 and no draw is taken), lower, cell widths, then the
+                                                                 // CDF of cells + 1 entries
 
 struct Lay {  // record bases (elements) inside the blobs; spectra follow the records and are
               // addressed by absolute offsets stored in the component records
@@ -1248,6 +1253,35 @@ __device__ __forceinline__ V3 sample_phase(int type, double param, Rng& rng) {
 }
 
 // ----------------------------------------------------------- emission
+// Tabulated sources (include/pvtrace_hip.h, PvtSourceTables; the Python PositionGrid states the same rule): the local
+// launch position of a PVT_POS_GRID light from its record `g` (kSg*).  One draw picks the cell by the bisection the phase
+// tables use, cdf[a] <= u < cdf[b], so a cell of zero weight is never chosen; then one draw per bounded axis, x, y, z.
+__device__ __forceinline__ V3 emit_grid_position(const double* g, Rng& rng) {
+    const int ny = (int)g[kSgShape + 1], nz = (int)g[kSgShape + 2];
+    const double* cdf = g + kSgCdf;
+    const double u = rng_uniform(rng);
+    int a = 0, b = (int)g[kSgShape] * ny * nz;
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (cdf[m] <= u) a = m; else b = m;
+    }
+    const int iz = a % nz, ixy = a / nz;
+    const int iy = ixy % ny, ix = ixy / ny;
+    V3 p{0.0, 0.0, 0.0};
+    if (g[kSgBounded] != 0.0) p.x = g[kSgLower] + ((double)ix + rng_uniform(rng)) * g[kSgH];
+    if (g[kSgBounded + 1] != 0.0) p.y = g[kSgLower + 1] + ((double)iy + rng_uniform(rng)) * g[kSgH + 1];
+    if (g[kSgBounded + 2] != 0.0) p.z = g[kSgLower + 2] + ((double)iz + rng_uniform(rng)) * g[kSgH + 2];
+    return p;
+}
+// ... and the local direction of a PVT_DIR_TABLE light: `phase_table_turn` about the light's +z on the table's first row
+// (a wavelength below every row's takes it), u1 drawn whenever the table has several rows.
+__device__ __forceinline__ V3 emit_table_direction(const double* tab, Rng& rng) {
+    const double u1 = (int)tab[0] > 1 ? rng_uniform(rng) : 0.0;
+    const double u2 = rng_uniform(rng);
+    const double u3 = rng_uniform(rng);
+    return phase_table_turn(tab, -__builtin_inf(), u1, u2, u3, 0.0, 0.0, 1.0);
+}
+
 // One ray from its own stream (mirrors oracle pvt_oracle_emit; distributions of
 // reference pvtrace/engine/emit.py:22-89).
 __device__ __forceinline__ void emit_one(const KArgs& A, unsigned long long gi, V3& pos, V3& dir, double& wl) {
@@ -1295,6 +1329,8 @@ __device__ __forceinline__ void emit_one(const KArgs& A, unsigned long long gi, 
         lp.x = -pp[0] + 2.0 * pp[0] * rng_uniform(rng);
         lp.y = -pp[1] + 2.0 * pp[1] * rng_uniform(rng);
         lp.z = -pp[2] + 2.0 * pp[2] * rng_uniform(rng);
+    } else if (pt == PVT_POS_GRID) {
+        lp = emit_grid_position(ed + (int)pp[0], rng);   // (the packer wrote where the grid's record lies)
     }
     double prm = ed[E.dir_param + li];
     int dt = ei[E.dir_type + li];
@@ -1304,6 +1340,8 @@ __device__ __forceinline__ void emit_one(const KArgs& A, unsigned long long gi, 
     else if (dt == PVT_DIR_LAMBERTIAN) {
         double p1 = rng_uniform(rng), p2 = rng_uniform(rng);
         ld = lambert_direction(p1, p2);
+    } else if (dt == PVT_DIR_TABLE) {
+        ld = emit_table_direction(ed + (int)prm, rng);   // (... and where the table's)
     }
     const double* m = ed + E.l2w + li * 16;
     pos.x = m[0] * lp.x + m[1] * lp.y + m[2] * lp.z + m[3];

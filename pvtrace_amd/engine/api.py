@@ -447,6 +447,10 @@ def _scene_key(compiled, emitter, device):
                      "dir_param", "light_to_world", "spec_x", "spec_cdf"):
             a = np.ascontiguousarray(getattr(emitter, name))
             h.update(repr(a.shape).encode()); h.update(a.data if a.size else b"")
+        if getattr(emitter, "has_sources", False):   # the pooled position grids and direction tables, every byte
+            for name in emitter.SOURCE_FIELDS:
+                a = np.ascontiguousarray(getattr(emitter, name))
+                h.update(name.encode()); h.update(repr(a.shape).encode()); h.update(a.data if a.size else b"")
     return h.digest()
 
 

@@ -12,6 +12,14 @@ is lowered to a small `EmitterTables` record that either
 * the HIP emission kernel draws on the GPU from per-ray RNG streams, so a
   10^8-photon run never materialises a 5.6 GB host array.
 
+**Tabulated sources.**  Two delegates are tables rather than closed forms and are lowered all the same: a
+`light.PositionGrid` as `position` (POS_GRID: a weight per cell of a lattice in the light's frame; one draw picks the cell
+through the CDF, one draw per bounded axis places the point in it) and a `light.DirectionTable` -- a wrapped
+`material.PhaseFunctionTable` -- as `direction` (DIR_TABLE: its first row about the light's +z; u1 drawn whenever it has several rows, u2 the polar cosine, u3 the
+azimuth).  `EmitterTables` pools the grids (shape, bounded, lower, h, CDF) and the tables (the record layout the kernel's
+`phase_table_turn` reads), equal ones once; the device takes them through `pvt_scene_set_sources` (PvtSourceTables in
+include/pvtrace_hip.h states both rules), the host sampler below draws them in the same order.
+
 A delegate that cannot be lowered (a lambda, a user function) keeps working in
 host mode: THAT delegate is called once per ray, the light's other delegates are
 still sampled vectorised and no Ray object is built per photon.
@@ -37,8 +45,8 @@ from pvtrace_amd import material as Mm
 from pvtrace_amd.engine.compiler import UnsupportedSceneError
 
 WL_CONSTANT, WL_SPECTRUM, WL_SPECTRUM_HIST = 0, 1, 2
-POS_POINT, POS_RECT, POS_CIRCLE, POS_CUBE = 0, 1, 2, 3
-DIR_Z, DIR_CONE, DIR_ISOTROPIC, DIR_LAMBERTIAN, DIR_HG = 0, 1, 2, 3, 4
+POS_POINT, POS_RECT, POS_CIRCLE, POS_CUBE, POS_GRID = 0, 1, 2, 3, 4
+DIR_Z, DIR_CONE, DIR_ISOTROPIC, DIR_LAMBERTIAN, DIR_HG, DIR_TABLE = 0, 1, 2, 3, 4, 5
 
 
 def _partial_of(delegate, func, nargs):
@@ -82,6 +90,8 @@ def classify_position(d):
         return (POS_CUBE, (float(d.x), float(d.y), float(d.z)))
     if _partial_of(d, Lm.cube_mask, 3):
         return (POS_CUBE, tuple(float(v) for v in d.args))
+    if isinstance(d, Lm.PositionGrid):
+        return (POS_GRID, d)      # (the grid itself: `EmitterTables` pools it, the packer writes where its record lies)
     return None
 
 
@@ -103,6 +113,10 @@ def classify_direction(d):
         g = float(d.args[0])
     if g is not None:
         return (DIR_ISOTROPIC, 0.0) if abs(g) < 1e-12 else (DIR_HG, g)
+    if isinstance(d, Lm.DirectionTable):
+        # the wrapped `PhaseFunctionTable`, sampled about the light's +z on its first row (a BARE table stays a user
+        # delegate, sampled on the host through its `sample(n)`, as it always was)
+        return (DIR_TABLE, d.table)
     return None
 
 
@@ -173,6 +187,12 @@ class EmitterTables:
         # delegates the tables cannot express, per light: {"wavelength" | "position" | "direction": callable};
         # the host sampler calls those once per ray and still samples the light's other delegates vectorised
         self.custom = [dict() for _ in range(n)]
+        # tabulated sources (PvtSourceTables): per light the grid and table it names, or -1; the pooled grids (shape,
+        # bounded, lower, h, CDF) and tables (the record layout phase_table_turn reads).  Equal ones are stored once.
+        self.light_grid = np.full(n, -1, dtype=np.int32)
+        self.light_table = np.full(n, -1, dtype=np.int32)
+        self.grids, self.tables = [], []
+        grid_of, table_of = {}, {}
         sx, sc = [], []
         for i, node in enumerate(nodes):
             light = node.light
@@ -202,10 +222,67 @@ class EmitterTables:
                 sx.extend(np.asarray(dist._x, dtype=np.float64).tolist())
                 sc.extend(np.asarray(dist._cdf, dtype=np.float64).tolist())
                 self.wl_spec_n[i] = len(sx) - self.wl_spec_start[i]
+            if p[0] == POS_GRID:
+                self.light_grid[i] = _pooled(p[1], _grid_key(p[1]), grid_of, self.grids)
+                p = (POS_GRID, (0.0, 0.0, 0.0))
+            if d[0] == DIR_TABLE:
+                self.light_table[i] = _pooled(d[1], _table_key(d[1]), table_of, self.tables)
+                d = (DIR_TABLE, 0.0)
             self.pos_type[i], self.pos_param[i] = p
             self.dir_type[i], self.dir_param[i] = d
         self.spec_x = np.array(sx, dtype=np.float64)
         self.spec_cdf = np.array(sc, dtype=np.float64)
+        self._pool_sources()
+
+    SOURCE_FIELDS = ("light_grid", "light_table", "grid_shape", "grid_bounded", "grid_lower", "grid_h", "grid_cdf_start",
+                     "grid_cdf", "table_nw", "table_nmu", "table_wl_start", "table_mu_start", "table_cdf_start",
+                     "table_wavelength", "table_mu", "table_cdf")
+
+    @property
+    def has_sources(self):
+        return bool(self.grids or self.tables)
+
+    def _pool_sources(self):
+        g, t = self.grids, self.tables
+        self.n_grids, self.n_tables = len(g), len(t)
+        self.grid_shape = np.array([x.shape for x in g], dtype=np.int32).reshape(-1, 3)
+        self.grid_bounded = np.array([x.bounded for x in g], dtype=np.int32).reshape(-1, 3)
+        self.grid_lower = np.array([x.lower for x in g], dtype=np.float64).reshape(-1, 3)
+        self.grid_h = np.array([x.h for x in g], dtype=np.float64).reshape(-1, 3)
+        self.grid_cdf_start = _starts([x.cdf.size for x in g])
+        self.grid_cdf = np.concatenate([x.cdf for x in g]) if g else np.zeros(0)
+        self.table_nw = np.array([x.cdf.shape[0] for x in t], dtype=np.int32)
+        self.table_nmu = np.array([x.mu.size for x in t], dtype=np.int32)
+        rows = [_table_wavelengths(x) for x in t]
+        self.table_wl_start = _starts([r.size for r in rows])
+        self.table_mu_start = _starts([x.mu.size for x in t])
+        self.table_cdf_start = _starts([x.cdf.size for x in t])
+        self.table_wavelength = np.concatenate(rows) if t else np.zeros(0)
+        self.table_mu = np.concatenate([x.mu for x in t]) if t else np.zeros(0)
+        self.table_cdf = np.concatenate([x.cdf.reshape(-1) for x in t]) if t else np.zeros(0)
+
+
+def _starts(sizes):
+    return np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int32) if len(sizes) else np.zeros(0, dtype=np.int32)
+
+
+def _table_wavelengths(table):   # a single row has no wavelength: one 0.0 stands for it, as in the scene's phase tables
+    return np.zeros(1) if table.wavelength is None else np.asarray(table.wavelength, dtype=np.float64)
+
+
+def _grid_key(grid):
+    return (grid.shape, grid.bounded, tuple(map(float.hex, grid.lower + grid.upper)), grid.cdf.tobytes())
+
+
+def _table_key(table):
+    return (table.cdf.shape, _table_wavelengths(table).tobytes(), table.mu.tobytes(), table.cdf.tobytes())
+
+
+def _pooled(obj, key, index_of, pool):
+    if key not in index_of:
+        index_of[key] = len(pool)
+        pool.append(obj)
+    return index_of[key]
 
 
 _POOL = None
@@ -289,6 +366,8 @@ def _sample_light(tab, i, n, uniform):
         pos = np.column_stack((rad * np.cos(ang), rad * np.sin(ang), np.zeros(n)))
     elif kind == POS_CUBE:
         pos = np.column_stack([-pp[a] + 2 * pp[a] * uniform(n) for a in range(3)])
+    elif kind == POS_GRID:     # the cell draw, then one draw per bounded axis (x, y, z): `PositionGrid`, items 2 and 3
+        pos = tab.grids[tab.light_grid[i]].positions(uniform, n)
     else:
         pos = np.zeros((n, 3))
     kind, prm = tab.dir_type[i], tab.dir_param[i]
@@ -306,6 +385,12 @@ def _sample_light(tab, i, n, uniform):
         mu = (1 + prm * prm - ((1 - prm * prm) / (1 + prm * s)) ** 2) / (2 * prm)
         # (the quotient may leave [-1, 1] by a few ulp for small |g| and at the ends of the draw grid, where arccos is NaN)
         direc = _sphere(np.arccos(np.clip(mu, -1.0, 1.0)), 2 * np.pi * uniform(n))
+    elif kind == DIR_TABLE:    # the first row about +z; u1 is drawn (and not read) whenever the table has several rows
+        table = tab.tables[tab.light_table[i]]
+        if table.n_wavelength > 1:
+            uniform(n)
+        mu = table.sample_mu(uniform(n), 0)
+        direc = table.turn(np.array([0.0, 0.0, 1.0]), mu, uniform(n))
     else:
         direc = np.tile((0.0, 0.0, 1.0), (n, 1))
     return pos, direc, wl

@@ -284,6 +284,24 @@ class PvtEmitterTables(C.Structure):
     ABSENT = staticmethod(lambda e: False)
 
 
+class PvtSourceTables(C.Structure):
+    """Tabulated sources of an emitter (include/pvtrace_hip.h; pvt_scene_set_sources): position grids and direction tables,
+    read from an `emit.EmitterTables` (or any object with these fields); absent when no light names one."""
+    _fields_ = [
+        ("n_lights", C.c_int32), ("n_grids", C.c_int32), ("n_tables", C.c_int32), ("n_grid_cdf", C.c_int32),
+        ("n_table_wavelength", C.c_int32), ("n_table_mu", C.c_int32), ("n_table_cdf", C.c_int32),
+        ("light_grid", _p_i32), ("light_table", _p_i32), ("grid_shape", _p_i32), ("grid_bounded", _p_i32),
+        ("grid_lower", _p_f64), ("grid_h", _p_f64), ("grid_cdf_start", _p_i32), ("grid_cdf", _p_f64),
+        ("table_nw", _p_i32), ("table_nmu", _p_i32), ("table_wl_start", _p_i32), ("table_mu_start", _p_i32),
+        ("table_cdf_start", _p_i32), ("table_wavelength", _p_f64), ("table_mu", _p_f64), ("table_cdf", _p_f64),
+    ]
+    POINTERS = _same_names(_fields_)
+    COUNTS = {"n_lights": lambda e: e.n_lights, "n_grids": lambda e: e.n_grids, "n_tables": lambda e: e.n_tables,
+              "n_grid_cdf": lambda e: np.size(e.grid_cdf), "n_table_wavelength": lambda e: np.size(e.table_wavelength),
+              "n_table_mu": lambda e: np.size(e.table_mu), "n_table_cdf": lambda e: np.size(e.table_cdf)}
+    ABSENT = staticmethod(lambda e: int(getattr(e, "n_grids", 0)) == 0 and int(getattr(e, "n_tables", 0)) == 0)
+
+
 class PvtTraceParams(C.Structure):
     _fields_ = [
         ("n_rays", C.c_int64), ("seed", C.c_uint64), ("ray_offset", C.c_uint64),
@@ -463,6 +481,8 @@ def declare_signatures(lib, names):
         "pvt_trace_device_capture": ([vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
                                       C.POINTER(PvtEventRecords), C.POINTER(PvtCaptures), vp], C.c_int),
         "pvt_scene_set_emitter": ([vp, C.POINTER(PvtEmitterTables)], C.c_int),
+        "pvt_scene_set_sources": ([vp, C.POINTER(PvtEmitterTables), C.POINTER(PvtSourceTables)], C.c_int),
+        "pvt_sources_check": ([C.POINTER(PvtEmitterTables), C.POINTER(PvtSourceTables)], C.c_int),
         "pvt_scene_destroy": ([vp], None),
         "pvt_trace_device": (
             [vp, C.POINTER(PvtRays), C.POINTER(PvtTraceParams), C.POINTER(PvtTallies),
@@ -526,7 +546,7 @@ ABI_SYMBOLS = (
     "pvt_scene_create_maps", "pvt_scene_map_slots", "pvt_scene_variant", "pvt_scene_lean_check",
     "pvt_scene_create_capture", "pvt_scene_capture_rows", "pvt_trace_device_capture", "pvt_scene_create_absorb",
     "pvt_scene_create_origin", "pvt_scene_create_pattern", "pvt_scene_create_aligned", "pvt_scene_entry",
-    "pvt_scene_create_polyhedra", "pvt_scene_solo", "pvt_scene_solo_check",
+    "pvt_scene_create_polyhedra", "pvt_scene_solo", "pvt_scene_solo_check", "pvt_scene_set_sources", "pvt_sources_check",
 )
 VARIANT_NAMES = ("lean", "w4", "grid", "rough", "mesh")   # include/pvtrace_hip.h PVT_VARIANT_*
 # the family's entry point a launch ran (PVT_ENTRY_*): its usual kernel, or the lean family's parking one
@@ -645,6 +665,18 @@ def mesh_bvh_check(compiled, node):
     return tuple(int(v.value) for v in out)
 
 
+def sources_check(emitter):
+    """The packer's validation of an emitter and its tabulated sources (host only, no GPU needed; include/pvtrace_hip.h:
+    pvt_sources_check) -> None when they are accepted, else the refusal's message.  `emitter`: an `emit.EmitterTables`
+    or any object with its fields; without a grid or a table it is checked as pvt_scene_set_emitter checks it."""
+    lib = load_library()
+    st, keep = emitter_tables_struct(emitter)
+    sources, keep_sources = marshal(PvtSourceTables, emitter)
+    code = lib.pvt_sources_check(C.byref(st), None if sources is None else C.byref(sources))
+    del keep, keep_sources
+    return None if code == 0 else lib.pvt_last_error().decode()
+
+
 def lean_check(compiled):
     """True when the library proves the scene plain from its packed tables (host only, no GPU needed;
     include/pvtrace_hip.h: pvt_scene_lean_check): its launches may run the lean kernel family."""
@@ -740,7 +772,11 @@ class DeviceScene:
 
     def set_emitter(self, emitter):
         st, keep = emitter_tables_struct(emitter)
-        check(self.lib.pvt_scene_set_emitter(self.handle, C.byref(st)), "pvt_scene_set_emitter")
+        sources, keep_sources = marshal(PvtSourceTables, emitter)
+        if sources is None:
+            check(self.lib.pvt_scene_set_emitter(self.handle, C.byref(st)), "pvt_scene_set_emitter")
+        else:   # (the one entry that knows position grids and direction tables)
+            check(self.lib.pvt_scene_set_sources(self.handle, C.byref(st), C.byref(sources)), "pvt_scene_set_sources")
         self.has_emitter = True
 
     def close(self):
